@@ -21,8 +21,14 @@ Several GPUs (one process per GPU, torch.distributed, backend nccl = RCCL over x
       --shard sources   by source: rank r holds 1/N of every field's sources and of the grid chunks and
                         evaluates ALL rows, all-reduce(SUM) of B doubles;
       --shard auto      sources when a rank's slice of a block would be under four 16-walker tiles.
-With N > 1 and weak scaling the line also carries "strong_scaling": the metric's fixed 256-walker
+With N > 1, weak scaling and --full the line also carries "strong_scaling": the metric's fixed 256-walker
 ensemble timed in the same run, both ways of sharding.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit,
+ms_per_step, ...).  Everything else the benchmark measures - the roofline (with its census pass), the
+device sampler, host costs, the per-source kernel, the compressed catalogue, the CPU baselines and the
+strong-scaling legs - runs only with --full (--no-extras / --no-cpu-baseline trim that further).
+--dump-outputs DIR writes the lnprob arrays of the last timed step as DIR/<name>.npy (float64).
 """
 import argparse
 import json
@@ -574,7 +580,12 @@ def main():
     ap.add_argument("--walker-tile", type=int, default=0)
     ap.add_argument("--no-taper", action="store_true", help="(default) single pass over the catalogue")
     ap.add_argument("--taper", action="store_true", help="quarter-size tail tiles, see the taper option")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed loop: no device-sampler / compressed-catalogue / strong-scaling legs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline, device sampler, host costs, per-source kernel, compressed catalogue, "
+                         "CPU baselines, strong-scaling legs (off: the timed loop and the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the lnprob arrays of the last timed step to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no device-sampler / compressed-catalogue / strong-scaling legs (profiling runs)")
     ap.add_argument("--no-specialise", action="store_true", help="A/B: without the chunk-level term specialisation")
     ap.add_argument("--no-fuse", action="store_true", help="A/B: three launches per evaluation (lf_prepare, lf_free, lf_finalize) instead of one")
     ap.add_argument("--no-cells", action="store_true", help="A/B: every walker summed over the sources, not over the catalogue's cells")
@@ -606,6 +617,8 @@ def main():
         args.walkers = wtot if args.scaling == "strong" else wtot      # (weak presets are 1-GPU shapes: walkers per GPU = in all)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)                  # never returns; this process has not touched torch or the GPU
     # stdout carries exactly ONE line (the JSON): libraries that print there (RCCL's version banner at
@@ -675,6 +688,12 @@ def main():
                         profile_span=args.profile_span)
     dt = reduce_max(dt)
     assert torch.isfinite(out[0]).all() and torch.isfinite(out[1]).all(), "non-finite lnprob in the timed workload"
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path receives from its last step: lnprob of the step's two half-ensemble blocks
+        # (every rank holds the whole blocks after the gather / reduce), from seeded inputs fixed by the arguments
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in (("lnprob_half0", out[0]), ("lnprob_half1", out[1])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().cpu().numpy().astype(np.float64))
     step, theta_all, nblk = leg.step, leg.theta_all, leg.nblk
 
     evals = Wtot * args.steps
@@ -704,8 +723,9 @@ def main():
                                          "%d per GPU" % W if scaling == "weak" else "fixed ensemble", half),
                           "n_sources": args.nsrc, "walkers_per_gpu": Wtot // world if shard == "walkers" else Wtot,
                           "walkers_total": Wtot, "variant": args.variant, "shard": shard if world > 1 else "none",
-                          "parallelism": par},
-               "roofline": roofline_of(args, leg, model, kt, dt)}
+                          "parallelism": par}}
+        if args.full:
+            res["roofline"] = roofline_of(args, leg, model, kt, dt)
     ab = [n for n in AB_FLAGS if getattr(args, n)]
     if ab and rank == 0:
         res["config"]["ab_options"] = ab                    # an A/B run, not the default path
@@ -716,7 +736,7 @@ def main():
         # lf_create (flux sort, cells, proven grid bins, uploads) - once per run, not in `value`
         res["setup_s"] = {"host_setup": host_setup_s, "lf_create": getattr(leg, "create_s", None),
                           "note": "once per catalogue, before the timed region"}
-    if world > 1 and scaling == "weak" and not args.no_extras:
+    if args.full and world > 1 and scaling == "weak" and not args.no_extras:
         # the metric's literal shape - a FIXED ensemble of --walkers walkers - on the same GPUs, in the same run:
         # sharded by walker (all-gather) and by source (all-reduce)
         strong = {}
@@ -738,7 +758,7 @@ def main():
                 strong[sh] = {"error": repr(e)}
         if rank == 0:
             res["strong_scaling"] = strong
-    if rank == 0:
+    if rank == 0 and args.full:
         if world == 1 and not args.no_extras:
             # the same workload as real MCMC: the device-resident sampler (theta, accept/reject and the
             # chain stay in HBM; six launches per ensemble step, no host in the loop)
@@ -838,6 +858,7 @@ def main():
                 res["cpu_baseline_allcores"]["host_cpu_count"] = os.cpu_count()
             except Exception as e:            # the extra figure must never cost the bench line
                 res["cpu_baseline_allcores"] = {"error": str(e)}
+    if rank == 0:
         os.write(json_fd, (json.dumps(res) + "\n").encode())
     leg.close()
     if multi:

@@ -36,6 +36,12 @@ OUT = os.path.join(REPO, "tests", "golden")
 REF = "/root/reference"
 
 
+# the driver cases of tests/test_driver_contract.py, recorded for tests/test_driver_replay.py
+DRIVER_CASES = [("driver_plain", []), ("driver_fc", ["-fc"]), ("driver_fsa", ["-fsa"]), ("driver_default", ["--default-config"]),
+                ("driver_default_fc", ["--default-config", "-fc"]), ("driver_z", ["--z"]), ("driver_z_fsa", ["--z", "-fsa"]),
+                ("driver_z_default", ["--z", "--default-config"])]
+
+
 # --------------------------------------------------------------------------- shims
 def install_shims():
     for name, fn in (("asscalar", lambda a: a.item()), ("alen", len), ("rank", np.ndim)):
@@ -393,6 +399,19 @@ def main():
             save(name, dict(variant=variant, n=n, seed=seed, zslices=zsl, fix_sch_al=fsa, min_comp_frac=mcf,
                             faint=int(faint), theta=th, lnprob=lnp))
             print(name, lnp[:3], "-inf rows", int(np.isinf(lnp).sum()))
+    # ---- the reference's CLI drivers over the drop-in classes: the transcript of what the driver did with the class
+    #      (tests/driver_contract_runner.py --record), replayed without the reference by tests/test_driver_replay.py
+    if only in (None, "driver"):
+        import subprocess
+        import tempfile
+        for name, flags in DRIVER_CASES:
+            path = os.path.join(OUT, name + ".npz")
+            with tempfile.TemporaryDirectory() as work:
+                subprocess.run([sys.executable, os.path.join(REPO, "tests", "driver_contract_runner.py"), work, REF, "1000", "32",
+                                "50"] + flags + ["--record", path], check=True, stdout=subprocess.DEVNULL,
+                               env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
+            manifest[name] = {"bytes": os.path.getsize(path), "keys": sorted(np.load(path).files)}
+            print("wrote", path, os.path.getsize(path))
     if only:
         with open(os.path.join(OUT, "MANIFEST.json"), "w") as f:
             json.dump(manifest, f, indent=1, sort_keys=True)

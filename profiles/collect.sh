@@ -9,7 +9,7 @@ tag=${1:-run}
 out=gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-args="--steps 20 --warmup 3 --no-cpu-baseline --no-extras ${BENCH_ARGS:-}"
+args="--steps 20 --warmup 3 --no-cpu-baseline --no-extras --full ${BENCH_ARGS:-}"
 passes=${PASSES:-"trace fetch write sq grbm lds"}
 for p in $passes; do
   case $p in

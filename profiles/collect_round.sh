@@ -8,7 +8,7 @@ out=gpurun_out/round_$r
 mkdir -p $out
 export TMPDIR=/tmp
 # the driver's own command first (full line: cpu baseline, extras)
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_default.json 2> $out/bench_default.err || echo "default bench failed"
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_default.json 2> $out/bench_default.err || echo "default bench failed"
 if [ -z "${BENCH_ONLY:-}" ]; then
 # rocprofv3 passes (kernel trace + stats; FETCH_SIZE, WRITE_SIZE, SQ counters each in a run of its own)
 PASSES="trace fetch write sq" bash profiles/collect.sh free_1000000_w256 > $out/collect_w256.log 2>&1
@@ -19,7 +19,7 @@ BENCH_ARGS="--no-cells" PASSES="trace fetch write sq" bash profiles/collect.sh f
 BENCH_ARGS="--no-grid-shortcut" PASSES="trace" bash profiles/collect.sh free_1000000_w256_nogridshortcut > $out/collect_nogq.log 2>&1
 fi
 # the same runs without the profiler (the numbers quoted next to the profiles)
-b="--steps 20 --warmup 5 --no-cpu-baseline --no-extras"
+b="--steps 20 --warmup 5 --no-cpu-baseline --no-extras --full"
 for c in 1 2 3 5; do python3 bench.py $b --config $c > $out/bench_config$c.json 2>/dev/null; done
 python3 bench.py $b --walkers 1024 > $out/bench_w1024.json 2>/dev/null
 python3 bench.py $b --walkers 2048 > $out/bench_w2048.json 2>/dev/null

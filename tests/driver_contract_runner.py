@@ -7,7 +7,11 @@ sys.path order: dropin/ (lumfuncmcmc, lumfuncmcmc_z, VmaxLumFunc resolve to this
 only then the reference checkout (run_lumfuncmcmc.py, configLF.py).  The GPU is not needed: `_Base._evaluate` is
 pointed at the oracle (tests may use it) and the host sampler runs the chain; everything else - the constructor call
 with the driver's keywords, fit_model, set_median_fit, the attributes the driver writes out, add_fitinfo_to_table - is
-the product code.  Nothing of the reference is copied: it is imported where it lies."""
+the product code.  Nothing of the reference is copied: it is imported where it lies.
+
+--record FILE.npz: also keep, as data, what the driver did with the class - the constructor's arguments, and every
+attribute the driver's own code read or set and every method it called, in order, with the shapes it got back - for
+tests/test_driver_replay.py, which replays that transcript over the classes without the reference or astropy."""
 import json
 import os
 import sys
@@ -16,6 +20,11 @@ import numpy as np
 
 work, ref, nsrc, nwalk, nsteps = sys.argv[1], sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5])
 flags = sys.argv[6:]
+RECORD = None
+if "--record" in flags:
+    i = flags.index("--record")
+    RECORD = os.path.abspath(flags[i + 1])
+    del flags[i:i + 2]
 ZDRIVER = "--z" in flags
 DEFAULT_CONFIG = "--default-config" in flags
 flags = [f for f in flags if f not in ("--z", "--default-config")]
@@ -77,12 +86,84 @@ def evaluate(self, theta):                             # the oracle in place of 
 
 
 model._Base._evaluate = evaluate
-np.random.seed(12345)
+SEED = 12345
+
+if RECORD:
+    REFDIR = os.path.abspath(ref) + os.sep
+    arrays, events = {}, []
+
+    def from_driver():                                 # the caller of the hook is the reference driver's own code
+        return sys._getframe(2).f_code.co_filename.startswith(REFDIR)
+
+    def enc(v, key):                                   # arguments as data: arrays into the npz, the rest as JSON
+        if isinstance(v, np.ndarray):
+            arrays[key] = np.array(v)                  # (astropy columns as plain arrays)
+            return {"npz": key}
+        if isinstance(v, (list, tuple)):
+            return {"list": [enc(x, "%s_%d" % (key, i)) for i, x in enumerate(v)]}
+        if isinstance(v, np.generic):
+            return {"v": v.item()}
+        if v is None or isinstance(v, (bool, int, float, str)):
+            return {"v": v}
+        raise TypeError("cannot record %s of type %s" % (key, type(v).__name__))
+
+    def desc(v):
+        if isinstance(v, np.ndarray):
+            return {"type": "ndarray", "shape": list(v.shape), "dtype": v.dtype.kind}
+        if isinstance(v, (list, tuple)):
+            return {"type": "list", "len": len(v)}
+        if v is None or isinstance(v, (np.generic, bool, int, float, str)):
+            return {"type": "scalar"}
+        return {"type": type(v).__name__}
+
+    def last_row(obj):
+        return [x.decode() if isinstance(x, bytes) else x.item() if isinstance(x, np.generic) else x for x in obj.table[-1]]
+
+    class Recorded(cls):
+        def __init__(self, *a, **kw):
+            if from_driver():
+                events.append({"op": "init", "args": [enc(x, "arg%d" % i) for i, x in enumerate(a)],
+                               "kwargs": {k: enc(x, "kw_" + k) for k, x in kw.items()}})
+            super().__init__(*a, **kw)
+
+        def __getattribute__(self, name):
+            v = object.__getattribute__(self, name)
+            if not from_driver():
+                return v
+            if callable(v) and getattr(v, "__self__", None) is self:
+                def call(*a, **kw):
+                    n = len(events)
+                    ev = {"op": "call", "name": name, "args": [enc(x, "call%d_%d" % (n, i)) for i, x in enumerate(a)],
+                          "kwargs": {k: enc(x, "call%d_%s" % (n, k)) for k, x in kw.items()}}
+                    if name == "add_fitinfo_to_table":
+                        ev["row_before"] = last_row(self)
+                    r = v(*a, **kw)
+                    if name == "add_fitinfo_to_table":
+                        ev["row_after"] = last_row(self)
+                    ev["result"] = desc(r)
+                    events.append(ev)
+                    return r
+                return call
+            events.append({"op": "get", "name": name, "desc": desc(v)})
+            return v
+
+        def __setattr__(self, name, v):
+            if from_driver():
+                events.append({"op": "set", "name": name, "desc": desc(v)})
+            object.__setattr__(self, name, v)
+
+    setattr(drv, cls.__name__, Recorded)
+
+np.random.seed(SEED)
 drv.main(["-f", "cat.dat", "-o", "contract.dat", "-nw", str(nwalk), "-ns", str(nsteps), "-nbins", "10", "-nboot", "20"] + flags)
 
 out = sorted(os.listdir(outdir))
 from astropy.table import Table                        # noqa: E402
 post = [f for f in out if f.startswith("fitposterior")][0]
 t = Table.read(os.path.join(outdir, post), format="ascii.fixed_width_two_line")
+if RECORD:
+    tr = {"class": cls.__name__, "seed": SEED, "nsources": nsrc, "nwalkers": nwalk, "nsteps": nsteps, "driver_flags": flags,
+          "z_driver": ZDRIVER, "default_config": DEFAULT_CONFIG, "outdir": outdir, "files": out, "events": events}
+    np.savez_compressed(RECORD, transcript=np.array(json.dumps(tr)), **arrays)
 print(json.dumps({"files": out, "posterior_columns": len(t.colnames), "posterior_rows": len(t),
                   "finite_lnprob": int(np.isfinite(np.asarray(t[t.colnames[-1]], dtype=float)).sum())}))

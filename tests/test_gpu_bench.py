@@ -1,11 +1,12 @@
 """bench.py's contract, run as the driver runs it: one JSON line on stdout with the agreed keys; `--gpus 2` started as a
 plain script launches its own two ranks (here both on the one GPU of the box, gloo between them) and reports the whole
-job; strong scaling over walkers and over sources."""
+job; strong scaling over walkers and over sources (those figures with --full); the plain line and --dump-outputs."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,7 +29,7 @@ def run_bench(*flags, timeout=600):
 
 
 def test_one_gpu_line_has_the_contract_keys():
-    d = run_bench("--steps", "3", "--warmup", "1", "--nsrc", "40000", "--walkers", "64", "--cpu-budget", "1", "--no-extras")
+    d = run_bench("--steps", "3", "--warmup", "1", "--nsrc", "40000", "--walkers", "64", "--cpu-budget", "1", "--no-extras", "--full")
     for k in KEYS:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True
@@ -42,12 +43,32 @@ def test_one_gpu_line_has_the_contract_keys():
     assert cb["max_rel_diff_gpu_vs_port"] < 1e-12                                              # the baseline doubles as a parity check
 
 
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full: the headline keys only, --steps timed steps; --dump-outputs writes the last step's lnprob, the
+    same arrays from run to run."""
+    flags = ("--steps", "4", "--warmup", "1", "--nsrc", "40000", "--walkers", "64")
+    d = run_bench(*flags, "--dump-outputs", str(tmp_path / "a"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 64) < 1e-6 * 64
+    for k in ("roofline", "cpu_baseline", "mcmc_device_sampler", "compressed_catalogue"):
+        assert k not in d, k                                                                   # --full only
+    run_bench(*flags, "--dump-outputs", str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["lnprob_half0.npy", "lnprob_half1.npy"] and sorted(os.listdir(tmp_path / "b")) == names
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float64 and a.shape == (32,) and np.isfinite(a).all()
+        assert np.array_equal(a, b), n
+
+
 @pytest.mark.parametrize("extra,scaling,shard", [([], "weak", "walkers"),
                                                  (["--scaling", "strong", "--shard", "walkers"], "strong", "walkers"),
                                                  (["--scaling", "strong", "--shard", "sources"], "strong", "sources")])
 def test_two_ranks_self_launched(extra, scaling, shard):
     d = run_bench("--gpus", "2", "--share-gpu", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--nsrc", "40000",
-                  "--walkers", "64", "--no-cpu-baseline", *extra)
+                  "--walkers", "64", "--no-cpu-baseline", "--full", *extra)
     assert d["n_gpus"] == 2 and d["scaling"] == scaling
     assert d["config"]["shard"] == shard and ("all-reduce" if shard == "sources" else "all-gather") in d["config"]["parallelism"], d["config"]
     total = 128 if scaling == "weak" else 64                                                    # whole-job walkers per step
