@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LF_ABI_VERSION 2
+#define LF_ABI_VERSION 3
 #define LF_MAX_FIELDS 8
 
 /* model variants = the three log-posterior callables of the reference */
@@ -85,14 +85,14 @@ typedef struct lf_desc {
 typedef struct lf_ctx lf_ctx;
 
 /* ABI version of the loaded library (== LF_ABI_VERSION of the header it was built from). */
+int lf_abi_version(void);
+
 /* Host-only helper behind lf_free's deal of its chunks to its 32 virtual workgroups, exported so that
  * the CPU tests can check it: table[0 .. 32] = where rank r's cell chunks start in the list, table[33 .. 65] the same for its
  * flux bins, then the list (cell chunks rank by rank, then bins rank by rank).  table = NULL: returns the number of ints
  * (66 + n_cell_chunks + n_bins); else fills `table` (cap ints) and returns that number.  grid_part / grid_parts as in the
  * "grid_share" option (0, 0: the whole grid). */
 int lf_deal_table(int n_cell_chunks, int n_bins, int grid_part, int grid_parts, int32_t *table, int64_t cap);
-
-int lf_abi_version(void);
 
 /* Replaces the read side of LumFuncMCMC.__init__ / LumFuncMCMCz.__init__ (lumfuncmcmc.py:162-177):
  * copies the catalogue and grids to HBM, derives the parameter-independent per-source and
@@ -301,6 +301,24 @@ int64_t lf_grid_bins(const double *params, int S, const double *L, const double 
 int lf_veff(int device, int64_t n, const double *flux, const double *flim, const double *vol, double vol_all, double pref0,
             double alpha, double fcmin, const int32_t *bin_of, int32_t nbin, int32_t nboot, const int64_t *boot_idx, uint64_t seed,
             double *phi, double *sums);
+
+/* Percentiles over R posterior draws of the model LF at P points (post-fit; no context needed, synchronous, like lf_veff).
+ * Replaces the draw loop + np.median of LumFuncMCMC.set_median_fit (lumfuncmcmc.py:527-567) and gives the bands around it.
+ * draws: R x 3 (LF_FREE / LF_FIXCOMP: logLstar, logphistar, alpha) or R x 7 (LF_ZEVOL: aL, bL, cL, aphi, bphi, cphi, alpha -
+ * the quadratic coefficients of log L*(z) and log phi*(z), getQuadCoef of lumfuncmcmc_z.py:40-42) host doubles;
+ * logL[P]; z[P] (LF_ZEVOL only, else ignored: NULL);
+ * q[nq] in [0, 100] (LF_Q_LINEAR; nq <= 32) or ignored with nq == 1 (LF_Q_MEDIAN); out[nq * P] row-major;
+ * values[R * P] or NULL (row r = draw r's LF at every point).  1 <= R <= 4096, P >= 1.  LF_ERR_ARG on any violation
+ * (checked before touching the device).
+ * out[i][p] is what np.percentile(v, q[i], axis=0) (LF_Q_LINEAR) or np.median(v, axis=0) (LF_Q_MEDIAN) returns for the
+ * R x P matrix v of the values, bit for bit (a NaN among a point's values gives NaN). */
+enum { LF_Q_LINEAR = 0, LF_Q_MEDIAN = 1 };
+int lf_lumfunc_quantiles(int device, int variant, int32_t R, const double *draws, int64_t P, const double *logL,
+                         const double *z, int32_t nq, const double *q, int32_t method, double *out, double *values);
+
+/* Device time in ms of the kernel of the most recent successful lf_lumfunc_quantiles call in this process (hipEvents
+ * around the launch; measurement only).  LF_ERR_ARG when there is none. */
+int lf_lumfunc_quantiles_ms(double *ms);
 
 /* Last error message of this context (or of lf_create when ctx == NULL).  Never NULL. */
 const char *lf_last_error(const lf_ctx *ctx);

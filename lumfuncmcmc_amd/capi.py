@@ -12,11 +12,13 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "liblfmcmc.so")
 
-LF_ABI_VERSION = 2
+LF_ABI_VERSION = 3
 LF_MAX_FIELDS = 8
 LF_FREE, LF_FIXCOMP, LF_ZEVOL = 0, 1, 2
 VARIANTS = {"free": LF_FREE, "fixcomp": LF_FIXCOMP, "zevol": LF_ZEVOL}
 LF_OK = 0
+LF_ERR_ARG = -1
+LF_Q_LINEAR, LF_Q_MEDIAN = 0, 1
 LIM_ORDER = ("Lstar", "phistar", "sch_al", "Flim", "alpha")
 
 MPC_CM = 3.086e24                                  # lumfuncmcmc.py:70
@@ -43,7 +45,8 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_lnprob_batch_device", "lf_lnprob_batch_device_n", "lf_lnprob_pieces", "lf_set_profiling", "lf_kernel_times",
            "lf_set_option", "lf_last_error", "lf_sampler_create", "lf_sampler_destroy", "lf_sampler_start",
            "lf_sampler_run", "lf_sampler_read", "lf_sampler_steps", "lf_sampler_half_eval",
-           "lf_sampler_half_accept", "lf_compress_keys", "lf_compress_grid", "lf_grid_bins", "lf_deal_table", "lf_form_counts", "lf_last_launch", "lf_veff")
+           "lf_sampler_half_accept", "lf_compress_keys", "lf_compress_grid", "lf_grid_bins", "lf_deal_table", "lf_form_counts", "lf_last_launch", "lf_veff",
+           "lf_lumfunc_quantiles", "lf_lumfunc_quantiles_ms")
 
 _lib = None
 
@@ -101,6 +104,11 @@ def load():
     lib.lf_veff.argtypes = [ctypes.c_int, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p, ctypes.c_double, ctypes.c_double,
                             ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
                             _c_int64_p, ctypes.c_uint64, _c_double_p, _c_double_p]
+    lib.lf_lumfunc_quantiles.restype = ctypes.c_int
+    lib.lf_lumfunc_quantiles.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int32, _c_double_p, ctypes.c_int64, _c_double_p,
+                                         _c_double_p, ctypes.c_int32, _c_double_p, ctypes.c_int32, _c_double_p, _c_double_p]
+    lib.lf_lumfunc_quantiles_ms.restype = ctypes.c_int
+    lib.lf_lumfunc_quantiles_ms.argtypes = [_c_double_p]
     lib.lf_last_error.restype = ctypes.c_char_p
     lib.lf_last_error.argtypes = [ctypes.c_void_p]
     lib.lf_sampler_create.restype = ctypes.c_void_p
@@ -241,6 +249,38 @@ def veff_device(flux, flim, vol, pref0, alpha, fcmin, bin_of=None, nbin=0, nboot
     if rc != LF_OK:
         raise LFError("lf_veff failed (%d)" % rc)
     return phi, sums
+
+
+def lumfunc_quantiles(variant, draws, logL, z=None, q=(16.0, 50.0, 84.0), method=LF_Q_LINEAR, values=False, device=0):
+    """lf_lumfunc_quantiles (include/lfmcmc.h): percentiles over the R draw records `draws` (R x 3, or R x 7 for LF_ZEVOL)
+    of the model LF at the P points logL (and z, LF_ZEVOL).  Returns out (nq, P), or (out, values (R, P)) with
+    values=True.  method LF_Q_MEDIAN: one row, q ignored.  Raises LFError on a non-zero return."""
+    lib = load()
+    variant = VARIANTS.get(variant, variant)
+    np_rec = 7 if variant == LF_ZEVOL else 3
+    draws = _f64(draws).reshape(-1, np_rec)
+    logL = _f64(logL).ravel()
+    zz = None if z is None else _f64(z).ravel()
+    if zz is not None and zz.shape != logL.shape:
+        raise ValueError("z must have the shape of logL")
+    R, P = draws.shape[0], logL.size
+    qa = _f64(np.atleast_1d(q)).ravel() if method == LF_Q_LINEAR else np.zeros(1)
+    nq = qa.size
+    out = np.empty((nq, P))
+    val = np.empty((R, P)) if values else None
+    rc = lib.lf_lumfunc_quantiles(int(device), int(variant), R, _ptr(draws), P, _ptr(logL), _ptr(zz), nq, _ptr(qa), int(method),
+                                  _ptr(out), _ptr(val))
+    if rc != LF_OK:
+        raise LFError("lf_lumfunc_quantiles failed (%d)" % rc)
+    return (out, val) if values else out
+
+
+def lumfunc_quantiles_ms():
+    """Device time (ms) of the last lf_lumfunc_quantiles kernel in this process (hipEvents around the launch)."""
+    ms = np.zeros(1)
+    if load().lf_lumfunc_quantiles_ms(_ptr(ms)) != LF_OK:
+        raise LFError("no lf_lumfunc_quantiles call has completed")
+    return float(ms[0])
 
 
 def _ptr(a):

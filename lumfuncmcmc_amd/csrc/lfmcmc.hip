@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "lf_bands.h"
 #include "lf_compress.h"
 #include "lf_gridbound.h"
 #include "lf_kernels.h"
@@ -1894,6 +1895,109 @@ int lf_veff(int device, int64_t n, const double* flux, const double* flim, const
     }
     hipFree(d_flux); hipFree(d_flim); hipFree(d_vol); hipFree(d_phi); hipFree(d_sums); hipFree(d_bin); hipFree(d_idx);
     return rc;
+}
+
+static double g_bands_ms = -1.0;      // device time of the last lf_lumfunc_quantiles kernel (lf_lumfunc_quantiles_ms)
+
+int lf_lumfunc_quantiles(int device, int variant, int32_t R, const double* draws, int64_t P, const double* logL, const double* z,
+                         int32_t nq, const double* q, int32_t method, double* out, double* values) {
+#pragma clang fp contract(off)
+    // every argument is checked before the device is touched
+    if (variant < LF_FREE || variant > LF_ZEVOL || R < 1 || R > lf::BANDS_SLOTS || P < 1 || P > ((int64_t)1 << 40) || !draws ||
+        !logL || !out || (variant == LF_ZEVOL && !z))
+        return LF_ERR_ARG;
+    if (method == LF_Q_MEDIAN) {
+        if (nq != 1) return LF_ERR_ARG;
+    } else if (method == LF_Q_LINEAR) {
+        if (nq < 1 || nq > lf::BANDS_MAXQ || !q) return LF_ERR_ARG;
+        for (int i = 0; i < nq; ++i)
+            if (!(q[i] >= 0.0 && q[i] <= 100.0)) return LF_ERR_ARG;          // (NaN fails both)
+    } else {
+        return LF_ERR_ARG;
+    }
+    const int np_in = variant == LF_ZEVOL ? 7 : 3;
+    // the per-draw factors the kernel takes as they are (lf_bands.h): alpha + 1, and for the single Schechter
+    // LN10 * 10^logphistar - numpy scalar operations in the reference, made here with the host's pow (a volatile base keeps
+    // the compiler from turning pow(10, x) into exp10, which the C library does not round the same way)
+    std::vector<double> rec((size_t)R * np_in);
+    volatile double ten = 10.0;
+    for (int r = 0; r < R; ++r) {
+        const double* d = draws + (size_t)r * np_in;
+        double* o = rec.data() + (size_t)r * np_in;
+        if (np_in == 3) {
+            o[0] = d[0];
+            o[1] = 2.302585092994045684 * std::pow((double)ten, d[1]);
+            o[2] = d[2] + 1.0;
+        } else {
+            for (int c = 0; c < 6; ++c) o[c] = d[c];
+            o[6] = d[6] + 1.0;
+        }
+    }
+    // numpy 2.x's np.percentile(v, q, axis=0) index arithmetic (percentile: qf = q / 100; _QuantileMethods["linear"]:
+    // vi = (R - 1) qf; _get_indexes: prev = floor(vi), next = prev + 1, vi >= R - 1 -> both -1 (the last), vi < 0 -> both 0;
+    // _get_gamma: gamma = vi - prev with the CLAMPED prev, so vi + 1 past the end)
+    std::vector<double> qtab(3 * (size_t)std::max(nq, 1), 0.0);
+    if (method == LF_Q_LINEAR)
+        for (int i = 0; i < nq; ++i) {
+            const double qf = q[i] / 100.0;
+            const double vi = (double)(R - 1) * qf;
+            double prev = std::floor(vi), next = prev + 1.0;
+            if (vi >= (double)(R - 1)) prev = next = -1.0;
+            if (vi < 0.0) prev = next = 0.0;
+            qtab[3 * i + 2] = vi - prev;
+            qtab[3 * i] = prev < 0.0 ? (double)(R - 1) : prev;
+            qtab[3 * i + 1] = next < 0.0 ? (double)(R - 1) : next;
+        }
+    int lg = 0;
+    while ((1 << lg) < R) ++lg;
+    if (hipSetDevice(device) != hipSuccess) return LF_ERR_NODEV;
+    double *d_rec = nullptr, *d_logL = nullptr, *d_z = nullptr, *d_q = nullptr, *d_out = nullptr, *d_val = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    const size_t pb = (size_t)P * sizeof(double);
+    int rc = LF_OK;
+    auto ok = [&](hipError_t e) {
+        if (e != hipSuccess && rc == LF_OK) rc = LF_ERR_HIP;
+        return e == hipSuccess;
+    };
+    g_bands_ms = -1.0;
+    if (ok(hipMalloc((void**)&d_rec, rec.size() * sizeof(double))) && ok(hipMalloc((void**)&d_logL, pb)) &&
+        (variant != LF_ZEVOL || ok(hipMalloc((void**)&d_z, pb))) && ok(hipMalloc((void**)&d_q, qtab.size() * sizeof(double))) &&
+        ok(hipMalloc((void**)&d_out, (size_t)nq * pb)) && (!values || ok(hipMalloc((void**)&d_val, (size_t)R * pb))) &&
+        ok(hipEventCreate(&ev[0])) && ok(hipEventCreate(&ev[1]))) {
+        ok(hipMemcpy(d_rec, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
+        ok(hipMemcpy(d_logL, logL, pb, hipMemcpyHostToDevice));
+        if (d_z) ok(hipMemcpy(d_z, z, pb, hipMemcpyHostToDevice));
+        ok(hipMemcpy(d_q, qtab.data(), qtab.size() * sizeof(double), hipMemcpyHostToDevice));
+        if (rc == LF_OK) {
+            int ncu = 0;
+            if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu < 1) ncu = 256;
+            const int64_t G = lf::BANDS_SLOTS >> lg;
+            const unsigned grid = (unsigned)std::min<int64_t>((P + G - 1) / G, (int64_t)ncu * 5);       // five 32-KiB workgroups per CU (LDS)
+            ok(hipEventRecord(ev[0], 0));
+            if (variant == LF_ZEVOL)
+                hipLaunchKernelGGL(lf::lf_bands<7>, dim3(grid), dim3(lf::BANDS_THREADS), 0, 0, d_rec, (int)R, lg, d_logL, d_z, (long long)P,
+                                   d_q, (int)nq, method == LF_Q_MEDIAN ? 1 : 0, d_out, d_val);
+            else
+                hipLaunchKernelGGL(lf::lf_bands<3>, dim3(grid), dim3(lf::BANDS_THREADS), 0, 0, d_rec, (int)R, lg, d_logL, d_z, (long long)P,
+                                   d_q, (int)nq, method == LF_Q_MEDIAN ? 1 : 0, d_out, d_val);
+            ok(hipGetLastError());
+            ok(hipEventRecord(ev[1], 0));
+            ok(hipMemcpy(out, d_out, (size_t)nq * pb, hipMemcpyDeviceToHost));
+            if (values) ok(hipMemcpy(values, d_val, (size_t)R * pb, hipMemcpyDeviceToHost));
+            float ms = 0.0f;
+            if (rc == LF_OK && ok(hipEventElapsedTime(&ms, ev[0], ev[1]))) g_bands_ms = ms;
+        }
+    }
+    for (hipEvent_t e : ev)
+        if (e) hipEventDestroy(e);
+    hipFree(d_rec); hipFree(d_logL); hipFree(d_z); hipFree(d_q); hipFree(d_out); hipFree(d_val);
+    return rc;
+}
+
+int lf_lumfunc_quantiles_ms(double* ms) {
+    if (!ms) return LF_ERR_ARG;
+    *ms = g_bands_ms;
+    return g_bands_ms < 0.0 ? LF_ERR_ARG : LF_OK;
 }
 
 int lf_last_launch(const lf_ctx* c, int32_t info[8]) {

@@ -14,6 +14,7 @@ import time
 import numpy as np
 
 from . import hostsetup as hs
+from . import lfbands
 from . import veff
 from .cosmology import cosmo as _cosmo
 from .capi import LFContext
@@ -291,6 +292,15 @@ class _Base(object):
         self.log.info(nsamples.shape)
         return nsamples
 
+    def _posterior_rows(self, ndraws, lnprobcut):
+        """ndraws random rows of the selected samples, drawn as set_median_fit draws them: _select_samples, then one
+        np.random.randint per draw (numpy's global stream is consumed identically)."""
+        nsamples = self._select_samples(lnprobcut, keep_lnprob=True)
+        return np.array([nsamples[np.random.randint(0, nsamples.shape[0]), :] for _ in np.arange(ndraws)])
+
+    def _band_device(self, device):
+        return self._ctx is not None if device is None else bool(device)
+
     def add_fitinfo_to_table(self, percentiles, start_value=1, lnprobcut=7.5):
         """Percentiles of each parameter into the last row of self.table (lumfuncmcmc.py:653-667)."""
         nsamples = self._select_samples(lnprobcut, keep_lnprob=False)
@@ -429,19 +439,39 @@ class LumFuncMCMC(_Base):
         self.nfreeparams = len(vals)
         return vals
 
-    def set_median_fit(self, rndsamples=200, lnprobcut=7.5):
-        """Median model LF over random posterior draws, then the 1/Veff estimate (lumfuncmcmc.py:527-567)."""
+    def set_median_fit(self, rndsamples=200, lnprobcut=7.5, device=False):
+        """Median model LF over random posterior draws, then the 1/Veff estimate (lumfuncmcmc.py:527-567).  device=True
+        takes the rndsamples TrueLumFunc evaluations and their median on the GPU (lf_lumfunc_quantiles, LF_Q_MEDIAN); the
+        draws, the median Flim / alpha and VeffLF are the same either way."""
         nsamples = self._select_samples(lnprobcut, keep_lnprob=True)
         Flims, alphas = np.zeros((rndsamples, self.nfields)), np.zeros(rndsamples)
-        lf = []
+        lf, recs = [], []
         for i in np.arange(rndsamples):
             ind = np.random.randint(0, nsamples.shape[0])
             self.set_parameters_from_list(nsamples[ind, :])
             Flims[i], alphas[i] = self.Flim, self.alpha
-            lf.append(TrueLumFunc(self.lum, self.sch_al, self.Lstar, self.phistar))
-        self.medianLF = np.median(np.array(lf), axis=0)
+            if device:
+                recs.append((self.Lstar, self.phistar, self.sch_al))
+            else:
+                lf.append(TrueLumFunc(self.lum, self.sch_al, self.Lstar, self.phistar))
+        if device:
+            self.medianLF = lfbands.quantiles_device(self._variant(), recs, self.lum, method="median", device=self.device)[0]
+        else:
+            self.medianLF = np.median(np.array(lf), axis=0)
         self.Flim, self.alpha = list(np.median(Flims, axis=0)), np.median(alphas)
         self._veff_or_skip()
+
+    def lf_percentiles(self, percentiles=(16, 50, 84), logL=None, ndraws=200, lnprobcut=7.5, method="linear", device=None):
+        """Percentiles over ndraws random posterior draws of the model LF at logL (default: every source, self.lum):
+        (nq, P), np.percentile's rule ("linear") or np.median's ("median": one row, percentiles ignored).  The draws are
+        taken as set_median_fit takes them.  device=True: the GPU (lf_lumfunc_quantiles), False: NumPy; None = the GPU
+        when this object already holds a device context."""
+        lfbands._method(method)
+        rows = self._posterior_rows(ndraws, lnprobcut)
+        recs = lfbands.pack_draws(self._variant(), rows, fix_sch_al=self.fix_sch_al, sch_al=self.sch_al)
+        logL = self.lum if logL is None else np.asarray(logL, dtype=np.float64)
+        return lfbands.quantiles(self._variant(), recs, logL, q=percentiles, method=method, device=self._band_device(device),
+                                 device_index=self.device)
 
     def VeffLF(self, device=None):
         """1/Veff weights per source and the binned LF with bootstrap errors (lumfuncmcmc.py:515-525).  device=True
@@ -584,6 +614,25 @@ class LumFuncMCMCz(_Base):
             self.medianLF[i] = schechter_z(self.Lout, self.zout[i], self.sch_al, self.L1, self.L2, self.L3,
                                            self.phi1, self.phi2, self.phi3, self.z1, self.z2, self.z3)
         self._veff_or_skip()
+
+    def lf_percentiles(self, percentiles=(16, 50, 84), logL=None, z=None, ndraws=200, lnprobcut=7.5, method="linear",
+                       device=None):
+        """Posterior band of the z-evolving LF: percentiles over ndraws random posterior draws (taken as
+        LumFuncMCMC.set_median_fit takes them) on the (z, logL) mesh - by default set_median_fit's (zout, Lout, 100 x 100).
+        Returns (nq, len(z), len(logL)).  method and device as LumFuncMCMC.lf_percentiles."""
+        lfbands._method(method)
+        if logL is None:
+            logL = np.linspace(min(self.lum) - 0.2, max(self.lum) + 0.2, 100)
+        if z is None:
+            z = np.linspace(self.zmin, self.zmax, 100)
+        logL, z = np.asarray(logL, dtype=np.float64).ravel(), np.asarray(z, dtype=np.float64).ravel()
+        rows = self._posterior_rows(ndraws, lnprobcut)
+        recs = lfbands.pack_draws("zevol", rows, fix_sch_al=self.fix_sch_al, sch_al=self.sch_al, pivots=(self.z1, self.z2, self.z3))
+        Lp = np.tile(logL, z.size)
+        zp = np.repeat(z, logL.size)
+        out = lfbands.quantiles("zevol", recs, Lp, z=zp, q=percentiles, method=method, device=self._band_device(device),
+                                device_index=self.device)
+        return out.reshape(out.shape[0], z.size, logL.size)
 
     def VeffLF(self, device=None):
         """lumfuncmcmc_z.py:470-478 (device: see LumFuncMCMC.VeffLF)."""
