@@ -19,19 +19,10 @@
 // Results: every (walker, chunk) partial sum goes to its own slot of partA / partB and lf_finalize adds them in a fixed
 // order, as in lf_main - the bits depend on the launch geometry (ST), not on which workgroup served which item.
 #pragma once
-#include "lf_kernels.h"
+#include "lf_tile.h"
 
 namespace lf {
 
-constexpr int PB = 512;      // threads per persistent workgroup: 8 waves
-constexpr int PTW = 8;       // walkers per tile
-constexpr int QSTRIDE = 9;   // counters per tile: [0] grid queue, [1..8] catalogue queues of XCD 0..7
-// The cells' and the grid's chunks of a tile are dealt to VF VIRTUAL workgroups, and partB / partC hold one partial sum per
-// (walker, virtual workgroup): the workgroups that actually serve the tile (at most VF: 32 at 128 rows, 16 at 256, 8 when a
-// group serves several tiles in turn) take the virtual ranks r, r + fgroup, ... and keep their sums apart.  So a walker's
-// partial sums - and with them the bits of its lnprob - do not depend on how many rows share its call, on its place in
-// the batch, or on how a batch is sharded over GPUs.
-constexpr int VF = 32;
 // The deal table: [0 .. VF] where rank vr's cell chunks start in the list, [VF + 1 .. 2 VF + 1] the same for its bins, then the
 // list (cell chunks rank by rank, then bins rank by rank).  Who gets what is decided by COST: a flux bin costs a wave about
 // 2.7 cell chunks, and the workgroups of ranks >= VF / 2 are the younger ones of their CUs, behind their elders when the sums
@@ -41,19 +32,10 @@ constexpr int VF = 32;
 // rank with two cell chunks of its own.  A context's table depends on its numbers of bins and cell chunks only: a row's
 // partial sums (one per virtual rank) are the same whatever the batch.
 constexpr int DEAL_BINS = VF + 1, DEAL_LIST = 2 * (VF + 1), DEAL_MAX = 512;
-// The one-launch form's hand-over by POLLING (tiles whose walkers are all on the cells: the normal case).  The slots of partB /
-// partC hold PART_EMPTY between launches (the host fills them, every finisher leaves them so); a workgroup writes its partial
-// sums through and is done; the tile's FINISHER - the workgroup of the last physical rank, the lightest of the deal - reads the
-// slots past its caches until none is empty, adds them up and empties them again.  Against the counter (every workgroup:
-// wait for the stores' acknowledgements, count, wait for the count; the last one: load, add) the launch's critical path
-// loses two of its three trips to memory.  A partial sum is never PART_EMPTY (a NaN is made canonical before it is stored);
-// a finisher that has polled PART_POLLS times without success writes NaN (emcee raises on NaN) and sets the error word.
-constexpr unsigned long long PART_EMPTY = 0x7ff8dead7ff8deadull;
-constexpr int PART_POLLS = 1 << 19;
 
 // 512-thread block reduction: red[nw][512] -> out[(w0 + w) * stride + chunk], nw <= 8: wave w adds walker w's row
 // (eight columns per lane, stride 64) and runs one 64-lane sum on the DPP network.  Fixed order.
-// THROUGH: the partial sum is written through to memory (see pstore in lf_free).
+// THROUGH: the partial sum is written through to memory (lf_tile.h: pstore).
 template <bool THROUGH = false>
 __device__ __forceinline__ void reduce_store512(const double* __restrict__ red, int wlo, int whi, double* __restrict__ out,
                                                 size_t stride, int w0, int chunk, int tid) {
@@ -125,13 +107,6 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
                                              unsigned long long t_pre = 0) {
     const double* wrec = FUSED ? fa.wrec_w : wrec_arg;
     const int* wmode = FUSED ? fa.wmode_w : wmode_arg;
-    // A partial sum: in the fused form it is read by a workgroup on another XCD while the launch is still running, so it
-    // is written THROUGH this XCD's L2 (a relaxed store of agent scope: scope bits on the one store - no cache-wide
-    // write-back or invalidate, which is what a fence of that scope costs: measured 154 us per evaluation instead of 30)
-    auto pstore = [](double* p, double v) {
-        if (FUSED) __hip_atomic_store(p, v == v ? v : __builtin_nan(""), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (never PART_EMPTY)
-        else *p = v;
-    };
     __shared__ MathTables tab;
     __shared__ TermTables tt;
     __shared__ __attribute__((aligned(16))) double red[PTW * PB];         // per-walker lane sums of the item in hand
@@ -200,12 +175,8 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
         // Cell chunks and grid chunks all cost about the same (and with every walker on cells they are all there is): they
         // are dealt STATICALLY, chunk i to the workgroup of rank i mod fgroup among those serving the tile - no claims.
         // Only the source chunks - unequal, and only needed by walkers that cannot use the cells - are claimed from queues.
-        int fgroup = 8, frank = (int)blockIdx.x & 7;
-        if (fa.ntiles <= fa.tile_stride) {
-            const int k = (int)blockIdx.x >> 3;   // (here tile = k mod ntiles, and the groups k, k + ntiles, ... share it)
-            fgroup = 8 * ((fa.tile_stride - tile + fa.ntiles - 1) / fa.ntiles);
-            frank += 8 * ((k - tile) / fa.ntiles);
-        }
+        int fgroup, frank;
+        tile_ranks(tile, fa.ntiles, fa.tile_stride, fgroup, frank);
         bool no_src = false;                       // (thread 0's view) every walker of the tile is summed over the cells
         auto grab = [&]() -> int {
             if (no_src) return -1;
@@ -281,15 +252,7 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
                 if (t7 == 0) s_ttab = __builtin_amdgcn_s_memtime();
 #endif
             }
-            if (STEP && u >= PB - 64 && u < PB - 64 + nw) {
-                // (the last wave, idle once its share of the tables is on its way: the accept step's logarithms, from the same
-                // Philox draws as the proposal's stretch factor and the accept step's uniform - bit for bit what
-                // accept_walker would make in the epilogue)
-                const int wl = u - (PB - 64);
-                unsigned int rr[4];
-                sampler_draw(sp.step, sp.half, w0 + wl, 0, sp.seed, rr);
-                accept_terms(ap, w0 + wl, stretch_z(sp.a, u53(rr[0], rr[1])), spre[2 * wl], spre[2 * wl + 1]);
-            }
+            accept_terms_ahead<STEP>(sp, ap, w0, nw, u, spre);
             tables_loaded = true;
             __syncthreads();
         }
@@ -418,7 +381,7 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
                 acc = wave_sum_dpp(acc);          // lane 63: the wave's total
                 const int ln = fresh_tid() & 63;
                 double* __restrict__ row = fa.partC + (size_t)(w0 + v) * fa.nslot;
-                if (ln == 63) pstore(row + vr, acc);
+                if (ln == 63) pstore<FUSED>(row + vr, acc);
             }
             }
         }
@@ -507,7 +470,7 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
                 bsum = wave_sum_dpp(bsum);        // lane 63: the wave's total
                 const int ln = fresh_tid() & 63;
                 double* __restrict__ row = fa.partB + (size_t)(w0 + v) * fa.nslot;
-                if (ln == 63) pstore(row + vr, bsum);
+                if (ln == 63) pstore<FUSED>(row + vr, bsum);
             }
             }
         } else
@@ -562,7 +525,7 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
                 bsum = wave_sum_dpp(bsum);        // lane 63: the wave's total
                 const int ln = fresh_tid() & 63;
                 double* __restrict__ row = fa.partB + (size_t)(w0 + v) * fa.nslot;
-                if (ln == 63) pstore(row + vr, bsum);
+                if (ln == 63) pstore<FUSED>(row + vr, bsum);
             }
             }
         }
@@ -740,63 +703,31 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
 #endif
         }
         if (FUSED && fa.poll && uni(snosrc)) {
-            // Hand-over by polling (PART_EMPTY above): this workgroup's partial sums are on their way, written through; only
+            // Hand-over by polling (lf_tile.h: PART_EMPTY): this workgroup's partial sums are on their way, written through; only
             // the tile's finisher has more to do.
             if (frank == fgroup - 1) {
                 const int t = fresh_tid(), v = t >> 6, ln = t & 63;
                 const int nB = fa.nchB > 0 ? fa.nslot : 0, nC = fa.nchC > 0 ? fa.nslot : 0;
                 if (v < nw) {
-                    double* __restrict__ pb = fa.partB + (size_t)(w0 + v) * fa.nslot;
-                    double* __restrict__ pc = fa.partC + (size_t)(w0 + v) * fa.nslot;
                     double pre[2] = {0.0, 0.0};
-                    int tries = 0;
-                    bool have;
-                    do {
-                        if (ln < nC) pre[0] = __hip_atomic_load(pc + ln, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (ln < nB) pre[1] = __hip_atomic_load(pb + ln, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        have = !((ln < nC && (unsigned long long)__double_as_longlong(pre[0]) == PART_EMPTY) ||
-                                 (ln < nB && (unsigned long long)__double_as_longlong(pre[1]) == PART_EMPTY));
-                    } while (!__all(have) && ++tries < PART_POLLS);
-                    if (tries >= PART_POLLS) {        // (cannot happen while the device runs the launch's other workgroups)
-                        pre[0] = pre[1] = __builtin_nan("");
-                        if (ln == 0) atomicExch(fa.err, 1);
-                    }
-                    // the slots empty again for the next launch (visible to it: a kernel boundary lies between)
-                    if (ln < nC) __hip_atomic_store(pc + ln, __longlong_as_double((long long)PART_EMPTY), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (ln < nB) __hip_atomic_store(pb + ln, __longlong_as_double((long long)PART_EMPTY), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    poll_finish(fa.partB, fa.partC, w0 + v, fa.nslot, nB, nC, ln, fa.err, pre);
                     finalize_wave<true>(fa.partA, 0, fa.nchA, fa.partB, nB, nB, nC > 0 ? fa.partC : nullptr, nC, (int)STAT_CELLS,
                                         sstat - w0, sbase - w0, w0 + v, ln, ap, fa.out, nullptr, nullptr, 0,
                                         STEP ? sprop + v * 16 : nullptr, STEP ? szz + v : nullptr, STEP ? spre + 2 * v : nullptr, pre);
                 }
             }
         } else if (FUSED) {
-            // This workgroup's partial sums are out - written through, and complete once its waves have waited for their
-            // stores' acknowledgements (the explicit s_waitcnt: the compiler does not emit one for a workgroup-scope fence,
-            // and the count must not overtake a partial sum on its way to memory); the count (an atomic of agent scope)
-            // comes after the barrier.  The last of the tile's workgroups to count adds the partials up,
-            // reading them from memory (finalize_wave<true>); the walkers' records it needs are its own copies.
-            // (Tiles with source work: their per-chunk sums have no fixed writer to poll for.)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (every wave: its write-through stores have been acknowledged)
-            __threadfence_block();
-            __syncthreads();
-            if (fresh_tid() == 0) sitem[1] = atomicAdd(q, 1);
-            __syncthreads();
-            if (sitem[1] == fgroup - 1) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                const int t = fresh_tid(), v = t >> 6;
-                const int nB = fa.nchB > 0 ? fa.nslot : 0, nC = fa.nchC > 0 ? fa.nslot : 0;
-                if (v < nw) {
-                    finalize_wave<true>(fa.partA, fa.nchA, fa.nchA, fa.partB, nB, nB, nC > 0 ? fa.partC : nullptr, nC, (int)STAT_CELLS,
-                                        sstat - w0, sbase - w0, w0 + v, t & 63, ap, fa.out, nullptr, nullptr, 0,
-                                        STEP ? sprop + v * 16 : nullptr, STEP ? szz + v : nullptr, STEP ? spre + 2 * v : nullptr);
-                    if (fa.poll) {                // (the slots empty again: the next launch's tiles may poll)
-                        const int ln = t & 63;
-                        if (ln < nC) __hip_atomic_store(fa.partC + (size_t)(w0 + v) * fa.nslot + ln, __longlong_as_double((long long)PART_EMPTY), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (ln < nB) __hip_atomic_store(fa.partB + (size_t)(w0 + v) * fa.nslot + ln, __longlong_as_double((long long)PART_EMPTY), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-                if (t < QSTRIDE) q[t] = 0;        // the tile's counters, for the next launch
-            }
+            // Hand-over by the tile's counter (tiles with source work: their per-chunk sums have no fixed writer to poll for).
+            // The last of the tile's workgroups to count adds the partials up, reading them from memory; the walkers' records
+            // it needs are its own copies.
+            count_finish(q, sitem[1], fgroup, nw, [&] { const int t = fresh_tid(); return TileThread{t, t >> 6, t & 63}; },
+                         [&](int v, int ln) {
+                             const int nB = fa.nchB > 0 ? fa.nslot : 0, nC = fa.nchC > 0 ? fa.nslot : 0;
+                             finalize_wave<true>(fa.partA, fa.nchA, fa.nchA, fa.partB, nB, nB, nC > 0 ? fa.partC : nullptr, nC, (int)STAT_CELLS,
+                                                 sstat - w0, sbase - w0, w0 + v, ln, ap, fa.out, nullptr, nullptr, 0,
+                                                 STEP ? sprop + v * 16 : nullptr, STEP ? szz + v : nullptr, STEP ? spre + 2 * v : nullptr);
+                             if (fa.poll) empty_slots(fa.partB, fa.partC, w0 + v, fa.nslot, nB, nC, ln);
+                         });
         }
     }
 #ifdef LF_STAMPS

@@ -18,7 +18,8 @@
 // FUSED = false keeps lf_prepare and lf_finalize as launches of their own around the same kernel (the sampler's propose /
 // accept steps, lf_lnprob_pieces): the same partial sums in the same slots, so the same bits as the one-launch form.
 #pragma once
-#include "lf_free.h"
+#include "lf_kernels.h"
+#include "lf_tile.h"
 
 namespace lf {
 
@@ -46,7 +47,7 @@ struct PersArgs {
     const double* wrec;       // !FUSED: lf_prepare's records
     const int* wmode;
     const int* wstat;
-    int poll;                 // 1: the slots of partB / partC are PART_EMPTY: tiles without a careful path hand over by polling (lf_free.h)
+    int poll;                 // 1: the slots of partB / partC are PART_EMPTY: tiles without a careful path hand over by polling (lf_tile.h)
     int* err;
 };
 
@@ -54,10 +55,6 @@ struct PersArgs {
 template <int VARIANT, bool FUSED, bool STEP>
 __device__ __forceinline__ void lf_pers_body(const KConst& kc, const PersArgs& pa, const StepArgs& sp, const AcceptArgs& ap) {
     static_assert(VARIANT == LF_ZEVOL || VARIANT == LF_FIXCOMP, "the free variant has lf_free");
-    auto pstore = [](double* p, double v) {                 // (see lf_free: partial sums are written THROUGH in the one-launch form)
-        if (FUSED) __hip_atomic_store(p, v == v ? v : __builtin_nan(""), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (never PART_EMPTY)
-        else *p = v;
-    };
     __shared__ MathTables tab;
     __shared__ __attribute__((aligned(16))) double wsc[PTW * 8];              // per walker: ZEVOL aL bL cL aP bP cP c1 / FIXCOMP L* c0 c1 Q
     __shared__ __attribute__((aligned(16))) double wfc[PTW * MAXF * 8];       // per (walker, field): [0] ZEVOL slope bound, ints at [4]: mode
@@ -68,7 +65,7 @@ __device__ __forceinline__ void lf_pers_body(const KConst& kc, const PersArgs& p
     __shared__ double sbase[PTW];
     __shared__ double sprop[PTW * 16];     // STEP: the tile's proposals and stretch factors (the accept step's)
     __shared__ double szz[PTW];
-    __shared__ double spre[PTW * 2];       //       ... and the accept step's two logarithms per walker, made ahead (lf_free.h)
+    __shared__ double spre[PTW * 2];       //       ... and the accept step's two logarithms per walker, made ahead (lf_tile.h)
     __shared__ int smask[4];               // bit w: [0] walker on the cells, [1] needs the sources, [2] outside the prior (no grid)
     __shared__ int sdone;
     const int tid = threadIdx.x;
@@ -90,13 +87,8 @@ __device__ __forceinline__ void lf_pers_body(const KConst& kc, const PersArgs& p
         const int nw = min(PTW, pa.B - w0);
         __builtin_assume(nw >= 1 && nw <= PTW);
         int* __restrict__ q = pa.queues + tile * QSTRIDE;
-        // rank of this workgroup among the fgroup that serve the tile (lf_free.h)
-        int fgroup = 8, frank = (int)blockIdx.x & 7;
-        if (pa.ntiles <= pa.tile_stride) {
-            const int k = (int)blockIdx.x >> 3;
-            fgroup = 8 * ((pa.tile_stride - tile + pa.ntiles - 1) / pa.ntiles);
-            frank += 8 * ((k - tile) / pa.ntiles);
-        }
+        int fgroup, frank;
+        tile_ranks(tile, pa.ntiles, pa.tile_stride, fgroup, frank);
         __syncthreads();                          // the previous tile's last reads of the LDS records are done
         // ---- prologue: the tile's records in LDS; the exp table (first tile)
         if (FUSED) {
@@ -144,12 +136,7 @@ __device__ __forceinline__ void lf_pers_body(const KConst& kc, const PersArgs& p
             }
             if (tid >= 128 && tid < 128 + nw) sstat[tid - 128] = pa.wstat[w0 + tid - 128];
         }
-        if (FUSED && STEP && tid >= PB - 64 && tid < PB - 64 + nw) {
-            const int wl = tid - (PB - 64);
-            unsigned int rr[4];
-            sampler_draw(sp.step, sp.half, w0 + wl, 0, sp.seed, rr);
-            accept_terms(ap, w0 + wl, stretch_z(sp.a, u53(rr[0], rr[1])), spre[2 * wl], spre[2 * wl + 1]);
-        }
+        accept_terms_ahead<STEP>(sp, ap, w0, nw, tid, spre);      // (STEP implies FUSED)
         tables_loaded = true;
         __syncthreads();
         if (tid < 64) {
@@ -181,7 +168,7 @@ __device__ __forceinline__ void lf_pers_body(const KConst& kc, const PersArgs& p
         // middle rank up, the grid's chunks from rank 0 (lf_free.h: the younger workgroups of a CU run behind the elders)
         if (VARIANT == LF_ZEVOL && pa.nchC > 0 && mine_w) {
 #pragma unroll 1
-            for (int vr = frank; vr < VF; vr += fgroup) {         // (virtual ranks: lf_free.h)
+            for (int vr = frank; vr < VF; vr += fgroup) {         // (virtual ranks: lf_tile.h)
             double acc = 0.0;
             const int cfirst = (vr - VF / 2 + VF) % VF;
             if ((cellmask >> v) & 1) {
@@ -227,7 +214,7 @@ __device__ __forceinline__ void lf_pers_body(const KConst& kc, const PersArgs& p
             }
             acc = wave_sum_dpp(acc);              // lane 63: the wave's total
             double* __restrict__ row = pa.partC + (size_t)(w0 + v) * pa.nslot;
-            if (lane == 63) pstore(row + vr, acc);
+            if (lane == 63) pstore<FUSED>(row + vr, acc);
             }
         }
 #ifdef LF_STAMPS
@@ -308,7 +295,7 @@ __device__ __forceinline__ void lf_pers_body(const KConst& kc, const PersArgs& p
             }
             bsum = wave_sum_dpp(bsum);
             double* __restrict__ row = pa.partB + (size_t)(w0 + v) * pa.nslot;
-            if (lane == 63) pstore(row + vr, bsum);
+            if (lane == 63) pstore<FUSED>(row + vr, bsum);
             }
         }
 #ifdef LF_STAMPS
@@ -371,61 +358,34 @@ __device__ __forceinline__ void lf_pers_body(const KConst& kc, const PersArgs& p
                     for (int k = 0; k < PB / 64; ++k) s += red[tid + 64 * k];
                     s = wave_sum_dpp(s);
                     double* __restrict__ row = pa.partA + (size_t)(w0 + w) * pa.nslot;
-                    if (tid == 63) pstore(row + vr, s);
+                    if (tid == 63) pstore<FUSED>(row + vr, s);
                 }
                 }
             }
         }
         if (FUSED && pa.poll && needmask == 0) {
-            // hand-over by polling (lf_free.h: PART_EMPTY): no careful path in this tile, so every slot has its writer; this
+            // hand-over by polling (lf_tile.h: PART_EMPTY): no careful path in this tile, so every slot has its writer; this
             // workgroup's sums are on their way, and only the tile's finisher - the last physical rank - has more to do
             if (frank == fgroup - 1 && v < nw) {
                 const int nB = pa.nchB > 0 ? pa.nslot : 0, nC = VARIANT == LF_ZEVOL && pa.nchC > 0 ? pa.nslot : 0;
-                double* __restrict__ pb = pa.partB + (size_t)(w0 + v) * pa.nslot;
-                double* __restrict__ pc = pa.partC + (size_t)(w0 + v) * pa.nslot;
                 double pre[2] = {0.0, 0.0};
-                int tries = 0;
-                bool have;
-                do {
-                    if (lane < nC) pre[0] = __hip_atomic_load(pc + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (lane < nB) pre[1] = __hip_atomic_load(pb + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    have = !((lane < nC && (unsigned long long)__double_as_longlong(pre[0]) == PART_EMPTY) ||
-                             (lane < nB && (unsigned long long)__double_as_longlong(pre[1]) == PART_EMPTY));
-                } while (!__all(have) && ++tries < PART_POLLS);
-                if (tries >= PART_POLLS) {
-                    pre[0] = pre[1] = __builtin_nan("");
-                    if (lane == 0) atomicExch(pa.err, 1);
-                }
-                if (lane < nC) __hip_atomic_store(pc + lane, __longlong_as_double((long long)PART_EMPTY), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (lane < nB) __hip_atomic_store(pb + lane, __longlong_as_double((long long)PART_EMPTY), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                poll_finish(pa.partB, pa.partC, w0 + v, pa.nslot, nB, nC, lane, pa.err, pre);
                 finalize_wave<true>(pa.partA, 0, pa.nslot, pa.partB, nB, pa.nslot, nC > 0 ? pa.partC : nullptr, nC, (int)STAT_CELLS,
                                     sstat - w0, sbase - w0, w0 + v, lane, ap, pa.out, nullptr, nullptr,
                                     VARIANT == LF_FIXCOMP ? (int)STAT_SLOW : 0,
                                     STEP ? sprop + v * 16 : nullptr, STEP ? szz + v : nullptr, STEP ? spre + 2 * v : nullptr, pre);
             }
         } else if (FUSED) {
-            // as in lf_free: this workgroup's partial sums have been acknowledged, then it counts itself; the last of the
-            // tile's workgroups to count adds the partials up (finalize_wave: lf_finalize's body, the same slots and order)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __threadfence_block();
-            __syncthreads();
-            if (tid == 0) sdone = atomicAdd(q, 1);
-            __syncthreads();
-            if (sdone == fgroup - 1) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            // as in lf_free: the hand-over by the tile's counter; the last of the tile's workgroups to count adds the partials
+            // up (finalize_wave: lf_finalize's body, the same slots and order)
+            count_finish(q, sdone, fgroup, nw, [&] { return TileThread{tid, v, lane}; }, [&](int, int) {      // (this wave's v and lane)
                 const int nC = VARIANT == LF_ZEVOL && pa.nchC > 0 ? pa.nslot : 0;
-                if (v < nw) {
-                    finalize_wave<true>(pa.partA, pa.nslot, pa.nslot, pa.partB, pa.nslot, pa.nslot, nC > 0 ? pa.partC : nullptr, nC, (int)STAT_CELLS,
-                                        sstat - w0, sbase - w0, w0 + v, lane, ap, pa.out, nullptr, nullptr,
-                                        VARIANT == LF_FIXCOMP ? (int)STAT_SLOW : 0,       // (FIXCOMP: per-source partials exist for SLOW walkers only)
-                                        STEP ? sprop + v * 16 : nullptr, STEP ? szz + v : nullptr, STEP ? spre + 2 * v : nullptr);
-                    if (pa.poll) {                // (the slots empty again: the next launch's tiles may poll)
-                        if (lane < nC) __hip_atomic_store(pa.partC + (size_t)(w0 + v) * pa.nslot + lane, __longlong_as_double((long long)PART_EMPTY), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (lane < pa.nslot) __hip_atomic_store(pa.partB + (size_t)(w0 + v) * pa.nslot + lane, __longlong_as_double((long long)PART_EMPTY), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-                if (tid < QSTRIDE) q[tid] = 0;    // the tile's counters, for the next launch
-            }
+                finalize_wave<true>(pa.partA, pa.nslot, pa.nslot, pa.partB, pa.nslot, pa.nslot, nC > 0 ? pa.partC : nullptr, nC, (int)STAT_CELLS,
+                                    sstat - w0, sbase - w0, w0 + v, lane, ap, pa.out, nullptr, nullptr,
+                                    VARIANT == LF_FIXCOMP ? (int)STAT_SLOW : 0,       // (FIXCOMP: per-source partials exist for SLOW walkers only)
+                                    STEP ? sprop + v * 16 : nullptr, STEP ? szz + v : nullptr, STEP ? spre + 2 * v : nullptr);
+                if (pa.poll) empty_slots(pa.partB, pa.partC, w0 + v, pa.nslot, pa.nslot, nC, lane);
+            });
         }
     }
 #ifdef LF_STAMPS

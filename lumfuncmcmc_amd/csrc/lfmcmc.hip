@@ -85,7 +85,7 @@ struct lf_ctx {
     int64_t opt_fuse = 1;               // lf_free: prepare and finalize inside the one launch (plain evaluations)
     int64_t opt_fuse_step = 1;          // ... and the sampler's half-step too (0: three launches per half-step, A/B runs)
     bool queue_zero = false;            // d_queue is all zeros (what a fused launch needs and leaves behind)
-    bool parts_empty = false;           // every slot of d_partB / d_partR is lf::PART_EMPTY (what lf_free's polling hand-over needs and leaves behind)
+    bool parts_empty = false;           // every slot of d_partB / d_partR is lf::PART_EMPTY (what the polling hand-over needs and leaves behind, lf_tile.h)
     int* d_err = nullptr;               // device error word (a finisher gave up polling)
     int64_t opt_poll = 1;               // 0: the one-launch form hands over through the tile's counter only (A/B runs)
     int64_t opt_free_st = 0;            // lf_free: sources per lane, 0 = chosen from N and B, else 2 / 4 / 8 (tuning runs)
@@ -684,6 +684,56 @@ int ensure_deal(lf_ctx* c, int nchC, int nbq, hipStream_t s) {
     return LF_OK;
 }
 
+// The tiles' counters of the persistent kernels (d_queue: QSTRIDE per tile, lf_tile.h), grown to ntiles; a new buffer is not zero.
+int ensure_queue(lf_ctx* c, int ntiles) {
+    using namespace lf;
+    if (ntiles * QSTRIDE > c->cap_queue) {
+        LF_HIP(c, hipDeviceSynchronize());
+        release(c->d_queue);
+        c->cap_queue = 0;
+        const int cap = std::max(2 * ntiles * QSTRIDE, 1024);
+        LF_HIP(c, hipMalloc((void**)&c->d_queue, (size_t)cap * sizeof(int)));
+        c->cap_queue = cap;
+        c->queue_zero = false;
+    }
+    return LF_OK;
+}
+
+// Every evaluation, before its first launch.  The workspace is shared by consecutive calls: order a stream switch behind the
+// previous work.  Then the evaluation's place in the profile (one_launch: spans make sense).
+int begin_enqueue(lf_ctx* c, hipStream_t s, bool one_launch) {
+    if (c->any_enqueued && c->last_stream != s) LF_HIP(c, hipStreamSynchronize(c->last_stream));
+    c->last_stream = s;
+    c->any_enqueued = true;
+    c->prof_pos = c->prof_tick++ % c->opt_profile_every;
+    c->prof_this = c->profiling > 0 && c->prof_pos == 0;
+    c->prof_span_ok = one_launch;
+    return LF_OK;
+}
+
+// What the one-launch form's hand-over (lf_tile.h) finds before the launch.  The tiles' counters start at zero: a fused launch
+// leaves them so, lf_prepare zeroes them for the three-launch form.  The polling hand-over (PART_EMPTY) wants every slot of
+// the two partial-sum buffers empty: a fused launch leaves them so, every other form leaves sums behind.
+int ready_tiles(lf_ctx* c, hipStream_t s, bool fused, bool poll) {
+    using namespace lf;
+    if (fused && !c->queue_zero) {
+        LF_HIP(c, hipMemsetAsync(c->d_queue, 0, (size_t)c->cap_queue * sizeof(int), s));
+        c->queue_zero = true;
+    }
+    if (poll && !c->parts_empty) {
+        static_assert((PART_EMPTY >> 32) == (PART_EMPTY & 0xffffffffull), "filled by 32-bit words");
+        LF_HIP(c, hipMemsetD32Async((hipDeviceptr_t)c->d_partB, (int)(PART_EMPTY & 0xffffffffull), c->cap_partB * 2, s));
+        LF_HIP(c, hipMemsetD32Async((hipDeviceptr_t)c->d_partR, (int)(PART_EMPTY & 0xffffffffull), c->cap_partR * 2, s));
+        if (!c->d_err) {
+            LF_HIP(c, hipMalloc((void**)&c->d_err, sizeof(int)));
+            LF_HIP(c, hipMemsetAsync(c->d_err, 0, sizeof(int), s));
+        }
+        c->parts_empty = true;
+    }
+    if (!poll) c->parts_empty = false;
+    return LF_OK;
+}
+
 template <int ST>
 void launch_free(lf_ctx* c, int slot, int B, int ntiles, const lf::SrcArrays& sa, const lf::NodeArrays& na, lf::FreeArgs fa, hipStream_t s,
                  bool fused, const lf::StepArgs* sp = nullptr, const lf::AcceptArgs* ap = nullptr) {
@@ -718,46 +768,15 @@ int enqueue_free(lf_ctx* c, const double* d_theta, int B, double* d_out, double*
     rc = ensure_workspace(c, B, (size_t)B * std::max(nchA, 1), (size_t)B * nslot, (size_t)B * nslot);
     if (rc != LF_OK) return rc;
     if ((rc = ensure_deal(c, nchC, gq ? c->gridq.nb : 0, s)) != LF_OK) return rc;
-    if (ntiles * QSTRIDE > c->cap_queue) {
-        LF_HIP(c, hipDeviceSynchronize());
-        release(c->d_queue);
-        c->cap_queue = 0;
-        const int cap = std::max(2 * ntiles * QSTRIDE, 1024);
-        LF_HIP(c, hipMalloc((void**)&c->d_queue, (size_t)cap * sizeof(int)));
-        c->cap_queue = cap;
-        c->queue_zero = false;
-    }
+    if ((rc = ensure_queue(c, ntiles)) != LF_OK) return rc;
     // One launch instead of three (lf_free.h: FUSED) for the plain evaluation; the sampler's propose / accept steps, the
     // two-piece diagnostics, the census and the profile of every launch keep lf_prepare and lf_finalize.
     // ... and so is the sampler's half-step (proposal in the prologue, accept / reject by the tile's finishing workgroup)
     const bool stepf = sp.enabled && ap.enabled && c->opt_fuse_step;
     const bool fused = c->opt_fuse && (stepf || (!sp.enabled && !ap.enabled)) && !d_outA && !d_outB && d_out && !c->kc.forms && c->profiling < 2 &&
                        nchA + nchB > 0;
-    if (c->any_enqueued && c->last_stream != s) LF_HIP(c, hipStreamSynchronize(c->last_stream));
-    c->last_stream = s;
-    c->any_enqueued = true;
-    c->prof_pos = c->prof_tick++ % c->opt_profile_every;
-    c->prof_this = c->profiling > 0 && c->prof_pos == 0;
-    c->prof_span_ok = fused;
-    if (fused && !c->queue_zero) {
-        // the tiles' counters start at zero; a fused launch leaves them so, lf_prepare zeroes them for the three-launch form
-        LF_HIP(c, hipMemsetAsync(c->d_queue, 0, (size_t)c->cap_queue * sizeof(int), s));
-        c->queue_zero = true;
-    }
-    // the polling hand-over (lf_free.h: PART_EMPTY) wants every slot of the two partial-sum buffers empty; a fused launch
-    // leaves them so, every other form leaves sums behind
     const bool poll = fused && c->opt_poll && nslot <= 64;
-    if (poll && !c->parts_empty) {
-        static_assert((PART_EMPTY >> 32) == (PART_EMPTY & 0xffffffffull), "filled by 32-bit words");
-        LF_HIP(c, hipMemsetD32Async((hipDeviceptr_t)c->d_partB, (int)(PART_EMPTY & 0xffffffffull), c->cap_partB * 2, s));
-        LF_HIP(c, hipMemsetD32Async((hipDeviceptr_t)c->d_partR, (int)(PART_EMPTY & 0xffffffffull), c->cap_partR * 2, s));
-        if (!c->d_err) {
-            LF_HIP(c, hipMalloc((void**)&c->d_err, sizeof(int)));
-            LF_HIP(c, hipMemsetAsync(c->d_err, 0, sizeof(int), s));
-        }
-        c->parts_empty = true;
-    }
-    if (!poll) c->parts_empty = false;
+    if ((rc = begin_enqueue(c, s, fused)) != LF_OK || (rc = ready_tiles(c, s, fused, poll)) != LF_OK) return rc;
     if (!fused) {
         c->queue_zero = false;
         Prof p(c, s, 0);
@@ -811,38 +830,11 @@ int enqueue_pers_v(lf_ctx* c, const double* d_theta, int B, double* d_out, doubl
     const int nslot = VF;                  // one per (walker, VIRTUAL workgroup of its tile), lf_free.h
     int rc = ensure_workspace(c, B, (size_t)B * nslot, (size_t)B * nslot, (size_t)B * nslot);
     if (rc != LF_OK) return rc;
-    if (ntiles * QSTRIDE > c->cap_queue) {
-        LF_HIP(c, hipDeviceSynchronize());
-        release(c->d_queue);
-        c->cap_queue = 0;
-        const int cap = std::max(2 * ntiles * QSTRIDE, 1024);
-        LF_HIP(c, hipMalloc((void**)&c->d_queue, (size_t)cap * sizeof(int)));
-        c->cap_queue = cap;
-        c->queue_zero = false;
-    }
+    if ((rc = ensure_queue(c, ntiles)) != LF_OK) return rc;
     const bool stepf = sp.enabled && ap.enabled && c->opt_fuse_step;       // the sampler's half-step: one launch too
     const bool fused = c->opt_fuse && (stepf || (!sp.enabled && !ap.enabled)) && !d_outA && !d_outB && d_out && c->profiling < 2;
-    if (c->any_enqueued && c->last_stream != s) LF_HIP(c, hipStreamSynchronize(c->last_stream));
-    c->last_stream = s;
-    c->any_enqueued = true;
-    c->prof_pos = c->prof_tick++ % c->opt_profile_every;
-    c->prof_this = c->profiling > 0 && c->prof_pos == 0;
-    c->prof_span_ok = fused;
-    if (fused && !c->queue_zero) {
-        LF_HIP(c, hipMemsetAsync(c->d_queue, 0, (size_t)c->cap_queue * sizeof(int), s));
-        c->queue_zero = true;
-    }
-    const bool poll = fused && c->opt_poll;       // (lf_free.h: PART_EMPTY; see enqueue_free)
-    if (poll && !c->parts_empty) {
-        LF_HIP(c, hipMemsetD32Async((hipDeviceptr_t)c->d_partB, (int)(PART_EMPTY & 0xffffffffull), c->cap_partB * 2, s));
-        LF_HIP(c, hipMemsetD32Async((hipDeviceptr_t)c->d_partR, (int)(PART_EMPTY & 0xffffffffull), c->cap_partR * 2, s));
-        if (!c->d_err) {
-            LF_HIP(c, hipMalloc((void**)&c->d_err, sizeof(int)));
-            LF_HIP(c, hipMemsetAsync(c->d_err, 0, sizeof(int), s));
-        }
-        c->parts_empty = true;
-    }
-    if (!poll) c->parts_empty = false;
+    const bool poll = fused && c->opt_poll;       // (lf_tile.h: PART_EMPTY)
+    if ((rc = begin_enqueue(c, s, fused)) != LF_OK || (rc = ready_tiles(c, s, fused, poll)) != LF_OK) return rc;
     if (!fused) {
         Prof p(c, s, 0);
         hipLaunchKernelGGL(lf_prepare, dim3((B + 7) / 8), dim3(64), 0, s, c->kc, sp, d_theta, B, c->d_wrec,
@@ -943,13 +935,7 @@ int enqueue(lf_ctx* c, const double* d_theta, int B, double* d_out, double* d_ou
     rc = ensure_workspace(c, B, (size_t)B * std::max(nchA, 1), (size_t)B * std::max(nchB, 1), (size_t)B * std::max(nchD, nchC));
     if (rc != LF_OK) return rc;
     c->zcells = ZCells{c->d_cells, c->d_cc_start, c->d_cc_len, c->d_cc_field, nchC, c->d_partR, c->d_wstat, 0};
-    // the workspace is shared by consecutive calls: order a stream switch behind the previous work
-    if (c->any_enqueued && c->last_stream != s) LF_HIP(c, hipStreamSynchronize(c->last_stream));
-    c->last_stream = s;
-    c->any_enqueued = true;
-    c->prof_pos = c->prof_tick++ % c->opt_profile_every;
-    c->prof_this = c->profiling > 0 && c->prof_pos == 0;
-    c->prof_span_ok = false;
+    if ((rc = begin_enqueue(c, s, false)) != LF_OK) return rc;
 
     {
         Prof p(c, s, 0);
@@ -1746,7 +1732,7 @@ static int host_eval(lf_ctx* c, const double* theta, int B, double* out, double*
     }
     LF_HIP(c, hipStreamSynchronize(c->stream));
     if (out && c->d_err) {
-        // lnprob is never NaN - unless a polling finisher gave up (lf_free.h: PART_POLLS): then say so instead of handing NaN on
+        // lnprob is never NaN - unless a polling finisher gave up (lf_tile.h: PART_POLLS): then say so instead of handing NaN on
         bool nan = false;
         for (int i = 0; i < B; ++i) nan = nan || c->h_out[i] != c->h_out[i];
         if (nan) {

@@ -1,4 +1,4 @@
-"""The one-launch form's hand-over by polling (csrc/lf_free.h: PART_EMPTY; option "poll", default on) against the tile counter
+"""The one-launch form's hand-over by polling (csrc/lf_tile.h: PART_EMPTY; option "poll", default on) against the tile counter
 (poll = 0): the same partial sums added in the same order, so the same bits - for every variant, across changes of the batch
 size, after calls that leave sums in the partial-sum buffers (the two-piece diagnostics take three launches), with rows on the
 careful path (their tiles count, the others poll) and inside the device sampler."""

@@ -101,7 +101,7 @@ FUSED = [("_ZN2lf7lf_freeILi%dELb0ELb1EEE" % st) for st in (2, 4, 8)] + ["_ZN2lf
 
 @pytest.mark.parametrize("prefix", FUSED)
 def test_one_launch_form_hands_its_partial_sums_over_through_memory(asm, prefix):
-    """The hand-over between the workgroups of a tile (lf_free.h / lf_pers.h, FUSED) rests on four facts
+    """The hand-over between the workgroups of a tile (lf_tile.h, run by lf_free.h / lf_pers.h, FUSED) rests on four facts
     of the generated code, pinned here so that a compiler change cannot silently remove one:
       1. every partial sum is stored with the agent-scope cache policy (sc1: written through this XCD's L2);
       2. each wave waits for its stores' acknowledgements (s_waitcnt vmcnt(0)) directly in front of the workgroup barrier
@@ -116,7 +116,7 @@ def test_one_launch_form_hands_its_partial_sums_over_through_memory(asm, prefix)
     sc1_stores = [l for l in stores if l.endswith(" sc1")]
     # (the kernel's only 8-byte stores to memory are the partial sums, written through, lnprob itself and - the sampler's
     # half-step - the accept step's few: position, chain row, lnprob, counter)
-    # (there are two finishers - the counter's and the polling one, lf_free.h: PART_EMPTY - and so two copies of those)
+    # (there are two finishers - the counter's and the polling one, lf_tile.h: PART_EMPTY - and so two copies of those)
     two = 2
     assert len(sc1_stores) >= 2 and len(stores) - len(sc1_stores) <= two * (8 if "_step" in prefix else 1), stores
     assert not any(l.startswith(("buffer_wbl2", "buffer_inv")) for l in ins), "a cache-wide write-back / invalidate crept in (154 us per evaluation)"
@@ -140,7 +140,7 @@ def test_one_launch_form_hands_its_partial_sums_over_through_memory(asm, prefix)
     # (the half-step's accept reads the walker's current lnprob and position: data of earlier launches, plain loads)
     # (... once per finisher where the compiler has laid the polling one out behind the count)
     assert len(loads) - len(plain) >= 2 and len(plain) <= (6 if "_step" in prefix else 0), loads
-    # 5. the polling finisher (tiles without source work; lf_free.h: PART_EMPTY) reads the slots with the same cache policy, in a
+    # 5. the polling finisher (tiles without source work; lf_tile.h: PART_EMPTY) reads the slots with the same cache policy, in a
     #    loop that ends: the bound of PART_POLLS = 2^19 polls is compared against somewhere in the kernel
     allsc1 = [l for l in ins if l.startswith("global_load_dwordx2") and l.endswith(" sc1")]
     assert len(allsc1) >= 4, allsc1
