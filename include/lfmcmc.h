@@ -264,6 +264,31 @@ int64_t lf_sampler_steps(const lf_sampler *s);
 int lf_sampler_half_eval(lf_sampler *s, int half, int lo, int hi, double *d_newlp, void *hip_stream);
 int lf_sampler_half_accept(lf_sampler *s, int half, const double *d_newlp, void *hip_stream);
 
+/* Parallel-tempered device sampler (emcee 2.x's PTSampler: thermodynamic-integration evidence).
+ * ntemps T <= 64 temperatures with inverse temperatures betas[0] == 1 > betas[1] > ... > betas[T-1] > 0, nwalkers W
+ * (even, 2..4096) walkers each.  The prior is the context's flat box, so the tempered target at beta is beta * lnprob;
+ * a step is, per half, the stretch move of all T x W/2 walkers at once (one evaluation of T x W/2 rows, accept on
+ * lnq = (ln-z term + beta newl) - beta oldl), then the swaps between neighbouring temperatures from the hottest pair down,
+ * then the chain's row.  Philox4x32-10 keyed by seed: temperature 0 draws the numbers lf_sampler_run draws, so T = 1
+ * gives the ensemble sampler's chain bit for bit.  The sampler keeps untempered lnlike (= lnprob inside the box). */
+typedef struct lf_ptsampler lf_ptsampler;
+lf_ptsampler *lf_ptsampler_create(lf_ctx *ctx, int ntemps, int nwalkers, const double *betas, double a, uint64_t seed,
+                                  int64_t capacity_steps);
+void lf_ptsampler_destroy(lf_ptsampler *s);
+/* pos: [T][W][ndim] host; lnlike0: [T][W] or NULL (evaluated then).  Every lnlike must be finite: LF_ERR_ARG otherwise.
+ * Resets the chain and the counters. */
+int lf_ptsampler_start(lf_ptsampler *s, const double *pos, const double *lnlike0);
+/* Enqueue nsteps steps on hip_stream (NULL = the context's stream).  Asynchronous. */
+int lf_ptsampler_run(lf_ptsampler *s, int64_t nsteps, void *hip_stream);
+/* Synchronise and copy out; any pointer may be NULL.  chain: [T][W][steps][ndim], chain_lnlike: [T][W][steps],
+ * mean_lnlike: [T][steps] (the mean of lnlike over the W walkers of a temperature after the step's swaps), naccepted:
+ * [T][W] (stretch moves), nswap: [T-1] (entry i-1: swaps accepted between temperatures i and i-1), pos: [T][W][ndim],
+ * lnlike: [T][W]. */
+int lf_ptsampler_read(lf_ptsampler *s, double *chain, double *chain_lnlike, double *mean_lnlike, int64_t *naccepted,
+                      int64_t *nswap, double *pos, double *lnlike);
+/* Steps recorded so far. */
+int64_t lf_ptsampler_steps(const lf_ptsampler *s);
+
 /* Host-only helper behind "compress", exported for tests (touches no GPU): compress n coordinates `key` with
  * weights `wt` (NULL = 1) into pseudo-sources.  kind 0 (FREE): params = {|a/(1-a)|, alpha_lo, alpha_hi, flim_lo,
  * flim_hi}; kind 1 (ZEVOL): params = {L_lo, L_hi, z1, z2, z3}.  Returns the number of pseudo-sources (written to

@@ -46,7 +46,8 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_set_option", "lf_last_error", "lf_sampler_create", "lf_sampler_destroy", "lf_sampler_start",
            "lf_sampler_run", "lf_sampler_read", "lf_sampler_steps", "lf_sampler_half_eval",
            "lf_sampler_half_accept", "lf_compress_keys", "lf_compress_grid", "lf_grid_bins", "lf_deal_table", "lf_form_counts", "lf_last_launch", "lf_veff",
-           "lf_lumfunc_quantiles", "lf_lumfunc_quantiles_ms")
+           "lf_lumfunc_quantiles", "lf_lumfunc_quantiles_ms", "lf_ptsampler_create", "lf_ptsampler_destroy",
+           "lf_ptsampler_start", "lf_ptsampler_run", "lf_ptsampler_read", "lf_ptsampler_steps")
 
 _lib = None
 
@@ -72,6 +73,12 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise RuntimeError("liblfmcmc.so failed to load (%s). There is no CPU fallback." % e)
+    # a library built from older sources lacks entries the binding declares (the ABI version only moves when existing
+    # entries change): say so here rather than at the first call
+    missing = [n for n in EXPORTS if not hasattr(lib, n)]
+    if missing:
+        raise RuntimeError("liblfmcmc.so at %s lacks %s: rebuild the library (python -m lumfuncmcmc_amd.build --force)"
+                           % (LIB_PATH, ", ".join(missing)))
     lib.lf_abi_version.restype = ctypes.c_int
     lib.lf_abi_version.argtypes = []
     lib.lf_create.restype = ctypes.c_void_p
@@ -127,6 +134,20 @@ def load():
     lib.lf_sampler_half_eval.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.lf_sampler_half_accept.restype = ctypes.c_int
     lib.lf_sampler_half_accept.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    lib.lf_ptsampler_create.restype = ctypes.c_void_p
+    lib.lf_ptsampler_create.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_double, ctypes.c_uint64,
+                                        ctypes.c_int64]
+    lib.lf_ptsampler_destroy.restype = None
+    lib.lf_ptsampler_destroy.argtypes = [ctypes.c_void_p]
+    lib.lf_ptsampler_start.restype = ctypes.c_int
+    lib.lf_ptsampler_start.argtypes = [ctypes.c_void_p, _c_double_p, _c_double_p]
+    lib.lf_ptsampler_run.restype = ctypes.c_int
+    lib.lf_ptsampler_run.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    lib.lf_ptsampler_read.restype = ctypes.c_int
+    lib.lf_ptsampler_read.argtypes = [ctypes.c_void_p, _c_double_p, _c_double_p, _c_double_p, _c_int64_p, _c_int64_p, _c_double_p,
+                                      _c_double_p]
+    lib.lf_ptsampler_steps.restype = ctypes.c_int64
+    lib.lf_ptsampler_steps.argtypes = [ctypes.c_void_p]
     lib.lf_compress_keys.restype = ctypes.c_int64
     lib.lf_compress_keys.argtypes = [ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int64,
                                      _c_double_p, _c_double_p, ctypes.c_int64, _c_double_p]
@@ -371,7 +392,24 @@ class LFContext(object):
         self._h = ctypes.c_void_p(h)
         self.ndim = lib.lf_ndim(self._h)
         self.N, self.nf, self.S = N, nf, S
+        self.fix_sch_al = bool(d.fix_sch_al)
+        self.lims = {k: (float(lims[k][0]), float(lims[k][1])) for k in LIM_ORDER}
         self.device = int(device)
+
+    def prior_box(self):
+        """(ndim, 2) bounds of the flat prior in theta's order (the model classes' _theta_lims)."""
+        L = self.lims
+        if self.variant == "zevol":
+            rows = [L["Lstar"]] * 3 + [L["phistar"]] * 3
+        else:
+            rows = [L["Lstar"], L["phistar"]]
+        if not self.fix_sch_al:
+            rows.append(L["sch_al"])
+        if self.variant == "free":
+            rows += [L["Flim"]] * self.nf + [L["alpha"]]
+        box = np.array(rows, dtype=np.float64)
+        assert box.shape == (self.ndim, 2), (box.shape, self.ndim)
+        return box
 
     # ------------------------------------------------------------------ calls
     def _check(self, rc):

@@ -22,6 +22,7 @@
 #include "lf_kernels.h"
 #include "lf_free.h"
 #include "lf_pers.h"
+#include "lf_pt.h"
 
 namespace {
 
@@ -2372,5 +2373,181 @@ int lf_sampler_half_accept(lf_sampler* sm, int half, const double* d_newlp, void
     }
     return LF_OK;
 }
+
+/* ---------------------------------------------------------------------------------------------
+ * parallel-tempered sampler (lf_pt.h)
+ * ------------------------------------------------------------------------------------------- */
+struct lf_ptsampler {
+    lf_ctx* ctx = nullptr;
+    int T = 0, W = 0, ndim = 0;
+    double a = 2.0;
+    uint64_t seed = 0, step = 0;
+    int64_t cap = 0, t = 0;
+    double *d_betas = nullptr, *d_dbeta = nullptr;
+    double *d_pos = nullptr, *d_lnl = nullptr, *d_prop = nullptr, *d_zz = nullptr, *d_newl = nullptr;
+    double *d_chain = nullptr, *d_chain_lnl = nullptr, *d_mean = nullptr;
+    long long *d_nacc = nullptr, *d_nswap = nullptr;
+    int* d_sig = nullptr;
+    bool started = false;
+};
+
+lf_ptsampler* lf_ptsampler_create(lf_ctx* c, int ntemps, int nwalkers, const double* betas, double a, uint64_t seed,
+                                  int64_t capacity_steps) {
+    if (!c) return nullptr;
+    bool ok = ntemps >= 1 && ntemps <= lf::PT_MAXT && nwalkers >= 2 && !(nwalkers & 1) && nwalkers <= lf::PT_MAXW &&
+              capacity_steps >= 1 && a > 1.0 && betas && betas[0] == 1.0;
+    for (int i = 1; ok && i < ntemps; ++i) ok = betas[i] > 0.0 && betas[i] < betas[i - 1];
+    if (!ok) {
+        c->err = "lf_ptsampler_create: need 1 <= ntemps <= 64, even 2 <= nwalkers <= 4096, a > 1, capacity_steps >= 1, "
+                 "betas[0] == 1 > betas[1] > ... > 0";
+        return nullptr;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return nullptr;
+    lf_ptsampler* sm = new (std::nothrow) lf_ptsampler();
+    if (!sm) return nullptr;
+    sm->ctx = c;
+    sm->T = ntemps;
+    sm->W = nwalkers;
+    sm->ndim = c->kc.ndim;
+    sm->a = a;
+    sm->seed = seed;
+    sm->cap = capacity_steps;
+    const size_t T = (size_t)ntemps, TW = T * nwalkers, nd = (size_t)sm->ndim, cap = (size_t)capacity_steps, TH = TW / 2;
+    std::vector<double> dbeta(T, 0.0);
+    for (size_t i = 1; i < T; ++i) dbeta[i] = betas[i - 1] - betas[i];
+    ok = hipMalloc((void**)&sm->d_betas, T * 8) == hipSuccess && hipMalloc((void**)&sm->d_dbeta, T * 8) == hipSuccess &&
+         hipMalloc((void**)&sm->d_pos, TW * nd * 8) == hipSuccess && hipMalloc((void**)&sm->d_lnl, TW * 8) == hipSuccess &&
+         hipMalloc((void**)&sm->d_prop, TH * nd * 8) == hipSuccess && hipMalloc((void**)&sm->d_zz, TH * 8) == hipSuccess &&
+         hipMalloc((void**)&sm->d_newl, TH * 8) == hipSuccess &&
+         hipMalloc((void**)&sm->d_chain, TW * cap * nd * 8) == hipSuccess &&
+         hipMalloc((void**)&sm->d_chain_lnl, TW * cap * 8) == hipSuccess && hipMalloc((void**)&sm->d_mean, T * cap * 8) == hipSuccess &&
+         hipMalloc((void**)&sm->d_nacc, TW * sizeof(long long)) == hipSuccess &&
+         hipMalloc((void**)&sm->d_nswap, T * sizeof(long long)) == hipSuccess &&
+         hipMalloc((void**)&sm->d_sig, std::max<size_t>(T - 1, 1) * nwalkers * sizeof(int)) == hipSuccess &&
+         hipMemcpy(sm->d_betas, betas, T * 8, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(sm->d_dbeta, dbeta.data(), T * 8, hipMemcpyHostToDevice) == hipSuccess;
+    // the evaluation's workspace for the T x W / 2 rows of a half-step, now rather than by a resize inside a running chain
+    ok = ok && ensure_workspace(c, (int)TH, 0, 0) == LF_OK;
+    if (!ok) {
+        c->err = "lf_ptsampler_create: device allocation failed";
+        lf_ptsampler_destroy(sm);
+        return nullptr;
+    }
+    return sm;
+}
+
+void lf_ptsampler_destroy(lf_ptsampler* sm) {
+    if (!sm) return;
+    if (sm->ctx) {
+        hipSetDevice(sm->ctx->device);
+        hipDeviceSynchronize();
+    }
+    hipFree(sm->d_betas); hipFree(sm->d_dbeta); hipFree(sm->d_pos); hipFree(sm->d_lnl); hipFree(sm->d_prop);
+    hipFree(sm->d_zz); hipFree(sm->d_newl); hipFree(sm->d_chain); hipFree(sm->d_chain_lnl); hipFree(sm->d_mean);
+    hipFree(sm->d_nacc); hipFree(sm->d_nswap); hipFree(sm->d_sig);
+    delete sm;
+}
+
+int lf_ptsampler_start(lf_ptsampler* sm, const double* pos, const double* lnlike0) {
+    if (!sm || !pos) return LF_ERR_ARG;
+    lf_ctx* c = sm->ctx;
+    LF_HIP(c, hipSetDevice(c->device));
+    const size_t TW = (size_t)sm->T * sm->W, nd = (size_t)sm->ndim;
+    std::vector<double> l(TW);
+    if (lnlike0) {
+        std::copy(lnlike0, lnlike0 + TW, l.begin());
+    } else {
+        LF_HIP(c, hipMemcpy(sm->d_pos, pos, TW * nd * 8, hipMemcpyHostToDevice));
+        int rc = enqueue(c, sm->d_pos, (int)TW, sm->d_lnl, nullptr, nullptr, c->stream);
+        if (rc != LF_OK) return rc;
+        LF_HIP(c, hipStreamSynchronize(c->stream));
+        LF_HIP(c, hipMemcpy(l.data(), sm->d_lnl, TW * 8, hipMemcpyDeviceToHost));
+    }
+    for (size_t i = 0; i < TW; ++i) {
+        if (!std::isfinite(l[i])) {
+            c->err = "lf_ptsampler_start: every start position needs a finite lnprob";
+            return LF_ERR_ARG;
+        }
+    }
+    LF_HIP(c, hipMemcpy(sm->d_pos, pos, TW * nd * 8, hipMemcpyHostToDevice));
+    LF_HIP(c, hipMemcpy(sm->d_lnl, l.data(), TW * 8, hipMemcpyHostToDevice));
+    LF_HIP(c, hipMemset(sm->d_nacc, 0, TW * sizeof(long long)));
+    LF_HIP(c, hipMemset(sm->d_nswap, 0, (size_t)sm->T * sizeof(long long)));
+    sm->step = 0;
+    sm->t = 0;
+    sm->started = true;
+    return LF_OK;
+}
+
+int lf_ptsampler_run(lf_ptsampler* sm, int64_t nsteps, void* hip_stream) {
+    if (!sm || nsteps < 0) return LF_ERR_ARG;
+    lf_ctx* c = sm->ctx;
+    if (!sm->started) {
+        c->err = "lf_ptsampler_run: call lf_ptsampler_start first";
+        return LF_ERR_ARG;
+    }
+    if (sm->t + nsteps > sm->cap) {
+        c->err = "lf_ptsampler_run: chain capacity exceeded";
+        return LF_ERR_ARG;
+    }
+    LF_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const int halfW = sm->W / 2, rows = sm->T * halfW;
+    const dim3 grid((rows * 8 + 63) / 64);
+    for (int64_t it = 0; it < nsteps; ++it) {
+        for (int half = 0; half < 2; ++half) {
+            lf::PtArgs p{sm->T, sm->W, halfW, sm->ndim, half, sm->step, sm->seed, sm->a, sm->d_betas, sm->d_pos, sm->d_lnl,
+                         sm->d_prop, sm->d_zz, sm->d_newl, sm->d_nacc};
+            hipLaunchKernelGGL(lf::lf_pt_propose, grid, dim3(64), 0, s, p);
+            LF_HIP(c, hipGetLastError());
+            int rc = enqueue(c, sm->d_prop, rows, sm->d_newl, nullptr, nullptr, s);
+            if (rc != LF_OK) return rc;
+            hipLaunchKernelGGL(lf::lf_pt_accept, grid, dim3(64), 0, s, p);
+            LF_HIP(c, hipGetLastError());
+        }
+        lf::PtSwapArgs q{sm->T, sm->W, sm->ndim, sm->step, sm->seed, (long long)sm->t, (long long)sm->cap, sm->d_dbeta, sm->d_pos,
+                         sm->d_lnl, sm->d_sig, sm->d_nswap, sm->d_chain, sm->d_chain_lnl, sm->d_mean};
+        hipLaunchKernelGGL(lf::lf_pt_swap, dim3(1), dim3(lf::PT_SWAP_THREADS), 0, s, q);
+        LF_HIP(c, hipGetLastError());
+        sm->step += 1;
+        sm->t += 1;
+    }
+    return LF_OK;
+}
+
+int lf_ptsampler_read(lf_ptsampler* sm, double* chain, double* chain_lnlike, double* mean_lnlike, int64_t* naccepted,
+                      int64_t* nswap, double* pos, double* lnlike) {
+    if (!sm) return LF_ERR_ARG;
+    lf_ctx* c = sm->ctx;
+    LF_HIP(c, hipSetDevice(c->device));
+    LF_HIP(c, hipDeviceSynchronize());
+    const size_t T = (size_t)sm->T, TW = T * sm->W, nd = (size_t)sm->ndim, cap = (size_t)sm->cap, t = (size_t)sm->t;
+    // device arrays are [rows][cap](...); the caller's [rows][t](...): packed on the device, then one copy (lf_sampler_read)
+    struct Part { double* dst; const double* src; size_t rows, width; };
+    const Part parts[3] = {{chain, sm->d_chain, TW, nd}, {chain_lnlike, sm->d_chain_lnl, TW, 1}, {mean_lnlike, sm->d_mean, T, 1}};
+    if (t > 0 && (chain || chain_lnlike || mean_lnlike)) {
+        double* tmp = nullptr;
+        LF_HIP(c, hipMalloc((void**)&tmp, TW * t * nd * 8));
+        int rc = LF_OK;
+        for (const Part& p : parts) {
+            if (!p.dst || rc != LF_OK) continue;
+            if (hipMemcpy2D(tmp, t * p.width * 8, p.src, cap * p.width * 8, t * p.width * 8, p.rows, hipMemcpyDeviceToDevice) != hipSuccess ||
+                hipMemcpy(p.dst, tmp, p.rows * t * p.width * 8, hipMemcpyDeviceToHost) != hipSuccess)
+                rc = LF_ERR_HIP;
+        }
+        hipFree(tmp);
+        if (rc != LF_OK) {
+            c->err = "lf_ptsampler_read: copy failed";
+            return rc;
+        }
+    }
+    if (naccepted) LF_HIP(c, hipMemcpy(naccepted, sm->d_nacc, TW * sizeof(long long), hipMemcpyDeviceToHost));
+    if (nswap && T > 1) LF_HIP(c, hipMemcpy(nswap, sm->d_nswap, (T - 1) * sizeof(long long), hipMemcpyDeviceToHost));
+    if (pos) LF_HIP(c, hipMemcpy(pos, sm->d_pos, TW * nd * 8, hipMemcpyDeviceToHost));
+    if (lnlike) LF_HIP(c, hipMemcpy(lnlike, sm->d_lnl, TW * 8, hipMemcpyDeviceToHost));
+    return LF_OK;
+}
+
+int64_t lf_ptsampler_steps(const lf_ptsampler* sm) { return sm ? sm->t : LF_ERR_ARG; }
 
 }  // extern "C"

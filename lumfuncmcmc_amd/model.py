@@ -18,7 +18,7 @@ from . import lfbands
 from . import veff
 from .cosmology import cosmo as _cosmo
 from .capi import LFContext
-from .sampler import DeviceEnsembleSampler, EnsembleSampler
+from .sampler import DeviceEnsembleSampler, DevicePTSampler, EnsembleSampler, default_ntemps, integrated_time, tmax_from_box
 
 TrueLumFunc = hs.true_lum_func       # module-level names the reference exports (lumfuncmcmc.py:25)
 schechter_z = hs.schechter_z         # lumfuncmcmc_z.py:45
@@ -279,6 +279,71 @@ class _Base(object):
         self.log.info(self.samples.shape)
         self.log.info("Median lnprob: %.5f; Max lnprob: %.5f" % (np.median(sampler.lnprobability),
                                                                 np.amax(sampler.lnprobability)))
+
+    def fit_model_pt(self, ntemps=None, Tmax=None, betas=None, fburnin=0.1):
+        """Parallel-tempered fit (DevicePTSampler, sampler.py) and the Bayesian evidence of this model by thermodynamic
+        integration, for comparing the models the classes offer.  self.nwalkers walkers per temperature, self.nsteps
+        steps; every temperature starts from get_init_walker_values (a start with -inf lnprob is drawn again).  Ladder:
+        `betas`, or geometric up to Tmax (None: tmax_from_box on the prior box) over ntemps temperatures (None:
+        default_ntemps(Tmax)).  Sets self.samples from the beta = 1 chain as fit_model does, and self.pt_sampler,
+        self.lnZ, self.dlnZ (fburnin: the leading fraction of steps the estimator leaves out)."""
+        rank, world = self._dist_state()
+        if world > 1:
+            raise NotImplementedError("fit_model_pt runs on one GPU: parallel tempering over several ranks is not implemented")
+        if self.lnprob_fn is not None:
+            raise NotImplementedError("fit_model_pt runs the device sampler: it cannot use lnprob_fn")
+        self.log.info('Fitting Schechter model with parallel tempering (evidence by thermodynamic integration)')
+        ctx = self.context()
+        lims = self._theta_lims()
+        if betas is not None:
+            ntemps = len(betas)
+        else:
+            if Tmax is None:
+                Tmax = tmax_from_box(ctx.lnprob_batch, lims)
+            if ntemps is None:
+                ntemps = default_ntemps(Tmax)
+        W, ndim = self.nwalkers, len(lims)
+        pos = np.array([self.get_init_walker_values() for _ in range(ntemps)])
+        ll = ctx.lnprob_batch(pos.reshape(-1, ndim)).reshape(ntemps, W)
+        for _ in range(100):
+            bad = ~np.isfinite(ll)
+            if not bad.any():
+                break
+            fresh = self.get_init_walker_values(int(bad.sum()))
+            pos[bad] = fresh
+            ll[bad] = ctx.lnprob_batch(fresh)
+        else:
+            raise RuntimeError("fit_model_pt: no finite start in 100 draws of the prior box")
+        seed = int(np.random.randint(0, 2 ** 31 - 1))
+        self.start_pos, self.sampler_seed = pos.copy(), seed
+        start = time.time()
+        sampler = DevicePTSampler(ctx, ntemps, W, betas=betas, Tmax=Tmax, seed=seed, capacity=self.nsteps)
+        sampler.run_mcmc(pos, self.nsteps, lnlike0=ll)
+        elapsed = time.time() - start
+        self.log.info("Total time taken: %0.2f s" % elapsed)
+        self.log.info("Time taken per step per walker: %0.2f ms" % (elapsed / (self.nsteps) * 1000. / (W * ntemps)))
+        chain, lnp = sampler.chain[0], sampler.lnlikelihood[0]
+        tau = max(integrated_time(chain[:, :, d].T) for d in range(ndim))
+        burnin_step = int(tau * 3)
+        if burnin_step > self.nsteps // 2:
+            burnin_step = self.nsteps // 2
+        self.log.info("Mean acceptance fraction: %0.2f" % (np.mean(sampler.acceptance_fraction[0])))
+        self.log.info("AutoCorrelation Steps: %i, Number of Burn-in Steps: %i" % (np.round(tau), burnin_step))
+        new_chain = np.zeros((W, self.nsteps, ndim + 1))
+        new_chain[:, :, :-1] = chain
+        self.chain = chain
+        new_chain[:, :, -1] = lnp
+        self.samples = new_chain[:, burnin_step:, :].reshape((-1, ndim + 1))
+        self.pt_sampler = sampler
+        self.log.info("Shape of self.samples")
+        self.log.info(self.samples.shape)
+        self.log.info("Median lnprob: %.5f; Max lnprob: %.5f" % (np.median(lnp), np.amax(lnp)))
+        self.lnZ, self.dlnZ = sampler.thermodynamic_integration_log_evidence(fburnin)
+        self.log.info("Temperatures: %d, Tmax %.4g; swap acceptance %.2f-%.2f" % (
+            ntemps, 1.0 / sampler.betas[-1], np.min(sampler.tswap_acceptance_fraction, initial=1.0),
+            np.max(sampler.tswap_acceptance_fraction, initial=0.0)))
+        self.log.info("ln evidence: %.4f +/- %.4f" % (self.lnZ, self.dlnZ))
+        return self.lnZ, self.dlnZ
 
     def _select_samples(self, lnprobcut, keep_lnprob):
         """Rows within lnprobcut of the maximum, doubling the cut until a quarter survive

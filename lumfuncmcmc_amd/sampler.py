@@ -13,6 +13,8 @@ of the block and all-gathers, so the ensembles stay bitwise identical across ran
 """
 import numpy as np
 
+from .philox import draw, u53
+
 
 def integrated_time(x, c=5.0):
     """Integrated autocorrelation time of a (nsteps, nwalkers) series, Sokal windowing; finite for
@@ -258,6 +260,264 @@ class DeviceEnsembleSampler(object):
     def close(self):
         if getattr(self, "_h", None) is not None:
             self.ctx._lib.lf_sampler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---------------------------------------------------------------------------------------------------- parallel tempering
+# emcee 2.x's PTSampler read-back surface (betas, chain [T][W][S][ndim], lnlikelihood, lnprobability, acceptance_fraction,
+# tswap_acceptance_fraction, acor, thermodynamic_integration_log_evidence) over a flat prior box: the tempered target at
+# inverse temperature beta is beta * lnlike.  The stretch move runs on all T x W/2 walkers of a half at once (one block
+# for the likelihood), then neighbouring temperatures swap walkers (DESIGN.md section 3.10 states the random streams, the
+# swap order and the estimator).  PTSampler is the NumPy statement, DevicePTSampler runs it on the GPU (lf_ptsampler_*);
+# with the same seed, ladder and start they make the same chain.
+
+def geometric_betas(ntemps, Tmax):
+    """beta_i = Tmax^(-i / (ntemps - 1)): 1 down to 1 / Tmax."""
+    ntemps = int(ntemps)
+    if ntemps == 1:
+        return np.ones(1)
+    if not Tmax > 1.0:
+        raise ValueError("Tmax must be > 1")
+    b = np.power(float(Tmax), -np.arange(ntemps) / (ntemps - 1.0))
+    b[0] = 1.0
+    return b
+
+
+def tmax_from_box(loglike_fn, box, n=4096, seed=0):
+    """The ladder's top temperature from the data: the finite lnlike of n uniform draws in the prior box spread over
+    `spread` nats; Tmax = max(spread, 10) puts beta_min * spread <= 1 nat, so that the hottest chain samples close to the
+    prior and the estimator's closing piece over [0, beta_min] is small."""
+    box = np.asarray(box, dtype=np.float64)
+    u = np.random.default_rng(seed).random((int(n), box.shape[0]))
+    lp = np.asarray(loglike_fn(box[:, 0] + u * (box[:, 1] - box[:, 0])), dtype=np.float64)
+    lp = lp[np.isfinite(lp)]
+    spread = float(lp.max() - lp.min()) if lp.size > 1 else 0.0
+    return max(spread, 10.0)
+
+
+def default_ntemps(Tmax):
+    """Adjacent betas a factor of <= sqrt(2) apart: ceil(2 log2 Tmax) + 1 temperatures, 2 to 64 (a factor of 2 leaves the
+    estimator's trapezoid ~0.1 nat high at d = 5, and every other temperature - dlnZ - 0.4 off)."""
+    return int(min(max(int(np.ceil(2.0 * np.log2(Tmax))) + 1, 2), 64))
+
+
+def ti_log_evidence(betas, mean_lnlike, fburnin=0.1):
+    """(lnZ, dlnZ) by thermodynamic integration.  m_i = post-burn-in mean of mean_lnlike[i] (the walkers' mean lnlike at
+    beta_i per step), c = m_0:  lnZ = c + trapezoid in ln(beta) of beta (m - c) over the ladder + beta_min (m_min - c)
+    for [0, beta_min].  dlnZ = |lnZ - the same over every other temperature|."""
+    betas = np.asarray(betas, dtype=np.float64)
+    ml = np.asarray(mean_lnlike, dtype=np.float64)
+    istart = int(ml.shape[1] * fburnin + 0.5)
+    m = ml[:, istart:].mean(axis=1)
+
+    def est(b, mm):
+        c = mm[0]
+        y, x = b * (mm - c), np.log(b)
+        return c + np.sum(0.5 * (y[:-1] + y[1:]) * (x[:-1] - x[1:])) + b[-1] * (mm[-1] - c)
+
+    lnZ = est(betas, m)
+    return float(lnZ), float(abs(lnZ - est(betas[::2], m[::2])))
+
+
+class _PTSurface(object):
+    """What both PT samplers give back once `chain`, `lnlikelihood`, `mean_lnlike`, `naccepted`, `nswap` and
+    `iterations` are set."""
+
+    @property
+    def lnprobability(self):
+        return self.betas[:, None, None] * self.lnlikelihood
+
+    @property
+    def acceptance_fraction(self):
+        return self.naccepted / max(self.iterations, 1)
+
+    @property
+    def tswap_acceptance_fraction(self):
+        return self.nswap / float(max(self.iterations, 1) * self.nwalkers)
+
+    def get_autocorr_time(self, c=5.0):
+        return np.array([[integrated_time(self.chain[t, :, :, d].T, c=c) for d in range(self.ndim)]
+                         for t in range(self.ntemps)])
+
+    @property
+    def acor(self):
+        return self.get_autocorr_time()
+
+    @property
+    def flatchain(self):
+        return self.chain.reshape(self.ntemps, -1, self.ndim)
+
+    def thermodynamic_integration_log_evidence(self, fburnin=0.1):
+        return ti_log_evidence(self.betas, self.mean_lnlike, fburnin)
+
+    def _ladder(self, ntemps, betas, Tmax, loglike_fn, box):
+        if betas is not None:
+            b = np.array(betas, dtype=np.float64).ravel()
+        else:
+            if Tmax is None and ntemps > 1:
+                if box is None:
+                    raise ValueError("give betas, Tmax or the prior box")
+                Tmax = tmax_from_box(loglike_fn, box)
+            b = geometric_betas(ntemps, Tmax)
+        if len(b) != ntemps or b[0] != 1.0 or np.any(np.diff(b) >= 0) or b[-1] <= 0:
+            raise ValueError("betas must be %d values 1 = beta_0 > beta_1 > ... > 0" % ntemps)
+        return b
+
+
+class PTSampler(_PTSurface):
+    """The parallel-tempered stretch move in NumPy with the device's Philox streams: any vectorised loglike_fn
+    ((B, ndim) -> (B,)); the replay reference of DevicePTSampler.  box: (ndim, 2) prior box, only read to choose Tmax
+    when neither betas nor Tmax is given."""
+
+    def __init__(self, ntemps, nwalkers, ndim, loglike_fn, betas=None, Tmax=None, a=2.0, seed=0, box=None):
+        if nwalkers < 2 or nwalkers % 2 or not 1 <= ntemps <= 64 or nwalkers > 4096:
+            raise ValueError("need even 2 <= nwalkers <= 4096 and 1 <= ntemps <= 64")
+        self.ntemps, self.nwalkers, self.ndim, self.a, self.seed = int(ntemps), int(nwalkers), int(ndim), float(a), int(seed)
+        self.loglike_fn = loglike_fn
+        self.betas = self._ladder(self.ntemps, betas, Tmax, loglike_fn, box)
+        self._dbeta = np.concatenate([[0.0], self.betas[:-1] - self.betas[1:]])
+        self._p = None
+        self.iterations = 0
+        self.step = 0
+
+    def _ll(self, block):
+        return np.asarray(self.loglike_fn(block), dtype=np.float64)
+
+    def run_mcmc(self, pos, nsteps):
+        """pos (T, W, ndim), or None to continue.  Returns (pos, lnprob, lnlike) of the last step."""
+        T, W, nd, a = self.ntemps, self.nwalkers, self.ndim, self.a
+        half = W // 2
+        if pos is not None or self._p is None:
+            p = np.array(pos, dtype=np.float64)
+            if p.shape != (T, W, nd):
+                raise ValueError("pos must be (ntemps, nwalkers, ndim)")
+            self._p = p.reshape(T * W, nd).copy()
+            self._l = self._ll(self._p)
+            if not np.all(np.isfinite(self._l)):
+                raise ValueError("every start position needs a finite lnlike")
+            self.chain = np.empty((T, W, 0, nd))
+            self.lnlikelihood = np.empty((T, W, 0))
+            self.mean_lnlike = np.empty((T, 0))
+            self.naccepted = np.zeros((T, W), dtype=np.int64)
+            self.nswap = np.zeros(max(T - 1, 0), dtype=np.int64)
+            self.iterations = self.step = 0
+        P, L = self._p, self._l
+        nacc = self.naccepted.reshape(-1)
+        r = np.arange(T * half)
+        t, w = r // half, r % half
+        bt = self.betas[t]
+        chain = np.empty((T, W, nsteps, nd))
+        lnl = np.empty((T, W, nsteps))
+        mean = np.empty((T, nsteps))
+        for it in range(int(nsteps)):
+            s = self.step
+            for h in (0, 1):
+                r0, r1, r2, _ = draw(s, h, r, 0, self.seed)
+                z = ((a - 1.0) * u53(r0, r1) + 1.0) ** 2 / a
+                j = t * W + (1 - h) * half + ((r2 * np.uint64(half)) >> np.uint64(32)).astype(np.int64)
+                k = t * W + h * half + w
+                prop = P[j] - (P[j] - P[k]) * z[:, None]
+                newl = self._ll(prop)
+                if np.isnan(newl).any():
+                    raise ValueError("loglike_fn returned NaN")
+                q0, q1, _, _ = draw(s, h, r, 1, self.seed)
+                with np.errstate(all="ignore"):
+                    lnq = ((nd - 1.0) * np.log(z) + bt * newl) - bt * L[k]
+                    acc = (np.log(u53(q0, q1)) < lnq) & (newl > -np.inf)
+                P[k[acc]] = prop[acc]
+                L[k[acc]] = newl[acc]
+                nacc[k[acc]] += 1
+            if T > 1:
+                r0, r1, r2, r3 = draw(s, 0, np.arange(W, T * W), 2, self.seed)
+                keys = ((r0 << np.uint64(32)) | r1).reshape(T - 1, W)
+                logu = np.log(u53(r2, r3)).reshape(T - 1, W)
+                for i in range(T - 1, 0, -1):
+                    sig = np.argsort(keys[i - 1], kind="stable")
+                    ia, ib = i * W + np.arange(W), (i - 1) * W + sig
+                    acc = logu[i - 1] < self._dbeta[i] * (L[ia] - L[ib])
+                    ia, ib = ia[acc], ib[acc]
+                    P[ia], P[ib] = P[ib].copy(), P[ia].copy()
+                    L[ia], L[ib] = L[ib].copy(), L[ia].copy()
+                    self.nswap[i - 1] += int(acc.sum())
+            chain[:, :, it] = P.reshape(T, W, nd)
+            lnl[:, :, it] = L.reshape(T, W)
+            mean[:, it] = L.reshape(T, W).mean(axis=1)
+            self.step += 1
+        self.chain = np.concatenate([self.chain, chain], axis=2)
+        self.lnlikelihood = np.concatenate([self.lnlikelihood, lnl], axis=2)
+        self.mean_lnlike = np.concatenate([self.mean_lnlike, mean], axis=1)
+        self.iterations += int(nsteps)
+        lt = L.reshape(T, W).copy()
+        return P.reshape(T, W, nd).copy(), self.betas[:, None] * lt, lt
+
+
+class DevicePTSampler(_PTSurface):
+    """PTSampler on the GPU (lf_ptsampler_* of include/lfmcmc.h): positions, lnlike and the chain stay in HBM, a step is
+    three launches and one evaluation of T x W/2 rows per half plus one swap launch.  ntemps x nwalkers walkers; the
+    ladder is `betas`, or geometric up to Tmax (Tmax=None: tmax_from_box on the context's prior box)."""
+
+    def __init__(self, ctx, ntemps, nwalkers, betas=None, Tmax=None, a=2.0, seed=0, capacity=1000):
+        import ctypes
+        if nwalkers < 2 or nwalkers % 2:
+            raise ValueError("nwalkers must be even and >= 2")
+        self._ct = ctypes
+        self.ctx, self.ntemps, self.nwalkers, self.ndim = ctx, int(ntemps), int(nwalkers), ctx.ndim
+        self.a, self.seed, self.capacity = float(a), int(seed), int(capacity)
+        self.betas = self._ladder(self.ntemps, betas, Tmax, ctx.lnprob_batch, ctx.prior_box())
+        self._betas_c = np.ascontiguousarray(self.betas)
+        h = ctx._lib.lf_ptsampler_create(ctx._h, self.ntemps, self.nwalkers, self._p(self._betas_c), self.a,
+                                         ctypes.c_uint64(self.seed), self.capacity)
+        if not h:
+            raise RuntimeError("lf_ptsampler_create failed: %s" % ctx._lib.lf_last_error(ctx._h).decode())
+        self._h = ctypes.c_void_p(h)
+        self._started = False
+        self.iterations = 0
+
+    def _p(self, a):
+        return a.ctypes.data_as(self._ct.POINTER(self._ct.c_double)) if a is not None else None
+
+    def run_mcmc(self, pos, nsteps, lnlike0=None):
+        """pos (T, W, ndim), or None to continue.  Returns (pos, lnprob, lnlike) after the last step."""
+        self.enqueue(pos, nsteps, lnlike0)
+        return self.sync()
+
+    def enqueue(self, pos, nsteps, lnlike0=None):
+        lib = self.ctx._lib
+        if pos is not None or not self._started:
+            p = np.ascontiguousarray(pos, dtype=np.float64)
+            if p.shape != (self.ntemps, self.nwalkers, self.ndim):
+                raise ValueError("pos must be (ntemps, nwalkers, ndim)")
+            l0 = None if lnlike0 is None else np.ascontiguousarray(lnlike0, dtype=np.float64)
+            self.ctx._check(lib.lf_ptsampler_start(self._h, self._p(p), self._p(l0)))
+            self._started = True
+        self.ctx._check(lib.lf_ptsampler_run(self._h, int(nsteps), None))
+
+    def sync(self):
+        lib, ct = self.ctx._lib, self._ct
+        s = int(lib.lf_ptsampler_steps(self._h))
+        T, W, nd = self.ntemps, self.nwalkers, self.ndim
+        self.chain = np.empty((T, W, s, nd))
+        self.lnlikelihood = np.empty((T, W, s))
+        self.mean_lnlike = np.empty((T, s))
+        self.naccepted = np.empty((T, W), dtype=np.int64)
+        self.nswap = np.zeros(max(T - 1, 0), dtype=np.int64)
+        pos, ll = np.empty((T, W, nd)), np.empty((T, W))
+        i64 = ct.POINTER(ct.c_int64)
+        self.ctx._check(lib.lf_ptsampler_read(self._h, self._p(self.chain), self._p(self.lnlikelihood), self._p(self.mean_lnlike),
+                                              self.naccepted.ctypes.data_as(i64),
+                                              self.nswap.ctypes.data_as(i64) if T > 1 else None, self._p(pos), self._p(ll)))
+        self.iterations = s
+        return pos, self.betas[:, None] * ll, ll
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            self.ctx._lib.lf_ptsampler_destroy(self._h)
             self._h = None
 
     def __del__(self):
