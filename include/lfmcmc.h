@@ -230,6 +230,11 @@ int lf_form_counts(lf_ctx *ctx, int64_t counts[9]);
  * workgroups in the launch, catalogue chunks, grid chunks, theta rows. */
 int lf_last_launch(const lf_ctx *ctx, int32_t info[8]);
 
+/* How many times this context has uploaded the one-launch lf_free's block of launch-invariant arguments (measurement and
+ * tests only): once per sources-per-lane setting on first use, then only when a reallocated buffer or an option changes
+ * its bytes - never in steady state. */
+int lf_free_block_uploads(const lf_ctx *ctx, int64_t *n);
+
 /*
  * Device-resident ensemble sampler: the Goodman & Weare stretch move in its parallel form (two fixed
  * half-ensembles, as emcee 2.x - the API the reference calls - implements it), with theta, lnprob

@@ -45,7 +45,8 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_lnprob_batch_device", "lf_lnprob_batch_device_n", "lf_lnprob_pieces", "lf_set_profiling", "lf_kernel_times",
            "lf_set_option", "lf_last_error", "lf_sampler_create", "lf_sampler_destroy", "lf_sampler_start",
            "lf_sampler_run", "lf_sampler_read", "lf_sampler_steps", "lf_sampler_half_eval",
-           "lf_sampler_half_accept", "lf_compress_keys", "lf_compress_grid", "lf_grid_bins", "lf_deal_table", "lf_form_counts", "lf_last_launch", "lf_veff",
+           "lf_sampler_half_accept", "lf_compress_keys", "lf_compress_grid", "lf_grid_bins", "lf_deal_table", "lf_form_counts", "lf_last_launch",
+           "lf_free_block_uploads", "lf_veff",
            "lf_lumfunc_quantiles", "lf_lumfunc_quantiles_ms", "lf_ptsampler_create", "lf_ptsampler_destroy",
            "lf_ptsampler_start", "lf_ptsampler_run", "lf_ptsampler_read", "lf_ptsampler_steps")
 
@@ -107,6 +108,8 @@ def load():
     lib.lf_form_counts.argtypes = [ctypes.c_void_p, _c_int64_p]
     lib.lf_last_launch.restype = ctypes.c_int
     lib.lf_last_launch.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]
+    lib.lf_free_block_uploads.restype = ctypes.c_int
+    lib.lf_free_block_uploads.argtypes = [ctypes.c_void_p, _c_int64_p]
     lib.lf_veff.restype = ctypes.c_int
     lib.lf_veff.argtypes = [ctypes.c_int, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p, ctypes.c_double, ctypes.c_double,
                             ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
@@ -508,6 +511,12 @@ class LFContext(object):
             d["kind"] -= 1
         d["kernel"] = "lf_free<%d>" % d["st"] if d["kind"] == 2 else ("lf_pers" if d["kind"] == 4 else "lf_main")
         return d
+
+    def free_block_uploads(self):
+        """Uploads of the one-launch lf_free's argument block so far (lf_free.h: FreeBlock; none in steady state)."""
+        n = ctypes.c_int64(0)
+        self._check(self._lib.lf_free_block_uploads(self._h, ctypes.byref(n)))
+        return int(n.value)
 
     def set_option(self, key, value):
         self._check(self._lib.lf_set_option(self._h, key.encode(), int(value)))

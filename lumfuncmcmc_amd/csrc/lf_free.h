@@ -101,10 +101,12 @@ struct FreeArgs {
 // walker), every workgroup of the tile the same values), and the tile's finishing workgroup accepts or rejects them and
 // writes the chain's row (accept_walker, as lf_finalize does).  An instantiation of its own behind a kernel of its own
 // (lf_free_step): the sampler's arguments are not in everybody's argument block.
-template <int ST, bool CENSUS, bool FUSED, bool STEP>
+// LA: where the per-launch fields (B, ntiles, tile_stride, theta, out) are read - the FreeArgs itself (la is fa), or the block
+// entry's FreeLaunch, whose FreeArgs in the block leaves them zero (FreeBlock below).
+template <int ST, bool CENSUS, bool FUSED, bool STEP, class LA>
 __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& sa, const NodeArrays& na, const double* __restrict__ wrec_arg,
-                                             const int* __restrict__ wmode_arg, const FreeArgs& fa, const StepArgs& sp, const AcceptArgs& ap,
-                                             unsigned long long t_pre = 0) {
+                                             const int* __restrict__ wmode_arg, const FreeArgs& fa, const LA& la, const StepArgs& sp,
+                                             const AcceptArgs& ap, unsigned long long t_pre = 0) {
     const double* wrec = FUSED ? fa.wrec_w : wrec_arg;
     const int* wmode = FUSED ? fa.wmode_w : wmode_arg;
     __shared__ MathTables tab;
@@ -165,9 +167,9 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
 #endif
 
 #pragma unroll 1
-    for (int tile = ((int)blockIdx.x >> 3) % fa.ntiles; tile < fa.ntiles; tile += fa.tile_stride) {
+    for (int tile = ((int)blockIdx.x >> 3) % la.ntiles; tile < la.ntiles; tile += la.tile_stride) {
         const int w0 = tile * PTW;
-        const int nw = min(PTW, fa.B - w0);
+        const int nw = min(PTW, la.B - w0);
         __builtin_assume(nw >= 1 && nw <= PTW);
         int* __restrict__ q = fa.queues + tile * QSTRIDE;
         // next item of this tile: a node chunk while there are any (item = chunk), then a catalogue chunk of our XCD's
@@ -176,7 +178,7 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
         // are dealt STATICALLY, chunk i to the workgroup of rank i mod fgroup among those serving the tile - no claims.
         // Only the source chunks - unequal, and only needed by walkers that cannot use the cells - are claimed from queues.
         int fgroup, frank;
-        tile_ranks(tile, fa.ntiles, fa.tile_stride, fgroup, frank);
+        tile_ranks(tile, la.ntiles, la.tile_stride, fgroup, frank);
         bool no_src = false;                       // (thread 0's view) every walker of the tile is summed over the cells
         auto grab = [&]() -> int {
             if (no_src) return -1;
@@ -205,7 +207,7 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
             if (ticket < hi - lo) return lo + ticket;
             return grab();                        // our queue is empty: steal (the grid queue and ours just hand out misses)
         };
-        if (tile != ((int)blockIdx.x >> 3) % fa.ntiles) __syncthreads();      // the previous tile's last reads of wfc / wsc / sitem are done
+        if (tile != ((int)blockIdx.x >> 3) % la.ntiles) __syncthreads();      // the previous tile's last reads of wfc / wsc / sitem are done
         const int u = fresh_tid();
         if (FUSED) {
             // Wave 0 prepares the tile's 8 walkers (lf_prepare's body) and puts their records straight into LDS (wfc, wsc,
@@ -222,7 +224,7 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
             const int pw = (int)(blockIdx.x >> 8) & 1;
             const int up = u - 64 * pw;           // the preparing wave's threads: 0 .. 63
             if (up >= 0 && up < 64) {
-                prepare_lane<false, true, STEP, LF_FREE>(kc, sp, fa.theta, fa.B, nullptr, nullptr, nullptr, nullptr, nullptr, 1,
+                prepare_lane<false, true, STEP, LF_FREE>(kc, sp, la.theta, la.B, nullptr, nullptr, nullptr, nullptr, nullptr, 1,
                                           w0 + (up >> 3), up & 7, up >> 3, reinterpret_cast<double(*)[16]>(red), wfc, wsc, sstat, sbase, wlf,
 #ifdef LF_STAMPS
                                           s_tprep,
@@ -712,7 +714,7 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
                     double pre[2] = {0.0, 0.0};
                     poll_finish(fa.partB, fa.partC, w0 + v, fa.nslot, nB, nC, ln, fa.err, pre);
                     finalize_wave<true>(fa.partA, 0, fa.nchA, fa.partB, nB, nB, nC > 0 ? fa.partC : nullptr, nC, (int)STAT_CELLS,
-                                        sstat - w0, sbase - w0, w0 + v, ln, ap, fa.out, nullptr, nullptr, 0,
+                                        sstat - w0, sbase - w0, w0 + v, ln, ap, la.out, nullptr, nullptr, 0,
                                         STEP ? sprop + v * 16 : nullptr, STEP ? szz + v : nullptr, STEP ? spre + 2 * v : nullptr, pre);
                 }
             }
@@ -724,7 +726,7 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
                          [&](int v, int ln) {
                              const int nB = fa.nchB > 0 ? fa.nslot : 0, nC = fa.nchC > 0 ? fa.nslot : 0;
                              finalize_wave<true>(fa.partA, fa.nchA, fa.nchA, fa.partB, nB, nB, nC > 0 ? fa.partC : nullptr, nC, (int)STAT_CELLS,
-                                                 sstat - w0, sbase - w0, w0 + v, ln, ap, fa.out, nullptr, nullptr, 0,
+                                                 sstat - w0, sbase - w0, w0 + v, ln, ap, la.out, nullptr, nullptr, 0,
                                                  STEP ? sprop + v * 16 : nullptr, STEP ? szz + v : nullptr, STEP ? spre + 2 * v : nullptr);
                              if (fa.poll) empty_slots(fa.partB, fa.partC, w0 + v, fa.nslot, nB, nC, ln);
                          });
@@ -758,22 +760,62 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
 #endif
 }
 
+// The three-launch form (FUSED = false) and its census twin: every argument in the kernarg segment.
 template <int ST, bool CENSUS, bool FUSED = false>
 __global__ __launch_bounds__(PB, 4) void lf_free(KConst kc, SrcArrays sa, NodeArrays na, const double* __restrict__ wrec_arg,
                                                  const int* __restrict__ wmode_arg, FreeArgs fa) {
+    static_assert(!FUSED, "the one-launch form is the block entry below");
 #ifdef LF_STAMPS
     const unsigned long long t_pre = __builtin_amdgcn_s_memtime();
 #else
     const unsigned long long t_pre = 0;
 #endif
     warm_kernarg<sizeof(KConst) + sizeof(SrcArrays) + sizeof(NodeArrays) + 2 * 8 + sizeof(FreeArgs)>();      // (lf_math.h: one round trip)
-    lf_free_body<ST, CENSUS, FUSED, false>(kc, sa, na, wrec_arg, wmode_arg, fa, StepArgs{}, AcceptArgs{}, t_pre);
+    lf_free_body<ST, CENSUS, FUSED, false>(kc, sa, na, wrec_arg, wmode_arg, fa, fa, StepArgs{}, AcceptArgs{}, t_pre);
+}
+
+// The one-launch form (FUSED: the plain evaluation, the headline's kernel).  What does not change from call to call - KConst,
+// the catalogue's and the grid's arrays, the workspace - sits in a per-context block in device memory, uploaded by the host
+// only when its bytes change (lfmcmc.hip: free_block); the kernarg segment is the block's pointer and the FreeLaunch, one
+// 64-byte line.  With 1720 bytes of arguments the launch began with their 28 cold lines (1.4k cycles) and a preamble of
+// eight dependent scalar-cache waits (3.0k cycles: more arguments than SGPRs, parked in VGPR lanes as they arrived); the
+// block's fields are read where they are used instead - scalar loads of lines every workgroup of every launch reads, warm in
+// L2.  kc / sa / na / fa are references into the block, never copies (a copy brings the parking back).
+struct FreeLaunch {
+    const double* theta;      // [B][ndim]
+    double* out;              // [B] lnprob
+    int B, ntiles;            // theta rows, tiles of PTW walkers
+    int tile_stride;          // workgroup g serves tiles (g / 8) % ntiles, + tile_stride, ...
+};
+static_assert(sizeof(FreeLaunch) <= 64 - 8, "the block's pointer and the launch's fields: one line of kernel arguments");
+struct FreeBlock {
+    KConst kc;
+    SrcArrays sa;
+    NodeArrays na;
+    FreeArgs fa;              // its theta, out, B, ntiles and tile_stride are zero: the body reads those from the FreeLaunch
+};
+
+// (The block is passed in the constant address space: nothing in the kernel writes it, and the compiler, knowing so, treats the
+// pointers read from it as global ones - through a plain pointer they stay flat, and so do the hand-over's stores and loads.)
+typedef const __attribute__((address_space(4))) FreeBlock* FreeBlockPtr;
+
+template <int ST, bool CENSUS, bool FUSED>
+__global__ __launch_bounds__(PB, 4) void lf_free(FreeBlockPtr __restrict__ blkc, FreeLaunch la) {
+    static_assert(FUSED && !CENSUS, "the block entry is the one-launch form");
+    const FreeBlock* __restrict__ blk = (const FreeBlock*)blkc;
+#ifdef LF_STAMPS
+    const unsigned long long t_pre = __builtin_amdgcn_s_memtime();
+#else
+    const unsigned long long t_pre = 0;
+#endif
+    warm_kernarg<sizeof(FreeBlockPtr) + sizeof(FreeLaunch)>();      // (one line)
+    lf_free_body<ST, false, true, false>(blk->kc, blk->sa, blk->na, nullptr, nullptr, blk->fa, la, StepArgs{}, AcceptArgs{}, t_pre);
 }
 
 template <int ST>
 __global__ __launch_bounds__(PB, 4) void lf_free_step(KConst kc, SrcArrays sa, NodeArrays na, FreeArgs fa, StepArgs sp, AcceptArgs ap) {
     warm_kernarg<sizeof(KConst) + sizeof(SrcArrays) + sizeof(NodeArrays) + sizeof(FreeArgs) + sizeof(StepArgs) + sizeof(AcceptArgs)>();
-    lf_free_body<ST, false, true, true>(kc, sa, na, nullptr, nullptr, fa, sp, ap);
+    lf_free_body<ST, false, true, true>(kc, sa, na, nullptr, nullptr, fa, fa, sp, ap);
 }
 
 }  // namespace lf

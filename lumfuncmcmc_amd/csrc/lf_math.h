@@ -225,40 +225,43 @@ __device__ __forceinline__ double wave_sum(double v) {
 // memory (measured: 19.0 us per evaluation with the kernarg ring in device memory, 32.2 us with it in host memory,
 // HIP_FORCE_DEV_KERNARG=0: thirteen misses' worth of PCIe).  warm_kernarg issues loads of the whole segment back to
 // back, the results discarded, and waits once: afterwards every line is in the scalar cache (and in L2 for the vector
-// loads of fields indexed per lane).  BYTES = the size of the explicit arguments; the over-read up to the next multiple
-// of 256 stays inside the segment (the hidden arguments that follow are 256 bytes).
+// loads of fields indexed per lane).  BYTES = the size of the explicit arguments, which is the whole segment: these kernels
+// read no hidden arguments, and the code object says so (.amdhsa_kernarg_size).  So every load stays inside it - one per
+// 64-byte line at offset 64 k < BYTES (BYTES is a multiple of 4: the line's first dword is in the segment).  (An earlier
+// ladder rounded up to 256 bytes and read past the end of lf_free's, lf_free_step's and lf_pers_step's segments.)
 // ----------------------------------------------------------------------------------------------
 #define LF_KW1(o) "s_load_dword %0, %1, " #o "\n\t"
 #define LF_KW4(b) LF_KW1(b + 0x00) LF_KW1(b + 0x40) LF_KW1(b + 0x80) LF_KW1(b + 0xc0)
+// Q whole groups of four lines, then R more lines from byte b = 0x100 Q
+#define LF_KQ0
+#define LF_KQ1 LF_KW4(0x000)
+#define LF_KQ2 LF_KQ1 LF_KW4(0x100)
+#define LF_KQ3 LF_KQ2 LF_KW4(0x200)
+#define LF_KQ4 LF_KQ3 LF_KW4(0x300)
+#define LF_KQ5 LF_KQ4 LF_KW4(0x400)
+#define LF_KQ6 LF_KQ5 LF_KW4(0x500)
+#define LF_KQ7 LF_KQ6 LF_KW4(0x600)
+#define LF_KQ8 LF_KQ7 LF_KW4(0x700)
+#define LF_KQ9 LF_KQ8 LF_KW4(0x800)
+#define LF_KQ10 LF_KQ9 LF_KW4(0x900)
+#define LF_KR0(b)
+#define LF_KR1(b) LF_KW1(b + 0x00)
+#define LF_KR2(b) LF_KR1(b) LF_KW1(b + 0x40)
+#define LF_KR3(b) LF_KR2(b) LF_KW1(b + 0x80)
+#define LF_KCASE(q, r, b) \
+    if constexpr (N == 4 * q + r) asm volatile(LF_KQ##q LF_KR##r(b) "s_waitcnt lgkmcnt(0)" : "=&s"(t) : "s"(p) : "memory");
+#define LF_KROW(q, b) LF_KCASE(q, 0, b) LF_KCASE(q, 1, b) LF_KCASE(q, 2, b) LF_KCASE(q, 3, b)
 template <int BYTES>
 __device__ __forceinline__ void warm_kernarg() {
-    constexpr int N4 = (BYTES + 255) / 256;
-    static_assert(N4 >= 1 && N4 <= 10, "extend the ladder");
+    constexpr int N = (BYTES + 63) / 64;      // lines that hold arguments
+    static_assert(BYTES % 4 == 0 && N >= 1 && N <= 40, "extend the ladder");
     auto p = __builtin_amdgcn_kernarg_segment_ptr();
     int t;      // (one dword per 64-byte line: the line comes into the cache whatever the size of the load - and the cache's return
                 // path, shared by the 32 waves of two CUs that all do this at once, carries 4 bytes per line instead of 64)
-    if constexpr (N4 == 1) asm volatile(LF_KW4(0x000) "s_waitcnt lgkmcnt(0)" : "=&s"(t) : "s"(p) : "memory");
-    if constexpr (N4 == 2) asm volatile(LF_KW4(0x000) LF_KW4(0x100) "s_waitcnt lgkmcnt(0)" : "=&s"(t) : "s"(p) : "memory");
-    if constexpr (N4 == 3) asm volatile(LF_KW4(0x000) LF_KW4(0x100) LF_KW4(0x200) "s_waitcnt lgkmcnt(0)" : "=&s"(t) : "s"(p) : "memory");
-    if constexpr (N4 == 4)
-        asm volatile(LF_KW4(0x000) LF_KW4(0x100) LF_KW4(0x200) LF_KW4(0x300) "s_waitcnt lgkmcnt(0)" : "=&s"(t) : "s"(p) : "memory");
-    if constexpr (N4 == 5)
-        asm volatile(LF_KW4(0x000) LF_KW4(0x100) LF_KW4(0x200) LF_KW4(0x300) LF_KW4(0x400) "s_waitcnt lgkmcnt(0)" : "=&s"(t) : "s"(p) : "memory");
-    if constexpr (N4 == 6)
-        asm volatile(LF_KW4(0x000) LF_KW4(0x100) LF_KW4(0x200) LF_KW4(0x300) LF_KW4(0x400) LF_KW4(0x500) "s_waitcnt lgkmcnt(0)"
-                     : "=&s"(t) : "s"(p) : "memory");
-    if constexpr (N4 == 7)
-        asm volatile(LF_KW4(0x000) LF_KW4(0x100) LF_KW4(0x200) LF_KW4(0x300) LF_KW4(0x400) LF_KW4(0x500) LF_KW4(0x600) "s_waitcnt lgkmcnt(0)"
-                     : "=&s"(t) : "s"(p) : "memory");
-    if constexpr (N4 == 8)
-        asm volatile(LF_KW4(0x000) LF_KW4(0x100) LF_KW4(0x200) LF_KW4(0x300) LF_KW4(0x400) LF_KW4(0x500) LF_KW4(0x600) LF_KW4(0x700)
-                     "s_waitcnt lgkmcnt(0)" : "=&s"(t) : "s"(p) : "memory");
-    if constexpr (N4 == 9)
-        asm volatile(LF_KW4(0x000) LF_KW4(0x100) LF_KW4(0x200) LF_KW4(0x300) LF_KW4(0x400) LF_KW4(0x500) LF_KW4(0x600) LF_KW4(0x700)
-                     LF_KW4(0x800) "s_waitcnt lgkmcnt(0)" : "=&s"(t) : "s"(p) : "memory");
-    if constexpr (N4 == 10)
-        asm volatile(LF_KW4(0x000) LF_KW4(0x100) LF_KW4(0x200) LF_KW4(0x300) LF_KW4(0x400) LF_KW4(0x500) LF_KW4(0x600) LF_KW4(0x700)
-                     LF_KW4(0x800) LF_KW4(0x900) "s_waitcnt lgkmcnt(0)" : "=&s"(t) : "s"(p) : "memory");
+    LF_KROW(0, 0x000) LF_KROW(1, 0x100) LF_KROW(2, 0x200) LF_KROW(3, 0x300) LF_KROW(4, 0x400)
+    LF_KROW(5, 0x500) LF_KROW(6, 0x600) LF_KROW(7, 0x700) LF_KROW(8, 0x800) LF_KROW(9, 0x900) LF_KCASE(10, 0, 0xa00)
 }
+#undef LF_KROW
+#undef LF_KCASE
 
 }  // namespace lf

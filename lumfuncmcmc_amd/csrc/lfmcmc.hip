@@ -88,6 +88,13 @@ struct lf_ctx {
     bool queue_zero = false;            // d_queue is all zeros (what a fused launch needs and leaves behind)
     bool parts_empty = false;           // every slot of d_partB / d_partR is lf::PART_EMPTY (what the polling hand-over needs and leaves behind, lf_tile.h)
     int* d_err = nullptr;               // device error word (a finisher gave up polling)
+    // lf_free's one-launch form reads its launch-invariant arguments from a block in device memory (lf_free.h: FreeBlock), one
+    // per sources-per-lane slot (the chunk tables depend on it); the pinned shadow holds what was last uploaded: an upload
+    // only when the bytes change (free_block)
+    lf::FreeBlock* d_fblk[3] = {nullptr, nullptr, nullptr};
+    lf::FreeBlock* h_fblk[3] = {nullptr, nullptr, nullptr};
+    bool fblk_valid[3] = {false, false, false};
+    int64_t fblk_uploads = 0;           // uploads so far (lf_free_block_uploads: the tests' debug counter)
     int64_t opt_poll = 1;               // 0: the one-launch form hands over through the tile's counter only (A/B runs)
     int64_t opt_free_st = 0;            // lf_free: sources per lane, 0 = chosen from N and B, else 2 / 4 / 8 (tuning runs)
     int64_t opt_geometry = -1;          // index into GEOS, -1 = auto
@@ -618,11 +625,12 @@ int free_groups(lf_ctx* c, int slot, int ntiles, int nchA, int nchB, int nchC) {
     using namespace lf;
     if (c->slots_free[slot] == 0) {
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, lf_free<ST, false>, PB, 0) != hipSuccess || nb < 1) nb = 1;
+        auto* k = static_cast<void (*)(KConst, SrcArrays, NodeArrays, const double*, const int*, FreeArgs)>(lf_free<ST, false>);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, PB, 0) != hipSuccess || nb < 1) nb = 1;
         c->slots_free[slot] = nb * std::max(c->num_cu, 1);
         if (std::getenv("LF_DEBUG_OCC")) {
             hipFuncAttributes at{};
-            hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&lf_free<ST, false>));
+            hipFuncGetAttributes(&at, reinterpret_cast<const void*>(k));
             std::fprintf(stderr, "lf_free<%d>: %d workgroups per CU (occupancy API), %d VGPRs, %zu B LDS\n", ST, nb, at.numRegs, at.sharedSizeBytes);
         }
     }
@@ -735,16 +743,60 @@ int ready_tiles(lf_ctx* c, hipStream_t s, bool fused, bool poll) {
     return LF_OK;
 }
 
+// The one-launch lf_free's block (lf_free.h: FreeBlock) of this slot, made anew at every enqueue and uploaded only when its bytes
+// differ from the shadow's: the first use, a reallocated buffer (ensure_workspace / ensure_queue / ensure_deal), an option
+// that changes KConst or FreeArgs (cells, tables, specialise, grid_shortcut, skip_grid, poll, the stamps pointer).  The copy
+// is ordered on the launch's stream, like the launch (legal under stream capture); the shadow it reads from is not rewritten
+// before that copy is done.  The block's per-launch fields are zero: the kernel takes them from its FreeLaunch.
+int free_block(lf_ctx* c, int slot, const lf::SrcArrays& sa, const lf::NodeArrays& na, const lf::FreeArgs& fa, hipStream_t s) {
+    using namespace lf;
+    // The bytes are compared, padding included: the block is zeroed and filled member by member (a copy of a whole struct made
+    // on the stack would bring its padding's garbage along - and an upload with every call).  c->kc is zero-initialised with
+    // the context and only ever written member by member.
+    FreeBlock b;
+    std::memset(&b, 0, sizeof(b));
+    std::memcpy(&b.kc, &c->kc, sizeof(KConst));
+    b.sa = sa;                          // (pointers only: no padding)
+    static_assert(sizeof(SrcArrays) == 10 * sizeof(void*), "SrcArrays has no padding");
+    b.na.G = na.G, b.na.PG = na.PG, b.na.W = na.W, b.na.a3 = na.a3, b.na.a4 = na.a4, b.na.a4min = na.a4min, b.na.nnodes = na.nnodes;
+    FreeArgs& d = b.fa;                 // (theta, out, B, ntiles, tile_stride stay zero: the kernel takes them from its FreeLaunch)
+    d.nchA = fa.nchA, d.nchB = fa.nchB, d.nslot = fa.nslot, d.skip_grid = fa.skip_grid;
+    d.queues = fa.queues, d.partA = fa.partA, d.partB = fa.partB, d.cells = fa.cells, d.nodes8 = fa.nodes8, d.deal = fa.deal;
+    d.cc_len = fa.cc_len, d.cc_field = fa.cc_field, d.nchC = fa.nchC, d.partC = fa.partC, d.wstat = fa.wstat;
+    d.wrec_w = fa.wrec_w, d.wmode_w = fa.wmode_w, d.wstat_w = fa.wstat_w, d.wbase_w = fa.wbase_w;
+    d.gq_rec = fa.gq_rec, d.gq_omega = fa.gq_omega, d.gq_rows = fa.gq_rows, d.nbq = fa.nbq, d.poll = fa.poll, d.err = fa.err;
+    static_assert(sizeof(FreeArgs) == 208 && sizeof(NodeArrays) == 56, "a field was added: copy it above");
+    if (c->fblk_valid[slot] && std::memcmp(c->h_fblk[slot], &b, sizeof(b)) == 0) return LF_OK;
+    constexpr size_t bytes = (sizeof(FreeBlock) + 255) / 256 * 256;
+    if (!c->d_fblk[slot]) {
+        LF_HIP(c, hipMalloc((void**)&c->d_fblk[slot], bytes));
+        LF_HIP(c, hipHostMalloc((void**)&c->h_fblk[slot], bytes, hipHostMallocDefault));
+    } else {
+        // the previous upload may still be reading the shadow (nothing to wait for inside a capture: it began on an idle device)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        LF_HIP(c, hipStreamIsCapturing(s, &cs));
+        if (cs == hipStreamCaptureStatusNone) LF_HIP(c, hipStreamSynchronize(s));
+    }
+    std::memcpy(c->h_fblk[slot], &b, sizeof(b));
+    LF_HIP(c, hipMemcpyAsync(c->d_fblk[slot], c->h_fblk[slot], sizeof(b), hipMemcpyHostToDevice, s));
+    c->fblk_valid[slot] = true;
+    ++c->fblk_uploads;
+    return LF_OK;
+}
+
 template <int ST>
 void launch_free(lf_ctx* c, int slot, int B, int ntiles, const lf::SrcArrays& sa, const lf::NodeArrays& na, lf::FreeArgs fa, hipStream_t s,
                  bool fused, const lf::StepArgs* sp = nullptr, const lf::AcceptArgs* ap = nullptr) {
-    // (fa.nslot is set by the caller from free_groups(), which is also what the grid is made of here)
+    // (fa.nslot is set by the caller from free_groups(), which is also what the grid is made of here; fused without sp: the
+    // caller has brought the slot's block up to date, free_block)
     using namespace lf;
     const dim3 grid((unsigned)(8 * fa.tile_stride));
     const int info[8] = {ST, PTW, PTW, fused ? 3 : 2, (int)grid.x, fa.nchA, fa.nchB, B};
     std::memcpy(c->last_launch, info, sizeof(info));
     if (fused && sp) hipLaunchKernelGGL((lf_free_step<ST>), grid, dim3(PB), 0, s, c->kc, sa, na, fa, *sp, *ap);      // the sampler's half-step
-    else if (fused) hipLaunchKernelGGL((lf_free<ST, false, true>), grid, dim3(PB), 0, s, c->kc, sa, na, c->d_wrec, c->d_wmode, fa);
+    else if (fused)
+        hipLaunchKernelGGL((lf_free<ST, false, true>), grid, dim3(PB), 0, s, (FreeBlockPtr)c->d_fblk[slot],
+                           FreeLaunch{fa.theta, fa.out, fa.B, fa.ntiles, fa.tile_stride});
     else if (c->kc.forms) hipLaunchKernelGGL((lf_free<ST, true>), grid, dim3(PB), 0, s, c->kc, sa, na, c->d_wrec, c->d_wmode, fa);
     else hipLaunchKernelGGL((lf_free<ST, false>), grid, dim3(PB), 0, s, c->kc, sa, na, c->d_wrec, c->d_wmode, fa);
 }
@@ -791,6 +843,7 @@ int enqueue_free(lf_ctx* c, const double* d_theta, int B, double* d_out, double*
                 d_theta, d_out, c->d_wrec, c->d_wmode, c->d_wstat, c->d_wbase,
                 gq ? c->gridq.d_rec : nullptr, gq ? c->gridq.d_omega : nullptr, gq ? c->gridq.d_rows : nullptr, gq ? c->gridq.nb : 0,
                 poll ? 1 : 0, c->d_err};
+    if (fused && !stepf && (rc = free_block(c, slot, sa, na, fa, s)) != LF_OK) return rc;      // (outside the launch's event pair)
     {
         Prof p(c, s, 1);
         if (nchA + nchB > 0) {
@@ -1230,6 +1283,10 @@ void free_ctx(lf_ctx* c) {
     if (c->d_cc_start) hipFree(c->d_cc_start);
     if (c->d_deal) hipFree(c->d_deal);
     if (c->d_err) hipFree(c->d_err);
+    for (int i = 0; i < 3; ++i) {
+        if (c->d_fblk[i]) hipFree(c->d_fblk[i]);
+        if (c->h_fblk[i]) hipHostFree(c->h_fblk[i]);
+    }
     if (c->d_cc_len) hipFree(c->d_cc_len);
     if (c->d_cc_field) hipFree(c->d_cc_field);
     {
@@ -1990,6 +2047,12 @@ int lf_lumfunc_quantiles_ms(double* ms) {
 int lf_last_launch(const lf_ctx* c, int32_t info[8]) {
     if (!c || !info) return LF_ERR_ARG;
     for (int i = 0; i < 8; ++i) info[i] = c->last_launch[i];
+    return LF_OK;
+}
+
+int lf_free_block_uploads(const lf_ctx* c, int64_t* n) {
+    if (!c || !n) return LF_ERR_ARG;
+    *n = c->fblk_uploads;
     return LF_OK;
 }
 
