@@ -350,6 +350,35 @@ int lf_lumfunc_quantiles(int device, int variant, int32_t R, const double *draws
  * around the launch; measurement only).  LF_ERR_ARG when there is none. */
 int lf_lumfunc_quantiles_ms(double *ms);
 
+/* Mock catalogues drawn from the model on the device (csrc/lf_mock.h).  The intensity is the
+ * likelihood's own interpolant: the trapezoid sum of piece B over the integration grid is exactly the integral of
+ * f_f(z, L) = sum_{j,k} lambda_f[j][k] hat_k(z) hat_{j,k}(L), so the expected count M_f of field f sums to piece B of
+ * lf_lnprob_pieces over the fields.  A mock is the Poisson process of that intensity: n_f ~ Poisson(M_f) exactly, then
+ * each source picks a grid node with probability mass / M_f and inverts the two hat functions.  Philox4x32-10 keyed by
+ * seed; a row's catalogue depends only on (seed, row_ids[r], theta row r), never on R or the row's position.
+ * The handle reads only the grid and model fields of `desc` (variant, fix_sch_al, sch_al0, nf, S, logL, zarr, volume_part,
+ * dl_zarr, integ_part, omega0, fcmin, pivots, device; the catalogue arrays may be NULL and N may be 0).
+ * theta: host [R][ndim] (the context's layout; any finite values), row_ids: host [R] or NULL (= 0 .. R-1).  Every call is
+ * synchronous.  LF_ERR_ARG, with lf_mock_last_error saying why, for: a NULL pointer, R <= 0, a non-finite theta, an
+ * expected count that is not finite, negative or above 2^31 (the message names the row and field), a count < 0 or
+ * >= 2^32, nbins outside 1..1022, edges that are not finite and non-decreasing.  The handle stays usable after an error. */
+typedef struct lf_mock lf_mock;
+lf_mock *lf_mock_create(const lf_desc *desc);
+void lf_mock_destroy(lf_mock *m);
+/* mean, count: [R][nf] expected counts M and their Poisson draws n */
+int lf_mock_counts(lf_mock *m, const double *theta, int32_t R, const int64_t *row_ids, uint64_t seed, double *mean, int64_t *count);
+/* the sources of every (row, field) in that order, count[r][f] of them (what lf_mock_counts returned; any count gives the
+ * leading sources of the same stream): z, logL, field of length sum(count) */
+int lf_mock_draw(lf_mock *m, const double *theta, int32_t R, const int64_t *row_ids, uint64_t seed, const int64_t *count,
+                 double *z, double *logL, int32_t *field);
+/* histogram of logL per (row, field) of the catalogue lf_mock_draw would write, without writing sources:
+ * slot = searchsorted(edges, x, side="right"): 0 = below edges[0], nbins + 1 = at or above edges[nbins];
+ * edges [nbins + 1], hist [R][nf][nbins + 2] */
+int lf_mock_hist(lf_mock *m, const double *theta, int32_t R, const int64_t *row_ids, uint64_t seed, int32_t nbins,
+                 const double *edges, int64_t *hist);
+/* Last error of this handle; m == NULL: of the last failed lf_mock_create.  Never NULL. */
+const char *lf_mock_last_error(const lf_mock *m);
+
 /* Last error message of this context (or of lf_create when ctx == NULL).  Never NULL. */
 const char *lf_last_error(const lf_ctx *ctx);
 

@@ -48,7 +48,8 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_sampler_half_accept", "lf_compress_keys", "lf_compress_grid", "lf_grid_bins", "lf_deal_table", "lf_form_counts", "lf_last_launch",
            "lf_free_block_uploads", "lf_veff",
            "lf_lumfunc_quantiles", "lf_lumfunc_quantiles_ms", "lf_ptsampler_create", "lf_ptsampler_destroy",
-           "lf_ptsampler_start", "lf_ptsampler_run", "lf_ptsampler_read", "lf_ptsampler_steps")
+           "lf_ptsampler_start", "lf_ptsampler_run", "lf_ptsampler_read", "lf_ptsampler_steps", "lf_mock_create",
+           "lf_mock_destroy", "lf_mock_counts", "lf_mock_draw", "lf_mock_hist", "lf_mock_last_error")
 
 _lib = None
 
@@ -151,6 +152,20 @@ def load():
                                       _c_double_p]
     lib.lf_ptsampler_steps.restype = ctypes.c_int64
     lib.lf_ptsampler_steps.argtypes = [ctypes.c_void_p]
+    lib.lf_mock_create.restype = ctypes.c_void_p
+    lib.lf_mock_create.argtypes = [ctypes.POINTER(LfDesc)]
+    lib.lf_mock_destroy.restype = None
+    lib.lf_mock_destroy.argtypes = [ctypes.c_void_p]
+    lib.lf_mock_counts.restype = ctypes.c_int
+    lib.lf_mock_counts.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int32, _c_int64_p, ctypes.c_uint64, _c_double_p, _c_int64_p]
+    lib.lf_mock_draw.restype = ctypes.c_int
+    lib.lf_mock_draw.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int32, _c_int64_p, ctypes.c_uint64, _c_int64_p, _c_double_p,
+                                 _c_double_p, ctypes.POINTER(ctypes.c_int32)]
+    lib.lf_mock_hist.restype = ctypes.c_int
+    lib.lf_mock_hist.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int32, _c_int64_p, ctypes.c_uint64, ctypes.c_int32, _c_double_p,
+                                 _c_int64_p]
+    lib.lf_mock_last_error.restype = ctypes.c_char_p
+    lib.lf_mock_last_error.argtypes = [ctypes.c_void_p]
     lib.lf_compress_keys.restype = ctypes.c_int64
     lib.lf_compress_keys.argtypes = [ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int64,
                                      _c_double_p, _c_double_p, ctypes.c_int64, _c_double_p]

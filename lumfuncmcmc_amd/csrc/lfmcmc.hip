@@ -21,6 +21,7 @@
 #include "lf_gridbound.h"
 #include "lf_kernels.h"
 #include "lf_free.h"
+#include "lf_mock.h"
 #include "lf_pers.h"
 #include "lf_pt.h"
 
@@ -2612,5 +2613,287 @@ int lf_ptsampler_read(lf_ptsampler* sm, double* chain, double* chain_lnlike, dou
 }
 
 int64_t lf_ptsampler_steps(const lf_ptsampler* sm) { return sm ? sm->t : LF_ERR_ARG; }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Mock catalogues (csrc/lf_mock.h).  Rows go through the kernels in chunks of `rch` (the cumulative
+// sums of a chunk fit a fixed workspace budget); each row's work is independent of the chunk it is in.
+// ------------------------------------------------------------------------------------------------------------------------
+struct lf_mock {
+    int device = 0;
+    lf::MockConst mc{};
+    int rch = 1;                          // rows per chunk
+    double* d_grid[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // logL, zarr, volume_part, dl_zarr, integ_part
+    double *d_theta = nullptr, *d_cdfL = nullptr, *d_colm = nullptr, *d_cdfZ = nullptr, *d_mean = nullptr;
+    long long *d_rid = nullptr, *d_count = nullptr, *d_off = nullptr;
+    double *d_z = nullptr, *d_L = nullptr, *d_edges = nullptr;
+    int* d_fld = nullptr;
+    unsigned long long* d_hist = nullptr;
+    int64_t cap_src = 0, cap_hist = 0;
+    std::string err;
+};
+
+namespace {
+
+thread_local std::string g_mock_create_error = "";
+constexpr size_t MOCK_WORKSPACE = (size_t)512 << 20;      // bytes of cumulative sums per chunk of rows
+
+void mock_free(lf_mock* m) {
+    if (!m) return;
+    for (double* p : m->d_grid) hipFree(p);
+    hipFree(m->d_theta); hipFree(m->d_cdfL); hipFree(m->d_colm); hipFree(m->d_cdfZ); hipFree(m->d_mean);
+    hipFree(m->d_rid); hipFree(m->d_count); hipFree(m->d_off); hipFree(m->d_z); hipFree(m->d_L); hipFree(m->d_edges);
+    hipFree(m->d_fld); hipFree(m->d_hist);
+    delete m;
+}
+
+int mock_fail(lf_mock* m, const char* fn, const std::string& msg) {
+    m->err = std::string(fn) + ": " + msg;
+    return LF_ERR_ARG;
+}
+
+// the arguments every call shares; row r's theta must be finite
+int mock_check(lf_mock* m, const char* fn, const double* theta, int32_t R) {
+    if (R <= 0) return mock_fail(m, fn, "R must be >= 1");
+    if (!theta) return mock_fail(m, fn, "theta is NULL");
+    const int nd = m->mc.ndim;
+    for (int32_t r = 0; r < R; ++r)
+        for (int d = 0; d < nd; ++d)
+            if (!std::isfinite(theta[(size_t)r * nd + d]))
+                return mock_fail(m, fn, "row " + std::to_string(r) + ": theta is not finite");
+    m->err.clear();
+    return LF_OK;
+}
+
+// masses, cumulative sums, means and counts of rows r0 .. r0 + n - 1 (device), means / counts copied to the host
+int mock_masses(lf_mock* m, const char* fn, const double* theta, int32_t r0, int n, const int64_t* row_ids, uint64_t seed,
+                std::vector<double>& mean, std::vector<long long>& count) {
+    const int nf = m->mc.nf, S = m->mc.S, nd = m->mc.ndim;
+    std::vector<long long> rid((size_t)n);
+    for (int i = 0; i < n; ++i) rid[(size_t)i] = row_ids ? (long long)row_ids[r0 + i] : (long long)(r0 + i);
+    LF_HIP(m, hipMemcpy(m->d_theta, theta + (size_t)r0 * nd, (size_t)n * nd * sizeof(double), hipMemcpyHostToDevice));
+    LF_HIP(m, hipMemcpy(m->d_rid, rid.data(), (size_t)n * sizeof(long long), hipMemcpyHostToDevice));
+    const int nrf = n * nf;
+    hipLaunchKernelGGL(lf::lf_mock_mass, dim3((unsigned)S, (unsigned)nrf), dim3(lf::MOCK_THREADS), 0, 0, m->mc, m->d_theta, m->d_cdfL,
+                       m->d_colm);
+    LF_HIP(m, hipGetLastError());
+    hipLaunchKernelGGL(lf::lf_mock_total, dim3((unsigned)nrf), dim3(lf::MOCK_THREADS), 0, 0, S, nf, m->d_colm, m->d_rid,
+                       (unsigned long long)seed, m->d_cdfZ, m->d_mean, m->d_count);
+    LF_HIP(m, hipGetLastError());
+    mean.resize((size_t)nrf);
+    count.resize((size_t)nrf);
+    LF_HIP(m, hipMemcpy(mean.data(), m->d_mean, (size_t)nrf * sizeof(double), hipMemcpyDeviceToHost));
+    LF_HIP(m, hipMemcpy(count.data(), m->d_count, (size_t)nrf * sizeof(long long), hipMemcpyDeviceToHost));
+    for (int i = 0; i < nrf; ++i)
+        if (count[(size_t)i] < 0) {
+            char b[160];
+            std::snprintf(b, sizeof b, "row %d field %d: expected count %.17g is not finite, negative or above 2^31", r0 + i / nf, i % nf,
+                          mean[(size_t)i]);
+            return mock_fail(m, fn, b);
+        }
+    return LF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+lf_mock* lf_mock_create(const lf_desc* d) {
+    g_mock_create_error.clear();
+    auto bad = [&](const std::string& msg) {
+        g_mock_create_error = "lf_mock_create: " + msg;
+        return (lf_mock*)nullptr;
+    };
+    if (!d) return bad("NULL descriptor");
+    if (d->variant < LF_FREE || d->variant > LF_ZEVOL) return bad("unknown variant");
+    if (d->nf < 1 || d->nf > LF_MAX_FIELDS) return bad("nf out of range (1..LF_MAX_FIELDS)");
+    if (d->S < 2 || d->S > 4096) return bad("S out of range");
+    if (!d->logL || !d->zarr) return bad("NULL logL/zarr");
+    if (d->variant == LF_FREE) {
+        if (!d->volume_part || !d->dl_zarr || !d->omega0) return bad("FREE needs volume_part, dl_zarr, omega0");
+        if (!(d->fcmin > 0.0 && d->fcmin < 1.0) || d->fcmin == 0.5) return bad("fcmin must be in (0,1), != 0.5");
+    } else {
+        if (!d->integ_part) return bad("FIXCOMP/ZEVOL need integ_part");
+        if (d->variant == LF_ZEVOL && (d->pivots[0] == d->pivots[1] || d->pivots[0] == d->pivots[2] || d->pivots[1] == d->pivots[2]))
+            return bad("ZEVOL pivots must be distinct");
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return bad("no HIP device visible");
+    if (d->device < 0 || d->device >= ndev) return bad("device ordinal out of range");
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, d->device) != hipSuccess) return bad("hipGetDeviceProperties failed");
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return bad(std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+    if (hipSetDevice(d->device) != hipSuccess) return bad("hipSetDevice failed");
+    lf_mock* m = new (std::nothrow) lf_mock();
+    if (!m) return bad("out of host memory");
+    m->device = d->device;
+    lf::MockConst& mc = m->mc;
+    const int S = d->S, nf = d->nf;
+    mc.variant = d->variant;
+    mc.fix_sch_al = d->fix_sch_al ? 1 : 0;
+    mc.nf = nf;
+    mc.S = S;
+    mc.ndim = d->variant == LF_ZEVOL ? 6 + (mc.fix_sch_al ? 0 : 1) : 2 + (mc.fix_sch_al ? 0 : 1) + (d->variant == LF_FREE ? nf + 1 : 0);
+    mc.sch_al0 = d->sch_al0;
+    const double sq = 180.0 / M_PI * 3600.0, sqarcsec = sq * sq;       // VmaxLumFunc.py:43
+    for (int f = 0; f < nf; ++f) mc.om0s[f] = d->variant == LF_FREE ? d->omega0[f] / sqarcsec : 0.0;
+    if (d->variant == LF_FREE) {
+        const double a = (2.0 * d->fcmin - 1.0) * (2.0 * d->fcmin - 1.0);
+        mc.fc_ratio = std::fabs(a / (1.0 - a));
+    }
+    for (int i = 0; i < 3; ++i) mc.pivots[i] = d->pivots[i];
+    const size_t SS = (size_t)S * S;
+    const double* src[5] = {d->logL, d->zarr, d->variant == LF_FREE ? d->volume_part : nullptr,
+                            d->variant == LF_FREE ? d->dl_zarr : nullptr, d->variant == LF_FREE ? nullptr : d->integ_part};
+    const size_t len[5] = {SS, (size_t)S, (size_t)S, (size_t)S, (size_t)nf * SS};
+    const size_t per_rf = SS + 2 * (size_t)S;           // doubles of cumulative sums per (row, field)
+    m->rch = (int)std::max<size_t>(1, std::min<size_t>(1024, MOCK_WORKSPACE / (per_rf * nf * sizeof(double))));
+    const size_t nrf = (size_t)m->rch * nf;
+    bool ok = true;
+    for (int i = 0; i < 5 && ok; ++i)
+        if (src[i])
+            ok = hipMalloc((void**)&m->d_grid[i], len[i] * sizeof(double)) == hipSuccess &&
+                 hipMemcpy(m->d_grid[i], src[i], len[i] * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMalloc((void**)&m->d_theta, (size_t)m->rch * mc.ndim * sizeof(double)) == hipSuccess &&
+         hipMalloc((void**)&m->d_rid, (size_t)m->rch * sizeof(long long)) == hipSuccess &&
+         hipMalloc((void**)&m->d_cdfL, nrf * SS * sizeof(double)) == hipSuccess &&
+         hipMalloc((void**)&m->d_colm, nrf * S * sizeof(double)) == hipSuccess &&
+         hipMalloc((void**)&m->d_cdfZ, nrf * S * sizeof(double)) == hipSuccess &&
+         hipMalloc((void**)&m->d_mean, nrf * sizeof(double)) == hipSuccess &&
+         hipMalloc((void**)&m->d_count, nrf * sizeof(long long)) == hipSuccess &&
+         hipMalloc((void**)&m->d_off, (nrf + 1) * sizeof(long long)) == hipSuccess &&
+         hipMalloc((void**)&m->d_edges, (lf::MOCK_MAX_BINS + 1) * sizeof(double)) == hipSuccess;
+    if (!ok) {
+        mock_free(m);
+        return bad("device allocation or copy failed");
+    }
+    mc.logL = m->d_grid[0];
+    mc.zarr = m->d_grid[1];
+    mc.volume_part = m->d_grid[2];
+    mc.dl_zarr = m->d_grid[3];
+    mc.integ_part = m->d_grid[4];
+    return m;
+}
+
+void lf_mock_destroy(lf_mock* m) {
+    if (m) hipSetDevice(m->device);
+    mock_free(m);
+}
+
+const char* lf_mock_last_error(const lf_mock* m) { return m ? m->err.c_str() : g_mock_create_error.c_str(); }
+
+int lf_mock_counts(lf_mock* m, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed, double* mean, int64_t* count) {
+    static const char* fn = "lf_mock_counts";
+    if (!m) return LF_ERR_ARG;
+    int rc = mock_check(m, fn, theta, R);
+    if (rc != LF_OK) return rc;
+    if (!mean || !count) return mock_fail(m, fn, "mean or count is NULL");
+    LF_HIP(m, hipSetDevice(m->device));
+    const int nf = m->mc.nf;
+    std::vector<double> mu;
+    std::vector<long long> n;
+    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
+        const int rows = std::min<int32_t>(m->rch, R - r0);
+        if ((rc = mock_masses(m, fn, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
+        for (size_t i = 0; i < mu.size(); ++i) {
+            mean[(size_t)r0 * nf + i] = mu[i];
+            count[(size_t)r0 * nf + i] = n[i];
+        }
+    }
+    return LF_OK;
+}
+
+int lf_mock_draw(lf_mock* m, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed, const int64_t* count, double* z,
+                 double* logL, int32_t* field) {
+    static const char* fn = "lf_mock_draw";
+    if (!m) return LF_ERR_ARG;
+    int rc = mock_check(m, fn, theta, R);
+    if (rc != LF_OK) return rc;
+    if (!count) return mock_fail(m, fn, "count is NULL");
+    const int nf = m->mc.nf;
+    int64_t total = 0;
+    for (int64_t i = 0; i < (int64_t)R * nf; ++i) {
+        if (count[i] < 0 || count[i] > (int64_t)UINT32_MAX)
+            return mock_fail(m, fn, "row " + std::to_string(i / nf) + " field " + std::to_string(i % nf) + ": count out of range");
+        total += count[i];
+    }
+    if (total > 0 && (!z || !logL || !field)) return mock_fail(m, fn, "z, logL or field is NULL");
+    LF_HIP(m, hipSetDevice(m->device));
+    std::vector<double> mu;
+    std::vector<long long> n, off;
+    int64_t done = 0;
+    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
+        const int rows = std::min<int32_t>(m->rch, R - r0);
+        const int nrf = rows * nf;
+        off.assign((size_t)nrf + 1, 0);
+        for (int i = 0; i < nrf; ++i) off[(size_t)i + 1] = off[(size_t)i] + count[(size_t)r0 * nf + i];
+        const int64_t tot = off[(size_t)nrf];
+        if (tot == 0) continue;
+        if ((rc = mock_masses(m, fn, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
+        if (tot > m->cap_src) {
+            hipFree(m->d_z); hipFree(m->d_L); hipFree(m->d_fld);
+            m->d_z = m->d_L = nullptr;
+            m->d_fld = nullptr;
+            m->cap_src = 0;
+            LF_HIP(m, hipMalloc((void**)&m->d_z, (size_t)tot * sizeof(double)));
+            LF_HIP(m, hipMalloc((void**)&m->d_L, (size_t)tot * sizeof(double)));
+            LF_HIP(m, hipMalloc((void**)&m->d_fld, (size_t)tot * sizeof(int)));
+            m->cap_src = tot;
+        }
+        LF_HIP(m, hipMemcpy(m->d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(lf::lf_mock_draw, dim3((unsigned)((tot + lf::MOCK_THREADS - 1) / lf::MOCK_THREADS)), dim3(lf::MOCK_THREADS), 0, 0,
+                           m->mc, nrf, m->d_off, m->d_rid, (unsigned long long)seed, m->d_cdfL, m->d_cdfZ, m->d_z, m->d_L, m->d_fld);
+        LF_HIP(m, hipGetLastError());
+        LF_HIP(m, hipMemcpy(z + done, m->d_z, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
+        LF_HIP(m, hipMemcpy(logL + done, m->d_L, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
+        LF_HIP(m, hipMemcpy(field + done, m->d_fld, (size_t)tot * sizeof(int), hipMemcpyDeviceToHost));
+        done += tot;
+    }
+    return LF_OK;
+}
+
+int lf_mock_hist(lf_mock* m, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed, int32_t nbins, const double* edges,
+                 int64_t* hist) {
+    static const char* fn = "lf_mock_hist";
+    if (!m) return LF_ERR_ARG;
+    int rc = mock_check(m, fn, theta, R);
+    if (rc != LF_OK) return rc;
+    if (nbins < 1 || nbins > lf::MOCK_MAX_BINS)
+        return mock_fail(m, fn, "nbins must be in 1.." + std::to_string(lf::MOCK_MAX_BINS));
+    if (!edges || !hist) return mock_fail(m, fn, "edges or hist is NULL");
+    for (int i = 0; i <= nbins; ++i)
+        if (!std::isfinite(edges[i]) || (i > 0 && !(edges[i] >= edges[i - 1])))
+            return mock_fail(m, fn, "edges must be finite and non-decreasing");
+    LF_HIP(m, hipSetDevice(m->device));
+    LF_HIP(m, hipMemcpy(m->d_edges, edges, (size_t)(nbins + 1) * sizeof(double), hipMemcpyHostToDevice));
+    const int nf = m->mc.nf, ns = nbins + 2;
+    std::vector<double> mu;
+    std::vector<long long> n, blk;
+    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
+        const int rows = std::min<int32_t>(m->rch, R - r0);
+        const int nrf = rows * nf;
+        if ((rc = mock_masses(m, fn, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
+        if ((int64_t)nrf * ns > m->cap_hist) {
+            hipFree(m->d_hist);
+            m->d_hist = nullptr;
+            m->cap_hist = 0;
+            LF_HIP(m, hipMalloc((void**)&m->d_hist, (size_t)nrf * ns * sizeof(unsigned long long)));
+            m->cap_hist = (int64_t)nrf * ns;
+        }
+        blk.assign((size_t)nrf + 1, 0);
+        for (int i = 0; i < nrf; ++i) blk[(size_t)i + 1] = blk[(size_t)i] + (n[(size_t)i] + lf::MOCK_HIST_CHUNK - 1) / lf::MOCK_HIST_CHUNK;
+        LF_HIP(m, hipMemset(m->d_hist, 0, (size_t)nrf * ns * sizeof(unsigned long long)));
+        if (blk[(size_t)nrf] > 0) {
+            LF_HIP(m, hipMemcpy(m->d_off, blk.data(), blk.size() * sizeof(long long), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(lf::lf_mock_hist, dim3((unsigned)blk[(size_t)nrf]), dim3(lf::MOCK_THREADS), 0, 0, m->mc, nrf, m->d_off,
+                               m->d_count, m->d_rid, (unsigned long long)seed, m->d_cdfL, m->d_cdfZ, nbins, m->d_edges, m->d_hist);
+            LF_HIP(m, hipGetLastError());
+        }
+        LF_HIP(m, hipMemcpy(hist + (size_t)r0 * nf * ns, m->d_hist, (size_t)nrf * ns * sizeof(int64_t), hipMemcpyDeviceToHost));
+    }
+    return LF_OK;
+}
 
 }  // extern "C"

@@ -1,0 +1,497 @@
+"""Mock catalogues drawn from the model, and posterior predictive checks.
+
+The intensity is the likelihood's own interpolant.  For a theta row and field f, piece B of lnprob is the trapezoid sum
+trapz(trapz(lambda_f, logL, axis=0), zarr) on the integration grid, and that sum is exactly the integral of
+
+    f_f(z, L) = sum_{j,k} lambda_f[j, k] hat_k(z) hat_{j,k}(L)
+
+(unit hat functions on zarr and on column k's own luminosity nodes).  A mock catalogue is the Poisson process of intensity
+f_f in every field: n_f ~ Poisson(M_f) with M_f = sum m_f[j, k], m = (w_z[k] w_L[j, k]) lambda_f[j, k]; every source picks
+node (j, k) with probability m / M_f (cumulative sums column k major, then j) and inverts the two hats.  Random numbers are
+Philox4x32-10 keyed by the seed, counter (row_id, index, stream word) - csrc/lf_mock.h states the streams.
+
+`MockTwin` is that algorithm in NumPy (the tests' reference; it runs anywhere), `MockGenerator` the same on the GPU through
+the C ABI (lf_mock_*).  Both take the dict of `kernel_inputs()` that LFContext takes, and both give a row's catalogue as
+a function of (seed, row_id, theta) only.
+"""
+import ctypes
+
+import numpy as np
+
+from . import hostsetup as hs
+from . import philox
+
+TAG = 0x6d6f0000              # the Philox stream word of the mocks (lf_mock.h: MOCK_TAG)
+MAX_MEAN = 2.0 ** 31          # expected sources per (row, field) above which a call is refused
+MAX_BINS = 1022               # lf_mock_hist's limit on nbins
+SCAN_TILE = 256
+_LG2PI = 1.8378770664093453e+00
+_LOGGAM_A = (8.333333333333333e-02, -2.777777777777778e-03, 7.936507936507937e-04, -5.952380952380952e-04,
+             8.417508417508418e-04, -1.917526917526918e-03, 6.410256410256410e-03, -2.955065359477124e-02,
+             1.796443723688307e-01, -1.39243221690590e+00)
+
+
+class MockError(ValueError):
+    pass
+
+
+def _ndim(variant, fix_sch_al, nf):
+    if variant == "zevol":
+        return 6 + (0 if fix_sch_al else 1)
+    return 2 + (0 if fix_sch_al else 1) + (nf + 1 if variant == "free" else 0)
+
+
+def _integ_part(inp, nf, S):
+    ip = inp.get("integ_part")
+    if ip is None:            # a field-summed table: field 0 carries the sum (as LFContext)
+        ip = np.zeros((nf, S, S))
+        ip[0] = inp["integ_sum"]
+    return np.ascontiguousarray(ip, dtype=np.float64)
+
+
+def _rows(thetas, ndim):
+    th = np.ascontiguousarray(np.atleast_2d(np.asarray(thetas, dtype=np.float64)))
+    if th.ndim != 2 or th.shape[1] != ndim or th.shape[0] < 1:
+        raise ValueError("thetas must be (R, %d) with R >= 1, got %s" % (ndim, th.shape))
+    return th
+
+
+def _row_ids(row_ids, R):
+    if row_ids is None:
+        return np.arange(R, dtype=np.int64)
+    rid = np.ascontiguousarray(np.asarray(row_ids, dtype=np.int64).ravel())
+    if rid.size != R:
+        raise ValueError("row_ids must have one entry per row")
+    return rid
+
+
+# ----------------------------------------------------------------------------------------------------------- NumPy pieces
+def scan(x):
+    """Inclusive prefix sums along the last axis in lf_mock.h's order: tiles of 256, a Hillis-Steele scan of each tile
+    (x[t] = x[t - d] + x[t], d = 1, 2, .., 128) plus the total of the tiles before it.  Returns (prefix sums, total);
+    the total is the running sum of the tile totals (the scan's last lane), which may differ from the last prefix sum
+    in the last bit."""
+    x = np.asarray(x, dtype=np.float64)
+    n = x.shape[-1]
+    out = np.empty_like(x)
+    carry = np.zeros(x.shape[:-1])
+    for base in range(0, n, SCAN_TILE):
+        w = min(SCAN_TILE, n - base)
+        t = np.zeros(x.shape[:-1] + (SCAN_TILE,))
+        t[..., :w] = x[..., base:base + w]
+        d = 1
+        while d < SCAN_TILE:
+            t[..., d:] = t[..., :-d] + t[..., d:]
+            d <<= 1
+        out[..., base:base + w] = carry[..., None] + t[..., :w]
+        carry = carry + t[..., SCAN_TILE - 1]
+    return out, carry
+
+
+def trapz_weights(x, axis=0):
+    """Trapezoid weight of every node along `axis`: half the spacing to each neighbour (0.5 (left + right))."""
+    x = np.moveaxis(np.asarray(x, dtype=np.float64), axis, 0)
+    d = np.diff(x, axis=0)
+    zero = np.zeros((1,) + x.shape[1:])
+    left = np.concatenate([zero, d], axis=0)
+    right = np.concatenate([d, zero], axis=0)
+    return np.moveaxis(0.5 * (left + right), 0, axis)
+
+
+def hat_inverse(x0, a, b, u):
+    """Inverse CDF of the unit hat with left width a, right width b, peak x0 (a width of 0: no mass on that side)."""
+    x0, a, b, u = (np.asarray(v, dtype=np.float64) for v in (x0, a, b, u))
+    with np.errstate(all="ignore"):
+        ab = a + b
+        left = u < a / ab
+        xl = x0 - a * (1.0 - np.sqrt(u * ab / a))
+        xr = x0 + b * (1.0 - np.sqrt((1.0 - u) * ab / b))
+    return np.where(left, xl, xr)
+
+
+def _words(row_ids, index, purpose, f, seed):
+    rid = np.asarray(row_ids, dtype=np.int64).astype(np.uint64)
+    idx = np.asarray(index, dtype=np.uint64)
+    rid, idx, ff = np.broadcast_arrays(rid, idx, np.asarray(f, dtype=np.uint64))
+    c3 = np.uint64(TAG | (purpose << 8)) | ff
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return philox.philox4x32(rid & np.uint64(philox.MASK), rid >> np.uint64(32), idx, c3, seed & philox.MASK,
+                             (seed >> 32) & philox.MASK)
+
+
+def loggam(x):
+    """NumPy's random_loggam (the Stirling series its legacy Poisson sampler uses), vectorised, same operations."""
+    x = np.asarray(x, dtype=np.float64)
+    n = np.where(x < 7.0, np.floor(7.0 - x), 0.0).astype(np.int64)
+    x0 = x + n
+    x2 = (1.0 / x0) * (1.0 / x0)
+    gl0 = np.full_like(x, _LOGGAM_A[9])
+    for k in range(8, -1, -1):
+        gl0 = gl0 * x2
+        gl0 = gl0 + _LOGGAM_A[k]
+    gl = gl0 / x0 + 0.5 * _LG2PI + (x0 - 0.5) * np.log(x0) - x0
+    for k in range(1, 8):
+        m = (x < 7.0) & (n >= k)
+        gl = np.where(m, gl - np.log(x0 - 1.0), gl)
+        x0 = np.where(m, x0 - 1.0, x0)
+    return np.where((x == 1.0) | (x == 2.0), 0.0, gl)
+
+
+def poisson(mean, row_ids, f, seed):
+    """The exact Poisson draws of lf_mock.h (mock_poisson), one per entry of `mean`: 0 for mean 0, inversion by sequential
+    search below 10, PTRS (Hormann 1993) from 10 on with a fresh Philox block per rejection round.  -1 where the mean is
+    not finite, negative or above MAX_MEAN."""
+    mu = np.asarray(mean, dtype=np.float64)
+    rid, ff = np.broadcast_arrays(np.asarray(row_ids, dtype=np.int64), np.asarray(f, dtype=np.int64))
+    mu, rid, ff = np.broadcast_arrays(mu, rid, ff)
+    mu, rid, ff = mu.ravel(), rid.ravel(), ff.ravel()
+    k = np.zeros(mu.size, dtype=np.int64)
+    with np.errstate(all="ignore"):
+        bad = ~((mu >= 0.0) & (mu <= MAX_MEAN))
+        k[bad] = -1
+        small = np.flatnonzero(~bad & (mu > 0.0) & (mu < 10.0))
+        if small.size:
+            w = _words(rid[small], 0, 0, ff[small], seed)
+            u = philox.u53(w[0], w[1])
+            m = mu[small]
+            p = np.exp(-m)
+            F = p.copy()
+            ks = np.zeros(small.size, dtype=np.int64)
+            act = u > F
+            while act.any():
+                ks[act] += 1
+                p[act] = p[act] * (m[act] / ks[act])
+                act &= p != 0.0
+                F[act] = F[act] + p[act]
+                act &= u > F
+            k[small] = ks
+        big = np.flatnonzero(~bad & (mu >= 10.0))
+        if big.size:
+            m = mu[big]
+            slam, loglam = np.sqrt(m), np.log(m)
+            b = 0.931 + 2.53 * slam
+            a = -0.059 + 0.02483 * b
+            invalpha = 1.1239 + 1.1328 / (b - 3.4)
+            vr = 0.9277 - 3.6224 / (b - 2.0)
+            todo = np.arange(big.size)
+            rnd = 0
+            while todo.size:
+                w = _words(rid[big[todo]], rnd, 0, ff[big[todo]], seed)
+                U = philox.u53(w[0], w[1]) - 0.5
+                V = philox.u53(w[2], w[3])
+                us = 0.5 - np.abs(U)
+                aa, bb, mm = a[todo], b[todo], m[todo]
+                kk = np.floor((2.0 * aa / us + bb) * U + mm + 0.43).astype(np.int64)
+                acc = (us >= 0.07) & (V <= vr[todo])
+                rej = ~acc & ((kk < 0) | ((us < 0.013) & (V > us)))
+                test = ~acc & ~rej
+                lhs = np.log(V) + np.log(invalpha[todo]) - np.log(aa / (us * us) + bb)
+                rhs = -mm + kk * loglam[todo] - loggam(np.maximum(kk, 0) + 1.0)
+                acc |= test & (lhs <= rhs)
+                k[big[todo[acc]]] = kk[acc]
+                todo = todo[~acc]
+                rnd += 1
+    return k.reshape(np.shape(mean)) if np.ndim(mean) else int(k[0])
+
+
+def _first_above(cdf, t):
+    """Per row of cdf (n, S): the first index with cdf > t, else the first with cdf >= cdf[-1] (lf_mock.h: mock_search)."""
+    above = cdf > t[:, None]
+    out = above.argmax(axis=1)
+    none = ~above.any(axis=1)
+    if none.any():
+        out[none] = (cdf[none] >= cdf[none, -1:]).argmax(axis=1)
+    return out
+
+
+class MockTwin(object):
+    """NumPy statement of lf_mock_* (same densities, cumulative sums, streams and Poisson draws)."""
+
+    def __init__(self, inputs):
+        inp = inputs
+        self.variant = inp["variant"]
+        self.fix_sch_al = bool(inp.get("fix_sch_al", False))
+        self.sch_al0 = float(inp.get("sch_al0", 0.0))
+        self.nf = len(inp["field_ind"]) - 1
+        self.logL = np.ascontiguousarray(inp["logL"], dtype=np.float64)
+        self.S = S = self.logL.shape[0]
+        self.zarr = np.asarray(inp["zarr"], dtype=np.float64)
+        self.pivots = tuple(inp.get("pivots", (1.20, 1.53, 1.86)))
+        self.ndim = _ndim(self.variant, self.fix_sch_al, self.nf)
+        if self.variant == "free":
+            self.vp = np.asarray(inp["volume_part"], dtype=np.float64)
+            self.dl = np.asarray(inp["DL_zarr"], dtype=np.float64)
+            self.om0s = np.asarray(inp["Omega_0"], dtype=np.float64) / hs.SQARCSEC
+            self.fcmin = float(inp.get("fcmin", 0.1))
+        else:
+            self.ip = _integ_part(inp, self.nf, S)
+        self.wz = trapz_weights(self.zarr)
+        self.wL = trapz_weights(self.logL, axis=0)
+
+    # ---------------------------------------------------------------- the density
+    def lam(self, theta):
+        """lambda_f[j, k] for one theta row: (nf, S, S)."""
+        th = np.asarray(theta, dtype=np.float64)
+        L, S, nf = self.logL, self.S, self.nf
+        out = np.empty((nf, S, S))
+        with np.errstate(all="ignore"):
+            if self.variant == "zevol":
+                al = self.sch_al0 if self.fix_sch_al else th[6]
+                zrep = np.repeat(self.zarr[None], S, axis=0)
+                tlf = hs.schechter_z(L, zrep, al, th[0], th[1], th[2], th[3], th[4], th[5], *self.pivots)
+            else:
+                al = self.sch_al0 if self.fix_sch_al else th[2]
+                tlf = hs.true_lum_func(L, al, th[0], th[1])
+            if self.variant == "free":
+                k0 = 2 if self.fix_sch_al else 3
+                alpha = th[k0 + nf]
+                flux = 10 ** L / (4.0 * np.pi * (hs.MPC_CM * self.dl[None]) ** 2)
+                for f in range(nf):
+                    om = self.om0s[f] * hs.fleming(flux, 1.0e-17 * th[k0 + f], alpha, self.fcmin)
+                    out[f] = tlf * (self.vp[None] * om)
+            else:
+                for f in range(nf):
+                    out[f] = tlf * self.ip[f]
+        return out
+
+    def masses(self, theta):
+        """m_f[j, k] = (w_z[k] w_L[j, k]) lambda_f[j, k]: (nf, S, S)."""
+        return (self.wz[None, None, :] * self.wL[None]) * self.lam(theta)
+
+    def _cdfs(self, theta):
+        """cdfL (nf, S_k, S_j): column k's masses summed over j; cdfZ (nf, S): column totals summed over k; M (nf)."""
+        cdfL, colm = scan(np.swapaxes(self.masses(theta), 1, 2))
+        cdfZ, M = scan(colm)
+        return cdfL, cdfZ, M
+
+    def means(self, thetas):
+        """Expected counts M (R, nf), without the Poisson draws (and without their cap)."""
+        return np.array([self._cdfs(t)[2] for t in _rows(thetas, self.ndim)])
+
+    # ---------------------------------------------------------------- the API of MockGenerator
+    def counts(self, thetas, seed, row_ids=None):
+        """(mean (R, nf), count (R, nf) int64).  Raises MockError where lf_mock_counts returns LF_ERR_ARG."""
+        th = _rows(thetas, self.ndim)
+        rid = _row_ids(row_ids, th.shape[0])
+        if not np.isfinite(th).all():
+            raise MockError("row %d: theta is not finite" % int(np.flatnonzero(~np.isfinite(th).all(axis=1))[0]))
+        mean = np.array([self._cdfs(t)[2] for t in th])
+        cnt = poisson(mean, rid[:, None], np.arange(self.nf)[None, :], seed)
+        if (cnt < 0).any():
+            r, f = np.argwhere(cnt < 0)[0]
+            raise MockError("row %d field %d: expected count %.17g is not finite, negative or above 2^31" % (r, f, mean[r, f]))
+        return mean, cnt
+
+    def sources(self, theta, row_id, f, seed, index, cdfs=None):
+        """(z, logL) of sources `index` of field f of one row."""
+        cdfL, cdfZ = (self._cdfs(theta) if cdfs is None else cdfs)[:2]
+        idx = np.asarray(index, dtype=np.uint64)
+        r = _words(row_id, idx, 1, f, seed)
+        q = _words(row_id, idx, 2, f, seed)
+        cz = cdfZ[f]
+        t = philox.u53(r[0], r[1]) * cz[-1]
+        k = _first_above(np.broadcast_to(cz, (t.size, self.S)), t)
+        tl = t - np.where(k > 0, cz[np.maximum(k - 1, 0)], 0.0)
+        j = np.empty_like(k)
+        for kk in np.unique(k):
+            sel = k == kk
+            j[sel] = _first_above(np.broadcast_to(cdfL[f, kk], (int(sel.sum()), self.S)), tl[sel])
+        zr, S = self.zarr, self.S
+        a = np.where(k > 0, zr[k] - zr[np.maximum(k - 1, 0)], 0.0)
+        b = np.where(k < S - 1, zr[np.minimum(k + 1, S - 1)] - zr[k], 0.0)
+        z = hat_inverse(zr[k], a, b, philox.u53(r[2], r[3]))
+        L = self.logL
+        x0 = L[j, k]
+        a = np.where(j > 0, x0 - L[np.maximum(j - 1, 0), k], 0.0)
+        b = np.where(j < S - 1, L[np.minimum(j + 1, S - 1), k] - x0, 0.0)
+        return z, hat_inverse(x0, a, b, philox.u53(q[0], q[1]))
+
+    def draw(self, thetas, seed, row_ids=None, count=None):
+        """(z, logL, field, offsets): the sources of every (row, field) in that order; offsets [R nf + 1]."""
+        th = _rows(thetas, self.ndim)
+        rid = _row_ids(row_ids, th.shape[0])
+        if count is None:
+            count = self.counts(th, seed, rid)[1]
+        count = np.asarray(count, dtype=np.int64).reshape(th.shape[0], self.nf)
+        zs, Ls, fs = [], [], []
+        for r in range(th.shape[0]):
+            cdfs = self._cdfs(th[r]) if count[r].any() else None
+            for f in range(self.nf):
+                n = int(count[r, f])
+                if n:
+                    z, L = self.sources(th[r], rid[r], f, seed, np.arange(n), cdfs)
+                    zs.append(z)
+                    Ls.append(L)
+                    fs.append(np.full(n, f, dtype=np.int32))
+        off = np.concatenate([[0], np.cumsum(count.ravel())]).astype(np.int64)
+        cat = lambda v, dt: np.concatenate(v).astype(dt) if v else np.zeros(0, dtype=dt)   # noqa: E731
+        return cat(zs, np.float64), cat(Ls, np.float64), cat(fs, np.int32), off
+
+    def hist(self, thetas, edges, seed, row_ids=None):
+        """(R, nf, nbins + 2) counts of logL per slot searchsorted(edges, logL, side="right")."""
+        edges = _edges(edges)
+        z, L, fld, off = self.draw(thetas, seed, row_ids)
+        R = np.atleast_2d(thetas).shape[0]
+        return bin_sources(L, off, edges).reshape(R, self.nf, edges.size + 1)
+
+
+def _edges(edges):
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).ravel())
+    if e.size < 2 or e.size - 1 > MAX_BINS:
+        raise ValueError("edges must hold 2 .. %d values" % (MAX_BINS + 1))
+    if not np.isfinite(e).all() or (np.diff(e) < 0).any():
+        raise ValueError("edges must be finite and non-decreasing")
+    return e
+
+
+def bin_sources(logL, offsets, edges):
+    """[len(offsets) - 1, nbins + 2] histogram of each segment of logL by searchsorted(edges, x, side="right")."""
+    ns = len(edges) + 1
+    slot = np.searchsorted(edges, logL, side="right")
+    seg = np.repeat(np.arange(len(offsets) - 1), np.diff(offsets))
+    return np.bincount(seg * ns + slot, minlength=(len(offsets) - 1) * ns).reshape(-1, ns).astype(np.int64)
+
+
+# --------------------------------------------------------------------------------------------------------------- device
+class MockGenerator(object):
+    """lf_mock_* on the GPU.  `inputs` is the dict LFContext takes (kernel_inputs()); the catalogue arrays are not read."""
+
+    def __init__(self, inputs, device=0):
+        from . import capi
+        lib = capi.load()
+        self._lib, self._h = lib, None
+        inp = inputs
+        variant = inp["variant"]
+        if variant not in capi.VARIANTS:
+            raise ValueError("variant must be one of %s" % (sorted(capi.VARIANTS),))
+        self.variant = variant
+        self.nf = len(inp["field_ind"]) - 1
+        logL = capi._f64(inp["logL"])
+        S = logL.shape[0]
+        if logL.shape != (S, S):
+            raise ValueError("logL must be (S, S)")
+        self.S = S
+        self.fix_sch_al = bool(inp.get("fix_sch_al", False))
+        self.ndim = _ndim(variant, self.fix_sch_al, self.nf)
+        keep = {"logL": logL, "zarr": capi._f64(inp["zarr"]), "omega0": capi._f64(inp["Omega_0"])}
+        if variant == "free":
+            keep["volume_part"] = capi._f64(inp["volume_part"])
+            keep["dl_zarr"] = capi._f64(inp["DL_zarr"])
+        else:
+            keep["integ_part"] = _integ_part(inp, self.nf, S)
+            if keep["integ_part"].shape != (self.nf, S, S):
+                raise ValueError("integ_part must be (nf, S, S)")
+        d = capi.LfDesc()
+        d.variant = capi.VARIANTS[variant]
+        d.fix_sch_al = 1 if self.fix_sch_al else 0
+        d.nf, d.S, d.N = self.nf, S, 0
+        for k in ("logL", "zarr", "omega0", "volume_part", "dl_zarr", "integ_part"):
+            setattr(d, k, capi._ptr(keep.get(k)))
+        d.sch_al0 = float(inp.get("sch_al0", 0.0))
+        d.fcmin = float(inp.get("fcmin", 0.1))
+        piv = inp.get("pivots", (1.20, 1.53, 1.86))
+        for i in range(3):
+            d.pivots[i] = float(piv[i])
+        lims = inp.get("lims")
+        if lims:
+            for i, name in enumerate(capi.LIM_ORDER):
+                d.lims[i][0], d.lims[i][1] = float(lims[name][0]), float(lims[name][1])
+        d.device = int(device)
+        h = lib.lf_mock_create(ctypes.byref(d))
+        if not h:
+            raise capi.LFError(lib.lf_mock_last_error(None).decode())
+        self._h = ctypes.c_void_p(h)
+        self.device = int(device)
+
+    def _check(self, rc):
+        from . import capi
+        if rc == capi.LF_ERR_ARG:
+            raise MockError(self._lib.lf_mock_last_error(self._h).decode())
+        if rc != capi.LF_OK:
+            raise capi.LFError("liblfmcmc error %d: %s" % (rc, self._lib.lf_mock_last_error(self._h).decode()))
+
+    def counts(self, thetas, seed, row_ids=None):
+        """(mean (R, nf), count (R, nf) int64): expected counts M and their Poisson draws."""
+        from . import capi
+        th = _rows(thetas, self.ndim)
+        R = th.shape[0]
+        rid = _row_ids(row_ids, R)
+        mean = np.empty((R, self.nf))
+        cnt = np.empty((R, self.nf), dtype=np.int64)
+        self._check(self._lib.lf_mock_counts(self._h, capi._ptr(th), R, rid.ctypes.data_as(capi._c_int64_p), ctypes.c_uint64(int(seed)),
+                                             capi._ptr(mean), cnt.ctypes.data_as(capi._c_int64_p)))
+        return mean, cnt
+
+    def draw(self, thetas, seed, row_ids=None, count=None):
+        """(z, logL, field, offsets): the sources of every (row, field) in that order (count: from .counts unless given);
+        sources of (r, f) are [offsets[r nf + f], offsets[r nf + f + 1])."""
+        from . import capi
+        th = _rows(thetas, self.ndim)
+        R = th.shape[0]
+        rid = _row_ids(row_ids, R)
+        if count is None:
+            count = self.counts(th, seed, rid)[1]
+        cnt = np.ascontiguousarray(np.asarray(count, dtype=np.int64).reshape(R, self.nf))
+        total = int(cnt.sum())
+        z, L = np.empty(total), np.empty(total)
+        fld = np.empty(total, dtype=np.int32)
+        self._check(self._lib.lf_mock_draw(self._h, capi._ptr(th), R, rid.ctypes.data_as(capi._c_int64_p), ctypes.c_uint64(int(seed)),
+                                           cnt.ctypes.data_as(capi._c_int64_p), capi._ptr(z), capi._ptr(L),
+                                           fld.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        off = np.concatenate([[0], np.cumsum(cnt.ravel())]).astype(np.int64)
+        return z, L, fld, off
+
+    def hist(self, thetas, edges, seed, row_ids=None):
+        """(R, nf, nbins + 2) int64: logL of every (row, field) binned by searchsorted(edges, x, side="right")."""
+        from . import capi
+        th = _rows(thetas, self.ndim)
+        R = th.shape[0]
+        rid = _row_ids(row_ids, R)
+        e = _edges(edges)
+        nb = e.size - 1
+        out = np.empty((R, self.nf, nb + 2), dtype=np.int64)
+        self._check(self._lib.lf_mock_hist(self._h, capi._ptr(th), R, rid.ctypes.data_as(capi._c_int64_p), ctypes.c_uint64(int(seed)), nb,
+                                           capi._ptr(e), out.ctypes.data_as(capi._c_int64_p)))
+        return out
+
+    def close(self):
+        if self._h is not None:
+            self._lib.lf_mock_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def generator(inputs, device=True, device_index=0):
+    """MockGenerator on the GPU (device=True) or the NumPy MockTwin."""
+    return MockGenerator(inputs, device=device_index) if device else MockTwin(inputs)
+
+
+def catalogue_lists(z, logL, field, nf):
+    """Per-field lists in the form the model constructors take: z, lum, lum_e (zeros), field_ind."""
+    order = np.argsort(field, kind="stable")
+    z, logL, field = z[order], logL[order], field[order]
+    fi = np.concatenate([[0], np.cumsum(np.bincount(field, minlength=nf))]).astype(np.int64)
+    split = lambda a: [a[fi[f]:fi[f + 1]].copy() for f in range(nf)]    # noqa: E731
+    return {"z": split(z), "lum": split(logL), "lum_e": [np.zeros(fi[f + 1] - fi[f]) for f in range(nf)], "field_ind": fi}
+
+
+def predictive(gen, rows, edges, observed_lum, observed_fi, seed):
+    """Posterior predictive check of the logL histogram per field: `rows` (R, ndim) posterior draws, `edges` (B + 1),
+    the observed catalogue's lum and field_ind.  Returns the dict of _Base.posterior_predictive."""
+    edges = _edges(edges)
+    nf = len(observed_fi) - 1
+    obs = bin_sources(np.asarray(observed_lum, dtype=np.float64), np.asarray(observed_fi, dtype=np.int64), edges)
+    rep = gen.hist(rows, edges, seed)
+    expected = gen.counts(rows, seed)[0]
+    obs_tot, rep_tot = obs.sum(axis=1), rep.sum(axis=2)
+    return {"edges": edges, "observed": obs, "replicated": rep, "expected": expected,
+            "percentiles": np.percentile(rep, (16.0, 50.0, 84.0), axis=0),
+            "p_upper": np.mean(rep >= obs[None], axis=0), "p_lower": np.mean(rep <= obs[None], axis=0),
+            "observed_total": obs_tot, "replicated_total": rep_tot,
+            "p_upper_total": np.mean(rep_tot >= obs_tot[None], axis=0), "p_lower_total": np.mean(rep_tot <= obs_tot[None], axis=0),
+            "seed": int(seed), "nf": nf}

@@ -15,6 +15,7 @@ import numpy as np
 
 from . import hostsetup as hs
 from . import lfbands
+from . import mock
 from . import veff
 from .cosmology import cosmo as _cosmo
 from .capi import LFContext
@@ -366,6 +367,48 @@ class _Base(object):
     def _band_device(self, device):
         return self._ctx is not None if device is None else bool(device)
 
+    def _mock_generator(self, device):
+        """MockGenerator (GPU) or MockTwin (NumPy) over this object's unsharded kernel_inputs(); device=None = the GPU when
+        this object already holds a context.  The device generator is kept for the object's configuration."""
+        if not self._band_device(device):
+            return mock.MockTwin(self.kernel_inputs())
+        key = (self._variant(), bool(self.fix_sch_al), float(self.sch_al) if self.fix_sch_al else None, self.device)
+        if getattr(self, "_mock", None) is None or self._mock_key != key:
+            self._mock = mock.MockGenerator(self.kernel_inputs(), device=self.device)
+            self._mock_key = key
+        return self._mock
+
+    def mock_catalogue(self, theta, seed=None, device=None):
+        """One catalogue drawn from the model at `theta`: the Poisson process whose likelihood
+        lnprob evaluates, on this object's integration grid.  Returns the per-field lists both constructors take - z, lum,
+        lum_e (zeros), field_ind - plus theta and seed.  seed=None draws one from numpy's global state (as fit_model does);
+        device=True the GPU, False NumPy, None the GPU when this object already holds a device context (one GPU; with
+        several ranks call it on one)."""
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+        theta = np.asarray(theta, dtype=np.float64).ravel()
+        gen = self._mock_generator(device)
+        z, lum, fld, _ = gen.draw(theta[None], seed)
+        out = mock.catalogue_lists(z, lum, fld, self.nfields)
+        out["theta"], out["seed"] = theta.copy(), int(seed)
+        return out
+
+    def posterior_predictive(self, edges=None, ndraws=200, lnprobcut=7.5, seed=None, device=None):
+        """Posterior predictive check of the observed luminosities per field: ndraws posterior rows (drawn as
+        set_median_fit draws them), one mock catalogue each, binned in logL with `edges` (default: 20 equal bins over
+        [min(lum), max(lum)]) by searchsorted(edges, x, side="right") - slot 0 below edges[0], slot B + 1 at or above
+        edges[B].  Returns a dict: edges, observed [nf, B + 2], replicated [R, nf, B + 2], expected [R, nf] (the mocks'
+        expected counts), percentiles (16, 50, 84) of replicated, p_upper = mean(rep >= obs) and p_lower = mean(rep <= obs)
+        per bin, and the same for the per-field totals (observed_total, replicated_total, p_upper_total, p_lower_total).
+        seed and device as mock_catalogue."""
+        rows = self._posterior_rows(ndraws, lnprobcut)[:, :-1]
+        if edges is None:
+            edges = np.linspace(np.min(self.lum), np.max(self.lum), 21)
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+        gen = self._mock_generator(device)
+        return mock.predictive(gen, rows, edges, self.lum, np.asarray(self.field_ind, dtype=np.int64), seed)
+
     def add_fitinfo_to_table(self, percentiles, start_value=1, lnprobcut=7.5):
         """Percentiles of each parameter into the last row of self.table (lumfuncmcmc.py:653-667)."""
         nsamples = self._select_samples(lnprobcut, keep_lnprob=False)
@@ -398,6 +441,9 @@ class _Base(object):
         if self._ctx is not None:
             self._ctx.close()
             self._ctx = None
+        if getattr(self, "_mock", None) is not None:
+            self._mock.close()
+            self._mock = None
 
 
 class LumFuncMCMC(_Base):
