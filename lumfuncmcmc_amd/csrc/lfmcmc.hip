@@ -18,6 +18,7 @@
 
 #include "lf_bands.h"
 #include "lf_compress.h"
+#include "lf_devmem.h"
 #include "lf_gridbound.h"
 #include "lf_kernels.h"
 #include "lf_free.h"
@@ -31,10 +32,8 @@ thread_local std::string g_create_error = "";
 
 struct ChunkTable {
     int n = 0;
-    int* d_start = nullptr;
-    int* d_len = nullptr;
-    int* d_field = nullptr;
-    int* d_keys = nullptr;     // FREE, real catalogue: lf::KEY_STRIDE ints per chunk (get_chunks)
+    Buf<int> d_start, d_len, d_field;
+    Buf<int> d_keys;           // FREE, real catalogue: lf::KEY_STRIDE ints per chunk (get_chunks)
 };
 
 struct EventPair {
@@ -48,10 +47,19 @@ struct CompressedCat {
     bool built = false;
     int64_t n = 0;
     std::vector<int64_t> field_ind;
-    double *d_lum = nullptr, *d_a1 = nullptr, *d_U = nullptr, *d_W = nullptr;
+    Buf<double> d_lum, d_a1, d_U, d_W;
     std::map<int, ChunkTable> chunks;
     int nbins = 0;
     double bound = 0.0;
+};
+
+// FREE: the compressed integration grid (lf_compress.h), built with the compressed catalogue when the grid is separable
+struct CompressedGrid {
+    bool built = false;
+    int nb = 0;
+    double bound = 0.0;
+    Buf<double> d_U, d_A4, d_omega, d_L, d_PGL;
+    Buf<int> d_row0, d_nrows, d_off;
 };
 
 }  // namespace
@@ -63,24 +71,24 @@ struct lf_ctx {
     int nnodes = 0;
     std::vector<int64_t> field_ind;
     std::vector<double> h_x;            // FREE: host copy of the flux-sorted logf (chunk keys are derived from it)
-    unsigned long long* d_forms = nullptr;   // census of the term forms (option "count_forms"), FORM_COUNT slots
+    Buf<unsigned long long> d_forms;         // census of the term forms (option "count_forms"), FORM_COUNT slots
     int last_launch[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // lf_last_launch
-    int* d_queue = nullptr;              // FREE: item counters of the persistent workgroups, [tiles][lf::QSTRIDE]
+    Buf<unsigned long long> d_stamps;        // kc.stamps (LF_STAMPS builds, lf_debug_stamps)
+    Buf<int> d_queue;                    // FREE: item counters of the persistent workgroups, [tiles][lf::QSTRIDE]
     // the catalogue's cells (lf_kernels.h: CELL_M, ZCELL_M) - {x_c, S_0 .. S_M} per cell, chunks of 64 (FREE) / 256 (ZEVOL) cells of one field
-    double* d_cells = nullptr;           // [ncell][8]
-    int* d_cc_start = nullptr;           // [ncchunk] first cell of the chunk
-    int* d_deal = nullptr;               // lf_free's deal of cell chunks and flux bins to its virtual workgroups (lf_free.h: DEAL_*)
+    Buf<double> d_cells;                 // [ncell][8]
+    Buf<int> d_cc_start;                 // [ncchunk] first cell of the chunk
+    Buf<int> d_deal;                     // lf_free's deal of cell chunks and flux bins to its virtual workgroups (lf_free.h: DEAL_*)
     int64_t deal_key = -1;               // ... made for this (cell chunks, bins, grid share)
-    int* d_cc_len = nullptr;             // [ncchunk] cells in the chunk (<= 64)
-    int* d_cc_field = nullptr;           // [ncchunk]
+    Buf<int> d_cc_len;                   // [ncchunk] cells in the chunk (<= 64)
+    Buf<int> d_cc_field;                 // [ncchunk]
     int ncell = 0, ncchunk = 0;
     int64_t opt_cells = 1;               // 0: sum every walker over the sources (A/B runs)
-    int cap_queue = 0;
     int slots_free[3] = {0, 0, 0};       // workgroups of lf_free<2 / 4 / 8> the chip holds at once (0 = not asked yet)
     int num_cu = 0;
     // device tables
-    double *d_lum = nullptr, *d_a1 = nullptr, *d_P = nullptr, *d_U = nullptr;
-    double *d_G = nullptr, *d_PG = nullptr, *d_W = nullptr, *d_a3 = nullptr, *d_a4 = nullptr, *d_a4min = nullptr, *d_nodes8 = nullptr;
+    Buf<double> d_lum, d_a1, d_P, d_U;
+    Buf<double> d_G, d_PG, d_W, d_a3, d_a4, d_a4min, d_nodes8;
     std::map<int, ChunkTable> chunks;   // keyed by sources-per-chunk
     std::map<int, ChunkTable> chunks_free;   // the persistent FREE kernel's (lf_free.h): 512 ST sources per chunk, lanes of ST
     int64_t opt_persistent = 1;         // FREE: 1 = lf_free (persistent 512-thread workgroups) for catalogues that fill it
@@ -88,12 +96,12 @@ struct lf_ctx {
     int64_t opt_fuse_step = 1;          // ... and the sampler's half-step too (0: three launches per half-step, A/B runs)
     bool queue_zero = false;            // d_queue is all zeros (what a fused launch needs and leaves behind)
     bool parts_empty = false;           // every slot of d_partB / d_partR is lf::PART_EMPTY (what the polling hand-over needs and leaves behind, lf_tile.h)
-    int* d_err = nullptr;               // device error word (a finisher gave up polling)
+    Buf<int> d_err;                     // device error word (a finisher gave up polling)
     // lf_free's one-launch form reads its launch-invariant arguments from a block in device memory (lf_free.h: FreeBlock), one
     // per sources-per-lane slot (the chunk tables depend on it); the pinned shadow holds what was last uploaded: an upload
     // only when the bytes change (free_block)
-    lf::FreeBlock* d_fblk[3] = {nullptr, nullptr, nullptr};
-    lf::FreeBlock* h_fblk[3] = {nullptr, nullptr, nullptr};
+    Buf<unsigned char> d_fblk[3];       // (bytes: a FreeBlock rounded up to whole 256-byte lines)
+    Buf<unsigned char, true> h_fblk[3];
     bool fblk_valid[3] = {false, false, false};
     int64_t fblk_uploads = 0;           // uploads so far (lf_free_block_uploads: the tests' debug counter)
     int64_t opt_poll = 1;               // 0: the one-launch form hands over through the tile's counter only (A/B runs)
@@ -108,39 +116,30 @@ struct lf_ctx {
     // FREE: the factors of a separable integration grid (every redshift column has the same luminosity nodes),
     // kept on the host for the compressed grid; empty when the grid is not separable
     std::vector<double> h_L, h_wL, h_ck, h_Dk;
-    struct {
-        bool built = false;
-        int nb = 0;
-        double bound = 0.0;
-        double *d_U = nullptr, *d_A4 = nullptr, *d_omega = nullptr, *d_L = nullptr, *d_PGL = nullptr;
-        int *d_row0 = nullptr, *d_nrows = nullptr, *d_off = nullptr;
-    } gridc;
+    CompressedGrid gridc;
     // FREE, separable grid: piece B over flux bins with a proven bound (lf_gridbound.h); lf_free's default when built
     struct {
         bool built = false;
         int nb = 0;
         double margin = 0.0;
-        double *d_rec = nullptr, *d_omega = nullptr;
-        int* d_rows = nullptr;
+        Buf<double> d_rec, d_omega;
+        Buf<int> d_rows;
     } gridq;
     int64_t opt_grid_shortcut = 1;      // 0: lf_free integrates the lattice (A/B runs)
     // FIXCOMP, ZEVOL: the grid's nodes as 32-byte records {G, PG, W, column} padded to chunks of 64, and the columns' redshifts
     // (lf_pers.h: the persistent kernel of these variants)
-    double *d_nodes4 = nullptr, *d_zcol = nullptr;
+    Buf<double> d_nodes4, d_zcol;
     int nch4 = 0;
     int slots_pers = 0;                 // workgroups of lf_pers the chip holds at once (0 = not asked yet)
-    double* d_partR = nullptr;          // rescue partials [B][chunks of the real catalogue]
-    int* d_slow = nullptr;              // {count, walker indices...} of the walkers lf_prepare flagged SLOW (compressed mode)
-    int cap_slow = 0;
-    size_t cap_partR = 0;
+    Buf<double> d_partR;                // rescue partials [B][chunks of the real catalogue]
+    Buf<int> d_slow;                    // {count, walker indices...} of the walkers lf_prepare flagged SLOW (compressed mode)
     // workspace
     int cap_B = 0;                      // padded walker capacity
-    size_t cap_partA = 0, cap_partB = 0;
-    double *d_theta = nullptr, *d_out = nullptr, *d_outA = nullptr, *d_outB = nullptr;
-    double *d_wrec = nullptr, *d_partA = nullptr, *d_partB = nullptr;
-    int *d_wstat = nullptr, *d_wmode = nullptr;
-    double* d_wbase = nullptr;
-    double *h_theta = nullptr, *h_out = nullptr;   // pinned staging
+    Buf<double> d_theta, d_out, d_outA, d_outB;
+    Buf<double> d_wrec, d_partA, d_partB;
+    Buf<int> d_wstat, d_wmode;
+    Buf<double> d_wbase;
+    Buf<double, true> h_theta, h_out;   // pinned staging
     hipStream_t stream = nullptr;
     hipStream_t last_stream = nullptr;   // stream of the previous enqueue (workspace is shared)
     bool any_enqueued = false;
@@ -174,9 +173,17 @@ namespace {
     } while (0)
 
 template <typename T>
-int upload(lf_ctx* c, T** dst, const T* src, size_t n) {
-    LF_HIP(c, hipMalloc((void**)dst, std::max<size_t>(n, 1) * sizeof(T)));
-    if (n) LF_HIP(c, hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+int upload(lf_ctx* c, Buf<T>& dst, const T* src, size_t n) {
+    LF_HIP(c, dst.upload(src, n));
+    return LF_OK;
+}
+
+// Replace `b` by a new allocation of n elements (not initialised; the old contents go).  sync: launches enqueued earlier may
+// still use the old one - wait for the device first.  `o`: who takes the error (a context, a mock generator).
+template <typename Owner, typename T, bool PINNED>
+int grow(Owner* o, Buf<T, PINNED>& b, size_t n, bool sync = true) {
+    if (sync) LF_HIP(o, hipDeviceSynchronize());
+    LF_HIP(o, b.alloc(n));
     return LF_OK;
 }
 
@@ -290,10 +297,10 @@ int build_cells(lf_ctx* c, lf::KConst& kc, const std::vector<double>& x, int nf,
     // 17.5 in lf_main's three launches, 12 over cells)
     if (nreal == 0 || ((size_t)c->N < 4 * nreal && c->N > 65536)) return LF_OK;
     int rc;
-    if ((rc = upload(c, &c->d_cells, cd.data(), cd.size())) != LF_OK) return rc;
-    if ((rc = upload(c, &c->d_cc_start, cst.data(), cst.size())) != LF_OK) return rc;
-    if ((rc = upload(c, &c->d_cc_len, cln.data(), cln.size())) != LF_OK) return rc;
-    if ((rc = upload(c, &c->d_cc_field, cfl.data(), cfl.size())) != LF_OK) return rc;
+    if ((rc = upload(c, c->d_cells, cd.data(), cd.size())) != LF_OK) return rc;
+    if ((rc = upload(c, c->d_cc_start, cst.data(), cst.size())) != LF_OK) return rc;
+    if ((rc = upload(c, c->d_cc_len, cln.data(), cln.size())) != LF_OK) return rc;
+    if ((rc = upload(c, c->d_cc_field, cfl.data(), cfl.size())) != LF_OK) return rc;
     c->ncell = (int)ncell;
     c->ncchunk = (int)cst.size();
     kc.cells = c->opt_cells ? 1 : 0;
@@ -401,12 +408,11 @@ int get_chunks(lf_ctx* c, std::map<int, ChunkTable>& tables, const std::vector<i
     ChunkTable t;
     t.n = (int)st.size();
     int rc;
-    if ((rc = upload(c, &t.d_start, st.data(), st.size())) != LF_OK) return rc;
-    if ((rc = upload(c, &t.d_len, ln.data(), ln.size())) != LF_OK) return rc;
-    if ((rc = upload(c, &t.d_field, fl.data(), fl.size())) != LF_OK) return rc;
-    if ((rc = upload(c, &t.d_keys, keys.data(), keys.size())) != LF_OK) return rc;
-    tables[ch] = t;
-    *out = &tables[ch];
+    if ((rc = upload(c, t.d_start, st.data(), st.size())) != LF_OK) return rc;
+    if ((rc = upload(c, t.d_len, ln.data(), ln.size())) != LF_OK) return rc;
+    if ((rc = upload(c, t.d_field, fl.data(), fl.size())) != LF_OK) return rc;
+    if ((rc = upload(c, t.d_keys, keys.data(), keys.size())) != LF_OK) return rc;
+    *out = &tables.emplace(ch, std::move(t)).first->second;       // (only a complete table enters the map)
     return LF_OK;
 }
 
@@ -435,61 +441,33 @@ int pick_geometry(const lf_ctx* c, int B) {
     return 1;
 }
 
-// free a device / pinned buffer and clear the pointer: a failed re-allocation below must leave nothing dangling
-template <typename T>
-void release(T*& p) {
-    if (p) hipFree(p);
-    p = nullptr;
-}
-template <typename T>
-void release_host(T*& p) {
-    if (p) hipHostFree(p);
-    p = nullptr;
-}
-
 int ensure_workspace(lf_ctx* c, int Bpad, size_t partA, size_t partB, size_t partR = 0) {
+    int rc;
     if (Bpad > c->cap_B) {
-        int nb = std::max(Bpad, c->cap_B * 2);
+        const size_t nb = (size_t)std::max(Bpad, c->cap_B * 2);
         LF_HIP(c, hipDeviceSynchronize());
-        c->cap_B = 0;
-        release(c->d_theta); release(c->d_out); release(c->d_outA); release(c->d_outB);
-        release(c->d_wrec); release(c->d_wstat); release(c->d_wmode); release(c->d_wbase); release(c->d_slow);
-        release_host(c->h_theta); release_host(c->h_out);
-        LF_HIP(c, hipMalloc((void**)&c->d_theta, (size_t)nb * 16 * sizeof(double)));
-        LF_HIP(c, hipMalloc((void**)&c->d_out, (size_t)nb * sizeof(double)));
-        LF_HIP(c, hipMalloc((void**)&c->d_outA, (size_t)nb * sizeof(double)));
-        LF_HIP(c, hipMalloc((void**)&c->d_outB, (size_t)nb * sizeof(double)));
-        LF_HIP(c, hipMalloc((void**)&c->d_wrec, (size_t)nb * lf::REC * sizeof(double)));
-        LF_HIP(c, hipMalloc((void**)&c->d_wstat, (size_t)nb * sizeof(int)));
-        LF_HIP(c, hipMalloc((void**)&c->d_wmode, (size_t)nb * lf::MAXF * lf::WM * sizeof(int)));
-        LF_HIP(c, hipMalloc((void**)&c->d_wbase, (size_t)nb * sizeof(double)));
-        LF_HIP(c, hipMalloc((void**)&c->d_slow, ((size_t)nb + 1) * sizeof(int)));
-        LF_HIP(c, hipMemset(c->d_slow, 0, ((size_t)nb + 1) * sizeof(int)));
-        LF_HIP(c, hipHostMalloc((void**)&c->h_theta, (size_t)nb * 16 * sizeof(double), hipHostMallocDefault));
-        LF_HIP(c, hipHostMalloc((void**)&c->h_out, (size_t)nb * 3 * sizeof(double), hipHostMallocDefault));
-        c->cap_B = nb;
+        c->cap_B = 0;                    // (a failed allocation below: everything is made anew by the next call)
+        LF_HIP(c, c->d_theta.alloc(nb * 16));
+        LF_HIP(c, c->d_out.alloc(nb));
+        LF_HIP(c, c->d_outA.alloc(nb));
+        LF_HIP(c, c->d_outB.alloc(nb));
+        LF_HIP(c, c->d_wrec.alloc(nb * lf::REC));
+        LF_HIP(c, c->d_wstat.alloc(nb));
+        LF_HIP(c, c->d_wmode.alloc(nb * lf::MAXF * lf::WM));
+        LF_HIP(c, c->d_wbase.alloc(nb));
+        LF_HIP(c, c->d_slow.alloc(nb + 1));
+        LF_HIP(c, hipMemset(c->d_slow, 0, (nb + 1) * sizeof(int)));
+        LF_HIP(c, c->h_theta.alloc(nb * 16));
+        LF_HIP(c, c->h_out.alloc(nb * 3));
+        c->cap_B = (int)nb;
     }
-    if (partA > c->cap_partA) {
-        LF_HIP(c, hipDeviceSynchronize());
-        c->cap_partA = 0;
-        release(c->d_partA);
-        LF_HIP(c, hipMalloc((void**)&c->d_partA, partA * sizeof(double)));
-        c->cap_partA = partA;
-    }
-    if (partR > c->cap_partR) {
-        LF_HIP(c, hipDeviceSynchronize());
-        c->cap_partR = 0;
-        release(c->d_partR);
-        LF_HIP(c, hipMalloc((void**)&c->d_partR, partR * sizeof(double)));
-        c->cap_partR = partR;
+    if (partA > c->d_partA.size() && (rc = grow(c, c->d_partA, partA)) != LF_OK) return rc;
+    if (partR > c->d_partR.size()) {
+        if ((rc = grow(c, c->d_partR, partR)) != LF_OK) return rc;
         c->parts_empty = false;
     }
-    if (partB > c->cap_partB) {
-        LF_HIP(c, hipDeviceSynchronize());
-        c->cap_partB = 0;
-        release(c->d_partB);
-        LF_HIP(c, hipMalloc((void**)&c->d_partB, partB * sizeof(double)));
-        c->cap_partB = partB;
+    if (partB > c->d_partB.size()) {
+        if ((rc = grow(c, c->d_partB, partB)) != LF_OK) return rc;
         c->parts_empty = false;
     }
     return LF_OK;
@@ -686,7 +664,7 @@ int ensure_deal(lf_ctx* c, int nchC, int nbq, hipStream_t s) {
     if (key == c->deal_key) return LF_OK;
     if (key > 0) {
         const std::vector<int> t = make_deal(nchC, nbq, c->kc.grid_part, c->kc.grid_parts);
-        if (!c->d_deal) LF_HIP(c, hipMalloc((void**)&c->d_deal, (size_t)DEAL_MAX * sizeof(int)));
+        if (!c->d_deal) LF_HIP(c, c->d_deal.alloc(DEAL_MAX));
         if (c->any_enqueued) LF_HIP(c, hipStreamSynchronize(c->last_stream));        // (a launch may still be reading the old table)
         LF_HIP(c, hipMemcpy(c->d_deal, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
     }
@@ -697,13 +675,9 @@ int ensure_deal(lf_ctx* c, int nchC, int nbq, hipStream_t s) {
 // The tiles' counters of the persistent kernels (d_queue: QSTRIDE per tile, lf_tile.h), grown to ntiles; a new buffer is not zero.
 int ensure_queue(lf_ctx* c, int ntiles) {
     using namespace lf;
-    if (ntiles * QSTRIDE > c->cap_queue) {
-        LF_HIP(c, hipDeviceSynchronize());
-        release(c->d_queue);
-        c->cap_queue = 0;
-        const int cap = std::max(2 * ntiles * QSTRIDE, 1024);
-        LF_HIP(c, hipMalloc((void**)&c->d_queue, (size_t)cap * sizeof(int)));
-        c->cap_queue = cap;
+    if ((size_t)(ntiles * QSTRIDE) > c->d_queue.size()) {
+        const int rc = grow(c, c->d_queue, (size_t)std::max(2 * ntiles * QSTRIDE, 1024));
+        if (rc != LF_OK) return rc;
         c->queue_zero = false;
     }
     return LF_OK;
@@ -727,15 +701,15 @@ int begin_enqueue(lf_ctx* c, hipStream_t s, bool one_launch) {
 int ready_tiles(lf_ctx* c, hipStream_t s, bool fused, bool poll) {
     using namespace lf;
     if (fused && !c->queue_zero) {
-        LF_HIP(c, hipMemsetAsync(c->d_queue, 0, (size_t)c->cap_queue * sizeof(int), s));
+        LF_HIP(c, hipMemsetAsync(c->d_queue, 0, c->d_queue.size() * sizeof(int), s));
         c->queue_zero = true;
     }
     if (poll && !c->parts_empty) {
         static_assert((PART_EMPTY >> 32) == (PART_EMPTY & 0xffffffffull), "filled by 32-bit words");
-        LF_HIP(c, hipMemsetD32Async((hipDeviceptr_t)c->d_partB, (int)(PART_EMPTY & 0xffffffffull), c->cap_partB * 2, s));
-        LF_HIP(c, hipMemsetD32Async((hipDeviceptr_t)c->d_partR, (int)(PART_EMPTY & 0xffffffffull), c->cap_partR * 2, s));
+        LF_HIP(c, hipMemsetD32Async((hipDeviceptr_t)c->d_partB, (int)(PART_EMPTY & 0xffffffffull), c->d_partB.size() * 2, s));
+        LF_HIP(c, hipMemsetD32Async((hipDeviceptr_t)c->d_partR, (int)(PART_EMPTY & 0xffffffffull), c->d_partR.size() * 2, s));
         if (!c->d_err) {
-            LF_HIP(c, hipMalloc((void**)&c->d_err, sizeof(int)));
+            LF_HIP(c, c->d_err.alloc(1));
             LF_HIP(c, hipMemsetAsync(c->d_err, 0, sizeof(int), s));
         }
         c->parts_empty = true;
@@ -770,8 +744,8 @@ int free_block(lf_ctx* c, int slot, const lf::SrcArrays& sa, const lf::NodeArray
     if (c->fblk_valid[slot] && std::memcmp(c->h_fblk[slot], &b, sizeof(b)) == 0) return LF_OK;
     constexpr size_t bytes = (sizeof(FreeBlock) + 255) / 256 * 256;
     if (!c->d_fblk[slot]) {
-        LF_HIP(c, hipMalloc((void**)&c->d_fblk[slot], bytes));
-        LF_HIP(c, hipHostMalloc((void**)&c->h_fblk[slot], bytes, hipHostMallocDefault));
+        LF_HIP(c, c->d_fblk[slot].alloc(bytes));
+        LF_HIP(c, c->h_fblk[slot].alloc(bytes));
     } else {
         // the previous upload may still be reading the shadow (nothing to wait for inside a capture: it began on an idle device)
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -796,7 +770,7 @@ void launch_free(lf_ctx* c, int slot, int B, int ntiles, const lf::SrcArrays& sa
     std::memcpy(c->last_launch, info, sizeof(info));
     if (fused && sp) hipLaunchKernelGGL((lf_free_step<ST>), grid, dim3(PB), 0, s, c->kc, sa, na, fa, *sp, *ap);      // the sampler's half-step
     else if (fused)
-        hipLaunchKernelGGL((lf_free<ST, false, true>), grid, dim3(PB), 0, s, (FreeBlockPtr)c->d_fblk[slot],
+        hipLaunchKernelGGL((lf_free<ST, false, true>), grid, dim3(PB), 0, s, (FreeBlockPtr)(const FreeBlock*)c->d_fblk[slot].get(),
                            FreeLaunch{fa.theta, fa.out, fa.B, fa.ntiles, fa.tile_stride});
     else if (c->kc.forms) hipLaunchKernelGGL((lf_free<ST, true>), grid, dim3(PB), 0, s, c->kc, sa, na, c->d_wrec, c->d_wmode, fa);
     else hipLaunchKernelGGL((lf_free<ST, false>), grid, dim3(PB), 0, s, c->kc, sa, na, c->d_wrec, c->d_wmode, fa);
@@ -1078,20 +1052,6 @@ int enqueue(lf_ctx* c, const double* d_theta, int B, double* d_out, double* d_ou
     return LF_OK;
 }
 
-void free_cmp(CompressedCat& cc) {
-    for (auto& kv : cc.chunks) {
-        hipFree(kv.second.d_start);
-        hipFree(kv.second.d_len);
-        hipFree(kv.second.d_field);
-        hipFree(kv.second.d_keys);
-    }
-    cc.chunks.clear();
-    double* bufs[] = {cc.d_lum, cc.d_a1, cc.d_U, cc.d_W};
-    for (double* b : bufs)
-        if (b) hipFree(b);
-    cc = CompressedCat{};
-}
-
 // Build the compressed catalogue from the per-source tables already in HBM (lf_compress.h).  FREE: key = logf_i,
 // weight 1; ZEVOL: key = z_i, weight 10^(lum_i - 42).
 int build_compressed(lf_ctx* c) {
@@ -1159,15 +1119,14 @@ int build_compressed(lf_ctx* c) {
     for (int64_t i = 0; i < cc.n; ++i)
         U[(size_t)i] = c->kc.variant == LF_FREE ? std::pow(10.0, out.node[(size_t)i] - LF_FREF) : out.node[(size_t)i] * out.node[(size_t)i];
     int rc;
-    if ((rc = upload(c, &cc.d_lum, lumc.data(), (size_t)cc.n)) != LF_OK || (rc = upload(c, &cc.d_a1, out.node.data(), (size_t)cc.n)) != LF_OK ||
-        (rc = upload(c, &cc.d_U, U.data(), (size_t)cc.n)) != LF_OK || (rc = upload(c, &cc.d_W, out.weight.data(), (size_t)cc.n)) != LF_OK) {
-        free_cmp(cc);                                        // nothing half-built stays behind
+    if ((rc = upload(c, cc.d_lum, lumc.data(), (size_t)cc.n)) != LF_OK || (rc = upload(c, cc.d_a1, out.node.data(), (size_t)cc.n)) != LF_OK ||
+        (rc = upload(c, cc.d_U, U.data(), (size_t)cc.n)) != LF_OK || (rc = upload(c, cc.d_W, out.weight.data(), (size_t)cc.n)) != LF_OK)
         return rc;
-    }
     cc.built = true;
-    c->cmp = cc;
-    // the integration grid, when it is separable (a failure here only leaves the full grid in use)
-    if (c->kc.variant == LF_FREE && !c->h_L.empty() && !c->gridc.built) {
+    // the integration grid, when it is separable (no bins found: the full grid stays in use).  Both are built here and enter the
+    // context together, complete: a failed upload leaves nothing behind
+    CompressedGrid g;
+    if (c->kc.variant == LF_FREE && !c->h_L.empty()) {
         lfc::Model mg = m;
         mg.kind = 2;
         lfc::GridOut go;
@@ -1176,20 +1135,21 @@ int build_compressed(lf_ctx* c) {
             std::vector<double> A4(go.u.size()), PGL((size_t)S);
             for (size_t i = 0; i < go.u.size(); ++i) A4[i] = std::pow(10.0, go.u[i] - LF_FREF);
             for (int j = 0; j < S; ++j) PGL[(size_t)j] = std::pow(10.0, c->h_L[(size_t)j] - LF_LREF);
-            auto& g = c->gridc;
-            if ((rc = upload(c, &g.d_U, go.u.data(), go.u.size())) != LF_OK) return rc;
-            if ((rc = upload(c, &g.d_A4, A4.data(), A4.size())) != LF_OK) return rc;
-            if ((rc = upload(c, &g.d_omega, go.omega.data(), go.omega.size())) != LF_OK) return rc;
-            if ((rc = upload(c, &g.d_L, c->h_L.data(), (size_t)S)) != LF_OK) return rc;
-            if ((rc = upload(c, &g.d_PGL, PGL.data(), (size_t)S)) != LF_OK) return rc;
-            if ((rc = upload(c, &g.d_row0, go.row0.data(), go.row0.size())) != LF_OK) return rc;
-            if ((rc = upload(c, &g.d_nrows, go.nrows.data(), go.nrows.size())) != LF_OK) return rc;
-            if ((rc = upload(c, &g.d_off, go.off.data(), go.off.size())) != LF_OK) return rc;
+            if ((rc = upload(c, g.d_U, go.u.data(), go.u.size())) != LF_OK) return rc;
+            if ((rc = upload(c, g.d_A4, A4.data(), A4.size())) != LF_OK) return rc;
+            if ((rc = upload(c, g.d_omega, go.omega.data(), go.omega.size())) != LF_OK) return rc;
+            if ((rc = upload(c, g.d_L, c->h_L.data(), (size_t)S)) != LF_OK) return rc;
+            if ((rc = upload(c, g.d_PGL, PGL.data(), (size_t)S)) != LF_OK) return rc;
+            if ((rc = upload(c, g.d_row0, go.row0.data(), go.row0.size())) != LF_OK) return rc;
+            if ((rc = upload(c, g.d_nrows, go.nrows.data(), go.nrows.size())) != LF_OK) return rc;
+            if ((rc = upload(c, g.d_off, go.off.data(), go.off.size())) != LF_OK) return rc;
             g.nb = go.nb;
             g.bound = go.bound;
             g.built = true;
         }
     }
+    c->cmp = std::move(cc);
+    c->gridc = std::move(g);
     return LF_OK;
 }
 
@@ -1266,58 +1226,8 @@ void free_ctx(lf_ctx* c) {
         hipEventDestroy(e.a);
         hipEventDestroy(e.b);
     }
-    for (auto& kv : c->chunks) {
-        hipFree(kv.second.d_start);
-        hipFree(kv.second.d_len);
-        hipFree(kv.second.d_field);
-        hipFree(kv.second.d_keys);
-    }
-    for (auto& kv : c->chunks_free) {
-        hipFree(kv.second.d_start);
-        hipFree(kv.second.d_len);
-        hipFree(kv.second.d_field);
-        hipFree(kv.second.d_keys);
-    }
-    free_cmp(c->cmp);
-    if (c->d_partR) hipFree(c->d_partR);
-    if (c->d_cells) hipFree(c->d_cells);
-    if (c->d_cc_start) hipFree(c->d_cc_start);
-    if (c->d_deal) hipFree(c->d_deal);
-    if (c->d_err) hipFree(c->d_err);
-    for (int i = 0; i < 3; ++i) {
-        if (c->d_fblk[i]) hipFree(c->d_fblk[i]);
-        if (c->h_fblk[i]) hipHostFree(c->h_fblk[i]);
-    }
-    if (c->d_cc_len) hipFree(c->d_cc_len);
-    if (c->d_cc_field) hipFree(c->d_cc_field);
-    {
-        auto& g = c->gridc;
-        double* gb[] = {g.d_U, g.d_A4, g.d_omega, g.d_L, g.d_PGL};
-        for (double* b : gb)
-            if (b) hipFree(b);
-        int* gi_[] = {g.d_row0, g.d_nrows, g.d_off};
-        for (int* b : gi_)
-            if (b) hipFree(b);
-        if (c->d_nodes4) hipFree(c->d_nodes4);
-        if (c->d_zcol) hipFree(c->d_zcol);
-        if (c->gridq.d_rec) hipFree(c->gridq.d_rec);
-        if (c->gridq.d_omega) hipFree(c->gridq.d_omega);
-        if (c->gridq.d_rows) hipFree(c->gridq.d_rows);
-    }
-    double* bufs[] = {c->d_lum, c->d_a1, c->d_P, c->d_U, c->d_G, c->d_PG, c->d_W, c->d_a3, c->d_a4, c->d_a4min, c->d_nodes8,
-                      c->d_theta, c->d_out, c->d_outA, c->d_outB, c->d_wrec, c->d_partA, c->d_partB};
-    for (double* b : bufs)
-        if (b) hipFree(b);
-    if (c->d_wstat) hipFree(c->d_wstat);
-    if (c->d_wmode) hipFree(c->d_wmode);
-    if (c->d_wbase) hipFree(c->d_wbase);
-    if (c->d_slow) hipFree(c->d_slow);
-    if (c->d_forms) hipFree(c->d_forms);
-    if (c->d_queue) hipFree(c->d_queue);
-    if (c->h_theta) hipHostFree(c->h_theta);
-    if (c->h_out) hipHostFree(c->h_out);
     if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                            // (its buffers go with it: lf_devmem.h)
 }
 
 int build(lf_ctx* c, const lf_desc* d) {
@@ -1472,10 +1382,10 @@ int build(lf_ctx* c, const lf_desc* d) {
         kc.zcell_rho = zcell_rho_for_box(kc, nf);
         if ((rc = build_cells(c, kc, a1, nf, wts.data())) != LF_OK) return rc;
     }
-    if ((rc = upload(c, &c->d_lum, lumv.data(), (size_t)N)) != LF_OK) return rc;
-    if ((rc = upload(c, &c->d_a1, a1.data(), (size_t)N)) != LF_OK) return rc;
-    if ((rc = upload(c, &c->d_P, P.data(), (size_t)N)) != LF_OK) return rc;
-    if ((rc = upload(c, &c->d_U, U.data(), (size_t)N)) != LF_OK) return rc;
+    if ((rc = upload(c, c->d_lum, lumv.data(), (size_t)N)) != LF_OK) return rc;
+    if ((rc = upload(c, c->d_a1, a1.data(), (size_t)N)) != LF_OK) return rc;
+    if ((rc = upload(c, c->d_P, P.data(), (size_t)N)) != LF_OK) return rc;
+    if ((rc = upload(c, c->d_U, U.data(), (size_t)N)) != LF_OK) return rc;
 
     // ---- grid-node tables.  trapz weights from the actual spacings (scipy trapz = sum d*(y1+y0)/2)
     size_t nn = (size_t)S * S;
@@ -1543,9 +1453,9 @@ int build(lf_ctx* c, const lf_desc* d) {
                 lfq::GridQ gq;
                 if (lfq::build_gridq(bx, S, c->h_L.data(), c->h_wL.data(), c->h_ck.data(), c->h_Dk.data(), LF_FREF, LF_LREF, gq)) {
                     auto& g = c->gridq;
-                    if ((rc = upload(c, &g.d_rec, gq.rec.data(), gq.rec.size())) != LF_OK) return rc;
-                    if ((rc = upload(c, &g.d_omega, gq.omega.data(), gq.omega.size())) != LF_OK) return rc;
-                    if ((rc = upload(c, &g.d_rows, gq.rows.data(), gq.rows.size())) != LF_OK) return rc;
+                    if ((rc = upload(c, g.d_rec, gq.rec.data(), gq.rec.size())) != LF_OK) return rc;
+                    if ((rc = upload(c, g.d_omega, gq.omega.data(), gq.omega.size())) != LF_OK) return rc;
+                    if ((rc = upload(c, g.d_rows, gq.rows.data(), gq.rows.size())) != LF_OK) return rc;
                     g.nb = gq.nb;
                     g.margin = gq.margin;
                     g.built = true;
@@ -1591,11 +1501,11 @@ int build(lf_ctx* c, const lf_desc* d) {
             c->nnodes = S;
         }
     }
-    if ((rc = upload(c, &c->d_G, G.data(), nn)) != LF_OK) return rc;
-    if ((rc = upload(c, &c->d_PG, PG.data(), nn)) != LF_OK) return rc;
-    if ((rc = upload(c, &c->d_W, W.data(), nn)) != LF_OK) return rc;
-    if ((rc = upload(c, &c->d_a3, a3.data(), nn)) != LF_OK) return rc;
-    if ((rc = upload(c, &c->d_a4, a4.data(), nn)) != LF_OK) return rc;
+    if ((rc = upload(c, c->d_G, G.data(), nn)) != LF_OK) return rc;
+    if ((rc = upload(c, c->d_PG, PG.data(), nn)) != LF_OK) return rc;
+    if ((rc = upload(c, c->d_W, W.data(), nn)) != LF_OK) return rc;
+    if ((rc = upload(c, c->d_a3, a3.data(), nn)) != LF_OK) return rc;
+    if ((rc = upload(c, c->d_a4, a4.data(), nn)) != LF_OK) return rc;
     if (d->variant != LF_FREE) {
         // lf_pers reads the nodes as 32-byte records {G, PG, W, redshift column}, padded to whole chunks of 64 (pads: W = 0)
         const size_t nch = (nn + 63) / 64;
@@ -1608,14 +1518,14 @@ int build(lf_ctx* c, const lf_desc* d) {
             r[2] = g < nn ? W[gg] : 0.0;
             r[3] = kc.zgrid_cols ? (double)(gg / (size_t)S) : 0.0;      // (column-major lattice: node = k S + j)
         }
-        if ((rc = upload(c, &c->d_nodes4, n4.data(), n4.size())) != LF_OK) return rc;
+        if ((rc = upload(c, c->d_nodes4, n4.data(), n4.size())) != LF_OK) return rc;
         c->nch4 = (int)nch;
         std::vector<double> zc((size_t)S * 2);
         for (int k = 0; k < S; ++k) {
             zc[(size_t)2 * k] = d->zarr[k];
             zc[(size_t)2 * k + 1] = d->zarr[k] * d->zarr[k];
         }
-        if ((rc = upload(c, &c->d_zcol, zc.data(), zc.size())) != LF_OK) return rc;
+        if ((rc = upload(c, c->d_zcol, zc.data(), zc.size())) != LF_OK) return rc;
     }
     {
         // per chunk of 256 nodes the smallest a4 (FREE; NaN-safe: a NaN node keeps the general form)
@@ -1625,7 +1535,7 @@ int build(lf_ctx* c, const lf_desc* d) {
             for (size_t g = ch * lf::BLOCK; g < std::min(nn, (ch + 1) * lf::BLOCK); ++g) m = std::isnan(a4[g]) ? 0.0 : std::fmin(m, a4[g]);
             a4min[ch] = d->variant == LF_FREE ? m : 0.0;
         }
-        if ((rc = upload(c, &c->d_a4min, a4min.data(), a4min.size())) != LF_OK) return rc;
+        if ((rc = upload(c, c->d_a4min, a4min.data(), a4min.size())) != LF_OK) return rc;
         // lf_free reads the nodes as 64-byte records {G, PG, W, a3, a4, smallest a4 of the node's chunk of 64, -, -}, padded
         // to whole chunks (pads: the last node again with W = 0): one contiguous load per lane, nothing to mask
         if (d->variant == LF_FREE) {
@@ -1645,16 +1555,15 @@ int build(lf_ctx* c, const lf_desc* d) {
                     r[5] = m;
                 }
             }
-            if ((rc = upload(c, &c->d_nodes8, n8.data(), n8.size())) != LF_OK) return rc;
+            if ((rc = upload(c, c->d_nodes8, n8.data(), n8.size())) != LF_OK) return rc;
         }
     }
     {
         hipDeviceProp_t prop;
         LF_HIP(c, hipGetDeviceProperties(&prop, c->device));
         c->num_cu = prop.multiProcessorCount;
-        LF_HIP(c, hipMalloc((void**)&c->d_queue, 1024 * sizeof(int)));
+        LF_HIP(c, c->d_queue.alloc(1024));
         LF_HIP(c, hipMemset(c->d_queue, 0, 1024 * sizeof(int)));
-        c->cap_queue = 1024;
     }
     LF_HIP(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     const int mb = d->max_batch > 0 ? d->max_batch : 1024;
@@ -1872,11 +1781,13 @@ int lf_debug_stamps(lf_ctx* c, uint64_t* out, int64_t nblocks) {
     LF_HIP(c, hipSetDevice(c->device));
     LF_HIP(c, hipDeviceSynchronize());
     if (!out) {                                   // arm for nblocks workgroups
-        if (c->kc.stamps) hipFree(c->kc.stamps);
+        c->d_stamps.reset();
         c->kc.stamps = nullptr;
         if (nblocks > 0) {
-            LF_HIP(c, hipMalloc((void**)&c->kc.stamps, (size_t)nblocks * 8 * sizeof(uint64_t)));
-            LF_HIP(c, hipMemset(c->kc.stamps, 0, (size_t)nblocks * 8 * sizeof(uint64_t)));
+            const int rc = grow(c, c->d_stamps, (size_t)nblocks * 8, false);       // (the device is idle already)
+            if (rc != LF_OK) return rc;
+            LF_HIP(c, hipMemset(c->d_stamps, 0, (size_t)nblocks * 8 * sizeof(uint64_t)));
+            c->kc.stamps = c->d_stamps;
         }
         return LF_OK;
     }
@@ -1896,17 +1807,16 @@ int lf_veff(int device, int64_t n, const double* flux, const double* flim, const
         for (int64_t i = 0; i < n * (int64_t)nboot; ++i)
             if (boot_idx[i] < 0 || boot_idx[i] >= n) return LF_ERR_ARG;
     if (hipSetDevice(device) != hipSuccess) return LF_ERR_NODEV;
-    double *d_flux = nullptr, *d_flim = nullptr, *d_vol = nullptr, *d_phi = nullptr, *d_sums = nullptr;
-    int* d_bin = nullptr;
-    long long* d_idx = nullptr;
+    Buf<double> d_flux, d_flim, d_vol, d_phi, d_sums;
+    Buf<int> d_bin;
+    Buf<long long> d_idx;
     const size_t nb = (size_t)n * sizeof(double);
     int rc = LF_OK;
     auto ok = [&](hipError_t e) {
         if (e != hipSuccess && rc == LF_OK) rc = LF_ERR_HIP;
         return e == hipSuccess;
     };
-    if (ok(hipMalloc((void**)&d_flux, nb)) && ok(hipMalloc((void**)&d_flim, nb)) && ok(hipMalloc((void**)&d_phi, nb)) &&
-        (!vol || ok(hipMalloc((void**)&d_vol, nb)))) {
+    if (ok(d_flux.alloc((size_t)n)) && ok(d_flim.alloc((size_t)n)) && ok(d_phi.alloc((size_t)n)) && (!vol || ok(d_vol.alloc((size_t)n)))) {
         ok(hipMemcpy(d_flux, flux, nb, hipMemcpyHostToDevice));
         ok(hipMemcpy(d_flim, flim, nb, hipMemcpyHostToDevice));
         if (vol) ok(hipMemcpy(d_vol, vol, nb, hipMemcpyHostToDevice));
@@ -1922,8 +1832,7 @@ int lf_veff(int device, int64_t n, const double* flux, const double* flim, const
         }
         if (rc == LF_OK && nbin > 0) {
             const size_t sb = (size_t)(nboot + 1) * nbin * sizeof(double);
-            if (ok(hipMalloc((void**)&d_bin, (size_t)n * sizeof(int))) && ok(hipMalloc((void**)&d_sums, sb)) &&
-                (!boot_idx || ok(hipMalloc((void**)&d_idx, (size_t)n * nboot * sizeof(long long))))) {
+            if (ok(d_bin.alloc((size_t)n)) && ok(d_sums.alloc((size_t)(nboot + 1) * nbin)) && (!boot_idx || ok(d_idx.alloc((size_t)n * nboot)))) {
                 ok(hipMemcpy(d_bin, bin_of, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
                 ok(hipMemset(d_sums, 0, sb));
                 if (boot_idx) ok(hipMemcpy(d_idx, boot_idx, (size_t)n * nboot * sizeof(long long), hipMemcpyHostToDevice));
@@ -1938,7 +1847,6 @@ int lf_veff(int device, int64_t n, const double* flux, const double* flim, const
         }
         if (rc == LF_OK) ok(hipMemcpy(phi, d_phi, nb, hipMemcpyDeviceToHost));
     }
-    hipFree(d_flux); hipFree(d_flim); hipFree(d_vol); hipFree(d_phi); hipFree(d_sums); hipFree(d_bin); hipFree(d_idx);
     return rc;
 }
 
@@ -1996,7 +1904,7 @@ int lf_lumfunc_quantiles(int device, int variant, int32_t R, const double* draws
     int lg = 0;
     while ((1 << lg) < R) ++lg;
     if (hipSetDevice(device) != hipSuccess) return LF_ERR_NODEV;
-    double *d_rec = nullptr, *d_logL = nullptr, *d_z = nullptr, *d_q = nullptr, *d_out = nullptr, *d_val = nullptr;
+    Buf<double> d_rec, d_logL, d_z, d_q, d_out, d_val;
     hipEvent_t ev[2] = {nullptr, nullptr};
     const size_t pb = (size_t)P * sizeof(double);
     int rc = LF_OK;
@@ -2005,9 +1913,8 @@ int lf_lumfunc_quantiles(int device, int variant, int32_t R, const double* draws
         return e == hipSuccess;
     };
     g_bands_ms = -1.0;
-    if (ok(hipMalloc((void**)&d_rec, rec.size() * sizeof(double))) && ok(hipMalloc((void**)&d_logL, pb)) &&
-        (variant != LF_ZEVOL || ok(hipMalloc((void**)&d_z, pb))) && ok(hipMalloc((void**)&d_q, qtab.size() * sizeof(double))) &&
-        ok(hipMalloc((void**)&d_out, (size_t)nq * pb)) && (!values || ok(hipMalloc((void**)&d_val, (size_t)R * pb))) &&
+    if (ok(d_rec.alloc(rec.size())) && ok(d_logL.alloc((size_t)P)) && (variant != LF_ZEVOL || ok(d_z.alloc((size_t)P))) &&
+        ok(d_q.alloc(qtab.size())) && ok(d_out.alloc((size_t)nq * P)) && (!values || ok(d_val.alloc((size_t)R * P))) &&
         ok(hipEventCreate(&ev[0])) && ok(hipEventCreate(&ev[1]))) {
         ok(hipMemcpy(d_rec, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
         ok(hipMemcpy(d_logL, logL, pb, hipMemcpyHostToDevice));
@@ -2035,7 +1942,6 @@ int lf_lumfunc_quantiles(int device, int variant, int32_t R, const double* draws
     }
     for (hipEvent_t e : ev)
         if (e) hipEventDestroy(e);
-    hipFree(d_rec); hipFree(d_logL); hipFree(d_z); hipFree(d_q); hipFree(d_out); hipFree(d_val);
     return rc;
 }
 
@@ -2094,7 +2000,8 @@ int lf_set_option(lf_ctx* c, const char* key, int64_t value) {
             // context's prior box: 64 theta rows (deterministic stream), both paths, lnprob to 1e-12 and the same -inf
             // pattern - otherwise the option is refused and the compressed tables are dropped.
             if (fresh && c->cmp.built && (rc = compress_selfcheck(c)) != LF_OK) {
-                free_cmp(c->cmp);
+                c->cmp = CompressedCat{};
+                c->gridc = CompressedGrid{};
                 return rc;
             }
         }
@@ -2103,7 +2010,7 @@ int lf_set_option(lf_ctx* c, const char* key, int64_t value) {
     }
     if (std::strcmp(key, "count_forms") == 0) {
         hipSetDevice(c->device);
-        if (value != 0 && !c->d_forms) LF_HIP(c, hipMalloc((void**)&c->d_forms, lf::FORM_COUNT * sizeof(unsigned long long)));
+        if (value != 0 && !c->d_forms) LF_HIP(c, c->d_forms.alloc(lf::FORM_COUNT));
         if (c->d_forms) {
             LF_HIP(c, hipDeviceSynchronize());
             LF_HIP(c, hipMemset(c->d_forms, 0, lf::FORM_COUNT * sizeof(unsigned long long)));
@@ -2268,11 +2175,40 @@ struct lf_sampler {
     double a = 2.0;
     uint64_t seed = 0, step = 0;
     int64_t cap = 0, t = 0;
-    double *d_pos = nullptr, *d_lnp = nullptr, *d_prop = nullptr, *d_zz = nullptr, *d_newlp = nullptr;
-    double *d_chain = nullptr, *d_chain_lnp = nullptr;
-    long long* d_nacc = nullptr;
+    Buf<double> d_pos, d_lnp, d_prop, d_zz, d_newlp;
+    Buf<double> d_chain, d_chain_lnp;
+    Buf<long long> d_nacc;
     bool started = false;
 };
+
+namespace {
+
+// A sampler's chains on the device are [rows][cap][width], the caller's [rows][t][width] (t steps taken): packed on the device
+// first, then ONE copy to the host (a strided copy into pageable host memory goes row by row).  parts[0] is the widest.
+struct ChainPart {
+    double* dst;            // host (NULL: not asked for)
+    const double* src;
+    size_t rows, width;
+};
+int read_chains(lf_ctx* c, const char* fn, const ChainPart* parts, int nparts, size_t cap, size_t t) {
+    bool any = false;
+    for (int i = 0; i < nparts; ++i) any = any || parts[i].dst;
+    if (t == 0 || !any) return LF_OK;
+    Buf<double> tmp;
+    LF_HIP(c, tmp.alloc(parts[0].rows * t * parts[0].width));
+    for (int i = 0; i < nparts; ++i) {
+        const ChainPart& p = parts[i];
+        if (!p.dst) continue;
+        if (hipMemcpy2D(tmp, t * p.width * 8, p.src, cap * p.width * 8, t * p.width * 8, p.rows, hipMemcpyDeviceToDevice) != hipSuccess ||
+            hipMemcpy(p.dst, tmp, p.rows * t * p.width * 8, hipMemcpyDeviceToHost) != hipSuccess) {
+            c->err = std::string(fn) + ": copy failed";
+            return LF_ERR_HIP;
+        }
+    }
+    return LF_OK;
+}
+
+}  // namespace
 
 lf_sampler* lf_sampler_create(lf_ctx* c, int nwalkers, double a, uint64_t seed, int64_t capacity_steps) {
     if (!c) return nullptr;
@@ -2290,12 +2226,9 @@ lf_sampler* lf_sampler_create(lf_ctx* c, int nwalkers, double a, uint64_t seed, 
     sm->seed = seed;
     sm->cap = capacity_steps;
     const size_t W = (size_t)nwalkers, nd = (size_t)sm->ndim, cap = (size_t)capacity_steps;
-    bool ok = hipMalloc((void**)&sm->d_pos, W * nd * 8) == hipSuccess && hipMalloc((void**)&sm->d_lnp, W * 8) == hipSuccess &&
-              hipMalloc((void**)&sm->d_prop, W * nd * 8) == hipSuccess && hipMalloc((void**)&sm->d_zz, W * 8) == hipSuccess &&
-              hipMalloc((void**)&sm->d_newlp, W * 8) == hipSuccess &&
-              hipMalloc((void**)&sm->d_chain, W * cap * nd * 8) == hipSuccess &&
-              hipMalloc((void**)&sm->d_chain_lnp, W * cap * 8) == hipSuccess &&
-              hipMalloc((void**)&sm->d_nacc, W * sizeof(long long)) == hipSuccess;
+    bool ok = sm->d_pos.alloc(W * nd) == hipSuccess && sm->d_lnp.alloc(W) == hipSuccess && sm->d_prop.alloc(W * nd) == hipSuccess &&
+              sm->d_zz.alloc(W) == hipSuccess && sm->d_newlp.alloc(W) == hipSuccess && sm->d_chain.alloc(W * cap * nd) == hipSuccess &&
+              sm->d_chain_lnp.alloc(W * cap) == hipSuccess && sm->d_nacc.alloc(W) == hipSuccess;
     if (!ok) {
         c->err = "lf_sampler_create: device allocation failed";
         lf_sampler_destroy(sm);
@@ -2310,8 +2243,6 @@ void lf_sampler_destroy(lf_sampler* sm) {
         hipSetDevice(sm->ctx->device);
         hipDeviceSynchronize();
     }
-    hipFree(sm->d_pos); hipFree(sm->d_lnp); hipFree(sm->d_prop); hipFree(sm->d_zz); hipFree(sm->d_newlp);
-    hipFree(sm->d_chain); hipFree(sm->d_chain_lnp); hipFree(sm->d_nacc);
     delete sm;
 }
 
@@ -2368,29 +2299,10 @@ int lf_sampler_read(lf_sampler* sm, double* chain, double* chain_lnprob, int64_t
     lf_ctx* c = sm->ctx;
     LF_HIP(c, hipSetDevice(c->device));
     LF_HIP(c, hipDeviceSynchronize());
-    const size_t W = (size_t)sm->W, nd = (size_t)sm->ndim, cap = (size_t)sm->cap, t = (size_t)sm->t;
-    // device chain is [W][cap][ndim]; the caller's is [W][t][ndim]: one strided copy each
-    // (packed on the device first, then ONE copy to the host: a strided copy into pageable host memory goes row by row)
-    if (t > 0 && (chain || chain_lnprob)) {
-        double* tmp = nullptr;
-        LF_HIP(c, hipMalloc((void**)&tmp, W * t * nd * 8));
-        int rc = LF_OK;
-        if (chain) {
-            if (hipMemcpy2D(tmp, t * nd * 8, sm->d_chain, cap * nd * 8, t * nd * 8, W, hipMemcpyDeviceToDevice) != hipSuccess ||
-                hipMemcpy(chain, tmp, W * t * nd * 8, hipMemcpyDeviceToHost) != hipSuccess)
-                rc = LF_ERR_HIP;
-        }
-        if (rc == LF_OK && chain_lnprob) {
-            if (hipMemcpy2D(tmp, t * 8, sm->d_chain_lnp, cap * 8, t * 8, W, hipMemcpyDeviceToDevice) != hipSuccess ||
-                hipMemcpy(chain_lnprob, tmp, W * t * 8, hipMemcpyDeviceToHost) != hipSuccess)
-                rc = LF_ERR_HIP;
-        }
-        hipFree(tmp);
-        if (rc != LF_OK) {
-            c->err = "lf_sampler_read: copy failed";
-            return rc;
-        }
-    }
+    const size_t W = (size_t)sm->W, nd = (size_t)sm->ndim;
+    const ChainPart parts[2] = {{chain, sm->d_chain, W, nd}, {chain_lnprob, sm->d_chain_lnp, W, 1}};
+    const int rc = read_chains(c, "lf_sampler_read", parts, 2, (size_t)sm->cap, (size_t)sm->t);
+    if (rc != LF_OK) return rc;
     if (naccepted) LF_HIP(c, hipMemcpy(naccepted, sm->d_nacc, W * sizeof(long long), hipMemcpyDeviceToHost));
     if (pos) LF_HIP(c, hipMemcpy(pos, sm->d_pos, W * nd * 8, hipMemcpyDeviceToHost));
     if (lnprob) LF_HIP(c, hipMemcpy(lnprob, sm->d_lnp, W * 8, hipMemcpyDeviceToHost));
@@ -2447,11 +2359,11 @@ struct lf_ptsampler {
     double a = 2.0;
     uint64_t seed = 0, step = 0;
     int64_t cap = 0, t = 0;
-    double *d_betas = nullptr, *d_dbeta = nullptr;
-    double *d_pos = nullptr, *d_lnl = nullptr, *d_prop = nullptr, *d_zz = nullptr, *d_newl = nullptr;
-    double *d_chain = nullptr, *d_chain_lnl = nullptr, *d_mean = nullptr;
-    long long *d_nacc = nullptr, *d_nswap = nullptr;
-    int* d_sig = nullptr;
+    Buf<double> d_betas, d_dbeta;
+    Buf<double> d_pos, d_lnl, d_prop, d_zz, d_newl;
+    Buf<double> d_chain, d_chain_lnl, d_mean;
+    Buf<long long> d_nacc, d_nswap;
+    Buf<int> d_sig;
     bool started = false;
 };
 
@@ -2479,17 +2391,11 @@ lf_ptsampler* lf_ptsampler_create(lf_ctx* c, int ntemps, int nwalkers, const dou
     const size_t T = (size_t)ntemps, TW = T * nwalkers, nd = (size_t)sm->ndim, cap = (size_t)capacity_steps, TH = TW / 2;
     std::vector<double> dbeta(T, 0.0);
     for (size_t i = 1; i < T; ++i) dbeta[i] = betas[i - 1] - betas[i];
-    ok = hipMalloc((void**)&sm->d_betas, T * 8) == hipSuccess && hipMalloc((void**)&sm->d_dbeta, T * 8) == hipSuccess &&
-         hipMalloc((void**)&sm->d_pos, TW * nd * 8) == hipSuccess && hipMalloc((void**)&sm->d_lnl, TW * 8) == hipSuccess &&
-         hipMalloc((void**)&sm->d_prop, TH * nd * 8) == hipSuccess && hipMalloc((void**)&sm->d_zz, TH * 8) == hipSuccess &&
-         hipMalloc((void**)&sm->d_newl, TH * 8) == hipSuccess &&
-         hipMalloc((void**)&sm->d_chain, TW * cap * nd * 8) == hipSuccess &&
-         hipMalloc((void**)&sm->d_chain_lnl, TW * cap * 8) == hipSuccess && hipMalloc((void**)&sm->d_mean, T * cap * 8) == hipSuccess &&
-         hipMalloc((void**)&sm->d_nacc, TW * sizeof(long long)) == hipSuccess &&
-         hipMalloc((void**)&sm->d_nswap, T * sizeof(long long)) == hipSuccess &&
-         hipMalloc((void**)&sm->d_sig, std::max<size_t>(T - 1, 1) * nwalkers * sizeof(int)) == hipSuccess &&
-         hipMemcpy(sm->d_betas, betas, T * 8, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(sm->d_dbeta, dbeta.data(), T * 8, hipMemcpyHostToDevice) == hipSuccess;
+    ok = sm->d_betas.upload(betas, T) == hipSuccess && sm->d_dbeta.upload(dbeta.data(), T) == hipSuccess &&
+         sm->d_pos.alloc(TW * nd) == hipSuccess && sm->d_lnl.alloc(TW) == hipSuccess && sm->d_prop.alloc(TH * nd) == hipSuccess &&
+         sm->d_zz.alloc(TH) == hipSuccess && sm->d_newl.alloc(TH) == hipSuccess && sm->d_chain.alloc(TW * cap * nd) == hipSuccess &&
+         sm->d_chain_lnl.alloc(TW * cap) == hipSuccess && sm->d_mean.alloc(T * cap) == hipSuccess && sm->d_nacc.alloc(TW) == hipSuccess &&
+         sm->d_nswap.alloc(T) == hipSuccess && sm->d_sig.alloc(std::max<size_t>(T - 1, 1) * nwalkers) == hipSuccess;
     // the evaluation's workspace for the T x W / 2 rows of a half-step, now rather than by a resize inside a running chain
     ok = ok && ensure_workspace(c, (int)TH, 0, 0) == LF_OK;
     if (!ok) {
@@ -2506,9 +2412,6 @@ void lf_ptsampler_destroy(lf_ptsampler* sm) {
         hipSetDevice(sm->ctx->device);
         hipDeviceSynchronize();
     }
-    hipFree(sm->d_betas); hipFree(sm->d_dbeta); hipFree(sm->d_pos); hipFree(sm->d_lnl); hipFree(sm->d_prop);
-    hipFree(sm->d_zz); hipFree(sm->d_newl); hipFree(sm->d_chain); hipFree(sm->d_chain_lnl); hipFree(sm->d_mean);
-    hipFree(sm->d_nacc); hipFree(sm->d_nswap); hipFree(sm->d_sig);
     delete sm;
 }
 
@@ -2585,26 +2488,10 @@ int lf_ptsampler_read(lf_ptsampler* sm, double* chain, double* chain_lnlike, dou
     lf_ctx* c = sm->ctx;
     LF_HIP(c, hipSetDevice(c->device));
     LF_HIP(c, hipDeviceSynchronize());
-    const size_t T = (size_t)sm->T, TW = T * sm->W, nd = (size_t)sm->ndim, cap = (size_t)sm->cap, t = (size_t)sm->t;
-    // device arrays are [rows][cap](...); the caller's [rows][t](...): packed on the device, then one copy (lf_sampler_read)
-    struct Part { double* dst; const double* src; size_t rows, width; };
-    const Part parts[3] = {{chain, sm->d_chain, TW, nd}, {chain_lnlike, sm->d_chain_lnl, TW, 1}, {mean_lnlike, sm->d_mean, T, 1}};
-    if (t > 0 && (chain || chain_lnlike || mean_lnlike)) {
-        double* tmp = nullptr;
-        LF_HIP(c, hipMalloc((void**)&tmp, TW * t * nd * 8));
-        int rc = LF_OK;
-        for (const Part& p : parts) {
-            if (!p.dst || rc != LF_OK) continue;
-            if (hipMemcpy2D(tmp, t * p.width * 8, p.src, cap * p.width * 8, t * p.width * 8, p.rows, hipMemcpyDeviceToDevice) != hipSuccess ||
-                hipMemcpy(p.dst, tmp, p.rows * t * p.width * 8, hipMemcpyDeviceToHost) != hipSuccess)
-                rc = LF_ERR_HIP;
-        }
-        hipFree(tmp);
-        if (rc != LF_OK) {
-            c->err = "lf_ptsampler_read: copy failed";
-            return rc;
-        }
-    }
+    const size_t T = (size_t)sm->T, TW = T * sm->W, nd = (size_t)sm->ndim;
+    const ChainPart parts[3] = {{chain, sm->d_chain, TW, nd}, {chain_lnlike, sm->d_chain_lnl, TW, 1}, {mean_lnlike, sm->d_mean, T, 1}};
+    const int rc = read_chains(c, "lf_ptsampler_read", parts, 3, (size_t)sm->cap, (size_t)sm->t);
+    if (rc != LF_OK) return rc;
     if (naccepted) LF_HIP(c, hipMemcpy(naccepted, sm->d_nacc, TW * sizeof(long long), hipMemcpyDeviceToHost));
     if (nswap && T > 1) LF_HIP(c, hipMemcpy(nswap, sm->d_nswap, (T - 1) * sizeof(long long), hipMemcpyDeviceToHost));
     if (pos) LF_HIP(c, hipMemcpy(pos, sm->d_pos, TW * nd * 8, hipMemcpyDeviceToHost));
@@ -2624,13 +2511,12 @@ struct lf_mock {
     int device = 0;
     lf::MockConst mc{};
     int rch = 1;                          // rows per chunk
-    double* d_grid[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // logL, zarr, volume_part, dl_zarr, integ_part
-    double *d_theta = nullptr, *d_cdfL = nullptr, *d_colm = nullptr, *d_cdfZ = nullptr, *d_mean = nullptr;
-    long long *d_rid = nullptr, *d_count = nullptr, *d_off = nullptr;
-    double *d_z = nullptr, *d_L = nullptr, *d_edges = nullptr;
-    int* d_fld = nullptr;
-    unsigned long long* d_hist = nullptr;
-    int64_t cap_src = 0, cap_hist = 0;
+    Buf<double> d_grid[5];                // logL, zarr, volume_part, dl_zarr, integ_part
+    Buf<double> d_theta, d_cdfL, d_colm, d_cdfZ, d_mean;
+    Buf<long long> d_rid, d_count, d_off;
+    Buf<double> d_z, d_L, d_edges;        // d_z, d_L, d_fld: the sources of the largest chunk drawn so far
+    Buf<int> d_fld;
+    Buf<unsigned long long> d_hist;
     std::string err;
 };
 
@@ -2638,15 +2524,6 @@ namespace {
 
 thread_local std::string g_mock_create_error = "";
 constexpr size_t MOCK_WORKSPACE = (size_t)512 << 20;      // bytes of cumulative sums per chunk of rows
-
-void mock_free(lf_mock* m) {
-    if (!m) return;
-    for (double* p : m->d_grid) hipFree(p);
-    hipFree(m->d_theta); hipFree(m->d_cdfL); hipFree(m->d_colm); hipFree(m->d_cdfZ); hipFree(m->d_mean);
-    hipFree(m->d_rid); hipFree(m->d_count); hipFree(m->d_off); hipFree(m->d_z); hipFree(m->d_L); hipFree(m->d_edges);
-    hipFree(m->d_fld); hipFree(m->d_hist);
-    delete m;
-}
 
 int mock_fail(lf_mock* m, const char* fn, const std::string& msg) {
     m->err = std::string(fn) + ": " + msg;
@@ -2753,20 +2630,13 @@ lf_mock* lf_mock_create(const lf_desc* d) {
     const size_t nrf = (size_t)m->rch * nf;
     bool ok = true;
     for (int i = 0; i < 5 && ok; ++i)
-        if (src[i])
-            ok = hipMalloc((void**)&m->d_grid[i], len[i] * sizeof(double)) == hipSuccess &&
-                 hipMemcpy(m->d_grid[i], src[i], len[i] * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMalloc((void**)&m->d_theta, (size_t)m->rch * mc.ndim * sizeof(double)) == hipSuccess &&
-         hipMalloc((void**)&m->d_rid, (size_t)m->rch * sizeof(long long)) == hipSuccess &&
-         hipMalloc((void**)&m->d_cdfL, nrf * SS * sizeof(double)) == hipSuccess &&
-         hipMalloc((void**)&m->d_colm, nrf * S * sizeof(double)) == hipSuccess &&
-         hipMalloc((void**)&m->d_cdfZ, nrf * S * sizeof(double)) == hipSuccess &&
-         hipMalloc((void**)&m->d_mean, nrf * sizeof(double)) == hipSuccess &&
-         hipMalloc((void**)&m->d_count, nrf * sizeof(long long)) == hipSuccess &&
-         hipMalloc((void**)&m->d_off, (nrf + 1) * sizeof(long long)) == hipSuccess &&
-         hipMalloc((void**)&m->d_edges, (lf::MOCK_MAX_BINS + 1) * sizeof(double)) == hipSuccess;
+        if (src[i]) ok = m->d_grid[i].upload(src[i], len[i]) == hipSuccess;
+    ok = ok && m->d_theta.alloc((size_t)m->rch * mc.ndim) == hipSuccess && m->d_rid.alloc((size_t)m->rch) == hipSuccess &&
+         m->d_cdfL.alloc(nrf * SS) == hipSuccess && m->d_colm.alloc(nrf * S) == hipSuccess && m->d_cdfZ.alloc(nrf * S) == hipSuccess &&
+         m->d_mean.alloc(nrf) == hipSuccess && m->d_count.alloc(nrf) == hipSuccess && m->d_off.alloc(nrf + 1) == hipSuccess &&
+         m->d_edges.alloc(lf::MOCK_MAX_BINS + 1) == hipSuccess;
     if (!ok) {
-        mock_free(m);
+        delete m;
         return bad("device allocation or copy failed");
     }
     mc.logL = m->d_grid[0];
@@ -2778,8 +2648,9 @@ lf_mock* lf_mock_create(const lf_desc* d) {
 }
 
 void lf_mock_destroy(lf_mock* m) {
-    if (m) hipSetDevice(m->device);
-    mock_free(m);
+    if (!m) return;
+    hipSetDevice(m->device);
+    delete m;
 }
 
 const char* lf_mock_last_error(const lf_mock* m) { return m ? m->err.c_str() : g_mock_create_error.c_str(); }
@@ -2832,16 +2703,10 @@ int lf_mock_draw(lf_mock* m, const double* theta, int32_t R, const int64_t* row_
         const int64_t tot = off[(size_t)nrf];
         if (tot == 0) continue;
         if ((rc = mock_masses(m, fn, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
-        if (tot > m->cap_src) {
-            hipFree(m->d_z); hipFree(m->d_L); hipFree(m->d_fld);
-            m->d_z = m->d_L = nullptr;
-            m->d_fld = nullptr;
-            m->cap_src = 0;
-            LF_HIP(m, hipMalloc((void**)&m->d_z, (size_t)tot * sizeof(double)));
-            LF_HIP(m, hipMalloc((void**)&m->d_L, (size_t)tot * sizeof(double)));
-            LF_HIP(m, hipMalloc((void**)&m->d_fld, (size_t)tot * sizeof(int)));
-            m->cap_src = tot;
-        }
+        // (each by its own size: after a failed allocation the empty one is made again)
+        if ((size_t)tot > m->d_z.size() && (rc = grow(m, m->d_z, (size_t)tot, false)) != LF_OK) return rc;
+        if ((size_t)tot > m->d_L.size() && (rc = grow(m, m->d_L, (size_t)tot, false)) != LF_OK) return rc;
+        if ((size_t)tot > m->d_fld.size() && (rc = grow(m, m->d_fld, (size_t)tot, false)) != LF_OK) return rc;
         LF_HIP(m, hipMemcpy(m->d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice));
         hipLaunchKernelGGL(lf::lf_mock_draw, dim3((unsigned)((tot + lf::MOCK_THREADS - 1) / lf::MOCK_THREADS)), dim3(lf::MOCK_THREADS), 0, 0,
                            m->mc, nrf, m->d_off, m->d_rid, (unsigned long long)seed, m->d_cdfL, m->d_cdfZ, m->d_z, m->d_L, m->d_fld);
@@ -2875,13 +2740,7 @@ int lf_mock_hist(lf_mock* m, const double* theta, int32_t R, const int64_t* row_
         const int rows = std::min<int32_t>(m->rch, R - r0);
         const int nrf = rows * nf;
         if ((rc = mock_masses(m, fn, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
-        if ((int64_t)nrf * ns > m->cap_hist) {
-            hipFree(m->d_hist);
-            m->d_hist = nullptr;
-            m->cap_hist = 0;
-            LF_HIP(m, hipMalloc((void**)&m->d_hist, (size_t)nrf * ns * sizeof(unsigned long long)));
-            m->cap_hist = (int64_t)nrf * ns;
-        }
+        if ((size_t)nrf * ns > m->d_hist.size() && (rc = grow(m, m->d_hist, (size_t)nrf * ns, false)) != LF_OK) return rc;
         blk.assign((size_t)nrf + 1, 0);
         for (int i = 0; i < nrf; ++i) blk[(size_t)i + 1] = blk[(size_t)i] + (n[(size_t)i] + lf::MOCK_HIST_CHUNK - 1) / lf::MOCK_HIST_CHUNK;
         LF_HIP(m, hipMemset(m->d_hist, 0, (size_t)nrf * ns * sizeof(unsigned long long)));
