@@ -222,7 +222,7 @@ def compress_grid(params, L, wL, ck, Dk):
 
 
 def deal_table(n_cell_chunks, n_bins, grid_part=0, grid_parts=0):
-    """Host-only helper behind lf_free's deal of its cell chunks and flux bins to its 32 virtual workgroups (lfmcmc.hip:
+    """Host-only helper behind lf_free's deal of its cell chunks and flux bins to its 32 virtual workgroups (csrc/lf_hostprep.h:
     make_deal).  Returns (cells, bins): two lists of 32 lists - the chunk / bin numbers each rank
     takes, in the order it takes them.  Touches no GPU."""
     lib = load()

@@ -23,15 +23,7 @@
 
 namespace lf {
 
-// The deal table: [0 .. VF] where rank vr's cell chunks start in the list, [VF + 1 .. 2 VF + 1] the same for its bins, then the
-// list (cell chunks rank by rank, then bins rank by rank).  Who gets what is decided by COST: a flux bin costs a wave about
-// 2.7 cell chunks, and the workgroups of ranks >= VF / 2 are the younger ones of their CUs, behind their elders when the sums
-// begin (tools/stamps_fused.py) - the host deals bins, then cells, each to the rank that would be done first (lfmcmc.hip:
-// ensure_deal has the costs and the sweep they come from).  With the arithmetic deal (bin c to rank c mod VF, cell chunk cc to rank (cc + VF / 2) mod VF) the busiest rank of the
-// benchmark's context had a bin and two cell chunks (10.4k cycles), the average being 6.6k, and the 17th bin sat on a younger
-// rank with two cell chunks of its own.  A context's table depends on its numbers of bins and cell chunks only: a row's
-// partial sums (one per virtual rank) are the same whatever the batch.
-constexpr int DEAL_BINS = VF + 1, DEAL_LIST = 2 * (VF + 1), DEAL_MAX = 512;
+// (the deal table of cell chunks and flux bins to the VF virtual workgroups, DEAL_*: lf_layout.h)
 
 // 512-thread block reduction: red[nw][512] -> out[(w0 + w) * stride + chunk], nw <= 8: wave w adds walker w's row
 // (eight columns per lane, stride 64) and runs one 64-lane sum on the DPP network.  Fixed order.

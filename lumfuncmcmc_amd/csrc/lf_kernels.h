@@ -26,14 +26,12 @@
 // The mode is per (walker, field) and wave-uniform inside the walker loop: one scalar branch per walker,
 // and a walker's result never depends on which other walkers share its tile.
 #pragma once
+#include "lf_layout.h"
 #include "lf_math.h"
 
 namespace lf {
 
-constexpr int BLOCK = 256;   // 4 waves
-constexpr int MAXF = 8;
 constexpr int REC = 8 + 8 * MAXF;   // doubles per walker record: 8 walker scalars, then one block of 8 per field
-constexpr int KEY_STRIDE = 12;   // ints per chunk in SrcArrays::chunk_keys
 constexpr int WM = 8;        // ints per (walker, field) in wmode: {mode, klo, khi, kne, kaC, -, -, -}
 // SKIP: the walker failed the prior - lnprob is -inf whatever the sums are (the reference returns before lnlike,
 // lumfuncmcmc.py:408): neither its terms nor its grid nodes are evaluated.  SKIPSRC: piece A is already known to be
@@ -61,11 +59,11 @@ constexpr double CELL_RHO_G = 1.5e-2, CELL_RHO_H = 3.0e-3;
 // 2 rho wide, and a walker takes them when |a| rho <= ZCELL_X1 over the field's redshifts and |b| rho^2 <= ZCELL_X2
 // (lf_prepare): the orders above CELL_M then sum to less than 1e-17 (tests/test_tables_cpu.py recomputes the bound from
 // the majorant series exp(X1 t + X2 t^2)).  Records {z_c, S_0 .. S_6}: ZCELL_M = 6.  rho (KConst::zcell_rho) is chosen when the context is made, at most
-// ZCELL_RHO and small enough that EVERY walker inside the prior box of L1..L3 passes (lfmcmc.hip: zcell_rho_for_box).
+// ZCELL_RHO and small enough that EVERY walker inside the prior box of L1..L3 passes (lf_hostprep.h: zcell_rho_for_box).
 constexpr double ZCELL_RHO = 1.0e-3, ZCELL_X1 = 6.0e-3, ZCELL_X2 = 1.0e-5;
-constexpr int ZCOLS = 3;                  // redshift columns a chunk of the column-major z-evolving grid may touch
 constexpr int ZCELL_M = 6;
 constexpr int ZCELL_REC = ZCELL_M + 2;
+// (the host's preparation takes these as arguments; the integer keys KEY_* and ZCOLS: lf_layout.h)
 
 // walker record, FREE / FIXCOMP: walker scalars ...
 enum { R_LSTAR = 0, R_C0 = 1, R_C1 = 2, R_Q = 3, R_ALPHAC = 4 };
@@ -79,54 +77,8 @@ enum { M_MODE = 0, M_KLO = 1, M_KHI = 2, M_KNE = 3, M_KAC = 4 };
 // slots of the census KConst::forms (lf_form_counts)
 enum { FORM_GENERAL = 0, FORM_GENERAL_NOEXP = 1, FORM_TABLE = 2, FORM_TABLE_NOEXP = 3, FORM_CAREFUL = 4, FORM_SKIPPED = 5,
        FORM_NODE_GENERAL = 6, FORM_NODE_BRIGHT = 7, FORM_CELL = 8, FORM_COUNT = 9 };
-constexpr double KEY_SCALE = 1048576.0;     // keys of log-flux: (x - x0) * 2^20, 1e-6 dex
-constexpr double KEY_ASCALE = 65536.0;      // keys of alpha_C
-constexpr int KEY_MAX = 2147483000;
 // walker record, ZEVOL
 enum { Z_AL = 0, Z_BL = 1, Z_CL = 2, Z_AP = 3, Z_BP = 4, Z_CP = 5, Z_C1 = 6 };
-
-struct KConst {
-    int variant, fix_sch_al, nf, S, ndim;
-    int specialise;           // 1: chunk-level term specialisation (term_free_noexp); 0 for A/B runs
-    int cells;                // FREE, ZEVOL: 1 = the catalogue's cells exist and lf_prepare may flag walkers STAT_CELLS
-    int cc_fstart[MAXF + 1];  // FREE: cell chunks (64 cells) of field f are [cc_fstart[f], cc_fstart[f + 1])
-    int zgrid_cols;           // ZEVOL: 1 = the grid's nodes are stored column by column (node = k S + j) and S >= BLOCK / (ZCOLS - 1),
-                              // so that a chunk of BLOCK nodes touches at most ZCOLS redshift columns (gridsum_body)
-    double zcell_rho;         // ZEVOL: half the largest width of a cell in redshift (ZCELL_RHO below)
-    int kf_first[MAXF], kf_last[MAXF];   // FREE: keys (floor / ceil) of each field's faintest / brightest source
-    int grid_part, grid_parts; // source-sharded ranks split piece B too: this context integrates the node chunks c with
-                              // c % grid_parts == grid_part (the others contribute 0); 0 / 1 = the whole grid
-    double lnom0_src[MAXF];   // ln(trunc(Omega_0[f]) / sqarcsec)   (int-truncated, lumfuncmcmc.py:285)
-    double om0_grid[MAXF];    // Omega_0[f] / sqarcsec              (float, lumfuncmcmc.py:375)
-    double fc_ratio;          // |a / (1 - a)|, a = (2 fcmin - 1)^2 (VmaxLumFunc.py:164-165)
-    double lims[5][2];
-    double pivots[3];
-    double sch_al0, alpha0;
-    double flim0[MAXF];
-    // per-field extremes of the catalogue, for the mode classification
-    int nsrc[MAXF];
-    double pmax[MAXF];        // max 10^(lum-42)            (FREE, FIXCOMP)
-    double lum_min[MAXF], lum_max[MAXF];
-    double a_min[MAXF];       // FREE: min logf             FIXCOMP/ZEVOL: min ln(Om_arr)
-    double u_min[MAXF];       // FREE: 10^(min logf + 17)
-    double u_max[MAXF];       // FREE: 10^(max logf + 17)
-    double z_lo[MAXF], z_hi[MAXF];   // ZEVOL
-    double key_x0;            // FREE: origin of the integer keys of log-flux (the catalogue's smallest logf)
-    int tables;               // FREE: 1 = table-driven form of the term where it applies (default), 0 = general form only
-    // optional census of which form of the term / node ran (bench.py's flop accounting, tests): terms or node-fields
-    // added per (walker, chunk) by one lane; NULL = off (the default: no atomics on the path)
-    unsigned long long* forms;
-#ifdef LF_STAMPS
-    // diagnostic build (tools/stamps.py): s_memtime at four points of every source workgroup; never in the product
-    unsigned long long* stamps;
-#endif
-    // per-field sums for the closed-form part of piece A:
-    //   sum_i ln TrueLumFunc_i = n (ln ln10 + ln10 phi*) + c1 (sum(lum_i - 42) - n (L* - 42)) - Q sum P_i
-    double slc[MAXF];         // sum (lum_i - 42)
-    double sp[MAXF];          // sum 10^(lum_i - 42)
-    double som[MAXF];         // FIXCOMP/ZEVOL: sum ln(Om_arr_i)
-    double sz[MAXF], sz2[MAXF];   // ZEVOL: sum z_i, sum z_i^2  (L*(z), phi*(z) enter the log-terms linearly)
-};
 
 // getQuadCoef, lumfuncmcmc_z.py:40-42, with the reference's operation order and no FMA contraction
 __device__ inline void quad_coef(double y1, double y2, double y3, double z1, double z2, double z3,
@@ -1309,7 +1261,6 @@ __device__ __forceinline__ void gridsum_body(const KConst& kc, const NodeArrays&
 // values T_w(L_j) in LDS (one exponential per thread), then every thread takes its node's field sum (the same
 // field_sum as the full grid) times its short dot product with T_w.
 // ----------------------------------------------------------------------------------------------
-constexpr int GRIDC_MAX_S = 512;
 struct GridC {
     const double* U;       // [nb * 16] node log-flux
     const double* A4;      // [nb * 16] 10^(U + 17)

@@ -1,0 +1,84 @@
+// lf_layout.h - what the host's table preparation (lf_hostprep.h) and the kernels (lf_kernels.h, lf_tile.h, lf_free.h) must
+// agree on: the constants block KConst and the sizes, strides and scales of the tables.  No device code and nothing included: any
+// C++17 compiler reads it.
+#pragma once
+
+#define LF_LN10 2.302585092994045684
+#define LF_LREF 42.0        // P_i = 10^(lum_i - LF_LREF),  Q_w = 10^(LF_LREF - L*_w)
+#define LF_FREF (-17.0)     // U_i = 10^(logf_i - LF_FREF)
+#define LF_SQARCSEC 42545170296.152206       // (180/pi*3600)^2, VmaxLumFunc.py:43
+#define LF_MPC_CM 3.086e24                   // lumfuncmcmc.py:70
+
+namespace lf {
+
+constexpr int BLOCK = 256;   // 4 waves
+constexpr int MAXF = 8;
+constexpr int KEY_STRIDE = 12;   // ints per chunk in SrcArrays::chunk_keys
+constexpr int ZCOLS = 3;                  // redshift columns a chunk of the column-major z-evolving grid may touch
+constexpr double KEY_SCALE = 1048576.0;     // keys of log-flux: (x - x0) * 2^20, 1e-6 dex
+constexpr double KEY_ASCALE = 65536.0;      // keys of alpha_C
+constexpr int KEY_MAX = 2147483000;
+
+struct KConst {
+    int variant, fix_sch_al, nf, S, ndim;
+    int specialise;           // 1: chunk-level term specialisation (term_free_noexp); 0 for A/B runs
+    int cells;                // FREE, ZEVOL: 1 = the catalogue's cells exist and lf_prepare may flag walkers STAT_CELLS
+    int cc_fstart[MAXF + 1];  // FREE: cell chunks (64 cells) of field f are [cc_fstart[f], cc_fstart[f + 1])
+    int zgrid_cols;           // ZEVOL: 1 = the grid's nodes are stored column by column (node = k S + j) and S >= BLOCK / (ZCOLS - 1),
+                              // so that a chunk of BLOCK nodes touches at most ZCOLS redshift columns (gridsum_body)
+    double zcell_rho;         // ZEVOL: half the largest width of a cell in redshift (lf_kernels.h: ZCELL_RHO)
+    int kf_first[MAXF], kf_last[MAXF];   // FREE: keys (floor / ceil) of each field's faintest / brightest source
+    int grid_part, grid_parts; // source-sharded ranks split piece B too: this context integrates the node chunks c with
+                              // c % grid_parts == grid_part (the others contribute 0); 0 / 1 = the whole grid
+    double lnom0_src[MAXF];   // ln(trunc(Omega_0[f]) / sqarcsec)   (int-truncated, lumfuncmcmc.py:285)
+    double om0_grid[MAXF];    // Omega_0[f] / sqarcsec              (float, lumfuncmcmc.py:375)
+    double fc_ratio;          // |a / (1 - a)|, a = (2 fcmin - 1)^2 (VmaxLumFunc.py:164-165)
+    double lims[5][2];
+    double pivots[3];
+    double sch_al0, alpha0;
+    double flim0[MAXF];
+    // per-field extremes of the catalogue, for the mode classification
+    int nsrc[MAXF];
+    double pmax[MAXF];        // max 10^(lum-42)            (FREE, FIXCOMP)
+    double lum_min[MAXF], lum_max[MAXF];
+    double a_min[MAXF];       // FREE: min logf             FIXCOMP/ZEVOL: min ln(Om_arr)
+    double u_min[MAXF];       // FREE: 10^(min logf + 17)
+    double u_max[MAXF];       // FREE: 10^(max logf + 17)
+    double z_lo[MAXF], z_hi[MAXF];   // ZEVOL
+    double key_x0;            // FREE: origin of the integer keys of log-flux (the catalogue's smallest logf)
+    int tables;               // FREE: 1 = table-driven form of the term where it applies (default), 0 = general form only
+    // optional census of which form of the term / node ran (bench.py's flop accounting, tests): terms or node-fields
+    // added per (walker, chunk) by one lane; NULL = off (the default: no atomics on the path)
+    unsigned long long* forms;
+#ifdef LF_STAMPS
+    // diagnostic build (tools/stamps.py): s_memtime at four points of every source workgroup; never in the product
+    unsigned long long* stamps;
+#endif
+    // per-field sums for the closed-form part of piece A:
+    //   sum_i ln TrueLumFunc_i = n (ln ln10 + ln10 phi*) + c1 (sum(lum_i - 42) - n (L* - 42)) - Q sum P_i
+    double slc[MAXF];         // sum (lum_i - 42)
+    double sp[MAXF];          // sum 10^(lum_i - 42)
+    double som[MAXF];         // FIXCOMP/ZEVOL: sum ln(Om_arr_i)
+    double sz[MAXF], sz2[MAXF];   // ZEVOL: sum z_i, sum z_i^2  (L*(z), phi*(z) enter the log-terms linearly)
+};
+
+constexpr int GRIDC_MAX_S = 512;   // FREE: the largest grid side the compressed grid and the flux bins are built for
+
+constexpr int PB = 512;      // threads per persistent workgroup: 8 waves
+// The cells' and the grid's chunks of a tile are dealt to VF VIRTUAL workgroups, and partB / partC hold one partial sum per
+// (walker, virtual workgroup): the workgroups that actually serve the tile (at most VF: 32 at 128 rows, 16 at 256, 8 when a
+// group serves several tiles in turn) take the virtual ranks r, r + fgroup, ... and keep their sums apart.  So a walker's
+// partial sums - and with them the bits of its lnprob - do not depend on how many rows share its call, on its place in
+// the batch, or on how a batch is sharded over GPUs.
+constexpr int VF = 32;
+// The deal table: [0 .. VF] where rank vr's cell chunks start in the list, [VF + 1 .. 2 VF + 1] the same for its bins, then the
+// list (cell chunks rank by rank, then bins rank by rank).  Who gets what is decided by COST: a flux bin costs a wave about
+// 2.7 cell chunks, and the workgroups of ranks >= VF / 2 are the younger ones of their CUs, behind their elders when the sums
+// begin (tools/stamps_fused.py) - the host deals bins, then cells, each to the rank that would be done first (lf_hostprep.h:
+// make_deal has the costs and the sweep they come from).  With the arithmetic deal (bin c to rank c mod VF, cell chunk cc to rank (cc + VF / 2) mod VF) the busiest rank of the
+// benchmark's context had a bin and two cell chunks (10.4k cycles), the average being 6.6k, and the 17th bin sat on a younger
+// rank with two cell chunks of its own.  A context's table depends on its numbers of bins and cell chunks only: a row's
+// partial sums (one per virtual rank) are the same whatever the batch.
+constexpr int DEAL_BINS = VF + 1, DEAL_LIST = 2 * (VF + 1), DEAL_MAX = 512;
+
+}  // namespace lf

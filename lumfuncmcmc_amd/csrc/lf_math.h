@@ -15,17 +15,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "lf_layout.h"      // LF_LN10, LF_LREF, LF_FREF, LF_SQARCSEC, LF_MPC_CM
 #include "lf_tables.h"
 
-#define LF_LN10 2.302585092994045684
 #define LF_LNLN10 0.834032445247955959       // ln(ln 10)
 #define LF_LN2 0.693147180559945309
 // exp(-v) rounds to +0 in binary64 for v > ln(2^1075); log of a product below 2^-1075 is -inf.
 #define LF_UNDERFLOW 745.13321910194122
-#define LF_LREF 42.0        // P_i = 10^(lum_i - LF_LREF),  Q_w = 10^(LF_LREF - L*_w)
-#define LF_FREF (-17.0)     // U_i = 10^(logf_i - LF_FREF)
-#define LF_SQARCSEC 42545170296.152206       // (180/pi*3600)^2, VmaxLumFunc.py:43
-#define LF_MPC_CM 3.086e24                   // lumfuncmcmc.py:70
 
 namespace lf {
 

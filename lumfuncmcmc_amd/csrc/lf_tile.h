@@ -5,15 +5,9 @@
 
 namespace lf {
 
-constexpr int PB = 512;      // threads per persistent workgroup: 8 waves
+// (PB, the threads of a persistent workgroup, and VF, the virtual workgroups of a tile: lf_layout.h)
 constexpr int PTW = 8;       // walkers per tile
 constexpr int QSTRIDE = 9;   // counters per tile: [0] grid queue, [1..8] catalogue queues of XCD 0..7
-// The cells' and the grid's chunks of a tile are dealt to VF VIRTUAL workgroups, and partB / partC hold one partial sum per
-// (walker, virtual workgroup): the workgroups that actually serve the tile (at most VF: 32 at 128 rows, 16 at 256, 8 when a
-// group serves several tiles in turn) take the virtual ranks r, r + fgroup, ... and keep their sums apart.  So a walker's
-// partial sums - and with them the bits of its lnprob - do not depend on how many rows share its call, on its place in
-// the batch, or on how a batch is sharded over GPUs.
-constexpr int VF = 32;
 // The one-launch form's hand-over by POLLING (tiles whose walkers are all on the cells: the normal case).  The slots of partB /
 // partC hold PART_EMPTY between launches (the host fills them, every finisher leaves them so); a workgroup writes its partial
 // sums through and is done; the tile's FINISHER - the workgroup of the last physical rank, the lightest of the deal - reads the

@@ -20,6 +20,7 @@
 #include "lf_compress.h"
 #include "lf_devmem.h"
 #include "lf_gridbound.h"
+#include "lf_hostprep.h"
 #include "lf_kernels.h"
 #include "lf_free.h"
 #include "lf_mock.h"
@@ -172,10 +173,12 @@ namespace {
         }                                                                                  \
     } while (0)
 
-template <typename T>
-int upload(lf_ctx* c, Buf<T>& dst, const T* src, size_t n) {
-    LF_HIP(c, dst.upload(src, n));
-    return LF_OK;
+// upload(c, buffer, vector, buffer, vector, ...): each vector to a new allocation of its size; stops at the first error
+inline int upload(lf_ctx*) { return LF_OK; }
+template <typename T, typename... Rest>
+int upload(lf_ctx* c, Buf<T>& dst, const std::vector<T>& src, Rest&... rest) {
+    LF_HIP(c, dst.upload(src.data(), src.size()));
+    return upload(c, rest...);
 }
 
 // Replace `b` by a new allocation of n elements (not initialised; the old contents go).  sync: launches enqueued earlier may
@@ -187,126 +190,18 @@ int grow(Owner* o, Buf<T, PINNED>& b, size_t n, bool sync = true) {
     return LF_OK;
 }
 
-// The cells of a FREE catalogue (lf_kernels.h: CELL_M): runs of flux-neighbouring sources of one field no wider than
-// 2 rho, rho = min(CELL_RHO_H, CELL_RHO_G / alpha_hi) with alpha_hi the prior box's largest alpha_C (walkers outside the
-// box are -inf before any sum is looked at).  x = the flux-sorted logf.  Walker-independent: built once.  A field with a
-// non-finite flux, or a prior box so wide in alpha_C that cells would hold fewer than four sources on average, gets
-// none (kc.cells = 0: every walker is summed over the sources, as before).
-// ZEVOL: half the width of a cell in redshift such that every walker inside the prior box of (L1, L2, L3) may be summed
-// over the cells (lf_kernels.h: ZCELL_X1, ZCELL_X2).  L*(z) is the parabola through (pivot_i, L_i): its slope at a given
-// z and its curvature are linear in (L1, L2, L3), so their largest magnitudes over the box are taken at its corners, and
-// the slope's over the catalogue's redshifts at their ends.  0: no cells (an unbounded box, coinciding pivots).
-double zcell_rho_for_box(const lf::KConst& kc, int nf) {
-    using namespace lf;
-    const double lo = kc.lims[LF_LIM_LSTAR][0], hi = kc.lims[LF_LIM_LSTAR][1];
-    double zmin = HUGE_VAL, zmax = -HUGE_VAL;
-    for (int f = 0; f < nf; ++f)
-        if (kc.nsrc[f] > 0) {
-            zmin = std::fmin(zmin, kc.z_lo[f]);
-            zmax = std::fmax(zmax, kc.z_hi[f]);
-        }
-    if (!(std::isfinite(lo) && std::isfinite(hi) && std::isfinite(zmin) && std::isfinite(zmax))) return 0.0;
-    const double z1 = kc.pivots[0], z2 = kc.pivots[1], z3 = kc.pivots[2];
-    if (!(z1 != z2 && z2 != z3 && z1 != z3)) return 0.0;
-    double smax = 0.0, amax = 0.0;
-    for (int corner = 0; corner < 8; ++corner) {
-        const double L1 = corner & 1 ? hi : lo, L2 = corner & 2 ? hi : lo, L3 = corner & 4 ? hi : lo;
-        const double d12 = (L2 - L1) / (z2 - z1), d23 = (L3 - L2) / (z3 - z2);
-        const double a = (d23 - d12) / (z3 - z1);                     // divided differences: L* = L1 + d12 (z - z1) + a (z - z1)(z - z2)
-        for (double z : {zmin, zmax}) smax = std::fmax(smax, std::fabs(d12 + a * (2.0 * z - z1 - z2)));
-        amax = std::fmax(amax, std::fabs(a));
-    }
-    double rho = ZCELL_RHO;
-    // (a little inside the limits: lf_prepare evaluates the same quantities from its own rounded coefficients)
-    if (smax > 0.0) rho = std::fmin(rho, 0.98 * ZCELL_X1 / (LF_LN10 * smax));
-    if (amax > 0.0) rho = std::fmin(rho, std::sqrt(0.98 * ZCELL_X2 / (LF_LN10 * amax)));
-    return std::isfinite(rho) ? rho : 0.0;
-}
-
-// wts: NULL (FREE: cells in log-flux, plain power sums, chunks of 64 cells) or the sources' weights (ZEVOL: cells in
-// redshift, S_j = sum_i wts_i d_i^j, chunks of BLOCK cells; lf_kernels.h: ZCELL_RHO)
-int build_cells(lf_ctx* c, lf::KConst& kc, const std::vector<double>& x, int nf, const double* wts = nullptr) {
-    using namespace lf;
-    const double ahi = kc.lims[LF_LIM_ALPHA][1];
-    if (!wts && (!(ahi > 0.0) || !std::isfinite(ahi))) return LF_OK;
-    const double rho = wts ? kc.zcell_rho : std::fmin(CELL_RHO_H, CELL_RHO_G / ahi);
-    if (!(rho > 0.0)) return LF_OK;
-    const size_t per_chunk = wts ? (size_t)BLOCK : 64;
-    const int M = wts ? ZCELL_M : CELL_M;                 // orders kept
-    const size_t rec = (size_t)M + 2;                     // doubles per cell: midpoint, S_0 .. S_M
-    std::vector<double> cd;
-    std::vector<int> cst, cln, cfl;
-    size_t nreal = 0;                    // cells with sources
-    for (int f = 0; f < nf; ++f) {
-        const int64_t lo = c->field_ind[f], hi = c->field_ind[f + 1];
-        if (hi <= lo) continue;
-        for (int64_t i = lo; i < hi; ++i)
-            if (!std::isfinite(x[(size_t)i]) || (wts && !(std::isfinite(wts[(size_t)i]) && wts[(size_t)i] > 0.0))) return LF_OK;
-        if (!wts) {
-            const double k0 = std::floor((x[(size_t)lo] - kc.key_x0) * KEY_SCALE), k1 = std::ceil((x[(size_t)hi - 1] - kc.key_x0) * KEY_SCALE);
-            if (!(k0 >= 0.0 && k1 < (double)KEY_MAX)) return LF_OK;
-            kc.kf_first[f] = (int)k0;
-            kc.kf_last[f] = (int)k1;
-        }
-        const size_t first_cell = cd.size() / rec;
-        for (int64_t i = lo; i < hi;) {
-            int64_t j = i + 1;
-            while (j < hi && x[(size_t)j] - x[(size_t)i] <= 2.0 * rho) ++j;
-            const double xc = 0.5 * (x[(size_t)i] + x[(size_t)j - 1]);
-            long double S[CELL_M + 1] = {0};
-            static_assert(ZCELL_M <= CELL_M, "S is sized for the larger");
-            for (int64_t k = i; k < j; ++k) {
-                const long double dlt = (long double)x[(size_t)k] - (long double)xc;
-                long double pw = wts ? (long double)wts[(size_t)k] : 1.0L;
-                for (int m = 0; m <= M; ++m) {
-                    S[m] += pw;
-                    pw *= dlt;
-                }
-            }
-            cd.push_back(xc);
-            for (int m = 0; m <= M; ++m) cd.push_back((double)S[m]);
-            i = j;
-        }
-        size_t ncf = cd.size() / rec - first_cell;
-        nreal += ncf;
-        if (!wts) {
-            // lf_free addresses chunk cc at cell 64 cc and masks nothing: pad the field to whole chunks with cells of no
-            // sources (all sums 0) at the last real midpoint (inside the tables wherever the real cell is)
-            kc.cc_fstart[f] = (int)cst.size();
-            const double xlast = cd[cd.size() - rec];
-            while (ncf % 64) {
-                cd.push_back(xlast);
-                for (int m = 0; m <= M; ++m) cd.push_back(0.0);
-                ++ncf;
-            }
-        }
-        for (size_t s0 = 0; s0 < ncf; s0 += per_chunk) {                // a cell chunk = one wave's lanes (lf_free.h) / one workgroup's threads
-            cst.push_back((int)(first_cell + s0));
-            cln.push_back((int)std::min<size_t>(per_chunk, ncf - s0));        // (FREE: pads included; they add 0)
-            cfl.push_back(f);
-        }
-    }
-    const size_t ncell = cd.size() / rec;
-    if (!wts) {                                                       // (a field without cells starts where the next one does)
-        for (int f = nf; f <= MAXF; ++f) kc.cc_fstart[f] = (int)cst.size();
-        for (int f = nf - 1; f >= 0; --f)
-            if (c->field_ind[f + 1] <= c->field_ind[f]) kc.cc_fstart[f] = kc.cc_fstart[f + 1];
-    }
-    // (too few sources per cell to pay - for a big catalogue: for a small one even cells of one source apiece beat the
-    // per-source path, whose cost is its per-item overhead: 10^3 sources, 16 rows: 23.5 us per evaluation over the sources,
-    // 17.5 in lf_main's three launches, 12 over cells)
-    if (nreal == 0 || ((size_t)c->N < 4 * nreal && c->N > 65536)) return LF_OK;
-    int rc;
-    if ((rc = upload(c, c->d_cells, cd.data(), cd.size())) != LF_OK) return rc;
-    if ((rc = upload(c, c->d_cc_start, cst.data(), cst.size())) != LF_OK) return rc;
-    if ((rc = upload(c, c->d_cc_len, cln.data(), cln.size())) != LF_OK) return rc;
-    if ((rc = upload(c, c->d_cc_field, cfl.data(), cfl.size())) != LF_OK) return rc;
-    c->ncell = (int)ncell;
-    c->ncchunk = (int)cst.size();
-    kc.cells = c->opt_cells ? 1 : 0;
+// The catalogue's cells (lf_hostprep.h: build_cells), to the device.  No cells: nothing happens (kc.cells stays 0).
+int upload_cells(lf_ctx* c, const lfh::Cells& cl) {
+    if (!cl.built) return LF_OK;
+    const int rc = upload(c, c->d_cells, cl.rec, c->d_cc_start, cl.start, c->d_cc_len, cl.len, c->d_cc_field, cl.field);
+    if (rc != LF_OK) return rc;
+    c->ncell = (int)(cl.rec.size() / (c->kc.variant == LF_ZEVOL ? lf::ZCELL_REC : lf::CELL_REC));
+    c->ncchunk = (int)cl.start.size();
+    c->kc.cells = c->opt_cells ? 1 : 0;
     return LF_OK;
 }
 
+// The table of chunks of `ch` sources (lf_hostprep.h: chunk_table), made and uploaded when it is first asked for.
 // hx: the flux-sorted logf of the REAL catalogue (FREE), or NULL (no keys: the chunks never take the table form)
 int get_chunks(lf_ctx* c, std::map<int, ChunkTable>& tables, const std::vector<int64_t>& field_ind, int ch,
                ChunkTable** out, const double* hx = nullptr, int lane_w = 0) {
@@ -315,103 +210,11 @@ int get_chunks(lf_ctx* c, std::map<int, ChunkTable>& tables, const std::vector<i
         *out = &it->second;
         return LF_OK;
     }
-    std::vector<int> st, ln, fl;
-    for (int f = 0; f < c->kc.nf; ++f) {
-        for (int64_t s = field_ind[f]; s < field_ind[f + 1]; s += ch) {
-            st.push_back((int)s);
-            ln.push_back((int)std::min<int64_t>(ch, field_ind[f + 1] - s));
-            fl.push_back(f);
-        }
-    }
-    // Keys for the table-driven form of the FREE term (lf_free.h), rounded so that a key test that
-    // passes implies the real-valued condition: kfirst = floor, klast = ceil of (x - x0) 2^20 for the chunk's
-    // faintest / brightest source; kamax = the largest alpha_C (x 2^16, floor) for which alpha_C times the widest
-    // lane of the chunk (a lane = lane_w neighbours in flux) stays within the g table's margin - 0 when that
-    // width already exceeds the h table's margin.  A chunk with a non-finite flux gets keys that fail every test.
-    // KS ints per chunk: {kfirst, klast, kamax of the whole chunk, -, kamax of each of its 8 waves}: with lanes of
-    // flux-neighbours a wave is 64 lane_w consecutive sources, and a chunk's widest lanes cluster in one or two waves (the
-    // sparse end of a field): decided per wave, 0.4 % of the (walker, wave) pairs of the bench workload miss the table
-    // form instead of 3.4 %.
-    constexpr int KS = lf::KEY_STRIDE;
-    std::vector<int> keys((size_t)KS * st.size(), 0);
-    for (size_t i = 0; i < st.size(); ++i) {
-        keys[KS * i] = -1;
-        keys[KS * i + 1] = lf::KEY_MAX;
-        if (!hx) continue;
-        const int64_t s = st[i], n = ln[i];
-        if (lane_w <= 0) continue;                // (a kernel that holds no lanes of flux-neighbours: no keys)
-        bool finite = true;
-        for (int64_t j = 0; j < n; ++j) finite = finite && std::isfinite(hx[s + j]);
-        if (!finite) continue;
-        const double k0 = std::floor((hx[s] - c->kc.key_x0) * lf::KEY_SCALE), k1 = std::ceil((hx[s + n - 1] - c->kc.key_x0) * lf::KEY_SCALE);
-        if (!(k0 >= 0.0 && k1 < (double)lf::KEY_MAX)) continue;
-        auto amax_key = [&](double spread) {
-            double amax = spread > 0.0 ? lf::G_MARGIN / spread : 3.0e4;
-            if (spread > lf::H_MARGIN) amax = 0.0;
-            return (int)std::floor(std::fmin(amax, 3.0e4) * lf::KEY_ASCALE);
-        };
-        double spread = 0.0, wspread[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const int64_t per_wave = 64 * (int64_t)lane_w;
-        for (int64_t j = 0; j < n; j += lane_w) {
-            const double sp = hx[s + std::min<int64_t>(j + lane_w, n) - 1] - hx[s + j];
-            spread = std::fmax(spread, sp);
-            const int64_t wv = std::min<int64_t>(j / per_wave, 7);
-            wspread[wv] = std::fmax(wspread[wv], sp);
-        }
-        keys[KS * i] = (int)k0;
-        keys[KS * i + 1] = (int)k1;
-        keys[KS * i + 2] = amax_key(spread);
-        for (int wv = 0; wv < 8; ++wv) keys[KS * i + 4 + wv] = amax_key(wspread[wv]);
-    }
-    // Chunk order.  The kernels deal contiguous runs of chunk indices to the 8 XCDs (lf_main: in dispatch order inside
-    // each run; lf_free: one queue per run), and with the catalogue sorted by flux a chunk's cost depends on its rank
-    // in its field (bright chunks run the forms without the exponential for most walkers).  So: deal the chunks
-    // round-robin into 8 groups (every group gets the same mix of ranks and fields: natural order would hand one XCD
-    // only full-cost chunks), and inside a group put the expensive chunks first - longest first keeps the drain of
-    // the launch short: the faint ones before the bright ones, and, with lanes of flux-neighbours (lf_free), before
-    // both the chunks whose lanes are too wide for the tables at ordinary alpha_C (the sparse ends of a field: the
-    // general form, twice the cost per term).
-    {
-        const size_t n = st.size();
-        if (n > 8) {
-            std::vector<size_t> rank(n);                  // rank of the chunk inside its field (natural order is field-major)
-            for (size_t i = 0, r = 0; i < n; ++i) {
-                r = (i > 0 && fl[i] == fl[i - 1]) ? r + 1 : 0;
-                rank[i] = r;
-            }
-            const int wide = (int)(32.0 * lf::KEY_ASCALE);
-            auto cls = [&](size_t i) { return (lane_w > 0 && hx) ? std::min(keys[KS * i + 2], wide) : wide; };
-            std::vector<size_t> order;
-            order.reserve(n);
-            for (size_t g = 0; g < 8; ++g) {
-                std::vector<size_t> grp;
-                for (size_t i = g; i < n; i += 8) grp.push_back(i);
-                std::stable_sort(grp.begin(), grp.end(), [&](size_t a, size_t b) {
-                    const int ca = cls(a), cb = cls(b);
-                    return ca != cb ? ca < cb : rank[a] < rank[b];
-                });
-                order.insert(order.end(), grp.begin(), grp.end());
-            }
-            std::vector<int> st2(n), ln2(n), fl2(n), keys2((size_t)KS * n);
-            for (size_t i = 0; i < n; ++i) {
-                st2[i] = st[order[i]];
-                ln2[i] = ln[order[i]];
-                fl2[i] = fl[order[i]];
-                for (int j = 0; j < KS; ++j) keys2[KS * i + j] = keys[KS * order[i] + j];
-            }
-            st.swap(st2);
-            ln.swap(ln2);
-            fl.swap(fl2);
-            keys.swap(keys2);
-        }
-    }
+    const lfh::Chunks h = lfh::chunk_table(field_ind, c->kc.nf, ch, c->kc.key_x0, lf::G_MARGIN, lf::H_MARGIN, hx, lane_w);
     ChunkTable t;
-    t.n = (int)st.size();
-    int rc;
-    if ((rc = upload(c, t.d_start, st.data(), st.size())) != LF_OK) return rc;
-    if ((rc = upload(c, t.d_len, ln.data(), ln.size())) != LF_OK) return rc;
-    if ((rc = upload(c, t.d_field, fl.data(), fl.size())) != LF_OK) return rc;
-    if ((rc = upload(c, t.d_keys, keys.data(), keys.size())) != LF_OK) return rc;
+    t.n = (int)h.start.size();
+    const int rc = upload(c, t.d_start, h.start, t.d_len, h.len, t.d_field, h.field, t.d_keys, h.keys);
+    if (rc != LF_OK) return rc;
     *out = &tables.emplace(ch, std::move(t)).first->second;       // (only a complete table enters the map)
     return LF_OK;
 }
@@ -618,43 +421,11 @@ int free_groups(lf_ctx* c, int slot, int ntiles, int nchA, int nchB, int nchC) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(c->slots_free[slot] / 8, (int64_t)ntiles * std::max<int64_t>(per_tile, 1)));
 }
 
-// lf_free's static deal (lf_free.h: DEAL_*): flux bins, then cell chunks, each to the virtual workgroup that would be done
-// first - a bin costs a wave 8 units, a cell chunk 3 (tools/stamps_fused.py), and the ranks of the younger half are
-// counted 8 units behind (swept on one box, tools/deal_sweep.sh: 13.4 us per 128-row evaluation at 8-10, 13.75 at 0-6,
-// 14.0 at 16; the arithmetic deal 15.25; at 256 rows, where a workgroup serves an elder and a younger rank, all within 2 %).  Bins that a source-sharded rank does not integrate (grid_share) cost nothing.  The table depends
-// on the context (numbers of cell chunks and bins, grid share) only - never on the batch.  No table (the arithmetic deal):
-// no bins, or more entries than the kernel keeps in LDS.
-// (host only; also behind lf_deal_table for the CPU tests)
-static std::vector<int> make_deal(int nchC, int nbq, int grid_part, int grid_parts) {
-    using namespace lf;
-    std::vector<int> load(VF), cnt_c(VF, 0), cnt_b(VF, 0), own_c(nchC), own_b(nbq);
-    const int cost_h = std::getenv("LF_DEAL_H") ? std::atoi(std::getenv("LF_DEAL_H")) : 8;       // (tuning runs: tools/deal_sweep.sh)
-    const int cost_b = std::getenv("LF_DEAL_B") ? std::atoi(std::getenv("LF_DEAL_B")) : 8;
-    for (int v = 0; v < VF; ++v) load[v] = v >= VF / 2 ? cost_h : 0;
-    auto next = [&]() { return (int)(std::min_element(load.begin(), load.end()) - load.begin()); };      // (ties: the lowest rank)
-    for (int b = 0; b < nbq; ++b) {
-        const int v = next();
-        own_b[b] = v;
-        ++cnt_b[v];
-        load[v] += grid_parts > 1 && b % grid_parts != grid_part ? 0 : cost_b;
-    }
-    for (int i = 0; i < nchC; ++i) {
-        const int v = next();
-        own_c[i] = v;
-        ++cnt_c[v];
-        load[v] += 3;
-    }
-    std::vector<int> t(DEAL_LIST + nchC + nbq);
-    t[0] = 0;
-    t[DEAL_BINS] = 0;
-    for (int v = 0; v < VF; ++v) {
-        t[v + 1] = t[v] + cnt_c[v];
-        t[DEAL_BINS + v + 1] = t[DEAL_BINS + v] + cnt_b[v];
-    }
-    std::vector<int> at_c(t.begin(), t.begin() + VF), at_b(t.begin() + DEAL_BINS, t.begin() + DEAL_BINS + VF);
-    for (int i = 0; i < nchC; ++i) t[DEAL_LIST + at_c[own_c[i]]++] = i;
-    for (int b = 0; b < nbq; ++b) t[DEAL_LIST + nchC + at_b[own_b[b]]++] = b;
-    return t;
+// lf_free's static deal (lf_hostprep.h: make_deal) with the costs of the tuning runs (tools/deal_sweep.sh), if any.  No table (the
+// arithmetic deal): no bins, or more entries than the kernel keeps in LDS.
+std::vector<int> make_deal(int nchC, int nbq, int grid_part, int grid_parts) {
+    const char *h = std::getenv("LF_DEAL_H"), *b = std::getenv("LF_DEAL_B");
+    return lfh::make_deal(nchC, nbq, grid_part, grid_parts, h ? std::atoi(h) : 8, b ? std::atoi(b) : 8);
 }
 
 int ensure_deal(lf_ctx* c, int nchC, int nbq, hipStream_t s) {
@@ -918,11 +689,9 @@ int enqueue(lf_ctx* c, const double* d_theta, int B, double* d_out, double* d_ou
         // down to N x rows ~ 1.2e6 from 32 rows.
         const int64_t ntiles = (B + PTW - 1) / PTW;
         const int64_t items = free_shape(c).items_per_tile * ntiles;
-        const bool plain = !sp.enabled && !ap.enabled && !d_outA && !d_outB && c->opt_fuse;
         // (an evaluation over cells costs 12-18 us whatever N and B are: always - the sampler's steps and the diagnostics
         // included, so that a row has the same bits whichever entry point evaluates it)
         const bool wins = c->kc.cells ? true : items >= 4 * 2 * (int64_t)std::max(c->num_cu, 1);
-        (void)plain;
         if (wins || shared_bins || c->opt_persistent == 2 || c->opt_free_st)
             return enqueue_free(c, d_theta, B, d_out, d_outA, d_outB, s, sp, ap);
     }
@@ -1052,102 +821,37 @@ int enqueue(lf_ctx* c, const double* d_theta, int B, double* d_out, double* d_ou
     return LF_OK;
 }
 
-// Build the compressed catalogue from the per-source tables already in HBM (lf_compress.h).  FREE: key = logf_i,
-// weight 1; ZEVOL: key = z_i, weight 10^(lum_i - 42).
+// Build the compressed catalogue and grid (lf_hostprep.h: compress) from the host's copy of the keys and the device's of lum.
 int build_compressed(lf_ctx* c) {
-    using namespace lf;
     if (c->cmp.built) return LF_OK;
     if (c->kc.variant == LF_FIXCOMP) return LF_OK;          // piece A is closed-form already
-    const int64_t N = c->N;
-    std::vector<double> key((size_t)N), wt;
-    if (N) LF_HIP(c, hipMemcpy(key.data(), c->d_a1, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
-    lfc::Model m{};
-    if (c->kc.variant == LF_FREE) {
-        m.kind = 0;
-        m.fc_ratio = c->kc.fc_ratio;
-        m.alpha_lo = c->kc.lims[LF_LIM_ALPHA][0];
-        m.alpha_hi = c->kc.lims[LF_LIM_ALPHA][1];
-        m.flim_lo = c->kc.lims[LF_LIM_FLIM][0];
-        m.flim_hi = c->kc.lims[LF_LIM_FLIM][1];
-    } else {
-        m.kind = 1;
-        m.L_lo = c->kc.lims[LF_LIM_LSTAR][0];
-        m.L_hi = c->kc.lims[LF_LIM_LSTAR][1];
-        for (int i = 0; i < 3; ++i) m.piv[i] = c->kc.pivots[i];
-        wt.resize((size_t)N);
-        if (N) LF_HIP(c, hipMemcpy(wt.data(), c->d_lum, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < N; ++i) wt[(size_t)i] = std::pow(10.0, wt[(size_t)i] - LF_LREF);
+    std::vector<double> lum;
+    if (c->kc.variant == LF_ZEVOL) {
+        lum.resize((size_t)c->N);
+        if (c->N) LF_HIP(c, hipMemcpy(lum.data(), c->d_lum, lum.size() * sizeof(double), hipMemcpyDeviceToHost));
     }
-    lfc::Out out;
+    lfh::Compressed h = lfh::compress(c->kc, c->field_ind, c->h_x, lum, c->h_L, c->h_wL, c->h_ck, c->h_Dk);
+    if (h.bad_field >= 0) {
+        c->err = "compress: the catalogue of field " + std::to_string(h.bad_field) + " cannot be compressed to the error bound "
+                 "(non-finite coordinate, or a prior box the bins cannot resolve)";
+        return LF_ERR_ARG;
+    }
+    // Both are built here and enter the context together, complete: a failed upload leaves nothing behind
     CompressedCat cc;
-    cc.field_ind.assign(1, 0);
-    // one validated set of bins for the whole catalogue's coordinate range, shared by the fields
-    double klo = HUGE_VAL, khi = -HUGE_VAL;
-    for (int64_t i = 0; i < N; ++i) {
-        klo = std::fmin(klo, key[(size_t)i]);
-        khi = std::fmax(khi, key[(size_t)i]);
-    }
-    const lfc::Bins bins = lfc::shared_bins(m, klo, khi);
-    for (int f = 0; f < c->kc.nf; ++f) {
-        const int64_t lo = c->field_ind[f], hi = c->field_ind[f + 1];
-        if (!lfc::compress_field(m, key.data() + lo, wt.empty() ? nullptr : wt.data() + lo, hi - lo, out, &bins)) {
-            c->err = "compress: the catalogue of field " + std::to_string(f) + " cannot be compressed to the error bound "
-                     "(non-finite coordinate, or a prior box the bins cannot resolve)";
-            return LF_ERR_ARG;
-        }
-        // in order of the coordinate inside the field, like the real catalogue (bins that kept their sources hold
-        // them in catalogue order): a chunk's first pseudo-source is its faintest
-        {
-            const size_t a = (size_t)cc.field_ind.back(), b = out.node.size();
-            std::vector<size_t> idx(b - a);
-            for (size_t i = 0; i < idx.size(); ++i) idx[i] = a + i;
-            std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) { return out.node[x] < out.node[y]; });
-            std::vector<double> nn(idx.size()), ww(idx.size());
-            for (size_t i = 0; i < idx.size(); ++i) {
-                nn[i] = out.node[idx[i]];
-                ww[i] = out.weight[idx[i]];
-            }
-            std::copy(nn.begin(), nn.end(), out.node.begin() + (std::ptrdiff_t)a);
-            std::copy(ww.begin(), ww.end(), out.weight.begin() + (std::ptrdiff_t)a);
-        }
-        cc.field_ind.push_back((int64_t)out.node.size());
-    }
-    cc.n = (int64_t)out.node.size();
-    cc.nbins = out.nbins;
-    cc.bound = out.bound;
-    std::vector<double> lumc((size_t)cc.n, c->kc.variant == LF_ZEVOL ? LF_LREF : 0.0), U((size_t)cc.n);
-    for (int64_t i = 0; i < cc.n; ++i)
-        U[(size_t)i] = c->kc.variant == LF_FREE ? std::pow(10.0, out.node[(size_t)i] - LF_FREF) : out.node[(size_t)i] * out.node[(size_t)i];
-    int rc;
-    if ((rc = upload(c, cc.d_lum, lumc.data(), (size_t)cc.n)) != LF_OK || (rc = upload(c, cc.d_a1, out.node.data(), (size_t)cc.n)) != LF_OK ||
-        (rc = upload(c, cc.d_U, U.data(), (size_t)cc.n)) != LF_OK || (rc = upload(c, cc.d_W, out.weight.data(), (size_t)cc.n)) != LF_OK)
-        return rc;
-    cc.built = true;
-    // the integration grid, when it is separable (no bins found: the full grid stays in use).  Both are built here and enter the
-    // context together, complete: a failed upload leaves nothing behind
     CompressedGrid g;
-    if (c->kc.variant == LF_FREE && !c->h_L.empty()) {
-        lfc::Model mg = m;
-        mg.kind = 2;
-        lfc::GridOut go;
-        const int S = c->kc.S;
-        if (lfc::compress_grid(mg, S, c->h_L.data(), c->h_wL.data(), c->h_ck.data(), c->h_Dk.data(), go)) {
-            std::vector<double> A4(go.u.size()), PGL((size_t)S);
-            for (size_t i = 0; i < go.u.size(); ++i) A4[i] = std::pow(10.0, go.u[i] - LF_FREF);
-            for (int j = 0; j < S; ++j) PGL[(size_t)j] = std::pow(10.0, c->h_L[(size_t)j] - LF_LREF);
-            if ((rc = upload(c, g.d_U, go.u.data(), go.u.size())) != LF_OK) return rc;
-            if ((rc = upload(c, g.d_A4, A4.data(), A4.size())) != LF_OK) return rc;
-            if ((rc = upload(c, g.d_omega, go.omega.data(), go.omega.size())) != LF_OK) return rc;
-            if ((rc = upload(c, g.d_L, c->h_L.data(), (size_t)S)) != LF_OK) return rc;
-            if ((rc = upload(c, g.d_PGL, PGL.data(), (size_t)S)) != LF_OK) return rc;
-            if ((rc = upload(c, g.d_row0, go.row0.data(), go.row0.size())) != LF_OK) return rc;
-            if ((rc = upload(c, g.d_nrows, go.nrows.data(), go.nrows.size())) != LF_OK) return rc;
-            if ((rc = upload(c, g.d_off, go.off.data(), go.off.size())) != LF_OK) return rc;
-            g.nb = go.nb;
-            g.bound = go.bound;
-            g.built = true;
-        }
-    }
+    int rc = upload(c, cc.d_lum, h.lum, cc.d_a1, h.node, cc.d_U, h.U, cc.d_W, h.weight);
+    if (rc == LF_OK && h.grid)
+        rc = upload(c, g.d_U, h.go.u, g.d_A4, h.A4, g.d_omega, h.go.omega, g.d_L, c->h_L, g.d_PGL, h.PGL, g.d_row0, h.go.row0,
+                    g.d_nrows, h.go.nrows, g.d_off, h.go.off);
+    if (rc != LF_OK) return rc;
+    cc.n = (int64_t)h.node.size();
+    cc.field_ind.swap(h.field_ind);
+    cc.nbins = h.nbins;
+    cc.bound = h.bound;
+    cc.built = true;
+    g.nb = h.go.nb;
+    g.bound = h.go.bound;
+    g.built = h.grid;
     c->cmp = std::move(cc);
     c->gridc = std::move(g);
     return LF_OK;
@@ -1230,143 +934,18 @@ void free_ctx(lf_ctx* c) {
     delete c;                            // (its buffers go with it: lf_devmem.h)
 }
 
+// Derive every table (lf_hostprep.h), upload it, set the context's fields.  The three environment variables: A/B runs and tests.
 int build(lf_ctx* c, const lf_desc* d) {
     using namespace lf;
-    const int nf = d->nf, S = d->S;
-    const int64_t N = d->N;
+    const int nf = d->nf;
     KConst& kc = c->kc;
-    kc.variant = d->variant;
-    kc.fix_sch_al = d->fix_sch_al ? 1 : 0;
-    kc.specialise = 1;
-    kc.grid_part = 0;
-    kc.grid_parts = 1;
-    kc.tables = 1;
-    kc.key_x0 = 0.0;
     kc.forms = nullptr;
 #ifdef LF_STAMPS
     kc.stamps = nullptr;
 #endif
-    kc.nf = nf;
-    kc.S = S;
-    if (d->variant == LF_FREE) kc.ndim = 2 + (kc.fix_sch_al ? 0 : 1) + nf + 1;
-    else if (d->variant == LF_FIXCOMP) kc.ndim = 2 + (kc.fix_sch_al ? 0 : 1);
-    else kc.ndim = 6 + (kc.fix_sch_al ? 0 : 1);
-    for (int f = 0; f < MAXF; ++f) {
-        kc.lnom0_src[f] = 0.0;
-        kc.om0_grid[f] = 0.0;
-        kc.flim0[f] = 0.0;
-    }
-    for (int f = 0; f < nf; ++f) {
-        // per-source term: Omega_0_arr is dtype=int (lumfuncmcmc.py:285) -> truncation toward zero
-        kc.lnom0_src[f] = std::log(std::trunc(d->omega0[f]) / LF_SQARCSEC);
-        kc.om0_grid[f] = d->omega0[f] / LF_SQARCSEC;           // integral: float (lumfuncmcmc.py:375)
-        if (d->flim0) kc.flim0[f] = d->flim0[f];
-    }
-    {
-        const double a = (2.0 * d->fcmin - 1.0) * (2.0 * d->fcmin - 1.0);   // VmaxLumFunc.py:164
-        kc.fc_ratio = std::fabs(a / (1.0 - a));
-    }
-    std::memcpy(kc.lims, d->lims, sizeof(kc.lims));
-    std::memcpy(kc.pivots, d->pivots, sizeof(kc.pivots));
-    kc.sch_al0 = d->sch_al0;
-    kc.alpha0 = d->alpha0;
-    c->N = N;
-    c->nnodes = S * S;
+    c->N = d->N;
     c->field_ind.assign(d->field_ind, d->field_ind + nf + 1);
-
-    // ---- per-source tables.  FREE: the sources of a field are put in order of flux (the layout is ours to choose; a
-    // sum over sources does not care), so that a chunk's first source is its faintest and the kernels can pick
-    // a cheaper form of the term per (walker, chunk) - see term_free_noexp.  NaN fluxes go last.
-    std::vector<int64_t> perm((size_t)N);
-    for (int64_t i = 0; i < N; ++i) perm[(size_t)i] = i;
-    // ZEVOL: in order of redshift, so that a lane's ST sources are neighbours in z and 10^(-L*(z)) of all of them follows
-    // from ONE exponential at the lane's middle source (lf_kernels.h: the local form of the z-evolving term).
-    if (d->variant == LF_FREE || d->variant == LF_ZEVOL) {
-        const double* key = d->variant == LF_FREE ? d->logf : d->z;
-        for (int f = 0; f < nf; ++f)
-            std::stable_sort(perm.begin() + d->field_ind[f], perm.begin() + d->field_ind[f + 1], [&](int64_t a, int64_t b) {
-                const double x = key[a], y = key[b];
-                return std::isnan(y) ? !std::isnan(x) : x < y;
-            });
-    }
-    std::vector<double> lumv(N), a1(N), P(N), U(N);
-    for (int64_t i = 0; i < N; ++i) lumv[(size_t)i] = d->lum[perm[(size_t)i]];
-    for (int64_t i = 0; i < N; ++i) {
-        const double lum = lumv[(size_t)i];
-        if (d->variant == LF_FREE) {
-            a1[i] = d->logf[perm[(size_t)i]];
-            P[i] = std::pow(10.0, lum - LF_LREF);
-            U[i] = std::pow(10.0, d->logf[perm[(size_t)i]] - LF_FREF);
-        } else if (d->variant == LF_FIXCOMP) {
-            a1[i] = std::log(d->om_arr[perm[(size_t)i]]);
-            P[i] = std::pow(10.0, lum - LF_LREF);
-            U[i] = 0.0;
-        } else {
-            a1[i] = d->z[perm[(size_t)i]];
-            P[i] = std::log(d->om_arr[perm[(size_t)i]]);
-            U[i] = d->z[perm[(size_t)i]] * d->z[perm[(size_t)i]];
-        }
-    }
-    // per-field extremes for the mode classification in lf_prepare
-    for (int f = 0; f < MAXF; ++f) {
-        kc.nsrc[f] = 0;
-        kc.pmax[f] = kc.lum_min[f] = kc.lum_max[f] = kc.a_min[f] = kc.u_min[f] = kc.u_max[f] = kc.z_lo[f] = kc.z_hi[f] = kc.slc[f] = kc.sp[f] = kc.som[f] = kc.sz[f] = kc.sz2[f] = 0.0;
-    }
-    for (int f = 0; f < nf; ++f) {
-        const int64_t lo = d->field_ind[f], hi = d->field_ind[f + 1];
-        kc.nsrc[f] = (int)(hi - lo);
-        if (hi <= lo) continue;
-        double pmax = -HUGE_VAL, lmin = HUGE_VAL, lmax = -HUGE_VAL, amin = HUGE_VAL, amax = -HUGE_VAL, zlo = HUGE_VAL, zhi = -HUGE_VAL;
-        bool nan = false;
-        long double slc = 0.0L, sp = 0.0L, som = 0.0L, sz = 0.0L, sz2 = 0.0L;
-        for (int64_t i = lo; i < hi; ++i) {
-            const double lum = lumv[(size_t)i];
-            slc += (long double)(lum - LF_LREF);
-            if (d->variant != LF_ZEVOL) sp += (long double)P[i];
-            if (d->variant == LF_FIXCOMP) som += (long double)a1[i];
-            if (d->variant == LF_ZEVOL) {
-                som += (long double)P[i];
-                sz += (long double)d->z[perm[(size_t)i]];
-                sz2 += (long double)U[i];             // the rounded z_i^2 the kernels use
-            }
-            lmin = std::fmin(lmin, lum);
-            lmax = std::fmax(lmax, lum);
-            nan = nan || std::isnan(lum);
-            if (d->variant != LF_ZEVOL) pmax = std::fmax(pmax, P[i]);
-            const double a = d->variant == LF_FREE ? a1[i] : (d->variant == LF_FIXCOMP ? a1[i] : P[i]);
-            amin = std::fmin(amin, a);
-            amax = std::fmax(amax, a);
-            nan = nan || std::isnan(a);
-            if (d->variant == LF_ZEVOL) {
-                zlo = std::fmin(zlo, d->z[perm[(size_t)i]]);
-                zhi = std::fmax(zhi, d->z[perm[(size_t)i]]);
-                nan = nan || std::isnan(d->z[perm[(size_t)i]]);
-            }
-        }
-        if (nan) amin = -HUGE_VAL;                 // NaN input: force the careful path
-        kc.pmax[f] = pmax;
-        kc.lum_min[f] = lmin;
-        kc.lum_max[f] = lmax;
-        kc.a_min[f] = amin;
-        kc.u_min[f] = d->variant == LF_FREE ? std::pow(10.0, amin - LF_FREF) : 0.0;
-        kc.u_max[f] = d->variant == LF_FREE ? (nan ? HUGE_VAL : std::pow(10.0, amax - LF_FREF)) : 0.0;
-        kc.z_lo[f] = zlo;
-        kc.z_hi[f] = zhi;
-        kc.slc[f] = (double)slc;
-        kc.sp[f] = (double)sp;
-        kc.som[f] = (double)som;
-        kc.sz[f] = (double)sz;
-        kc.sz2[f] = (double)sz2;
-    }
-    if (d->variant == LF_FREE || d->variant == LF_ZEVOL) {
-        // origin of the integer keys of log-flux (ZEVOL: of redshift), and the host copy of the sorted values the chunk
-        // keys come from
-        double x0 = HUGE_VAL;
-        for (int64_t i = 0; i < N; ++i)
-            if (std::isfinite(a1[(size_t)i])) x0 = std::fmin(x0, a1[(size_t)i]);
-        kc.key_x0 = std::isfinite(x0) ? x0 : 0.0;
-        c->h_x = a1;
-    }
+    lfh::Catalogue cat = lfh::catalogue(d, kc);
     int rc;
     kc.cells = 0;
     kc.zcell_rho = 0.0;
@@ -1375,189 +954,36 @@ int build(lf_ctx* c, const lf_desc* d) {
         kc.kf_last[f] = lf::KEY_MAX;
     }
     for (int f = 0; f <= MAXF; ++f) kc.cc_fstart[f] = 0;
-    if (d->variant == LF_FREE && (rc = build_cells(c, kc, a1, nf)) != LF_OK) return rc;
+    if (d->variant == LF_FREE && (rc = upload_cells(c, lfh::build_cells(kc, c->field_ind, cat.a1, nf, CELL_M, CELL_RHO_G, CELL_RHO_H))) != LF_OK) return rc;
     if (d->variant == LF_ZEVOL) {
-        std::vector<double> wts((size_t)N);
-        for (int64_t i = 0; i < N; ++i) wts[(size_t)i] = std::pow(10.0, lumv[(size_t)i] - LF_LREF);
-        kc.zcell_rho = zcell_rho_for_box(kc, nf);
-        if ((rc = build_cells(c, kc, a1, nf, wts.data())) != LF_OK) return rc;
+        kc.zcell_rho = lfh::zcell_rho_for_box(kc, nf, ZCELL_RHO, ZCELL_X1, ZCELL_X2);
+        if ((rc = upload_cells(c, lfh::build_cells(kc, c->field_ind, cat.a1, nf, ZCELL_M, CELL_RHO_G, CELL_RHO_H, lfh::lum_weights(cat.lum).data()))) != LF_OK) return rc;
     }
-    if ((rc = upload(c, c->d_lum, lumv.data(), (size_t)N)) != LF_OK) return rc;
-    if ((rc = upload(c, c->d_a1, a1.data(), (size_t)N)) != LF_OK) return rc;
-    if ((rc = upload(c, c->d_P, P.data(), (size_t)N)) != LF_OK) return rc;
-    if ((rc = upload(c, c->d_U, U.data(), (size_t)N)) != LF_OK) return rc;
+    if ((rc = upload(c, c->d_lum, cat.lum, c->d_a1, cat.a1, c->d_P, cat.P, c->d_U, cat.U)) != LF_OK) return rc;
+    if (d->variant != LF_FIXCOMP) c->h_x.swap(cat.a1);      // (the sorted values the chunk keys come from)
 
-    // ---- grid-node tables.  trapz weights from the actual spacings (scipy trapz = sum d*(y1+y0)/2)
-    size_t nn = (size_t)S * S;
-    const size_t nn2 = nn;               // (the lattice; nn becomes S below when the fixed-completeness grid collapses to its rows)
-    std::vector<double> G(nn), PG(nn), W(nn), a3(nn, 0.0), a4(nn, 0.0), wz(S);
-    for (int k = 0; k < S; ++k) {
-        const double dl = k > 0 ? d->zarr[k] - d->zarr[k - 1] : 0.0;
-        const double dr = k < S - 1 ? d->zarr[k + 1] - d->zarr[k] : 0.0;
-        wz[k] = 0.5 * (dl + dr);
+    lfh::GridSwitches sw;
+    sw.gridq = !std::getenv("LF_NO_GRIDQ");
+    sw.zgrid_cols = !std::getenv("LF_NO_ZGRID_COLS");
+    sw.collapse = !std::getenv("LF_NO_COLLAPSE_GRID");
+    lfh::Grid gr = lfh::grid_tables(d, kc, sw);
+    c->nnodes = (int)gr.G.size();
+    kc.zgrid_cols = gr.zgrid_cols ? 1 : 0;
+    if (gr.binned) {
+        auto& g = c->gridq;
+        if ((rc = upload(c, g.d_rec, gr.gridq.rec, g.d_omega, gr.gridq.omega, g.d_rows, gr.gridq.rows)) != LF_OK) return rc;
+        g.nb = gr.gridq.nb;
+        g.margin = gr.gridq.margin;
+        g.built = true;
     }
-    for (int j = 0; j < S; ++j) {
-        for (int k = 0; k < S; ++k) {
-            const size_t g = (size_t)j * S + k;
-            const double x = d->logL[g];
-            const double dl = j > 0 ? x - d->logL[g - S] : 0.0;
-            const double dr = j < S - 1 ? d->logL[g + S] - x : 0.0;
-            const double w = 0.5 * (dl + dr) * wz[k];
-            G[g] = x;
-            PG[g] = std::pow(10.0, x - LF_LREF);
-            if (d->variant == LF_FREE) {
-                const double dlcm = LF_MPC_CM * d->dl_zarr[k];
-                const double lf = x - std::log10(4.0 * M_PI * dlcm * dlcm);
-                a3[g] = lf;
-                a4[g] = std::pow(10.0, lf - LF_FREF);
-                W[g] = w * d->volume_part[k];
-            } else {
-                double s = 0.0;
-                for (int f = 0; f < nf; ++f) s += d->integ_part[(size_t)f * nn2 + g];
-                W[g] = w * s;
-                if (d->variant == LF_ZEVOL) {
-                    a3[g] = d->zarr[k];
-                    a4[g] = d->zarr[k] * d->zarr[k];
-                }
-            }
-        }
-    }
-    if (d->variant == LF_FREE && S <= GRIDC_MAX_S) {
-        bool sep = true;
-        for (int j = 0; j < S && sep; ++j)
-            for (int k = 1; k < S; ++k)
-                if (d->logL[(size_t)j * S + k] != d->logL[(size_t)j * S]) {
-                    sep = false;
-                    break;
-                }
-        if (sep) {
-            c->h_L.resize(S); c->h_wL.resize(S); c->h_ck.resize(S); c->h_Dk.resize(S);
-            for (int j = 0; j < S; ++j) {
-                const double x = d->logL[(size_t)j * S];
-                const double dl = j > 0 ? x - d->logL[(size_t)(j - 1) * S] : 0.0;
-                const double dr = j < S - 1 ? d->logL[(size_t)(j + 1) * S] - x : 0.0;
-                c->h_L[j] = x;
-                c->h_wL[j] = 0.5 * (dl + dr);
-            }
-            for (int k = 0; k < S; ++k) {
-                const double dlcm = LF_MPC_CM * d->dl_zarr[k];
-                c->h_Dk[k] = std::log10(4.0 * M_PI * dlcm * dlcm);
-                c->h_ck[k] = wz[k] * d->volume_part[k];
-            }
-            // piece B over flux bins (lf_gridbound.h): the bins are proven for the context's whole prior box of (alpha_C, Flim),
-            // or the lattice stays.  Every rank of a sharded run derives the same bins from the same grid and box.
-            const double alo = kc.lims[LF_LIM_ALPHA][0], ahi = kc.lims[LF_LIM_ALPHA][1];
-            const double flo = kc.lims[LF_LIM_FLIM][0], fhi = kc.lims[LF_LIM_FLIM][1];
-            if (alo > 0.0 && ahi >= alo && flo > 0.0 && fhi >= flo && std::isfinite(ahi) && std::isfinite(fhi) && !std::getenv("LF_NO_GRIDQ")) {
-                const lfq::Box bx{std::sqrt(kc.fc_ratio), alo, ahi, std::log10(flo) + LF_FREF, std::log10(fhi) + LF_FREF};
-                lfq::GridQ gq;
-                if (lfq::build_gridq(bx, S, c->h_L.data(), c->h_wL.data(), c->h_ck.data(), c->h_Dk.data(), LF_FREF, LF_LREF, gq)) {
-                    auto& g = c->gridq;
-                    if ((rc = upload(c, g.d_rec, gq.rec.data(), gq.rec.size())) != LF_OK) return rc;
-                    if ((rc = upload(c, g.d_omega, gq.omega.data(), gq.omega.size())) != LF_OK) return rc;
-                    if ((rc = upload(c, g.d_rows, gq.rows.data(), gq.rows.size())) != LF_OK) return rc;
-                    g.nb = gq.nb;
-                    g.margin = gq.margin;
-                    g.built = true;
-                }
-            }
-        }
-    }
-    kc.zgrid_cols = 0;
-    if (d->variant == LF_ZEVOL && S >= lf::BLOCK / (lf::ZCOLS - 1) && !std::getenv("LF_NO_ZGRID_COLS")) {
-        // z-evolving: store the lattice column by column (a sum does not care; lf_kernels.h: gridsum_body takes what depends
-        // on the walker per COLUMN).  S >= 128: a chunk of 256 nodes then touches at most 3 columns.
-        std::vector<double> t(nn);
-        for (std::vector<double>* arr : {&G, &PG, &W, &a3, &a4}) {
-            for (int j = 0; j < S; ++j)
-                for (int k = 0; k < S; ++k) t[(size_t)k * S + j] = (*arr)[(size_t)j * S + k];
-            arr->swap(t);
-        }
-        kc.zgrid_cols = 1;
-    }
-    if (d->variant == LF_FIXCOMP && !std::getenv("LF_NO_COLLAPSE_GRID")) {        // (the variable: A/B runs and the test of this step)
-        // Fixed completeness: the integrand at node (j, k) is T_w(L_jk) W_jk with everything but the Schechter function
-        // T folded into W.  When every redshift column has the same luminosity nodes (the constructor clips the columns'
-        // lower ends to the catalogue's faintest luminosity: with min_comp_frac = 0 all of them) T depends on the row only
-        // and the double sum is sum_j T_w(L_j) (sum_k W_jk): S nodes instead of S^2, exactly - the trapezoid rule's sums
-        // in another order.  Row sums in extended precision.
-        bool sep = true;
-        for (int j = 0; j < S && sep; ++j)
-            for (int k = 1; k < S; ++k)
-                if (d->logL[(size_t)j * S + k] != d->logL[(size_t)j * S]) {
-                    sep = false;
-                    break;
-                }
-        if (sep) {
-            for (int j = 0; j < S; ++j) {
-                long double rs = 0.0L;
-                for (int k = 0; k < S; ++k) rs += (long double)W[(size_t)j * S + k];
-                G[(size_t)j] = G[(size_t)j * S];
-                PG[(size_t)j] = PG[(size_t)j * S];
-                W[(size_t)j] = (double)rs;
-                a3[(size_t)j] = a4[(size_t)j] = 0.0;
-            }
-            nn = (size_t)S;
-            c->nnodes = S;
-        }
-    }
-    if ((rc = upload(c, c->d_G, G.data(), nn)) != LF_OK) return rc;
-    if ((rc = upload(c, c->d_PG, PG.data(), nn)) != LF_OK) return rc;
-    if ((rc = upload(c, c->d_W, W.data(), nn)) != LF_OK) return rc;
-    if ((rc = upload(c, c->d_a3, a3.data(), nn)) != LF_OK) return rc;
-    if ((rc = upload(c, c->d_a4, a4.data(), nn)) != LF_OK) return rc;
+    if ((rc = upload(c, c->d_G, gr.G, c->d_PG, gr.PG, c->d_W, gr.W, c->d_a3, gr.a3, c->d_a4, gr.a4)) != LF_OK) return rc;
     if (d->variant != LF_FREE) {
-        // lf_pers reads the nodes as 32-byte records {G, PG, W, redshift column}, padded to whole chunks of 64 (pads: W = 0)
-        const size_t nch = (nn + 63) / 64;
-        std::vector<double> n4(nch * 64 * 4, 0.0);
-        for (size_t g = 0; g < nch * 64; ++g) {
-            const size_t gg = std::min(g, nn - 1);
-            double* r = &n4[g * 4];
-            r[0] = G[gg];
-            r[1] = PG[gg];
-            r[2] = g < nn ? W[gg] : 0.0;
-            r[3] = kc.zgrid_cols ? (double)(gg / (size_t)S) : 0.0;      // (column-major lattice: node = k S + j)
-        }
-        if ((rc = upload(c, c->d_nodes4, n4.data(), n4.size())) != LF_OK) return rc;
-        c->nch4 = (int)nch;
-        std::vector<double> zc((size_t)S * 2);
-        for (int k = 0; k < S; ++k) {
-            zc[(size_t)2 * k] = d->zarr[k];
-            zc[(size_t)2 * k + 1] = d->zarr[k] * d->zarr[k];
-        }
-        if ((rc = upload(c, c->d_zcol, zc.data(), zc.size())) != LF_OK) return rc;
+        if ((rc = upload(c, c->d_nodes4, gr.nodes4, c->d_zcol, gr.zcol)) != LF_OK) return rc;
+        c->nch4 = (int)(gr.nodes4.size() / (64 * 4));
     }
-    {
-        // per chunk of 256 nodes the smallest a4 (FREE; NaN-safe: a NaN node keeps the general form)
-        std::vector<double> a4min((nn + lf::BLOCK - 1) / lf::BLOCK, 0.0);
-        for (size_t ch = 0; ch < a4min.size(); ++ch) {
-            double m = HUGE_VAL;
-            for (size_t g = ch * lf::BLOCK; g < std::min(nn, (ch + 1) * lf::BLOCK); ++g) m = std::isnan(a4[g]) ? 0.0 : std::fmin(m, a4[g]);
-            a4min[ch] = d->variant == LF_FREE ? m : 0.0;
-        }
-        if ((rc = upload(c, c->d_a4min, a4min.data(), a4min.size())) != LF_OK) return rc;
-        // lf_free reads the nodes as 64-byte records {G, PG, W, a3, a4, smallest a4 of the node's chunk of 64, -, -}, padded
-        // to whole chunks (pads: the last node again with W = 0): one contiguous load per lane, nothing to mask
-        if (d->variant == LF_FREE) {
-            const size_t nch64 = (nn + 63) / 64;
-            std::vector<double> n8(nch64 * 64 * 8, 0.0);
-            for (size_t ch = 0; ch < nch64; ++ch) {
-                double m = HUGE_VAL;
-                for (size_t g = ch * 64; g < std::min(nn, (ch + 1) * 64); ++g) m = std::isnan(a4[g]) ? 0.0 : std::fmin(m, a4[g]);
-                for (size_t l = 0; l < 64; ++l) {
-                    const size_t g = std::min(ch * 64 + l, nn - 1);
-                    double* r = &n8[(ch * 64 + l) * 8];
-                    r[0] = G[g];
-                    r[1] = PG[g];
-                    r[2] = ch * 64 + l < nn ? W[g] : 0.0;
-                    r[3] = a3[g];
-                    r[4] = a4[g];
-                    r[5] = m;
-                }
-            }
-            if ((rc = upload(c, c->d_nodes8, n8.data(), n8.size())) != LF_OK) return rc;
-        }
-    }
+    if ((rc = upload(c, c->d_a4min, gr.a4min)) != LF_OK) return rc;
+    if (d->variant == LF_FREE && (rc = upload(c, c->d_nodes8, gr.nodes8)) != LF_OK) return rc;
+    c->h_L.swap(gr.L), c->h_wL.swap(gr.wL), c->h_ck.swap(gr.ck), c->h_Dk.swap(gr.Dk);
     {
         hipDeviceProp_t prop;
         LF_HIP(c, hipGetDeviceProperties(&prop, c->device));

@@ -1,4 +1,4 @@
-"""lf_free's deal of cell chunks and flux bins to its 32 virtual workgroups (csrc/lfmcmc.hip: make_deal, behind lf_deal_table;
+"""lf_free's deal of cell chunks and flux bins to its 32 virtual workgroups (csrc/lf_hostprep.h: make_deal, behind lf_deal_table;
 DESIGN.md section 3.4c) - host logic, no GPU: every chunk and every bin exactly once, whatever their numbers; the loads as the
 cost model wants them; a source-sharded rank's foreign bins cost nothing."""
 import numpy as np
@@ -22,7 +22,7 @@ def test_every_chunk_and_bin_exactly_once(nc, nb):
 
 def test_the_benchmark_context_is_balanced():
     """17 bins (8 units each), 55 cell chunks (3 each), the younger half of the ranks counted 8 units behind (the costs and the
-    sweep they come from: lfmcmc.hip, make_deal): with that handicap counted in, no rank is more than a bin above another"""
+    sweep they come from: lf_hostprep.h, make_deal): with that handicap counted in, no rank is more than a bin above another"""
     cells, bins = capi.deal_table(55, 17)
     load = np.array([8 * len(b) + 3 * len(c) for b, c in zip(bins, cells)])
     assert load.sum() == 17 * 8 + 55 * 3
