@@ -5,7 +5,7 @@
     catalogue file -> per-field lists -> LumFuncMCMC -> fit_model (device-resident sampler)
     -> set_median_fit (median LF + 1/Veff estimate) -> the reference's output tables.
 
-    python examples/fit_synthetic.py [--nsrc 20000] [--nwalkers 64] [--nsteps 300] [--fix-comp]
+    python examples/fit_synthetic.py [--nsrc 20000] [--nwalkers 64] [--nsteps 300] [--fix-comp] [--until-converged]
 """
 import argparse
 import os
@@ -40,6 +40,9 @@ def main():
     ap.add_argument("--nwalkers", type=int, default=64)
     ap.add_argument("--nsteps", type=int, default=300)
     ap.add_argument("--fix-comp", action="store_true")
+    ap.add_argument("--until-converged", action="store_true",
+                    help="run until steps > 50 tau and tau has settled (fit_model_converged, at most 10 x nsteps steps; "
+                         "DESIGN.md section 3.12) instead of exactly --nsteps steps")
     ap.add_argument("--out", default="LFMCMCOut")
     ap.add_argument("--compress", action="store_true", help="compressed catalogue and grid (DESIGN.md section 3.5)")
     args = ap.parse_args()
@@ -58,7 +61,12 @@ def main():
                         field_names=field_names, field_ind=field_ind, compress=args.compress)
     print("setup %.2f s for %d sources" % (time.time() - t0, len(LFmod.lum)))
     np.random.seed(3)
-    LFmod.fit_model()
+    if args.until_converged:
+        LFmod.fit_model_converged()
+        print("converged: %s after %d steps; tau per parameter %s" % (LFmod.converged, LFmod.tau_history[-1][0],
+                                                                     np.array2string(LFmod.tau_history[-1][1], precision=1)))
+    else:
+        LFmod.fit_model()
     LFmod.set_median_fit()
 
     names = LFmod.get_param_names() + ["Ln Prob"]

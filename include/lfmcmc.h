@@ -294,6 +294,40 @@ int lf_ptsampler_read(lf_ptsampler *s, double *chain, double *chain_lnlike, doub
 /* Steps recorded so far. */
 int64_t lf_ptsampler_steps(const lf_ptsampler *s);
 
+/* Chain diagnostics on the device (csrc/lf_diag.h).  Replace the read-back behind
+ *     tau = np.max(sampler.acor); burnin_step = int(tau * 3), at most nsteps // 2          lumfuncmcmc.py:499-501
+ * (emcee's acor: the whole chain on the host, one FFT pair per walker and parameter) by direct sums where the chain is.
+ * A chain is [W][steps][ndim] (emcee's sampler.chain layout), optionally with its lnprob [W][steps] as one more series
+ * (index ndim); the range is steps [t0, t1), n = t1 - t0.  Per series d, in this order of the D = ndim (+ 1) outputs:
+ *   acf[d][k] = (1 / W) sum_w a_w[k] / a_w[0],  a_w[k] = sum_{t < n-k} y[t] y[t+k],  y = x - mean(x)  (a walker with a_w[0] <= 0 is
+ *     left out of the sum) - the definition of the host's integrated_time, by direct summation in a fixed order: acf[d][k] has
+ *     the same bits whatever number of lags is computed and whatever else is in the chain;
+ *   tau[d], window[d]: taus[m] = 2 sum_{k <= m} acf[k] - 1, window = the first m with m >= c taus[m], tau = taus[window]; no
+ *     window below n: n - 1; a tau that is not finite or not positive: 1.0; n < 4: tau 1.0, window 0;
+ *   ess[d] = W n / tau[d];
+ *   rhat[d] = split-R-hat (Gelman et al. 2013) over the 2 W half-ranges [0, n/2), [n - n/2, n) of the walkers; NaN for n < 4.
+ *     The walkers of an ensemble are not independent chains: a sanity check, not a stopping rule.
+ * LF_ERR_ARG, before the device is touched, for: a NULL pointer (lnprob, acf may be NULL), W < 1, ndim < 1, t0 < 0, t1 > steps,
+ * t1 <= t0, c <= 0 or NaN, a sampler that has not been started (or has no step at or after t0), a temperature outside the ladder. */
+
+/* Host pointers, synchronous, no context (the form of lf_veff): for chains of the host sampler and for tests.  acf: NULL, or
+ * [D][acf_cap] - the first acf_cap lags of every series (zeros past n). */
+int lf_chain_diag(int device, const double *chain, const double *lnprob, int W, int64_t steps, int ndim, int64_t t0, int64_t t1,
+                  double c, double *tau, int64_t *window, double *ess, double *rhat, double *acf, int64_t acf_cap);
+/* The same over steps [t0, lf_sampler_steps) of the sampler's own chain in HBM (with_lnprob != 0: and of its lnprob chain).
+ * Synchronises the device; the chain is not copied to the host (per pass D x lags doubles are).  Changes no sampler state. */
+int lf_sampler_diag(lf_sampler *s, int64_t t0, double c, int with_lnprob, double *tau, int64_t *window, double *ess, double *rhat);
+/* The same for one temperature of the tempered sampler (with_lnlike != 0: and of its untempered lnlike chain). */
+int lf_ptsampler_diag(lf_ptsampler *s, int temperature, int64_t t0, double c, int with_lnlike, double *tau, int64_t *window,
+                      double *ess, double *rhat);
+/* Host-only, exported for tests (touches no GPU): the window rule above on a given curve acf[0 .. M) of a series of n steps.
+ * Returns 0 with *tau and *window set, 1 when no window lies below M and M < n (more lags are needed), LF_ERR_ARG for a
+ * NULL pointer, n < 1, M < 1 (with n >= 4) or c <= 0. */
+int lf_chain_window(const double *acf, int64_t M, double c, int64_t n, double *tau, int64_t *window);
+/* Device time in ms of the kernels of the most recent successful diagnostics call in this process (hipEvents around every
+ * bracket of launches) and the lags per series it computed (measurement only).  LF_ERR_ARG when there is none. */
+int lf_diag_last(double *kernel_ms, int64_t *lags);
+
 /* Host-only helper behind "compress", exported for tests (touches no GPU): compress n coordinates `key` with
  * weights `wt` (NULL = 1) into pseudo-sources.  kind 0 (FREE): params = {|a/(1-a)|, alpha_lo, alpha_hi, flim_lo,
  * flim_hi}; kind 1 (ZEVOL): params = {L_lo, L_hi, z1, z2, z3}.  Returns the number of pseudo-sources (written to

@@ -49,7 +49,8 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_free_block_uploads", "lf_veff",
            "lf_lumfunc_quantiles", "lf_lumfunc_quantiles_ms", "lf_ptsampler_create", "lf_ptsampler_destroy",
            "lf_ptsampler_start", "lf_ptsampler_run", "lf_ptsampler_read", "lf_ptsampler_steps", "lf_mock_create",
-           "lf_mock_destroy", "lf_mock_counts", "lf_mock_draw", "lf_mock_hist", "lf_mock_last_error")
+           "lf_mock_destroy", "lf_mock_counts", "lf_mock_draw", "lf_mock_hist", "lf_mock_last_error", "lf_chain_diag",
+           "lf_sampler_diag", "lf_ptsampler_diag", "lf_chain_window", "lf_diag_last")
 
 _lib = None
 
@@ -169,6 +170,20 @@ def load():
     lib.lf_compress_keys.restype = ctypes.c_int64
     lib.lf_compress_keys.argtypes = [ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int64,
                                      _c_double_p, _c_double_p, ctypes.c_int64, _c_double_p]
+    lib.lf_chain_diag.restype = ctypes.c_int
+    lib.lf_chain_diag.argtypes = [ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                  ctypes.c_int64, ctypes.c_double, _c_double_p, _c_int64_p, _c_double_p, _c_double_p, _c_double_p,
+                                  ctypes.c_int64]
+    lib.lf_sampler_diag.restype = ctypes.c_int
+    lib.lf_sampler_diag.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_int, _c_double_p, _c_int64_p, _c_double_p,
+                                    _c_double_p]
+    lib.lf_ptsampler_diag.restype = ctypes.c_int
+    lib.lf_ptsampler_diag.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_int, _c_double_p,
+                                      _c_int64_p, _c_double_p, _c_double_p]
+    lib.lf_chain_window.restype = ctypes.c_int
+    lib.lf_chain_window.argtypes = [_c_double_p, ctypes.c_int64, ctypes.c_double, ctypes.c_int64, _c_double_p, _c_int64_p]
+    lib.lf_diag_last.restype = ctypes.c_int
+    lib.lf_diag_last.argtypes = [_c_double_p, _c_int64_p]
     v = lib.lf_abi_version()
     if v != LF_ABI_VERSION:
         raise RuntimeError("liblfmcmc.so ABI %d != binding ABI %d: rebuild the library" % (v, LF_ABI_VERSION))

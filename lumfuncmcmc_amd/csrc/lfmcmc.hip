@@ -19,6 +19,7 @@
 #include "lf_bands.h"
 #include "lf_compress.h"
 #include "lf_devmem.h"
+#include "lf_diag.h"
 #include "lf_gridbound.h"
 #include "lf_hostprep.h"
 #include "lf_kernels.h"
@@ -1926,6 +1927,159 @@ int lf_ptsampler_read(lf_ptsampler* sm, double* chain, double* chain_lnlike, dou
 }
 
 int64_t lf_ptsampler_steps(const lf_ptsampler* sm) { return sm ? sm->t : LF_ERR_ARG; }
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------------------------------------
+ * chain diagnostics on the device (lf_diag.h)
+ * ------------------------------------------------------------------------------------------- */
+namespace {
+
+double g_diag_ms = -1.0;        // device time of the kernels of the last diagnostics call (lf_diag_last)
+int64_t g_diag_lags = 0;        // lags it computed per series
+
+// The diagnostics of a chain in device memory, [W][cap][ndim] (+ lnprob [W][cap]) over steps [t0, t1): tau, window, ess, rhat of
+// the D = ndim + (d_lnp != NULL) series; acf (host, [D][acf_cap]) when asked for.  Lags are computed in passes of whole tiles
+// of 512 - 512 first, then up to twice as many as there are, until every series has its window (or n lags exist) - and a
+// pass in slices whose partial sums stay below 64 MiB.  Launches go to `st`; synchronises it.  `err` takes the message.
+int diag_run(std::string& err, hipStream_t st, const double* d_chain, const double* d_lnp, int W, int64_t cap, int ndim, int64_t t0,
+             int64_t t1, double c, double* tau, int64_t* window, double* ess, double* rhat, double* acf, int64_t acf_cap) {
+#pragma clang fp contract(off)
+    const int D = ndim + (d_lnp ? 1 : 0);
+    const int64_t n = t1 - t0;
+    g_diag_ms = -1.0;
+    g_diag_lags = 0;
+    if (W > 65535 || D > 65535 || n > ((int64_t)1 << 30)) {
+        err = "diagnostics: at most 65535 walkers and 2^30 steps";
+        return LF_ERR_ARG;
+    }
+    int rc = LF_OK;
+    auto ok = [&](hipError_t e) {
+        if (e != hipSuccess && rc == LF_OK) {
+            rc = LF_ERR_HIP;
+            err = std::string("diagnostics: ") + hipGetErrorString(e);
+        }
+        return e == hipSuccess;
+    };
+    const size_t WD = (size_t)W * D;
+    Buf<double> d_mean, d_mom, d_a0, d_a, d_acf;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double ms_total = 0.0;
+    auto timed = [&]() {            // closes a bracket of launches: waits for it and adds its device time
+        float ms = 0.0f;
+        if (ok(hipEventRecord(ev[1], st)) && ok(hipEventSynchronize(ev[1])) && ok(hipEventElapsedTime(&ms, ev[0], ev[1]))) ms_total += ms;
+    };
+    const lf::DiagSeries ser{d_chain, d_lnp, (long long)cap, ndim, D, (long long)t0, (int)n};
+    std::vector<double> mom(4 * WD);
+    if (ok(d_mean.alloc(WD)) && ok(d_mom.alloc(4 * WD)) && ok(d_a0.alloc(WD)) && ok(hipEventCreate(&ev[0])) && ok(hipEventCreate(&ev[1]))) {
+        ok(hipEventRecord(ev[0], st));
+        hipLaunchKernelGGL(lf::lf_diag_moments, dim3((unsigned)W, (unsigned)D), dim3(lf::DIAG_THREADS), 0, st, ser, d_mean.get(), d_mom.get());
+        ok(hipGetLastError());
+        timed();
+        ok(hipMemcpy(mom.data(), d_mom, 4 * WD * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    std::vector<std::vector<double>> curve(D);
+    std::vector<char> decided(D, 0);
+    if (rc == LF_OK) {
+        for (int d = 0; d < D; ++d) {
+            rhat[d] = lfd::split_rhat(mom.data() + 4 * d, W, 4 * (size_t)D, n / 2);
+            if (n < 4) decided[d] = (char)(lfd::chain_window(nullptr, 0, c, n, &tau[d], &window[d]) == 0);
+        }
+    }
+    const int64_t Mmax = (n + lf::DIAG_LT - 1) / lf::DIAG_LT * lf::DIAG_LT;
+    int64_t have = 0, want = lf::DIAG_LT;
+    if (acf && acf_cap > want) want = std::min<int64_t>((acf_cap + lf::DIAG_LT - 1) / lf::DIAG_LT * lf::DIAG_LT, Mmax);
+    const int64_t slice = std::max<int64_t>(((int64_t)64 << 20) / (int64_t)(WD * sizeof(double)) / lf::DIAG_LT, 1) * lf::DIAG_LT;
+    const unsigned groups = (unsigned)((D + lf::DIAG_DG - 1) / lf::DIAG_DG);
+    while (rc == LF_OK && n >= 4) {
+        for (int64_t lo = have; rc == LF_OK && lo < want; lo += slice) {
+            const int64_t Mp = std::min(slice, want - lo);
+            std::vector<double> part((size_t)D * Mp);
+            if (!ok(d_a.alloc(WD * Mp)) || !ok(d_acf.alloc((size_t)D * Mp))) break;
+            ok(hipEventRecord(ev[0], st));
+            hipLaunchKernelGGL(lf::lf_diag_acf, dim3((unsigned)(Mp / lf::DIAG_LT), (unsigned)W, groups), dim3(lf::DIAG_THREADS), 0, st, ser,
+                               d_mean.get(), (int)lo, d_a.get(), d_a0.get());
+            ok(hipGetLastError());
+            hipLaunchKernelGGL(lf::lf_diag_norm, dim3((unsigned)(((int64_t)D * Mp + lf::DIAG_THREADS - 1) / lf::DIAG_THREADS)),
+                               dim3(lf::DIAG_THREADS), 0, st, d_a.get(), d_a0.get(), W, D, (long long)Mp, d_acf.get());
+            ok(hipGetLastError());
+            timed();
+            ok(hipMemcpy(part.data(), d_acf, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+            for (int d = 0; d < D && rc == LF_OK; ++d) curve[d].insert(curve[d].end(), part.begin() + (size_t)d * Mp, part.begin() + (size_t)(d + 1) * Mp);
+        }
+        if (rc != LF_OK) break;
+        have = want;
+        bool all = true;
+        for (int d = 0; d < D; ++d) {
+            if (!decided[d]) decided[d] = (char)(lfd::chain_window(curve[d].data(), have, c, n, &tau[d], &window[d]) == 0);
+            all = all && decided[d];
+        }
+        if (all || have >= Mmax) break;
+        want = std::min(2 * have, Mmax);
+    }
+    for (hipEvent_t e : ev)
+        if (e) hipEventDestroy(e);
+    if (rc != LF_OK) return rc;
+    for (int d = 0; d < D; ++d) {
+        ess[d] = (double)W * (double)n / tau[d];
+        if (acf)
+            for (int64_t k = 0; k < acf_cap; ++k) acf[(size_t)d * acf_cap + k] = k < (int64_t)curve[d].size() ? curve[d][k] : 0.0;
+    }
+    g_diag_ms = ms_total;
+    g_diag_lags = have;
+    return LF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lf_chain_window(const double* acf, int64_t M, double c, int64_t n, double* tau, int64_t* window) {
+    if (!tau || !window || n < 1 || M < 0 || !(c > 0.0) || (n >= 4 && (!acf || M < 1))) return LF_ERR_ARG;
+    return lfd::chain_window(acf, M, c, n, tau, window);
+}
+
+int lf_chain_diag(int device, const double* chain, const double* lnprob, int W, int64_t steps, int ndim, int64_t t0, int64_t t1, double c,
+                  double* tau, int64_t* window, double* ess, double* rhat, double* acf, int64_t acf_cap) {
+    if (!chain || !tau || !window || !ess || !rhat || W < 1 || ndim < 1 || t0 < 0 || t1 > steps || t1 <= t0 || !(c > 0.0) || acf_cap < 0 ||
+        (acf && acf_cap < 1))
+        return LF_ERR_ARG;
+    if (hipSetDevice(device) != hipSuccess) return LF_ERR_NODEV;
+    Buf<double> d_chain, d_lnp;
+    const size_t rows = (size_t)W * (size_t)steps;
+    if (d_chain.upload(chain, rows * ndim) != hipSuccess || (lnprob && d_lnp.upload(lnprob, rows) != hipSuccess)) return LF_ERR_HIP;
+    std::string err;
+    return diag_run(err, nullptr, d_chain, lnprob ? d_lnp.get() : nullptr, W, steps, ndim, t0, t1, c, tau, window, ess, rhat, acf, acf_cap);
+}
+
+int lf_sampler_diag(lf_sampler* sm, int64_t t0, double c, int with_lnprob, double* tau, int64_t* window, double* ess, double* rhat) {
+    if (!sm || !tau || !window || !ess || !rhat || !sm->started || t0 < 0 || sm->t <= t0 || !(c > 0.0)) return LF_ERR_ARG;
+    lf_ctx* cx = sm->ctx;
+    LF_HIP(cx, hipSetDevice(cx->device));
+    LF_HIP(cx, hipDeviceSynchronize());
+    return diag_run(cx->err, cx->stream, sm->d_chain, with_lnprob ? sm->d_chain_lnp.get() : nullptr, sm->W, sm->cap, sm->ndim, t0, sm->t, c, tau,
+                    window, ess, rhat, nullptr, 0);
+}
+
+int lf_ptsampler_diag(lf_ptsampler* sm, int temperature, int64_t t0, double c, int with_lnlike, double* tau, int64_t* window, double* ess,
+                      double* rhat) {
+    if (!sm || !tau || !window || !ess || !rhat || !sm->started || temperature < 0 || temperature >= sm->T || t0 < 0 || sm->t <= t0 ||
+        !(c > 0.0))
+        return LF_ERR_ARG;
+    lf_ctx* cx = sm->ctx;
+    LF_HIP(cx, hipSetDevice(cx->device));
+    LF_HIP(cx, hipDeviceSynchronize());
+    const size_t off = (size_t)temperature * sm->W * (size_t)sm->cap;
+    return diag_run(cx->err, cx->stream, sm->d_chain + off * sm->ndim, with_lnlike ? sm->d_chain_lnl + off : nullptr, sm->W, sm->cap, sm->ndim,
+                    t0, sm->t, c, tau, window, ess, rhat, nullptr, 0);
+}
+
+int lf_diag_last(double* kernel_ms, int64_t* lags) {
+    if (!kernel_ms || !lags) return LF_ERR_ARG;
+    *kernel_ms = g_diag_ms;
+    *lags = g_diag_lags;
+    return g_diag_ms < 0.0 ? LF_ERR_ARG : LF_OK;
+}
 
 }  // extern "C"
 

@@ -281,6 +281,67 @@ class _Base(object):
         self.log.info("Median lnprob: %.5f; Max lnprob: %.5f" % (np.median(sampler.lnprobability),
                                                                 np.amax(sampler.lnprobability)))
 
+    def fit_model_converged(self, max_steps=None, check_every=None, ntau=50, rtol=0.01):
+        """fit_model that runs until the chain is long enough instead of for a number of steps guessed beforehand: one
+        device sampler with room for max_steps (default 10 * self.nsteps) runs check_every steps at a time (default
+        max(100, self.nsteps // 10)) and asks the chain where it is for its autocorrelation times
+        (DeviceEnsembleSampler.diagnostics).  It stops when
+            steps > ntau * max(tau)   and   max |tau - tau_prev| / tau < rtol
+        - emcee's documented recipe, with its numbers 50 and 0.01 - or at max_steps with a warning.  The chain is read back
+        once, at the end.  Sets what fit_model sets (samples, chain, sampler, start_pos, sampler_seed; burn-in =
+        min(int(3 max tau), steps // 2) with the device's tau) plus self.converged and self.tau_history = [(steps, tau), ...];
+        returns the last tau.  One GPU, device sampler only."""
+        rank, world = self._dist_state()
+        if world > 1:
+            raise NotImplementedError("fit_model_converged runs on one GPU: diagnostics across several ranks are not implemented")
+        if self.lnprob_fn is not None:
+            raise NotImplementedError("fit_model_converged runs the device sampler: it cannot use lnprob_fn")
+        max_steps = int(10 * self.nsteps if max_steps is None else max_steps)
+        check_every = int(max(100, self.nsteps // 10) if check_every is None else check_every)
+        if max_steps < 1 or check_every < 1:
+            raise ValueError("max_steps and check_every must be positive")
+        self.log.info('Fitting Schechter model to true luminosity function until the chain has converged')
+        pos = self.get_init_walker_values()
+        ndim = pos.shape[1]
+        start = time.time()
+        seed = int(np.random.randint(0, 2 ** 31 - 1))
+        self.start_pos, self.sampler_seed = np.array(pos), seed       # (start, seed, steps) reproduce the chain
+        sampler = DeviceEnsembleSampler(self.context(), self.nwalkers, seed=seed, capacity=max_steps)
+        steps, tau, tau_prev = 0, None, None
+        self.converged, self.tau_history = False, []
+        while steps < max_steps and not self.converged:
+            k = min(check_every, max_steps - steps)
+            sampler.enqueue(pos if steps == 0 else None, k)
+            steps += k
+            tau_prev, tau = tau, sampler.diagnostics().tau
+            self.tau_history.append((steps, tau.copy()))
+            self.converged = bool(tau_prev is not None and steps > ntau * np.max(tau)
+                                  and np.max(np.abs(tau - tau_prev) / tau) < rtol)
+        if not self.converged:
+            self.log.warning("fit_model_converged: not converged after max_steps = %d steps (max tau %.1f, needs more than "
+                             "%d tau): going on with the chain there is" % (max_steps, np.max(tau), ntau))
+        sampler.sync()
+        elapsed = time.time() - start
+        self.log.info("Total time taken: %0.2f s" % elapsed)
+        self.log.info("Time taken per step per walker: %0.2f ms" % (elapsed / steps * 1000. / self.nwalkers))
+        taumax = np.max(tau)
+        burnin_step = int(taumax * 3)
+        if burnin_step > steps // 2:
+            burnin_step = steps // 2
+        self.log.info("Mean acceptance fraction: %0.2f" % (np.mean(sampler.acceptance_fraction)))
+        self.log.info("AutoCorrelation Steps: %i, Number of Burn-in Steps: %i" % (np.round(taumax), burnin_step))
+        new_chain = np.zeros((self.nwalkers, steps, ndim + 1))
+        new_chain[:, :, :-1] = sampler.chain
+        self.chain = sampler.chain
+        new_chain[:, :, -1] = sampler.lnprobability
+        self.samples = new_chain[:, burnin_step:, :].reshape((-1, ndim + 1))
+        self.sampler = sampler
+        self.log.info("Shape of self.samples")
+        self.log.info(self.samples.shape)
+        self.log.info("Median lnprob: %.5f; Max lnprob: %.5f" % (np.median(sampler.lnprobability),
+                                                                np.amax(sampler.lnprobability)))
+        return tau
+
     def fit_model_pt(self, ntemps=None, Tmax=None, betas=None, fburnin=0.1):
         """Parallel-tempered fit (DevicePTSampler, sampler.py) and the Bayesian evidence of this model by thermodynamic
         integration, for comparing the models the classes offer.  self.nwalkers walkers per temperature, self.nsteps

@@ -39,6 +39,165 @@ def integrated_time(x, c=5.0):
     return tau if np.isfinite(tau) and tau > 0 else 1.0
 
 
+# ------------------------------------------------------------------------------------------------------ chain diagnostics
+# Autocorrelation time, effective sample size and split-R-hat of a chain by DIRECT sums: on the GPU
+# (lf_chain_diag, lf_sampler_diag, lf_ptsampler_diag of include/lfmcmc.h; csrc/lf_diag.h) and as a NumPy twin that states the
+# same sums in the same blocks.  The definitions are integrated_time's; the FFT above stays the yardstick.
+
+DIAG_TILE, DIAG_LAGS = 256, 512          # steps per tile and lags per pass of csrc/lf_diag.h
+
+
+class ChainDiagnostics(object):
+    """tau, window, ess, rhat: one entry per series (the ndim parameters, then lnprob when it was given); n steps of
+    nwalkers walkers; acf (D, nlags) when it was asked for."""
+
+    def __init__(self, tau, window, ess, rhat, n, nwalkers, acf=None):
+        self.tau, self.window, self.ess, self.rhat = tau, window, ess, rhat
+        self.n, self.nwalkers, self.acf = int(n), int(nwalkers), acf
+
+    def __repr__(self):
+        return "ChainDiagnostics(n=%d, nwalkers=%d, tau=%s, ess=%s, rhat=%s)" % (self.n, self.nwalkers, self.tau, self.ess, self.rhat)
+
+
+def _chain_args(chain, lnprob, t0):
+    chain = np.ascontiguousarray(chain, dtype=np.float64)
+    if chain.ndim != 3:
+        raise ValueError("chain must be (nwalkers, nsteps, ndim)")
+    if lnprob is not None:
+        lnprob = np.ascontiguousarray(lnprob, dtype=np.float64)
+        if lnprob.shape != chain.shape[:2]:
+            raise ValueError("lnprob must be (nwalkers, nsteps)")
+    t0 = int(t0)
+    if not 0 <= t0 < chain.shape[1]:
+        raise ValueError("t0 must lie inside the chain")
+    return chain, lnprob, t0
+
+
+def chain_window(acf, c, n):
+    """integrated_time's window rule on acf[0 .. M) of a series of n steps: (tau, window), or None when no window lies
+    below M and M < n (more lags are needed).  NumPy; lf_chain_window is the same rule in C."""
+    if n < 4:
+        return 1.0, 0
+    acf = np.asarray(acf, dtype=np.float64)[:n]
+    taus = 2.0 * np.cumsum(acf) - 1.0
+    m = np.arange(len(acf)) < c * taus
+    if m.all():
+        if len(acf) < n:
+            return None
+        win = n - 1
+    else:
+        win = int(np.argmin(m))
+    tau = float(taus[win])
+    return (tau if np.isfinite(tau) and tau > 0 else 1.0), win
+
+
+def _twin_mean(x):
+    """Two-pass mean along the last axis, as the device takes it."""
+    m0 = x.sum(axis=-1) / x.shape[-1]
+    return m0 + (x - m0[..., None]).sum(axis=-1) / x.shape[-1]
+
+
+def _twin_lag_sums(y, k_lo, k_hi):
+    """a[w][k] = sum_{t < n-k} y[w][t] y[w][t+k] for k_lo <= k < k_hi in the device's blocks: per tile of 256 steps four
+    runs of 64 steps, each run's totals added tile by tile, then ((q0 + q1) + q2) + q3."""
+    W, n = y.shape
+    nt = -(-n // DIAG_TILE)
+    pad = np.zeros((W, nt * DIAG_TILE + k_hi))
+    pad[:, :n] = y
+    base = pad[:, :nt * DIAG_TILE]
+    out = np.zeros((W, k_hi - k_lo))
+    for k in range(k_lo, min(k_hi, n)):
+        runs = (base * pad[:, k:k + nt * DIAG_TILE]).reshape(W, nt, 4, 64).sum(axis=3)
+        q = np.cumsum(runs, axis=1)[:, -1]
+        out[:, k - k_lo] = ((q[:, 0] + q[:, 1]) + q[:, 2]) + q[:, 3]
+    return out
+
+
+def split_rhat(x):
+    """Split-R-hat (Gelman et al. 2013) of a (nwalkers, n) series: every walker's range cut into [0, n/2) and [n - n/2, n),
+    2 W sequences of length h; Wv = mean of their variances, B / h = variance of their means, sqrt(((h-1)/h Wv + B/h) / Wv).
+    The walkers of an ensemble are not independent chains, so this is a sanity check (a stuck or drifting ensemble shows),
+    not a convergence proof: the stopping rule of fit_model_converged is built on tau."""
+    W, n = x.shape
+    h = n // 2
+    if h < 2:
+        return float("nan")
+    halves = np.concatenate([x[:, :h], x[:, n - h:]], axis=0)
+    mean = _twin_mean(halves)
+    s2 = ((halves - mean[:, None]) ** 2).sum(axis=1) / (h - 1)
+    Wv = s2.sum() / (2 * W)
+    Bh = ((mean - mean.sum() / (2 * W)) ** 2).sum() / (2 * W - 1)
+    with np.errstate(all="ignore"):
+        return float(np.sqrt(((h - 1.0) / h * Wv + Bh) / Wv))
+
+
+def chain_diagnostics_twin(chain, lnprob=None, t0=0, c=5.0, nlags=0):
+    """The NumPy twin of chain_diagnostics: the same direct sums in the same blocks and passes (512 lags, then twice as many
+    until every series has its window).  nlags > 0 also returns the first nlags lags of every ACF."""
+    chain, lnprob, t0 = _chain_args(chain, lnprob, t0)
+    W, steps, ndim = chain.shape
+    n = steps - t0
+    series = [chain[:, t0:, d] for d in range(ndim)] + ([lnprob[:, t0:]] if lnprob is not None else [])
+    D = len(series)
+    tau, window, rhat = np.ones(D), np.zeros(D, dtype=np.int64), np.empty(D)
+    curves = []
+    for d, x in enumerate(series):
+        rhat[d] = split_rhat(x)
+        y = x - _twin_mean(x)[:, None]
+        Mmax = -(-n // DIAG_LAGS) * DIAG_LAGS
+        have, want = 0, DIAG_LAGS
+        if nlags > want:
+            want = min(-(-nlags // DIAG_LAGS) * DIAG_LAGS, Mmax)
+        a = np.zeros((W, 0))
+        acf = np.zeros(0)
+        while n >= 4:
+            a = np.concatenate([a, _twin_lag_sums(y, have, want)], axis=1)
+            have = want
+            acf = np.zeros(have)
+            for w in range(W):
+                if a[w, 0] > 0:
+                    acf += a[w] / a[w, 0]
+            acf /= W
+            res = chain_window(acf[:min(have, n)], c, n)
+            if res is not None:
+                tau[d], window[d] = res
+                break
+            want = min(2 * have, Mmax)
+        curves.append(acf)
+    out = None
+    if nlags > 0:
+        out = np.zeros((D, nlags))
+        for d, acf in enumerate(curves):
+            k = min(nlags, len(acf))
+            out[d, :k] = acf[:k]
+    return ChainDiagnostics(tau, window, W * n / tau, rhat, n, W, out)
+
+
+def _diag_outputs(D):
+    return np.empty(D), np.empty(D, dtype=np.int64), np.empty(D), np.empty(D)
+
+
+def chain_diagnostics(chain, lnprob=None, t0=0, c=5.0, device=None, nlags=0):
+    """tau (integrated_time's definition and window rule), its window, ess = W n / tau and split-R-hat (see split_rhat) per
+    parameter of `chain` (nwalkers, nsteps, ndim) over steps t0 .. nsteps - and of `lnprob` (nwalkers, nsteps) as one more
+    series - computed on the GPU by direct sums (lf_chain_diag).  device: the HIP device ordinal (None = 0); there is no host
+    fall-back here, the NumPy statement is chain_diagnostics_twin.  nlags > 0 also returns that many lags of every ACF."""
+    import ctypes
+    from . import capi
+    chain, lnprob, t0 = _chain_args(chain, lnprob, t0)
+    lib = capi.load()
+    W, steps, ndim = chain.shape
+    D = ndim + (lnprob is not None)
+    tau, window, ess, rhat = _diag_outputs(D)
+    acf = np.empty((D, int(nlags))) if nlags > 0 else None
+    rc = lib.lf_chain_diag(0 if device is None else int(device), capi._ptr(chain), capi._ptr(lnprob), W, steps, ndim, t0, steps, float(c),
+                           capi._ptr(tau), window.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), capi._ptr(ess), capi._ptr(rhat),
+                           capi._ptr(acf), int(nlags))
+    if rc != capi.LF_OK:
+        raise capi.LFError("lf_chain_diag failed (%d)" % rc)
+    return ChainDiagnostics(tau, window, ess, rhat, steps - t0, W, acf)
+
+
 class EnsembleSampler(object):
     def __init__(self, nwalkers, ndim, log_prob_fn, a=2.0, vectorize=True, seed=None):
         if nwalkers < 2 * ndim or nwalkers % 2:
@@ -250,12 +409,26 @@ class DeviceEnsembleSampler(object):
     def flatchain(self):
         return self.chain.reshape(-1, self.ndim)
 
-    def get_autocorr_time(self, c=5.0):
+    def get_autocorr_time(self, c=5.0, device=False):
+        """device=False: integrated_time on the chain read back by sync(); device=True: diagnostics(c=c).tau, the chain
+        stays in HBM."""
+        if device:
+            return self.diagnostics(c=c).tau
         return np.array([integrated_time(self.chain[:, :, d].T, c=c) for d in range(self.ndim)])
 
     @property
     def acor(self):
         return self.get_autocorr_time()
+
+    def diagnostics(self, t0=0, c=5.0, with_lnprob=False):
+        """ChainDiagnostics of the steps t0 .. now of the chain where it is (lf_sampler_diag): waits for the enqueued steps,
+        copies no chain and changes nothing of the sampler's state.  with_lnprob adds the lnprob series as the last entry."""
+        D = self.ndim + bool(with_lnprob)
+        tau, window, ess, rhat = _diag_outputs(D)
+        lib = self.ctx._lib
+        self.ctx._check(lib.lf_sampler_diag(self._h, int(t0), float(c), int(bool(with_lnprob)), self._p(tau),
+                                            window.ctypes.data_as(self._ct.POINTER(self._ct.c_int64)), self._p(ess), self._p(rhat)))
+        return ChainDiagnostics(tau, window, ess, rhat, int(lib.lf_sampler_steps(self._h)) - int(t0), self.nwalkers)
 
     def close(self):
         if getattr(self, "_h", None) is not None:
@@ -514,6 +687,22 @@ class DevicePTSampler(_PTSurface):
                                               self.nswap.ctypes.data_as(i64) if T > 1 else None, self._p(pos), self._p(ll)))
         self.iterations = s
         return pos, self.betas[:, None] * ll, ll
+
+    def get_autocorr_time(self, c=5.0, device=False):
+        """device=False: integrated_time per temperature on the chain read back; device=True: diagnostics() per temperature."""
+        if device:
+            return np.array([self.diagnostics(t, c=c).tau for t in range(self.ntemps)])
+        return _PTSurface.get_autocorr_time(self, c=c)
+
+    def diagnostics(self, temperature=0, t0=0, c=5.0, with_lnlike=False):
+        """ChainDiagnostics of one temperature's chain where it is (lf_ptsampler_diag); see DeviceEnsembleSampler.diagnostics.
+        with_lnlike adds the untempered lnlike series as the last entry."""
+        D = self.ndim + bool(with_lnlike)
+        tau, window, ess, rhat = _diag_outputs(D)
+        lib = self.ctx._lib
+        self.ctx._check(lib.lf_ptsampler_diag(self._h, int(temperature), int(t0), float(c), int(bool(with_lnlike)), self._p(tau),
+                                              window.ctypes.data_as(self._ct.POINTER(self._ct.c_int64)), self._p(ess), self._p(rhat)))
+        return ChainDiagnostics(tau, window, ess, rhat, int(lib.lf_ptsampler_steps(self._h)) - int(t0), self.nwalkers)
 
     def close(self):
         if getattr(self, "_h", None) is not None:
