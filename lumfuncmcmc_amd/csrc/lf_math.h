@@ -7,7 +7,6 @@
 //              degree-4 polynomial on |r| <= ln2/512, ldexp
 //   flog_half  table-driven: 256 x {1/c, log c} in LDS, degree-5 log1p on |r| < 2^-9
 //   frsqrt     v_rsq_f64 seed (2^-24 measured on gfx950) + one cubic step
-//   frcp       v_rcp_f64 seed (2^-24) + one cubic Newton step
 //   TermTables piecewise degree-7 polynomials of the two univariate factors of the free-completeness term,
 //              g(num) = ln fc and h(y) = 1 / (1 - e^(-10^y)) (lf_tables.h, gen_tables.py): the per-source fast path
 // The "careful" path (rare walkers that may underflow, see lf_kernels.h) uses the ROCm device
@@ -69,7 +68,9 @@ __device__ __forceinline__ double fexp_neg(double u, const MathTables* __restric
     return ldexp(fma(T, p, T), k >> 8);
 }
 
-// the same with the argument clamped to [-750, 709] (grid kernels: arguments are not pre-screened)
+// the same with the argument clamped to [-750, 709] (grid kernels: arguments are not pre-screened): +-inf give e^709 and
+// +0.  NOT "NaN in -> NaN out": fmax / fmin return their other operand for a NaN, so the clamp turns a NaN into -750 and
+// fexp_c(NaN) = +0 (tests/test_gpu_terms.py pins it); a NaN node contributes nothing instead of poisoning its sum.
 __device__ __forceinline__ double fexp_c(double x, const MathTables* __restrict__ mt) {
     return fexp_t(fmin(fmax(x, -750.0), 709.0), mt);
 }
@@ -109,19 +110,17 @@ __device__ __forceinline__ double flog_half_upper(double w, const MathTables* __
     return (t.y - LF_LN2) + fma(p, r2, r);
 }
 
-// 1/sqrt(s), s >= 1: v_rsq_f64 seed (2^-24, measured) + one cubic step (error ~ e^3)
+// 1/sqrt(s) for normal s: v_rsq_f64 seed (2^-24, measured) + one cubic step (error ~ e^3).  The callers pass 1 + num^2
+// >= 1 (ln_fc_fast, term_free_noexp, field_sum_bright) and s d^2 with d = 1 - e^(-u) < 1 (term_free_fast, field_sum): the
+// FAST screen of prepare_lane keeps u > 9e-4, so s d^2 > 8e-7 there, and bounds |num| < e^350, s < 1e305.  field_sum
+// (grid nodes, not screened) floors d at 1e-100: s d^2 >= 1e-200; its upper end is not derived from a screen - num =
+// alpha_C (logf - lF) with alpha_C inside the prior box (walkers outside it are skipped) and the grid's log-fluxes, so s
+// overflows only for |num| > 1e154, tens of orders beyond any box.  Probed over [1e-200, 1e305] (tests/lf_problib.py).
 __device__ __forceinline__ double frsqrt(double s) {
     const double z0 = __builtin_amdgcn_rsq(s);
     const double e = fma(-(s * z0), z0, 1.0);
     const double p = fma(0.375, e, 0.5);
     return fma(z0, p * e, z0);
-}
-
-// 1/d for normal d: v_rcp_f64 seed (2^-24) + one cubic Newton step
-__device__ __forceinline__ double frcp(double d) {
-    const double y0 = __builtin_amdgcn_rcp(d);
-    const double e = fma(-d, y0, 1.0);
-    return fma(y0, fma(e, e, e), y0);
 }
 
 // LDS image of G_TABLE / H_TABLE (lf_tables.h): 8 coefficients (64 B) per piece
