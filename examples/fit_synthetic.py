@@ -5,7 +5,7 @@
     catalogue file -> per-field lists -> LumFuncMCMC -> fit_model (device-resident sampler)
     -> set_median_fit (median LF + 1/Veff estimate) -> the reference's output tables.
 
-    python examples/fit_synthetic.py [--nsrc 20000] [--nwalkers 64] [--nsteps 300] [--fix-comp] [--until-converged]
+    python examples/fit_synthetic.py [--nsrc 20000] [--nwalkers 64] [--nsteps 300] [--fix-comp] [--until-converged] [--map]
 """
 import argparse
 import os
@@ -43,6 +43,10 @@ def main():
     ap.add_argument("--until-converged", action="store_true",
                     help="run until steps > 50 tau and tau has settled (fit_model_converged, at most 10 x nsteps steps; "
                          "DESIGN.md section 3.12) instead of exactly --nsteps steps")
+    ap.add_argument("--map", action="store_true",
+                    help="maximum a posteriori fit first (fit_model_map; DESIGN.md section 3.14): prints the best fit with "
+                         "sqrt(diag(cov)) next to the medians and the Laplace evidence; with --until-converged the walkers "
+                         "start in a Gaussian ball around the maximum")
     ap.add_argument("--out", default="LFMCMCOut")
     ap.add_argument("--compress", action="store_true", help="compressed catalogue and grid (DESIGN.md section 3.5)")
     args = ap.parse_args()
@@ -61,8 +65,10 @@ def main():
                         field_names=field_names, field_ind=field_ind, compress=args.compress)
     print("setup %.2f s for %d sources" % (time.time() - t0, len(LFmod.lum)))
     np.random.seed(3)
+    if args.map:
+        LFmod.fit_model_map(seed=7)
     if args.until_converged:
-        LFmod.fit_model_converged()
+        LFmod.fit_model_converged(start="map" if args.map else "box")
         print("converged: %s after %d steps; tau per parameter %s" % (LFmod.converged, LFmod.tau_history[-1][0],
                                                                      np.array2string(LFmod.tau_history[-1][1], precision=1)))
     else:
@@ -85,6 +91,12 @@ def main():
                                        labels, formats={l: ("%s" if l == "Line" else "%0.3f") for l in labels})
     med = np.median(LFmod.samples[:, :-1], axis=0)
     print("posterior medians:", dict(zip(names[:-1], np.round(med, 3))))
+    if args.map:
+        sd = np.sqrt(np.diag(LFmod.map_cov))
+        print("MAP (converged: %s; on a bound: %s):" % (LFmod.map_info["converged"], [n for n, b in zip(names, LFmod.map_info["on_bound"]) if b]))
+        for n, t, e, m in zip(names[:-1], LFmod.map_theta, sd, med):
+            print("  %-22s %9.4f +/- %.4f   (median %9.4f)" % (n, t, e, m))
+        print("lnprob at the maximum %.4f; lnZ_laplace %.4f %s" % (LFmod.map_lnprob, LFmod.lnZ_laplace, LFmod.map_info["lnZ_reason"]))
     print("wrote", sorted(os.listdir(args.out)))
     LFmod.close()
 

@@ -135,6 +135,19 @@ int lf_lnprob_batch_device_n(lf_ctx *ctx, const double *d_theta, int B, int K, d
  * get NaN in both.  Synchronous. */
 int lf_lnprob_pieces(lf_ctx *ctx, const double *theta, int B, double *outA, double *outB);
 
+/* The gradient of lnprob = A - B (the two pieces above) with respect to the row's own theta elements, in theta's own units
+ * (csrc/lf_grad.h): grad[B][ndim] row-major.  lnprob: [B] or NULL; where given it is what
+ * lf_lnprob_batch returns for the same rows, bit for bit (the same path runs first).  A row whose lnprob is -INFINITY (outside
+ * the prior, or underflow) gets NaN in every element of its gradient; every other row finite values.  A row's gradient has the
+ * same bits whatever B is and wherever the row stands in the batch.  The option "compress" is ignored (the gradient always
+ * comes from the real catalogue); a context with "skip_grid" or "grid_share" set gets LF_ERR_ARG (source-sharded gradients are
+ * not provided).  Host pointers, synchronous. */
+int lf_lnprob_grad_batch(lf_ctx *ctx, const double *theta, int B, double *lnprob, double *grad);
+
+/* Same, with device pointers and the launches enqueued on `hip_stream` (NULL = the default stream), asynchronous like
+ * lf_lnprob_batch_device.  d_lnprob may be NULL. */
+int lf_lnprob_grad_batch_device(lf_ctx *ctx, const double *d_theta, int B, double *d_lnprob, double *d_grad, void *hip_stream);
+
 /* Kernel timing for bench.py: level 1 brackets lf_main, level 2 every launch, with hipEvents on
  * the stream the launch runs on (0 = off; each event pair costs a few microseconds of stream time: the events are
  * barrier packets, and the next launch no longer overlaps the previous one's tail - measured 7.6 us per evaluation

@@ -50,7 +50,8 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_lumfunc_quantiles", "lf_lumfunc_quantiles_ms", "lf_ptsampler_create", "lf_ptsampler_destroy",
            "lf_ptsampler_start", "lf_ptsampler_run", "lf_ptsampler_read", "lf_ptsampler_steps", "lf_mock_create",
            "lf_mock_destroy", "lf_mock_counts", "lf_mock_draw", "lf_mock_hist", "lf_mock_last_error", "lf_chain_diag",
-           "lf_sampler_diag", "lf_ptsampler_diag", "lf_chain_window", "lf_diag_last")
+           "lf_sampler_diag", "lf_ptsampler_diag", "lf_chain_window", "lf_diag_last", "lf_lnprob_grad_batch",
+           "lf_lnprob_grad_batch_device")
 
 _lib = None
 
@@ -98,6 +99,11 @@ def load():
     lib.lf_lnprob_batch_device_n.restype = ctypes.c_int
     lib.lf_lnprob_batch_device_n.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_void_p, ctypes.c_void_p]
+    lib.lf_lnprob_grad_batch.restype = ctypes.c_int
+    lib.lf_lnprob_grad_batch.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p]
+    lib.lf_lnprob_grad_batch_device.restype = ctypes.c_int
+    lib.lf_lnprob_grad_batch_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p]
     lib.lf_lnprob_pieces.restype = ctypes.c_int
     lib.lf_lnprob_pieces.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p]
     lib.lf_set_profiling.restype = ctypes.c_int
@@ -472,6 +478,35 @@ class LFContext(object):
             return a, b
         self._check(self._lib.lf_lnprob_pieces(self._h, _ptr(th), th.shape[0], _ptr(a), _ptr(b)))
         return a, b
+
+    def lnprob_grad(self, theta):
+        """theta (B, ndim) or (ndim,) host array -> (lnprob (B,), grad (B, ndim)): lf_lnprob_grad_batch.  lnprob is
+        lnprob_batch's, bit for bit; rows whose lnprob is -inf have NaN gradients."""
+        th = self._theta(theta)
+        lp = np.empty(th.shape[0], dtype=np.float64)
+        g = np.empty((th.shape[0], self.ndim), dtype=np.float64)
+        if th.shape[0]:
+            self._check(self._lib.lf_lnprob_grad_batch(self._h, _ptr(th), th.shape[0], _ptr(lp), _ptr(g)))
+        return lp, g
+
+    def lnprob_grad_torch(self, theta):
+        """theta: float64 device tensor (B, ndim) on this context's device; enqueues lf_lnprob_grad_batch_device on torch's
+        current stream and returns (lnprob (B,), grad (B, ndim)) device tensors."""
+        import torch
+        if theta.dtype != torch.float64 or not theta.is_cuda or theta.dim() != 2 or theta.shape[1] != self.ndim:
+            raise ValueError("theta must be a float64 device tensor of shape (B, %d)" % self.ndim)
+        if theta.device.index != self.device:
+            raise ValueError("theta is on device %s, context is on %d" % (theta.device, self.device))
+        theta = theta.contiguous()
+        B = theta.shape[0]
+        lp = torch.empty(B, dtype=torch.float64, device=theta.device)
+        g = torch.empty((B, self.ndim), dtype=torch.float64, device=theta.device)
+        if B:
+            stream = torch.cuda.current_stream(theta.device).cuda_stream
+            self._check(self._lib.lf_lnprob_grad_batch_device(self._h, ctypes.c_void_p(theta.data_ptr()), int(B),
+                                                              ctypes.c_void_p(lp.data_ptr()), ctypes.c_void_p(g.data_ptr()),
+                                                              ctypes.c_void_p(stream)))
+        return lp, g
 
     def lnprob_batch_device(self, theta_ptr, B, out_ptr, stream=0):
         """Raw device pointers (ints) and a hipStream_t handle (int, 0 = default stream)."""

@@ -633,6 +633,30 @@ inline Compressed compress(const KConst& kc, const std::vector<int64_t>& field_i
     return cc;
 }
 
+// ---- the gradient kernels' constants (lf_grad.h).  z: the sources' redshifts (ZEVOL; any order), else NULL.
+// sl[m] = sum_i l_m(z_i) with l_m the Lagrange basis on the pivots: d A / d phi_m = ln10 sl[m] does not depend on theta.
+inline GradConst grad_const(const KConst& kc, int64_t N, const double* z) {
+    GradConst g{};
+    g.variant = kc.variant, g.fix_sch_al = kc.fix_sch_al, g.nf = kc.nf, g.ndim = kc.ndim;
+    g.sch_al0 = kc.sch_al0;
+    g.kappa = std::sqrt(kc.fc_ratio);
+    for (int f = 0; f < MAXF; ++f) g.om0_grid[f] = kc.om0_grid[f];
+    for (int m = 0; m < 3; ++m) g.pivots[m] = kc.pivots[m];
+    g.nsrc = (double)N;
+    if (kc.variant == LF_ZEVOL && z) {
+        const long double z1 = kc.pivots[0], z2 = kc.pivots[1], z3 = kc.pivots[2];
+        long double s[3] = {0.0L, 0.0L, 0.0L};
+        for (int64_t i = 0; i < N; ++i) {
+            const long double a = z[i] - z1, b = z[i] - z2, c = z[i] - z3;
+            s[0] += b * c / ((z1 - z2) * (z1 - z3));
+            s[1] += a * c / ((z2 - z1) * (z2 - z3));
+            s[2] += a * b / ((z3 - z1) * (z3 - z2));
+        }
+        for (int m = 0; m < 3; ++m) g.sl[m] = (double)s[m];
+    }
+    return g;
+}
+
 // ---- lf_free's static deal (lf_layout.h: DEAL_*): flux bins, then cell chunks, each to the virtual workgroup that would be done
 // first - a bin costs a wave cost_b = 8 units, a cell chunk 3 (tools/stamps_fused.py), and the ranks of the younger half are
 // counted cost_h = 8 units behind (swept on one box, tools/deal_sweep.sh: 13.4 us per 128-row evaluation at 8-10, 13.75 at 0-6,

@@ -81,4 +81,18 @@ constexpr int VF = 32;
 // partial sums (one per virtual rank) are the same whatever the batch.
 constexpr int DEAL_BINS = VF + 1, DEAL_LIST = 2 * (VF + 1), DEAL_MAX = 512;
 
+// The gradient kernels (lf_grad.h): sources / nodes per block, doubles per block in its partial sums (7 used at most), and the
+// constants of a context they read (lf_hostprep.h: grad_const).
+constexpr int GRAD_CH = 1024;
+constexpr int GRAD_SLOTS = 8;
+struct GradConst {
+    int variant, fix_sch_al, nf, ndim;
+    double sch_al0;
+    double kappa;                // sqrt(KConst::fc_ratio): f_tau = F 10^(-kappa / alpha_C)
+    double om0_grid[MAXF];
+    double pivots[3];
+    double sl[3];                // ZEVOL: sum_i l_m(z_i), l_m the Lagrange basis on the pivots (else 0)
+    double nsrc;                 // N
+};
+
 }  // namespace lf

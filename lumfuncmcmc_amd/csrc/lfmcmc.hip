@@ -20,6 +20,7 @@
 #include "lf_compress.h"
 #include "lf_devmem.h"
 #include "lf_diag.h"
+#include "lf_grad.h"
 #include "lf_gridbound.h"
 #include "lf_hostprep.h"
 #include "lf_kernels.h"
@@ -142,6 +143,13 @@ struct lf_ctx {
     Buf<int> d_wstat, d_wmode;
     Buf<double> d_wbase;
     Buf<double, true> h_theta, h_out;   // pinned staging
+    // the gradient (lf_grad.h): its constants, its chunks of the catalogue (made at first use), the blocks' partial sums
+    // [rows][blocks][GRAD_SLOTS], and the host form's results {lnprob [B], grad [B][ndim]} with their pinned staging
+    lf::GradConst gradc{};
+    ChunkTable grad_chunks;
+    bool grad_chunks_built = false;
+    Buf<double> d_gpart, d_gout;
+    Buf<double, true> h_gout;
     hipStream_t stream = nullptr;
     hipStream_t last_stream = nullptr;   // stream of the previous enqueue (workspace is shared)
     bool any_enqueued = false;
@@ -822,6 +830,67 @@ int enqueue(lf_ctx* c, const double* d_theta, int B, double* d_out, double* d_ou
     return LF_OK;
 }
 
+// The gradient of lnprob for B rows (lf_grad.h): the lnprob path itself first (d_lnp: what lf_lnprob_batch_device gives, and what
+// decides which rows get NaN), then the blocks' partial sums and the rows' second stage, all on `s`.
+template <int VARIANT>
+void launch_grad(const lf::GradArgs& ga, int nblk, int B, hipStream_t s) {
+    using namespace lf;
+    // (a grid's second dimension holds 65 535 rows)
+    for (int b0 = 0; b0 < B; b0 += 32768) {
+        const int nb = std::min(32768, B - b0);
+        GradArgs g = ga;
+        g.theta += (size_t)b0 * g.gc.ndim;
+        g.lnprob += b0;
+        g.part += (size_t)b0 * nblk * GRAD_SLOTS;
+        g.grad += (size_t)b0 * g.gc.ndim;
+        if (nblk > 0) hipLaunchKernelGGL(lf_grad_part<VARIANT>, dim3((unsigned)nblk, (unsigned)nb), dim3(BLOCK), 0, s, g);
+        hipLaunchKernelGGL(lf_grad_final<VARIANT>, dim3((unsigned)nb), dim3(64), 0, s, g);
+    }
+}
+
+int enqueue_grad(lf_ctx* c, const double* d_theta, int B, double* d_lnp, double* d_grad, hipStream_t s) {
+    using namespace lf;
+    int rc;
+    if (!c->grad_chunks_built) {
+        const lfh::Chunks h = lfh::chunk_table(c->field_ind, c->kc.nf, GRAD_CH, 0.0, 0.0, 0.0);
+        ChunkTable& t = c->grad_chunks;
+        t.n = (int)h.start.size();
+        if ((rc = upload(c, t.d_start, h.start, t.d_len, h.len, t.d_field, h.field)) != LF_OK) return rc;
+        c->grad_chunks_built = true;
+    }
+    const int nchA = c->grad_chunks.n;
+    const int nchB = (c->nnodes + GRAD_CH - 1) / GRAD_CH;
+    const int nfB = c->kc.variant == LF_FREE ? c->kc.nf : 1;
+    const int nblk = nchA + nchB * nfB;
+    const size_t need = (size_t)B * std::max(nblk, 1) * GRAD_SLOTS;
+    if (need > c->d_gpart.size() && (rc = grow(c, c->d_gpart, need)) != LF_OK) return rc;
+    if ((rc = enqueue(c, d_theta, B, d_lnp, nullptr, nullptr, s)) != LF_OK) return rc;
+    const GradArgs ga{c->gradc, d_theta, d_lnp, c->d_gpart, d_grad, c->d_lum, c->d_a1, c->d_P, c->d_U,
+                      c->grad_chunks.d_start, c->grad_chunks.d_len, c->grad_chunks.d_field,
+                      c->d_G, c->d_PG, c->d_W, c->d_a3, c->d_a4, c->nnodes, nchA, nchB, nfB};
+    switch (c->kc.variant) {
+        case LF_FREE: launch_grad<LF_FREE>(ga, nblk, B, s); break;
+        case LF_FIXCOMP: launch_grad<LF_FIXCOMP>(ga, nblk, B, s); break;
+        default: launch_grad<LF_ZEVOL>(ga, nblk, B, s);
+    }
+    LF_HIP(c, hipGetLastError());
+    return LF_OK;
+}
+
+// what both gradient entry points refuse before the device is touched
+int grad_check(lf_ctx* c, const char* fn, const void* theta, int B, const void* grad) {
+    if (!c) return LF_ERR_ARG;
+    if (!theta || !grad || B <= 0) {
+        c->err = std::string(fn) + ": NULL pointer or B <= 0";
+        return LF_ERR_ARG;
+    }
+    if (c->opt_skip_grid || c->kc.grid_parts > 1) {
+        c->err = std::string(fn) + ": no gradient of a source-sharded context (options skip_grid, grid_share)";
+        return LF_ERR_ARG;
+    }
+    return LF_OK;
+}
+
 // Build the compressed catalogue and grid (lf_hostprep.h: compress) from the host's copy of the keys and the device's of lum.
 int build_compressed(lf_ctx* c) {
     if (c->cmp.built) return LF_OK;
@@ -947,6 +1016,7 @@ int build(lf_ctx* c, const lf_desc* d) {
     c->N = d->N;
     c->field_ind.assign(d->field_ind, d->field_ind + nf + 1);
     lfh::Catalogue cat = lfh::catalogue(d, kc);
+    c->gradc = lfh::grad_const(kc, d->N, d->variant == LF_ZEVOL ? cat.a1.data() : nullptr);
     int rc;
     kc.cells = 0;
     kc.zcell_rho = 0.0;
@@ -1161,6 +1231,39 @@ int lf_lnprob_pieces(lf_ctx* c, const double* theta, int B, double* outA, double
         return LF_ERR_ARG;
     }
     return host_eval(c, theta, B, nullptr, outA, outB);
+}
+
+int lf_lnprob_grad_batch_device(lf_ctx* c, const double* d_theta, int B, double* d_lnprob, double* d_grad, void* hip_stream) {
+    int rc = grad_check(c, "lf_lnprob_grad_batch_device", d_theta, B, d_grad);
+    if (rc != LF_OK) return rc;
+    LF_HIP(c, hipSetDevice(c->device));
+    if (!d_lnprob) {
+        // (the rows' lnprob decides their NaN: into the context's own buffer, sized before the lnprob path may replace it)
+        if ((rc = ensure_workspace(c, B, 0, 0)) != LF_OK) return rc;
+        d_lnprob = c->d_out;
+    }
+    return enqueue_grad(c, d_theta, B, d_lnprob, d_grad, (hipStream_t)hip_stream);
+}
+
+int lf_lnprob_grad_batch(lf_ctx* c, const double* theta, int B, double* lnprob, double* grad) {
+    int rc = grad_check(c, "lf_lnprob_grad_batch", theta, B, grad);
+    if (rc != LF_OK) return rc;
+    LF_HIP(c, hipSetDevice(c->device));
+    if ((rc = ensure_workspace(c, B, 0, 0)) != LF_OK) return rc;
+    const size_t nd = (size_t)c->kc.ndim, no = (size_t)B * (nd + 1);
+    if (no > c->d_gout.size()) {
+        if ((rc = grow(c, c->d_gout, no)) != LF_OK) return rc;
+        LF_HIP(c, c->h_gout.alloc(no));
+    }
+    const size_t tb = (size_t)B * nd * sizeof(double);
+    std::memcpy(c->h_theta, theta, tb);
+    LF_HIP(c, hipMemcpyAsync(c->d_theta, c->h_theta, tb, hipMemcpyHostToDevice, c->stream));
+    if ((rc = enqueue_grad(c, c->d_theta, B, c->d_gout, c->d_gout + B, c->stream)) != LF_OK) return rc;
+    LF_HIP(c, hipMemcpyAsync(c->h_gout, c->d_gout, no * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    LF_HIP(c, hipStreamSynchronize(c->stream));
+    if (lnprob) std::memcpy(lnprob, c->h_gout, (size_t)B * sizeof(double));
+    std::memcpy(grad, c->h_gout + B, tb);
+    return LF_OK;
 }
 
 int lf_set_profiling(lf_ctx* c, int enabled) {

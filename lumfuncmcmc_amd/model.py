@@ -281,7 +281,7 @@ class _Base(object):
         self.log.info("Median lnprob: %.5f; Max lnprob: %.5f" % (np.median(sampler.lnprobability),
                                                                 np.amax(sampler.lnprobability)))
 
-    def fit_model_converged(self, max_steps=None, check_every=None, ntau=50, rtol=0.01):
+    def fit_model_converged(self, max_steps=None, check_every=None, ntau=50, rtol=0.01, start="box"):
         """fit_model that runs until the chain is long enough instead of for a number of steps guessed beforehand: one
         device sampler with room for max_steps (default 10 * self.nsteps) runs check_every steps at a time (default
         max(100, self.nsteps // 10)) and asks the chain where it is for its autocorrelation times
@@ -290,7 +290,10 @@ class _Base(object):
         - emcee's documented recipe, with its numbers 50 and 0.01 - or at max_steps with a warning.  The chain is read back
         once, at the end.  Sets what fit_model sets (samples, chain, sampler, start_pos, sampler_seed; burn-in =
         min(int(3 max tau), steps // 2) with the device's tau) plus self.converged and self.tau_history = [(steps, tau), ...];
-        returns the last tau.  One GPU, device sampler only."""
+        returns the last tau.  One GPU, device sampler only.  start="map": the walkers start in a Gaussian ball around the
+        maximum a posteriori (map_init_walkers; fit_model_map runs first when it has not) instead of the prior box."""
+        if start not in ("box", "map"):
+            raise ValueError('start must be "box" or "map"')
         rank, world = self._dist_state()
         if world > 1:
             raise NotImplementedError("fit_model_converged runs on one GPU: diagnostics across several ranks are not implemented")
@@ -301,7 +304,9 @@ class _Base(object):
         if max_steps < 1 or check_every < 1:
             raise ValueError("max_steps and check_every must be positive")
         self.log.info('Fitting Schechter model to true luminosity function until the chain has converged')
-        pos = self.get_init_walker_values()
+        if start == "map" and getattr(self, "map_theta", None) is None:
+            self.fit_model_map()
+        pos = self.get_init_walker_values() if start == "box" else self.map_init_walkers()
         ndim = pos.shape[1]
         start = time.time()
         seed = int(np.random.randint(0, 2 ** 31 - 1))
@@ -341,6 +346,86 @@ class _Base(object):
         self.log.info("Median lnprob: %.5f; Max lnprob: %.5f" % (np.median(sampler.lnprobability),
                                                                 np.amax(sampler.lnprobability)))
         return tau
+
+    # ------------------------------------------------------------------ maximum a posteriori (mapfit.py)
+    def _grad_fn(self):
+        """The batched (lnprob, gradient) callable of the current configuration: the device's (LFContext.lnprob_grad)."""
+        rank, world = self._dist_state()
+        if world > 1:
+            raise NotImplementedError("the gradient runs on one GPU: source- or walker-sharded gradients are not implemented")
+        if self.lnprob_fn is not None:
+            raise NotImplementedError("the gradient comes from the device context: it cannot use lnprob_fn")
+        return self.context().lnprob_grad
+
+    def fit_model_map(self, nstarts=16, seed=None, tol=1e-6):
+        """Maximum a posteriori fit: box-constrained Newton iterations from nstarts draws of get_init_walker_values' box
+        (seed: a RandomState of its own instead of numpy's global one; a start with -inf lnprob is drawn again), every
+        iteration one batched gradient call on the device (mapfit.maximise).  For fixed completeness the context is
+        lnprob_fix_comp's, as in fit_model.  Sets map_theta, map_lnprob, map_hessian, map_cov = (-H)^-1 (over the
+        coordinates not held at a bound: rows and columns of a held coordinate are 0) and lnZ_laplace (NaN when a
+        coordinate is on its bound or -H is not positive definite: map_info["lnZ_reason"] says which); returns them in a
+        dict with converged, on_bound, niter and decrement."""
+        from . import mapfit
+        f = self._grad_fn()
+        box = self._theta_lims()
+        rs = np.random.RandomState(seed) if seed is not None else np.random
+        draw = lambda n: rs.rand(n, len(box)) * (box[:, 1] - box[:, 0]) + box[:, 0]    # noqa: E731
+        starts = draw(int(nstarts))
+        for _ in range(100):
+            bad = ~np.isfinite(f(starts)[0])
+            if not bad.any():
+                break
+            starts[bad] = draw(int(bad.sum()))
+        # (the z-evolving prior excludes the bounds of L and phi - lnprob is -inf on them: work a hair inside)
+        r = mapfit.maximise(f, box, starts, tol=tol, inset=1.0e-9 if self._variant() == "zevol" else 0.0)
+        H = r["hessian"]
+        free = ~r["on_bound"]
+        cov = np.zeros_like(H)
+        try:
+            cov[np.ix_(free, free)] = np.linalg.inv(-H[np.ix_(free, free)])
+        except np.linalg.LinAlgError:
+            cov[:] = np.nan
+        lnZ, why = mapfit.laplace_evidence(r["lnprob"], H, box, on_bound=r["on_bound"])
+        self.map_theta, self.map_lnprob, self.map_hessian, self.map_cov, self.lnZ_laplace = r["theta"], r["lnprob"], H, cov, lnZ
+        self.map_info = {"theta": r["theta"], "lnprob": r["lnprob"], "hessian": H, "cov": cov, "lnZ_laplace": lnZ,
+                         "lnZ_reason": why, "converged": r["converged"], "on_bound": r["on_bound"], "niter": r["niter"],
+                         "decrement": r["decrement"], "box": r["box"]}
+        self.log.info("MAP fit: lnprob %.5f after %d iterations (%sconverged), Laplace lnZ %.3f %s"
+                      % (r["lnprob"], r["niter"], "" if r["converged"] else "NOT ", lnZ, why))
+        return self.map_info
+
+    def map_init_walkers(self, num=None, scale=1.0):
+        """Start positions drawn from N(map_theta, scale^2 map_cov) (numpy's global state, like get_init_walker_values)
+        instead of the prior box; a row outside the box or with a lnprob that is not finite is drawn again, so every walker
+        starts with a finite lnprob.  A coordinate held at a bound has no variance in map_cov: it is scattered into the box
+        by |N(0, (1e-3 width)^2)| so that the ensemble is not degenerate there."""
+        if getattr(self, "map_theta", None) is None:
+            raise RuntimeError("map_init_walkers: call fit_model_map first")
+        if not np.all(np.isfinite(self.map_cov)):
+            raise RuntimeError("map_init_walkers: map_cov is not finite")
+        num = self.nwalkers if num is None else int(num)
+        box = self._theta_lims()
+        f = self._grad_fn()
+        held = self.map_info["on_bound"]
+        cov = 0.5 * (self.map_cov + self.map_cov.T) * scale ** 2
+
+        def draw(n):
+            x = np.random.multivariate_normal(self.map_theta, cov, size=n, check_valid="ignore")
+            if held.any():
+                into = np.where(self.map_theta[held] < 0.5 * (box[held, 0] + box[held, 1]), 1.0, -1.0)
+                x[:, held] += into * np.abs(np.random.randn(n, int(held.sum()))) * 1.0e-3 * (box[held, 1] - box[held, 0])
+            return x
+
+        pos = draw(num)
+        for _ in range(200):
+            bad = np.any((pos < box[:, 0]) | (pos > box[:, 1]), axis=1)
+            ok = ~bad
+            if ok.any():
+                bad[ok] = ~np.isfinite(f(pos[ok])[0])
+            if not bad.any():
+                return pos
+            pos[bad] = draw(int(bad.sum()))
+        raise RuntimeError("map_init_walkers: could not draw %d walkers with finite lnprob around the maximum" % num)
 
     def fit_model_pt(self, ntemps=None, Tmax=None, betas=None, fburnin=0.1):
         """Parallel-tempered fit (DevicePTSampler, sampler.py) and the Bayesian evidence of this model by thermodynamic
