@@ -273,10 +273,12 @@ class EnsembleSampler(object):
 
 class DeviceEnsembleSampler(object):
     """The same read-back surface, with the whole stretch move on the GPU (lf_sampler_* of
-    include/lfmcmc.h): positions, lnprob and the chain stay in HBM, a step is six kernel launches
-    and no host round trip.  Parallel stretch move with two fixed half-ensembles (emcee 2.x form);
+    include/lfmcmc.h): positions, lnprob and the chain stay in HBM, a step is two kernel launches
+    - one per half-ensemble (lf_free_step / lf_pers_step: proposal, likelihood and accept step; what
+    ctx.last_launch() reports as fused; six with the option "fuse_step" 0 or where lf_main serves)
+    - and no host round trip.  Parallel stretch move with two fixed half-ensembles (emcee 2.x form);
     Philox4x32-10 random numbers keyed by `seed`, so (seed, start) determines the chain
-    (tests/test_gpu_sampler.py replays it on the host)."""
+    (tests/test_gpu_sampler.py and tests/test_gpu_sampler_shapes.py replay it on the host)."""
 
     def __init__(self, ctx, nwalkers, a=2.0, seed=0, capacity=1000):
         import ctypes

@@ -1,8 +1,12 @@
 """The parallel-tempered device sampler (lf_ptsampler_*): T = 1 is the ensemble sampler bit for bit, T > 1 replays bit for
-bit on the host PTSampler over the same likelihood, and fit_model_pt's evidence agrees with brute-force quadrature."""
+bit on the host PTSampler over the same likelihood - also at the edges of lf_pt_swap's sort (pads, several passes, strided
+loops, all of LDS, a half of one walker) - and fit_model_pt's evidence agrees with brute-force quadrature."""
+import math
+
 import numpy as np
 import pytest
 
+from lf_replaylib import fixcomp_model as _fixcomp_model, grid_lnint as _grid_lnint
 from lf_testlib import make_inputs, synth
 
 pytestmark = pytest.mark.gpu
@@ -28,6 +32,21 @@ def test_one_temperature_is_the_ensemble_sampler(variant, n, W):
     pt.close(); ds.close(); ctx.close()
 
 
+def _assert_mean_lnlike(dev, host):
+    """mean_lnlike against math.fsum(l) / W per temperature and step, l the W values of the (bit-equal) lnlikelihood.  The
+    device adds the W numbers in an order of its own (64 lanes, then a butterfly); any recursive sum of W numbers is within
+    (W - 1) 2^-53 sum|l_i| of the exact one (Higham, Accuracy and Stability of Numerical Algorithms, 4.2, first order), hence
+    the mean within that over W."""
+    T, W, S = host.lnlikelihood.shape
+    assert dev.mean_lnlike.shape == (T, S)
+    for t in range(T):
+        for s in range(S):
+            l = host.lnlikelihood[t, :, s]
+            ref = math.fsum(l) / W
+            bound = (W - 1) * 2.0 ** -53 * math.fsum(np.abs(l)) / W
+            assert abs(dev.mean_lnlike[t, s] - ref) <= bound, (t, s, dev.mean_lnlike[t, s], ref, bound)
+
+
 @pytest.mark.parametrize("variant,n", [("free", 20000), ("fixcomp", 2000)])
 def test_device_chain_replays_on_the_host(variant, n):
     from lumfuncmcmc_amd.capi import LFContext
@@ -45,7 +64,7 @@ def test_device_chain_replays_on_the_host(variant, n):
     np.testing.assert_array_equal(dev.lnlikelihood, host.lnlikelihood)
     np.testing.assert_array_equal(dev.naccepted, host.naccepted)
     np.testing.assert_array_equal(dev.nswap, host.nswap)
-    np.testing.assert_allclose(dev.mean_lnlike, host.mean_lnlike, rtol=1e-12, atol=0)
+    _assert_mean_lnlike(dev, host)
     assert dev.nswap.sum() > 0 and dev.tswap_acceptance_fraction.shape == (T - 1,)
     with pytest.raises(Exception):
         dev.run_mcmc(None, 1)                              # capacity exceeded is an error
@@ -56,26 +75,40 @@ def test_device_chain_replays_on_the_host(variant, n):
     dev.close(); ctx.close()
 
 
-def _fixcomp_model(n, seed):
-    from lumfuncmcmc_amd.model import LumFuncMCMC
-    cat = synth.catalogue(n, seed=seed)
-    fi = cat["field_ind"]
-    return LumFuncMCMC(synth.split_fields(cat["z"], fi), lum=synth.split_fields(cat["lum"], fi),
-                       lum_e=synth.split_fields(cat["lum_e"], fi), Flim=list(synth.FLIM), alpha=synth.ALPHA_C,
-                       Omega_0=list(synth.OMEGA_0), sch_al=synth.SCH_AL, sch_al_lims=synth.SCH_AL_LIMS, Lstar=synth.LSTAR,
-                       Lstar_lims=synth.LSTAR_LIMS, phistar=synth.PHISTAR, phistar_lims=synth.PHISTAR_LIMS, Lc=synth.LC,
-                       Lh=synth.LH, nwalkers=32, nsteps=1000, min_comp_frac=0.0, field_ind=fi, fix_comp=True,
-                       fix_sch_al=True)
+# (T, W): Wp = the power of two >= W, 4096 / Wp runs of keys are sorted per pass, the kernel has 1024 threads
+SWAP_EDGES = [
+    (3, 20),        # pads: Wp = 32
+    (64, 70),       # Wp = 128: 32 runs per pass, 63 pairs in two passes, the second partial
+    (5, 1024),      # W = the thread count; 4 pairs fill exactly one pass
+    (3, 2050),      # Wp = 4096: one run per pass, two passes, nearly half the slots are pads, strided loops
+    (2, 4096),      # the maximum: all of LDS, no pads
+    (2, 2),         # a half of one walker
+]
 
 
-def _grid_lnint(ctx, lo, hi, n):
-    """ln of the midpoint rule for the integral of exp(lnprob) over [lo, hi] (2-d), n x n cells."""
-    x = lo[0] + (np.arange(n) + 0.5) * (hi[0] - lo[0]) / n
-    y = lo[1] + (np.arange(n) + 0.5) * (hi[1] - lo[1]) / n
-    th = np.column_stack([np.repeat(x, n), np.tile(y, n)])
-    lp = np.concatenate([ctx.lnprob_batch(th[i:i + 32768]) for i in range(0, len(th), 32768)])
-    mx = lp[np.isfinite(lp)].max()
-    return mx + np.log(np.sum(np.exp(lp - mx))) + np.log((hi[0] - lo[0]) * (hi[1] - lo[1]) / n / n), lp.reshape(n, n), x, y
+@pytest.mark.parametrize("T,W", SWAP_EDGES)
+def test_swap_replays_at_the_sort_edges(T, W):
+    """lf_pt_swap against sampler.PTSampler (NumPy's stable argsort) over ctx.lnprob_batch: fixed completeness and fixed
+    faint-end slope (ndim = 2), 2000 sources, 6 steps, a ladder close enough that every neighbouring pair swaps."""
+    from lumfuncmcmc_amd.capi import LFContext
+    from lumfuncmcmc_amd.sampler import DevicePTSampler, PTSampler, geometric_betas
+    ctx = LFContext(make_inputs("fixcomp", 2000, seed=65, fix_sch_al=True))
+    assert ctx.ndim == 2
+    nsteps, seed = 6, 0xC0FFEE1234567
+    betas = geometric_betas(64, 1e3) if T == 64 else geometric_betas(T, 4)
+    pos = synth.walkers("fixcomp", T * W, seed=66, fix_sch_al=True).reshape(T, W, 2)
+    dev = DevicePTSampler(ctx, T, W, betas=betas, seed=seed, capacity=nsteps)
+    dev.run_mcmc(pos, nsteps)
+    host = PTSampler(T, W, 2, ctx.lnprob_batch, betas=betas, seed=seed)
+    host.run_mcmc(pos, nsteps)
+    print("T %d W %d nswap %s" % (T, W, dev.nswap.tolist()))
+    np.testing.assert_array_equal(dev.nswap, host.nswap)
+    np.testing.assert_array_equal(dev.naccepted, host.naccepted)
+    np.testing.assert_array_equal(dev.lnlikelihood, host.lnlikelihood)
+    np.testing.assert_array_equal(dev.chain, host.chain)
+    assert dev.nswap.shape == (T - 1,) and np.all(dev.nswap > 0)
+    _assert_mean_lnlike(dev, host)
+    dev.close(); ctx.close()
 
 
 def test_evidence_agrees_with_quadrature():

@@ -3,69 +3,10 @@ Philox4x32-10 random numbers: identical accept/reject decisions, hence identical
 import numpy as np
 import pytest
 
+from lf_replaylib import host_replay
 from lf_testlib import make_inputs, synth
 
 pytestmark = pytest.mark.gpu
-
-M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
-MASK = 0xFFFFFFFF
-
-
-def philox4x32(c0, c1, c2, c3, k0, k1):
-    """Vectorised Philox4x32-10 (numpy uint64 arithmetic)."""
-    c0, c1, c2, c3 = (np.asarray(x, dtype=np.uint64) & MASK for x in (c0, c1, c2, c3))
-    k0, k1 = np.uint64(k0 & MASK), np.uint64(k1 & MASK)
-    for _ in range(10):
-        p0 = np.uint64(M0) * c0
-        p1 = np.uint64(M1) * c2
-        n0 = ((p1 >> np.uint64(32)) ^ c1 ^ k0) & MASK
-        n1 = p1 & MASK
-        n2 = ((p0 >> np.uint64(32)) ^ c3 ^ k1) & MASK
-        n3 = p0 & MASK
-        c0, c1, c2, c3 = n0, n1, n2, n3
-        k0 = (k0 + np.uint64(W0)) & MASK
-        k1 = (k1 + np.uint64(W1)) & MASK
-    return c0, c1, c2, c3
-
-
-def draw(step, half, w, stream, seed):
-    w = np.asarray(w, dtype=np.uint64)
-    c0 = np.full_like(w, step & MASK)
-    c1 = np.full_like(w, ((step >> 32) & MASK) ^ ((half << 31) & MASK))
-    return philox4x32(c0, c1, w, np.full_like(w, stream), seed & MASK, (seed >> 32) & MASK)
-
-
-def u53(hi, lo):
-    return (((hi << np.uint64(32)) | lo) >> np.uint64(11)).astype(np.float64) * 1.1102230246251565e-16
-
-
-def host_replay(ctx, pos, nsteps, seed, a=2.0):
-    W, nd = pos.shape
-    half = W // 2
-    p = pos.copy()
-    lp = ctx.lnprob_batch(p)
-    chain = np.empty((W, nsteps, nd))
-    lnps = np.empty((W, nsteps))
-    nacc = np.zeros(W, dtype=np.int64)
-    w = np.arange(half)
-    for step in range(nsteps):
-        for h in (0, 1):
-            r0, r1, r2, _ = draw(step, h, w, 0, seed)
-            z = ((a - 1.0) * u53(r0, r1) + 1.0) ** 2 / a
-            j = (1 - h) * half + ((r2 * np.uint64(half)) >> np.uint64(32)).astype(np.int64)
-            k = h * half + w
-            prop = p[j] - (p[j] - p[k]) * z[:, None]
-            newlp = ctx.lnprob_batch(prop)
-            q0, q1, _, _ = draw(step, h, w, 1, seed)
-            with np.errstate(all="ignore"):
-                lnq = (nd - 1.0) * np.log(z) + newlp - lp[k]
-                acc = (np.log(u53(q0, q1)) < lnq) & (newlp > -np.inf)
-            p[k[acc]] = prop[acc]
-            lp[k[acc]] = newlp[acc]
-            nacc[k[acc]] += 1
-            chain[k, step] = p[k]
-            lnps[k, step] = lp[k]
-    return chain, lnps, nacc
 
 
 @pytest.mark.parametrize("variant,n,W", [("fixcomp", 3000, 16), ("free", 2000, 32), ("zevol", 2000, 20)])
