@@ -6,6 +6,7 @@
     -> set_median_fit (median LF + 1/Veff estimate) -> the reference's output tables.
 
     python examples/fit_synthetic.py [--nsrc 20000] [--nwalkers 64] [--nsteps 300] [--fix-comp] [--until-converged] [--map]
+                                     [--integrals]
 """
 import argparse
 import os
@@ -34,6 +35,21 @@ def write_catalogue(path, n, seed):
             f.write("%s %d %r %r %r\n" % (field[i], i, float(cat["z"][i]), float(flux17[i]), float(0.1 * flux17[i])))
 
 
+def write_integrals(LFmod, path):
+    """The 16 / 50 / 84 % posterior values of n(>Lc) and rho(>Lc) (lf_integrals): one row, or for the
+    z-evolving model one row per z of lf_integrals's default mesh."""
+    cols, labels = [], []
+    if hasattr(LFmod, "z1"):
+        cols.append(np.linspace(LFmod.zmin, LFmod.zmax, 100))
+        labels.append("z")
+    for kind, name in (("number", "n"), ("lumdens", "rho")):
+        np.random.seed(4)                                    # the same draws for both kinds
+        band = LFmod.lf_integrals(kind=kind)
+        cols += list(band)
+        labels += ["%s_gt_Lc_%02d" % (name, p) for p in (16, 50, 84)]
+    tableio.write_fixed_width_two_line(path, cols, labels, formats={l: ("%0.4f" if l == "z" else "%0.6e") for l in labels})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nsrc", type=int, default=20000)
@@ -47,6 +63,9 @@ def main():
                     help="maximum a posteriori fit first (fit_model_map; DESIGN.md section 3.14): prints the best fit with "
                          "sqrt(diag(cov)) next to the medians and the Laplace evidence; with --until-converged the walkers "
                          "start in a Gaussian ball around the maximum")
+    ap.add_argument("--integrals", action="store_true",
+                    help="also write the 16 / 50 / 84 %% posterior values of the number density n(>Lc) [Mpc^-3] and the "
+                         "luminosity density rho(>Lc) [erg s^-1 Mpc^-3] (lf_integrals; DESIGN.md section 3.16)")
     ap.add_argument("--out", default="LFMCMCOut")
     ap.add_argument("--compress", action="store_true", help="compressed catalogue and grid (DESIGN.md section 3.5)")
     args = ap.parse_args()
@@ -97,6 +116,8 @@ def main():
         for n, t, e, m in zip(names[:-1], LFmod.map_theta, sd, med):
             print("  %-22s %9.4f +/- %.4f   (median %9.4f)" % (n, t, e, m))
         print("lnprob at the maximum %.4f; lnZ_laplace %.4f %s" % (LFmod.map_lnprob, LFmod.lnZ_laplace, LFmod.map_info["lnZ_reason"]))
+    if args.integrals:
+        write_integrals(LFmod, os.path.join(args.out, "integrals_%s.dat" % tag))
     print("wrote", sorted(os.listdir(args.out)))
     LFmod.close()
 

@@ -397,6 +397,22 @@ int lf_lumfunc_quantiles(int device, int variant, int32_t R, const double *draws
  * around the launch; measurement only).  LF_ERR_ARG when there is none. */
 int lf_lumfunc_quantiles_ms(double *ms);
 
+/* Percentiles over R posterior draws of the INTEGRATED LF above P lower limits: the number density
+ *   n(>Lmin) = 10^logphistar Gamma(alpha + 1, x)  [Mpc^-3]                       (LF_INT_NUMBER)
+ * or the luminosity density
+ *   rho(>Lmin) = 10^logphistar 10^logLstar Gamma(alpha + 2, x)  [erg s^-1 Mpc^-3]   (LF_INT_LUMDENS),
+ * x = 10^(logLmin - logLstar), Gamma(a, x) the upper incomplete gamma function (csrc/lf_gammainc.h).  Contract, argument
+ * checks, quantile rule and NaN rule are lf_lumfunc_quantiles's, with logLmin[P] in the place of logL; in addition
+ * LF_ERR_ARG for an unknown kind, a draw whose alpha is not finite or lies outside [-6, 5], and a NaN in logLmin
+ * (logLmin = -inf is allowed and means x = 0: the whole integral, +inf where alpha + 1 + kind <= 0). */
+enum { LF_INT_NUMBER = 0, LF_INT_LUMDENS = 1 };
+int lf_lumfunc_integral_quantiles(int device, int variant, int kind, int32_t R, const double *draws, int64_t P,
+                                  const double *logLmin, const double *z, int32_t nq, const double *q, int32_t method,
+                                  double *out, double *values);
+
+/* lf_lumfunc_quantiles_ms for lf_lumfunc_integral_quantiles. */
+int lf_lumfunc_integral_quantiles_ms(double *ms);
+
 /* Mock catalogues drawn from the model on the device (csrc/lf_mock.h).  The intensity is the
  * likelihood's own interpolant: the trapezoid sum of piece B over the integration grid is exactly the integral of
  * f_f(z, L) = sum_{j,k} lambda_f[j][k] hat_k(z) hat_{j,k}(L), so the expected count M_f of field f sums to piece B of

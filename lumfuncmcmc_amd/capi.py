@@ -19,6 +19,7 @@ VARIANTS = {"free": LF_FREE, "fixcomp": LF_FIXCOMP, "zevol": LF_ZEVOL}
 LF_OK = 0
 LF_ERR_ARG = -1
 LF_Q_LINEAR, LF_Q_MEDIAN = 0, 1
+LF_INT_NUMBER, LF_INT_LUMDENS = 0, 1
 LIM_ORDER = ("Lstar", "phistar", "sch_al", "Flim", "alpha")
 
 MPC_CM = 3.086e24                                  # lumfuncmcmc.py:70
@@ -51,7 +52,7 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_ptsampler_start", "lf_ptsampler_run", "lf_ptsampler_read", "lf_ptsampler_steps", "lf_mock_create",
            "lf_mock_destroy", "lf_mock_counts", "lf_mock_draw", "lf_mock_hist", "lf_mock_last_error", "lf_chain_diag",
            "lf_sampler_diag", "lf_ptsampler_diag", "lf_chain_window", "lf_diag_last", "lf_lnprob_grad_batch",
-           "lf_lnprob_grad_batch_device")
+           "lf_lnprob_grad_batch_device", "lf_lumfunc_integral_quantiles", "lf_lumfunc_integral_quantiles_ms")
 
 _lib = None
 
@@ -127,6 +128,12 @@ def load():
                                          _c_double_p, ctypes.c_int32, _c_double_p, ctypes.c_int32, _c_double_p, _c_double_p]
     lib.lf_lumfunc_quantiles_ms.restype = ctypes.c_int
     lib.lf_lumfunc_quantiles_ms.argtypes = [_c_double_p]
+    lib.lf_lumfunc_integral_quantiles.restype = ctypes.c_int
+    lib.lf_lumfunc_integral_quantiles.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, _c_double_p,
+                                                  ctypes.c_int64, _c_double_p, _c_double_p, ctypes.c_int32, _c_double_p,
+                                                  ctypes.c_int32, _c_double_p, _c_double_p]
+    lib.lf_lumfunc_integral_quantiles_ms.restype = ctypes.c_int
+    lib.lf_lumfunc_integral_quantiles_ms.argtypes = [_c_double_p]
     lib.lf_last_error.restype = ctypes.c_char_p
     lib.lf_last_error.argtypes = [ctypes.c_void_p]
     lib.lf_sampler_create.restype = ctypes.c_void_p
@@ -340,6 +347,39 @@ def lumfunc_quantiles_ms():
     ms = np.zeros(1)
     if load().lf_lumfunc_quantiles_ms(_ptr(ms)) != LF_OK:
         raise LFError("no lf_lumfunc_quantiles call has completed")
+    return float(ms[0])
+
+
+def lumfunc_integral_quantiles(variant, kind, draws, logLmin, z=None, q=(16.0, 50.0, 84.0), method=LF_Q_LINEAR, values=False,
+                               device=0):
+    """lf_lumfunc_integral_quantiles (include/lfmcmc.h): percentiles over the R draw records `draws` (as lumfunc_quantiles
+    takes them) of the integrated LF above the P limits logLmin (at z, LF_ZEVOL); kind LF_INT_NUMBER or LF_INT_LUMDENS.
+    Returns out (nq, P), or (out, values (R, P)) with values=True.  Raises LFError on a non-zero return."""
+    lib = load()
+    variant = VARIANTS.get(variant, variant)
+    np_rec = 7 if variant == LF_ZEVOL else 3
+    draws = _f64(draws).reshape(-1, np_rec)
+    logLmin = _f64(logLmin).ravel()
+    zz = None if z is None else _f64(z).ravel()
+    if zz is not None and zz.shape != logLmin.shape:
+        raise ValueError("z must have the shape of logLmin")
+    R, P = draws.shape[0], logLmin.size
+    qa = _f64(np.atleast_1d(q)).ravel() if method == LF_Q_LINEAR else np.zeros(1)
+    nq = qa.size
+    out = np.empty((nq, P))
+    val = np.empty((R, P)) if values else None
+    rc = lib.lf_lumfunc_integral_quantiles(int(device), int(variant), int(kind), R, _ptr(draws), P, _ptr(logLmin), _ptr(zz), nq,
+                                           _ptr(qa), int(method), _ptr(out), _ptr(val))
+    if rc != LF_OK:
+        raise LFError("lf_lumfunc_integral_quantiles failed (%d)" % rc)
+    return (out, val) if values else out
+
+
+def lumfunc_integral_quantiles_ms():
+    """Device time (ms) of the last lf_lumfunc_integral_quantiles kernel in this process."""
+    ms = np.zeros(1)
+    if load().lf_lumfunc_integral_quantiles_ms(_ptr(ms)) != LF_OK:
+        raise LFError("no lf_lumfunc_integral_quantiles call has completed")
     return float(ms[0])
 
 

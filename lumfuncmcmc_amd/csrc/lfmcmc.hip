@@ -1381,9 +1381,12 @@ int lf_veff(int device, int64_t n, const double* flux, const double* flim, const
 }
 
 static double g_bands_ms = -1.0;      // device time of the last lf_lumfunc_quantiles kernel (lf_lumfunc_quantiles_ms)
+static double g_integ_ms = -1.0;      // the same of lf_lumfunc_integral_quantiles
 
-int lf_lumfunc_quantiles(int device, int variant, int32_t R, const double* draws, int64_t P, const double* logL, const double* z,
-                         int32_t nq, const double* q, int32_t method, double* out, double* values) {
+// lf_lumfunc_quantiles (kind < 0: the differential LF, lf_bands) and lf_lumfunc_integral_quantiles (kind LF_INT_NUMBER /
+// LF_INT_LUMDENS: lf_bands_integ, logL holds the lower limits) share everything but the per-draw factors and the kernel.
+static int bands_run(int device, int variant, int kind, int32_t R, const double* draws, int64_t P, const double* logL, const double* z,
+                     int32_t nq, const double* q, int32_t method, double* out, double* values, double* ms_out) {
 #pragma clang fp contract(off)
     // every argument is checked before the device is touched
     if (variant < LF_FREE || variant > LF_ZEVOL || R < 1 || R > lf::BANDS_SLOTS || P < 1 || P > ((int64_t)1 << 40) || !draws ||
@@ -1399,6 +1402,14 @@ int lf_lumfunc_quantiles(int device, int variant, int32_t R, const double* draws
         return LF_ERR_ARG;
     }
     const int np_in = variant == LF_ZEVOL ? 7 : 3;
+    if (kind >= 0) {
+        for (int r = 0; r < R; ++r) {
+            const double al = draws[(size_t)r * np_in + np_in - 1];
+            if (!(al >= -6.0 && al <= 5.0)) return LF_ERR_ARG;              // (NaN fails both)
+        }
+        for (int64_t p = 0; p < P; ++p)
+            if (logL[p] != logL[p]) return LF_ERR_ARG;                      // -inf is allowed: x = 0
+    }
     // the per-draw factors the kernel takes as they are (lf_bands.h): alpha + 1, and for the single Schechter
     // LN10 * 10^logphistar - numpy scalar operations in the reference, made here with the host's pow (a volatile base keeps
     // the compiler from turning pow(10, x) into exp10, which the C library does not round the same way)
@@ -1409,12 +1420,17 @@ int lf_lumfunc_quantiles(int device, int variant, int32_t R, const double* draws
         double* o = rec.data() + (size_t)r * np_in;
         if (np_in == 3) {
             o[0] = d[0];
-            o[1] = 2.302585092994045684 * std::pow((double)ten, d[1]);
-            o[2] = d[2] + 1.0;
+            if (kind < 0)
+                o[1] = 2.302585092994045684 * std::pow((double)ten, d[1]);
+            else if (kind == LF_INT_LUMDENS)
+                o[1] = std::pow((double)ten, d[1]) * std::pow((double)ten, d[0]);
+            else
+                o[1] = std::pow((double)ten, d[1]);
         } else {
             for (int c = 0; c < 6; ++c) o[c] = d[c];
-            o[6] = d[6] + 1.0;
         }
+        o[np_in - 1] = d[np_in - 1] + 1.0;
+        if (kind > 0) o[np_in - 1] = o[np_in - 1] + 1.0;          // (alpha + 1) + 1, as lfintegrals adds them
     }
     // numpy 2.x's np.percentile(v, q, axis=0) index arithmetic (percentile: qf = q / 100; _QuantileMethods["linear"]:
     // vi = (R - 1) qf; _get_indexes: prev = floor(vi), next = prev + 1, vi >= R - 1 -> both -1 (the last), vi < 0 -> both 0;
@@ -1442,7 +1458,7 @@ int lf_lumfunc_quantiles(int device, int variant, int32_t R, const double* draws
         if (e != hipSuccess && rc == LF_OK) rc = LF_ERR_HIP;
         return e == hipSuccess;
     };
-    g_bands_ms = -1.0;
+    *ms_out = -1.0;
     if (ok(d_rec.alloc(rec.size())) && ok(d_logL.alloc((size_t)P)) && (variant != LF_ZEVOL || ok(d_z.alloc((size_t)P))) &&
         ok(d_q.alloc(qtab.size())) && ok(d_out.alloc((size_t)nq * P)) && (!values || ok(d_val.alloc((size_t)R * P))) &&
         ok(hipEventCreate(&ev[0])) && ok(hipEventCreate(&ev[1]))) {
@@ -1456,23 +1472,41 @@ int lf_lumfunc_quantiles(int device, int variant, int32_t R, const double* draws
             const int64_t G = lf::BANDS_SLOTS >> lg;
             const unsigned grid = (unsigned)std::min<int64_t>((P + G - 1) / G, (int64_t)ncu * 5);       // five 32-KiB workgroups per CU (LDS)
             ok(hipEventRecord(ev[0], 0));
-            if (variant == LF_ZEVOL)
-                hipLaunchKernelGGL(lf::lf_bands<7>, dim3(grid), dim3(lf::BANDS_THREADS), 0, 0, d_rec, (int)R, lg, d_logL, d_z, (long long)P,
-                                   d_q, (int)nq, method == LF_Q_MEDIAN ? 1 : 0, d_out, d_val);
-            else
-                hipLaunchKernelGGL(lf::lf_bands<3>, dim3(grid), dim3(lf::BANDS_THREADS), 0, 0, d_rec, (int)R, lg, d_logL, d_z, (long long)P,
-                                   d_q, (int)nq, method == LF_Q_MEDIAN ? 1 : 0, d_out, d_val);
+            using kernel_t = void (*)(const double*, int, int, const double*, const double*, long long, const double*, int, int, double*,
+                                      double*);
+            const kernel_t kernels[3][2] = {{lf::lf_bands<3>, lf::lf_bands<7>},
+                                            {lf::lf_bands_integ<3, 0>, lf::lf_bands_integ<7, 0>},
+                                            {lf::lf_bands_integ<3, 1>, lf::lf_bands_integ<7, 1>}};
+            hipLaunchKernelGGL(kernels[kind + 1][variant == LF_ZEVOL ? 1 : 0], dim3(grid), dim3(lf::BANDS_THREADS), 0, 0, d_rec, (int)R, lg,
+                               d_logL, d_z, (long long)P, d_q, (int)nq, method == LF_Q_MEDIAN ? 1 : 0, d_out, d_val);
             ok(hipGetLastError());
             ok(hipEventRecord(ev[1], 0));
             ok(hipMemcpy(out, d_out, (size_t)nq * pb, hipMemcpyDeviceToHost));
             if (values) ok(hipMemcpy(values, d_val, (size_t)R * pb, hipMemcpyDeviceToHost));
             float ms = 0.0f;
-            if (rc == LF_OK && ok(hipEventElapsedTime(&ms, ev[0], ev[1]))) g_bands_ms = ms;
+            if (rc == LF_OK && ok(hipEventElapsedTime(&ms, ev[0], ev[1]))) *ms_out = ms;
         }
     }
     for (hipEvent_t e : ev)
         if (e) hipEventDestroy(e);
     return rc;
+}
+
+int lf_lumfunc_quantiles(int device, int variant, int32_t R, const double* draws, int64_t P, const double* logL, const double* z,
+                         int32_t nq, const double* q, int32_t method, double* out, double* values) {
+    return bands_run(device, variant, -1, R, draws, P, logL, z, nq, q, method, out, values, &g_bands_ms);
+}
+
+int lf_lumfunc_integral_quantiles(int device, int variant, int kind, int32_t R, const double* draws, int64_t P, const double* logLmin,
+                                  const double* z, int32_t nq, const double* q, int32_t method, double* out, double* values) {
+    if (kind != LF_INT_NUMBER && kind != LF_INT_LUMDENS) return LF_ERR_ARG;
+    return bands_run(device, variant, kind, R, draws, P, logLmin, z, nq, q, method, out, values, &g_integ_ms);
+}
+
+int lf_lumfunc_integral_quantiles_ms(double* ms) {
+    if (!ms) return LF_ERR_ARG;
+    *ms = g_integ_ms;
+    return g_integ_ms < 0.0 ? LF_ERR_ARG : LF_OK;
 }
 
 int lf_lumfunc_quantiles_ms(double* ms) {

@@ -15,6 +15,7 @@ import numpy as np
 
 from . import hostsetup as hs
 from . import lfbands
+from . import lfintegrals
 from . import mock
 from . import veff
 from .cosmology import cosmo as _cosmo
@@ -730,6 +731,19 @@ class LumFuncMCMC(_Base):
         return lfbands.quantiles(self._variant(), recs, logL, q=percentiles, method=method, device=self._band_device(device),
                                  device_index=self.device)
 
+    def lf_integrals(self, kind="lumdens", logLmin=None, percentiles=(16, 50, 84), ndraws=200, lnprobcut=7.5, method="linear",
+                     device=None):
+        """Percentiles over ndraws random posterior draws of the integrated LF above each logLmin (default [self.Lc]):
+        kind "number" = n(>L) [Mpc^-3], "lumdens" = rho(>L) [erg s^-1 Mpc^-3] (lfintegrals).
+        Returns (nq, P).  Draws, lnprobcut, method and device as lf_percentiles."""
+        lfbands._method(method)
+        lfintegrals._kind(kind)
+        rows = self._posterior_rows(ndraws, lnprobcut)
+        recs = lfbands.pack_draws(self._variant(), rows, fix_sch_al=self.fix_sch_al, sch_al=self.sch_al)
+        logLmin = np.atleast_1d(np.asarray(self.Lc if logLmin is None else logLmin, dtype=np.float64)).ravel()
+        return lfintegrals.quantiles(self._variant(), kind, recs, logLmin, q=percentiles, method=method,
+                                     device=self._band_device(device), device_index=self.device)
+
     def VeffLF(self, device=None):
         """1/Veff weights per source and the binned LF with bootstrap errors (lumfuncmcmc.py:515-525).  device=True
         runs weights, binning and bootstrap on the GPU (lf_veff; resamples drawn with Philox instead of numpy's global
@@ -890,6 +904,24 @@ class LumFuncMCMCz(_Base):
         out = lfbands.quantiles("zevol", recs, Lp, z=zp, q=percentiles, method=method, device=self._band_device(device),
                                 device_index=self.device)
         return out.reshape(out.shape[0], z.size, logL.size)
+
+    def lf_integrals(self, kind="lumdens", logLmin=None, z=None, percentiles=(16, 50, 84), ndraws=200, lnprobcut=7.5,
+                     method="linear", device=None):
+        """Posterior band of the integrated z-evolving LF, n(>L; z) or rho(>L; z): percentiles over ndraws random
+        posterior draws at the redshifts z (default: 100 values across [zmin, zmax]) above logLmin (default self.Lc; a
+        scalar is broadcast over z, an array pairs with z).  Returns (nq, len(z)).  Otherwise as
+        LumFuncMCMC.lf_integrals."""
+        lfbands._method(method)
+        lfintegrals._kind(kind)
+        if z is None:
+            z = np.linspace(self.zmin, self.zmax, 100)
+        z = np.atleast_1d(np.asarray(z, dtype=np.float64)).ravel()
+        logLmin = np.asarray(self.Lc if logLmin is None else logLmin, dtype=np.float64)
+        logLmin = np.ascontiguousarray(np.broadcast_to(logLmin.ravel() if logLmin.ndim else logLmin, z.shape))
+        rows = self._posterior_rows(ndraws, lnprobcut)
+        recs = lfbands.pack_draws("zevol", rows, fix_sch_al=self.fix_sch_al, sch_al=self.sch_al, pivots=(self.z1, self.z2, self.z3))
+        return lfintegrals.quantiles("zevol", kind, recs, logLmin, z=z, q=percentiles, method=method,
+                                     device=self._band_device(device), device_index=self.device)
 
     def VeffLF(self, device=None):
         """lumfuncmcmc_z.py:470-478 (device: see LumFuncMCMC.VeffLF)."""
