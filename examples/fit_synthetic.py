@@ -50,6 +50,16 @@ def write_integrals(LFmod, path):
     tableio.write_fixed_width_two_line(path, cols, labels, formats={l: ("%0.4f" if l == "z" else "%0.6e") for l in labels})
 
 
+def write_veff_band(LFmod, path):
+    """The 1/Veff points with the band the completeness posterior gives them (veff_percentiles) next
+    to the bootstrap error of the catalogue alone."""
+    np.random.seed(4)
+    band = LFmod.veff_percentiles(percentiles=(16, 50, 84))
+    labels = ["Luminosity", "BinLF", "BinLFErr", "BinLF_16", "BinLF_50", "BinLF_84", "BinLFErrComp"]
+    tableio.write_fixed_width_two_line(path, [band["Lavg"], LFmod.lfbinorig, np.sqrt(LFmod.var)] + list(band["percentiles"]) +
+                                       [np.sqrt(band["var_comp"])], labels)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nsrc", type=int, default=20000)
@@ -66,9 +76,14 @@ def main():
     ap.add_argument("--integrals", action="store_true",
                     help="also write the 16 / 50 / 84 %% posterior values of the number density n(>Lc) [Mpc^-3] and the "
                          "luminosity density rho(>Lc) [erg s^-1 Mpc^-3] (lf_integrals; DESIGN.md section 3.16)")
+    ap.add_argument("--veff-band", action="store_true",
+                    help="also write the 1/Veff points with their 16 / 50 / 84 %% band over the completeness posterior and "
+                         "sqrt(var_comp) (veff_percentiles; DESIGN.md section 3.17; not with --fix-comp)")
     ap.add_argument("--out", default="LFMCMCOut")
     ap.add_argument("--compress", action="store_true", help="compressed catalogue and grid (DESIGN.md section 3.5)")
     args = ap.parse_args()
+    if args.veff_band and args.fix_comp:
+        ap.error("--veff-band needs the completeness parameters in the fit: not with --fix-comp")
     os.makedirs(args.out, exist_ok=True)
     cpath = os.path.join(args.out, "synthetic_catalogue.dat")
     write_catalogue(cpath, args.nsrc, seed=5)
@@ -118,6 +133,8 @@ def main():
         print("lnprob at the maximum %.4f; lnZ_laplace %.4f %s" % (LFmod.map_lnprob, LFmod.lnZ_laplace, LFmod.map_info["lnZ_reason"]))
     if args.integrals:
         write_integrals(LFmod, os.path.join(args.out, "integrals_%s.dat" % tag))
+    if args.veff_band:
+        write_veff_band(LFmod, os.path.join(args.out, "veffband_%s.dat" % tag))
     print("wrote", sorted(os.listdir(args.out)))
     LFmod.close()
 

@@ -413,6 +413,31 @@ int lf_lumfunc_integral_quantiles(int device, int variant, int kind, int32_t R, 
 /* lf_lumfunc_quantiles_ms for lf_lumfunc_integral_quantiles. */
 int lf_lumfunc_integral_quantiles_ms(double *ms);
 
+/* The 1/Veff luminosity function marginalised over the completeness posterior (csrc/lf_veffdraws.h; DESIGN.md section
+ * 3.17; post-fit, no context needed, synchronous, like lf_veff).  For R draws d_r = (Flim_0 .. Flim_{nf-1}, alpha) of the
+ * completeness parameters (draws[R][nf + 1], Flim in erg cm^-2 s^-1) and n sources (flux, field in [0, nf), vol or the shared
+ * vol_all when vol is NULL, bin_of in [0, nbin) or anything else for no bin)
+ *   values[r][b] = sum_{i : bin_of[i] == b} w_i(d_r),
+ *   w_i(d) = vol_i > 0 ? 1 / (pref0 fleming(flux_i, Flim_{field_i}, alpha, fcmin) vol_i) : 0     (lf_veff's phi)
+ * and out[k][b] = the percentile q[k] over r of values[r][b]: q, nq, method and the quantile rule (NumPy's, bit for bit,
+ * applied to values) are lf_lumfunc_quantiles's.  out[nq * nbin] row-major; values[R * nbin] or NULL.
+ * The sums are taken in one fixed order without atomics: two calls with the same inputs give the same bits, and row r of
+ * values depends on draw r and the catalogue only - not on R, on r or on the other draws.  A bin without sources is 0.0.
+ * LF_ERR_ARG, before the device is touched, for: a NULL pointer (vol, values and - LF_Q_MEDIAN - q may be NULL), n <= 0 or
+ * n >= 2^31, nbin outside 1..1024, nf outside 1..16, R outside 1..4096, nq outside 1..32 (LF_Q_MEDIAN: nq != 1), a q outside
+ * [0, 100], an unknown method, a field[i] outside [0, nf), pref0 <= 0, a draw that is not finite or has a Flim <= 0 or
+ * alpha == 0. */
+int lf_veff_draws(int device, int64_t n, const double *flux, const int32_t *field, const double *vol, double vol_all,
+                  double pref0, double fcmin, const int32_t *bin_of, int32_t nbin, int32_t nf, int32_t R, const double *draws,
+                  int32_t nq, const double *q, int32_t method, double *out, double *values);
+
+/* ms[3]: device times in ms of the three stages (per-chunk sums, per-bin sums, quantiles) of the most recent successful
+ * lf_veff_draws call in this process (hipEvents; measurement only).  LF_ERR_ARG when there is none. */
+int lf_veff_draws_ms(double *ms);
+
+/* Sources per chunk of lf_veff_draws's fixed summation order (VEFFD_CHUNK of csrc/lf_veffdraws.h). */
+int lf_veff_draws_chunk(void);
+
 /* Mock catalogues drawn from the model on the device (csrc/lf_mock.h).  The intensity is the
  * likelihood's own interpolant: the trapezoid sum of piece B over the integration grid is exactly the integral of
  * f_f(z, L) = sum_{j,k} lambda_f[j][k] hat_k(z) hat_{j,k}(L), so the expected count M_f of field f sums to piece B of

@@ -52,7 +52,8 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_ptsampler_start", "lf_ptsampler_run", "lf_ptsampler_read", "lf_ptsampler_steps", "lf_mock_create",
            "lf_mock_destroy", "lf_mock_counts", "lf_mock_draw", "lf_mock_hist", "lf_mock_last_error", "lf_chain_diag",
            "lf_sampler_diag", "lf_ptsampler_diag", "lf_chain_window", "lf_diag_last", "lf_lnprob_grad_batch",
-           "lf_lnprob_grad_batch_device", "lf_lumfunc_integral_quantiles", "lf_lumfunc_integral_quantiles_ms")
+           "lf_lnprob_grad_batch_device", "lf_lumfunc_integral_quantiles", "lf_lumfunc_integral_quantiles_ms", "lf_veff_draws", "lf_veff_draws_ms",
+           "lf_veff_draws_chunk")
 
 _lib = None
 
@@ -134,6 +135,14 @@ def load():
                                                   ctypes.c_int32, _c_double_p, _c_double_p]
     lib.lf_lumfunc_integral_quantiles_ms.restype = ctypes.c_int
     lib.lf_lumfunc_integral_quantiles_ms.argtypes = [_c_double_p]
+    lib.lf_veff_draws.restype = ctypes.c_int
+    lib.lf_veff_draws.argtypes = [ctypes.c_int, ctypes.c_int64, _c_double_p, ctypes.POINTER(ctypes.c_int32), _c_double_p, ctypes.c_double,
+                                  ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
+                                  ctypes.c_int32, _c_double_p, ctypes.c_int32, _c_double_p, ctypes.c_int32, _c_double_p, _c_double_p]
+    lib.lf_veff_draws_ms.restype = ctypes.c_int
+    lib.lf_veff_draws_ms.argtypes = [_c_double_p]
+    lib.lf_veff_draws_chunk.restype = ctypes.c_int
+    lib.lf_veff_draws_chunk.argtypes = []
     lib.lf_last_error.restype = ctypes.c_char_p
     lib.lf_last_error.argtypes = [ctypes.c_void_p]
     lib.lf_sampler_create.restype = ctypes.c_void_p
@@ -381,6 +390,48 @@ def lumfunc_integral_quantiles_ms():
     if load().lf_lumfunc_integral_quantiles_ms(_ptr(ms)) != LF_OK:
         raise LFError("no lf_lumfunc_integral_quantiles call has completed")
     return float(ms[0])
+
+
+def veff_draws_device(flux, field, vol, pref0, fcmin, bin_of, nbin, draws, q=(16.0, 50.0, 84.0), method=LF_Q_LINEAR, device=0):
+    """lf_veff_draws (include/lfmcmc.h): the binned 1/Veff sums of the catalogue under each of the R completeness draws
+    `draws` (R, nf + 1: Flim per field in erg cm^-2 s^-1, alpha) and their percentiles over the draws.  vol: scalar or
+    per-source array.  Returns (out (nq, nbin), values (R, nbin)); method LF_Q_MEDIAN: one row, q ignored.  Raises LFError
+    on a non-zero return."""
+    lib = load()
+    flux = _f64(flux).ravel()
+    n = flux.size
+    f32 = np.ascontiguousarray(field, dtype=np.int32).ravel()
+    b32 = np.ascontiguousarray(bin_of, dtype=np.int32).ravel()
+    draws = np.ascontiguousarray(np.atleast_2d(np.asarray(draws, dtype=np.float64)))
+    R, nf = draws.shape[0], draws.shape[1] - 1
+    volarr = None if np.ndim(vol) == 0 else _f64(vol).ravel()
+    if f32.size != n or b32.size != n or (volarr is not None and volarr.size != n):
+        raise ValueError("field, bin_of and a per-source vol must have the length of flux")
+    qa = _f64(np.atleast_1d(q)).ravel() if method == LF_Q_LINEAR else np.zeros(1)
+    nq = qa.size
+    out = np.empty((nq, nbin))
+    val = np.empty((R, nbin))
+    ip = ctypes.POINTER(ctypes.c_int32)
+    rc = lib.lf_veff_draws(int(device), n, _ptr(flux), f32.ctypes.data_as(ip), _ptr(volarr), float(vol) if volarr is None else 0.0,
+                           float(pref0), float(fcmin) if fcmin else 0.0, b32.ctypes.data_as(ip), int(nbin), int(nf), int(R),
+                           _ptr(draws), nq, _ptr(qa), int(method), _ptr(out), _ptr(val))
+    if rc != LF_OK:
+        raise LFError("lf_veff_draws failed (%d)" % rc)
+    return out, val
+
+
+def veff_draws_ms():
+    """Device times (ms) of the three stages of the last lf_veff_draws call in this process: per-chunk sums, per-bin
+    sums, quantiles."""
+    ms = np.zeros(3)
+    if load().lf_veff_draws_ms(_ptr(ms)) != LF_OK:
+        raise LFError("no lf_veff_draws call has completed")
+    return tuple(float(t) for t in ms)
+
+
+def veff_draws_chunk():
+    """Sources per chunk of lf_veff_draws's summation order."""
+    return int(load().lf_veff_draws_chunk())
 
 
 def _ptr(a):

@@ -28,6 +28,7 @@
 #include "lf_mock.h"
 #include "lf_pers.h"
 #include "lf_pt.h"
+#include "lf_veffdraws.h"
 
 namespace {
 
@@ -1383,6 +1384,36 @@ int lf_veff(int device, int64_t n, const double* flux, const double* flim, const
 static double g_bands_ms = -1.0;      // device time of the last lf_lumfunc_quantiles kernel (lf_lumfunc_quantiles_ms)
 static double g_integ_ms = -1.0;      // the same of lf_lumfunc_integral_quantiles
 
+// The quantile arguments of the band entries: q[nq] in [0, 100] (LF_Q_LINEAR), or nq == 1 and q ignored (LF_Q_MEDIAN).
+static bool quantile_args_ok(int32_t nq, const double* q, int32_t method) {
+    if (method == LF_Q_MEDIAN) return nq == 1;
+    if (method != LF_Q_LINEAR || nq < 1 || nq > lf::BANDS_MAXQ || !q) return false;
+    for (int i = 0; i < nq; ++i)
+        if (!(q[i] >= 0.0 && q[i] <= 100.0)) return false;                   // (NaN fails both)
+    return true;
+}
+
+// {prev, next, gamma} per quantile for bands_quantiles (lf_bands.h):
+// numpy 2.x's np.percentile(v, q, axis=0) index arithmetic (percentile: qf = q / 100; _QuantileMethods["linear"]:
+// vi = (R - 1) qf; _get_indexes: prev = floor(vi), next = prev + 1, vi >= R - 1 -> both -1 (the last), vi < 0 -> both 0;
+// _get_gamma: gamma = vi - prev with the CLAMPED prev, so vi + 1 past the end)
+static std::vector<double> quantile_table(int32_t R, int32_t nq, const double* q, int32_t method) {
+#pragma clang fp contract(off)
+    std::vector<double> qtab(3 * (size_t)std::max(nq, 1), 0.0);
+    if (method == LF_Q_LINEAR)
+        for (int i = 0; i < nq; ++i) {
+            const double qf = q[i] / 100.0;
+            const double vi = (double)(R - 1) * qf;
+            double prev = std::floor(vi), next = prev + 1.0;
+            if (vi >= (double)(R - 1)) prev = next = -1.0;
+            if (vi < 0.0) prev = next = 0.0;
+            qtab[3 * i + 2] = vi - prev;
+            qtab[3 * i] = prev < 0.0 ? (double)(R - 1) : prev;
+            qtab[3 * i + 1] = next < 0.0 ? (double)(R - 1) : next;
+        }
+    return qtab;
+}
+
 // lf_lumfunc_quantiles (kind < 0: the differential LF, lf_bands) and lf_lumfunc_integral_quantiles (kind LF_INT_NUMBER /
 // LF_INT_LUMDENS: lf_bands_integ, logL holds the lower limits) share everything but the per-draw factors and the kernel.
 static int bands_run(int device, int variant, int kind, int32_t R, const double* draws, int64_t P, const double* logL, const double* z,
@@ -1392,15 +1423,7 @@ static int bands_run(int device, int variant, int kind, int32_t R, const double*
     if (variant < LF_FREE || variant > LF_ZEVOL || R < 1 || R > lf::BANDS_SLOTS || P < 1 || P > ((int64_t)1 << 40) || !draws ||
         !logL || !out || (variant == LF_ZEVOL && !z))
         return LF_ERR_ARG;
-    if (method == LF_Q_MEDIAN) {
-        if (nq != 1) return LF_ERR_ARG;
-    } else if (method == LF_Q_LINEAR) {
-        if (nq < 1 || nq > lf::BANDS_MAXQ || !q) return LF_ERR_ARG;
-        for (int i = 0; i < nq; ++i)
-            if (!(q[i] >= 0.0 && q[i] <= 100.0)) return LF_ERR_ARG;          // (NaN fails both)
-    } else {
-        return LF_ERR_ARG;
-    }
+    if (!quantile_args_ok(nq, q, method)) return LF_ERR_ARG;
     const int np_in = variant == LF_ZEVOL ? 7 : 3;
     if (kind >= 0) {
         for (int r = 0; r < R; ++r) {
@@ -1432,21 +1455,7 @@ static int bands_run(int device, int variant, int kind, int32_t R, const double*
         o[np_in - 1] = d[np_in - 1] + 1.0;
         if (kind > 0) o[np_in - 1] = o[np_in - 1] + 1.0;          // (alpha + 1) + 1, as lfintegrals adds them
     }
-    // numpy 2.x's np.percentile(v, q, axis=0) index arithmetic (percentile: qf = q / 100; _QuantileMethods["linear"]:
-    // vi = (R - 1) qf; _get_indexes: prev = floor(vi), next = prev + 1, vi >= R - 1 -> both -1 (the last), vi < 0 -> both 0;
-    // _get_gamma: gamma = vi - prev with the CLAMPED prev, so vi + 1 past the end)
-    std::vector<double> qtab(3 * (size_t)std::max(nq, 1), 0.0);
-    if (method == LF_Q_LINEAR)
-        for (int i = 0; i < nq; ++i) {
-            const double qf = q[i] / 100.0;
-            const double vi = (double)(R - 1) * qf;
-            double prev = std::floor(vi), next = prev + 1.0;
-            if (vi >= (double)(R - 1)) prev = next = -1.0;
-            if (vi < 0.0) prev = next = 0.0;
-            qtab[3 * i + 2] = vi - prev;
-            qtab[3 * i] = prev < 0.0 ? (double)(R - 1) : prev;
-            qtab[3 * i + 1] = next < 0.0 ? (double)(R - 1) : next;
-        }
+    const std::vector<double> qtab = quantile_table(R, nq, q, method);
     int lg = 0;
     while ((1 << lg) < R) ++lg;
     if (hipSetDevice(device) != hipSuccess) return LF_ERR_NODEV;
@@ -1514,6 +1523,118 @@ int lf_lumfunc_quantiles_ms(double* ms) {
     *ms = g_bands_ms;
     return g_bands_ms < 0.0 ? LF_ERR_ARG : LF_OK;
 }
+
+static double g_veffd_ms[3] = {-1.0, -1.0, -1.0};      // device times of the last lf_veff_draws call's three stages
+
+int lf_veff_draws(int device, int64_t n, const double* flux, const int32_t* field, const double* vol, double vol_all, double pref0,
+                  double fcmin, const int32_t* bin_of, int32_t nbin, int32_t nf, int32_t R, const double* draws, int32_t nq,
+                  const double* q, int32_t method, double* out, double* values) {
+#pragma clang fp contract(off)
+    // every argument is checked before the device is touched
+    if (!flux || !field || !bin_of || !draws || !out || n <= 0 || n > (int64_t)INT32_MAX || nbin < 1 || nbin > lf::VEFF_MAXBIN || nf < 1 ||
+        nf > lf::VEFFD_MAXF || R < 1 || R > lf::BANDS_SLOTS || !(pref0 > 0.0) || !quantile_args_ok(nq, q, method))
+        return LF_ERR_ARG;
+    for (int64_t i = 0; i < n; ++i)
+        if (field[i] < 0 || field[i] >= nf) return LF_ERR_ARG;
+    for (int r = 0; r < R; ++r) {
+        const double* d = draws + (size_t)r * (nf + 1);
+        for (int f = 0; f < nf; ++f)
+            if (!std::isfinite(d[f]) || d[f] <= 0.0) return LF_ERR_ARG;
+        if (!std::isfinite(d[nf]) || d[nf] == 0.0) return LF_ERR_ARG;
+    }
+    // stable counting sort of the sources by bin; the sources outside [0, nbin) are dropped
+    std::vector<int64_t> first((size_t)nbin + 1, 0);
+    for (int64_t i = 0; i < n; ++i)
+        if (bin_of[i] >= 0 && bin_of[i] < nbin) ++first[(size_t)bin_of[i] + 1];
+    for (int b = 0; b < nbin; ++b) first[b + 1] += first[b];
+    const int64_t m = first[nbin];
+    std::vector<double> sflux((size_t)m), sipv((size_t)m);
+    std::vector<int> sfield((size_t)m);
+    {
+        std::vector<int64_t> at(first.begin(), first.end() - 1);
+        for (int64_t i = 0; i < n; ++i) {
+            if (bin_of[i] < 0 || bin_of[i] >= nbin) continue;
+            const int64_t k = at[bin_of[i]]++;
+            const double v = vol ? vol[i] : vol_all;
+            sflux[k] = flux[i];
+            sipv[k] = v > 0.0 ? 1.0 / (pref0 * v) : 0.0;
+            sfield[k] = field[i];
+        }
+    }
+    // chunks of at most VEFFD_CHUNK sources within a bin's segment; bin_c0[b] = the first chunk of bin b
+    std::vector<long long> cstart;
+    std::vector<int> clen, bin_c0((size_t)nbin + 1, 0);
+    for (int b = 0; b < nbin; ++b) {
+        bin_c0[b] = (int)cstart.size();
+        for (int64_t s = first[b]; s < first[b + 1]; s += lf::VEFFD_CHUNK) {
+            cstart.push_back((long long)s);
+            clen.push_back((int)std::min<int64_t>(lf::VEFFD_CHUNK, first[b + 1] - s));
+        }
+    }
+    const size_t nch = cstart.size();
+    bin_c0[nbin] = (int)nch;
+    double ratio = 0.0;
+    if (fcmin > 0.0) {
+        const double a = (2.0 * fcmin - 1.0) * (2.0 * fcmin - 1.0);      // VmaxLumFunc.py:164
+        ratio = std::fabs(a / (1.0 - a));
+    }
+    const std::vector<double> qtab = quantile_table(R, nq, q, method);
+    int lg = 0;
+    while ((1 << lg) < R) ++lg;
+    if (hipSetDevice(device) != hipSuccess) return LF_ERR_NODEV;
+    Buf<double> d_flux, d_ipv, d_draws, d_part, d_val, d_q, d_out;
+    Buf<int> d_field, d_clen, d_c0;
+    Buf<long long> d_cstart;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    int rc = LF_OK;
+    auto ok = [&](hipError_t e) {
+        if (e != hipSuccess && rc == LF_OK) rc = LF_ERR_HIP;
+        return e == hipSuccess;
+    };
+    for (double& t : g_veffd_ms) t = -1.0;
+    if (ok(d_flux.upload(sflux.data(), (size_t)m)) && ok(d_ipv.upload(sipv.data(), (size_t)m)) && ok(d_field.upload(sfield.data(), (size_t)m)) &&
+        ok(d_cstart.upload(cstart.data(), nch)) && ok(d_clen.upload(clen.data(), nch)) && ok(d_c0.upload(bin_c0.data(), bin_c0.size())) &&
+        ok(d_draws.upload(draws, (size_t)R * (nf + 1))) && ok(d_q.upload(qtab.data(), qtab.size())) && ok(d_part.alloc(nch * (size_t)R)) &&
+        ok(d_val.alloc((size_t)R * nbin)) && ok(d_out.alloc((size_t)nq * nbin)) && ok(hipEventCreate(&ev[0])) && ok(hipEventCreate(&ev[1])) &&
+        ok(hipEventCreate(&ev[2])) && ok(hipEventCreate(&ev[3]))) {
+        const unsigned tiles = (unsigned)((R + lf::VEFFD_THREADS - 1) / lf::VEFFD_THREADS);
+        ok(hipEventRecord(ev[0], 0));
+        if (nch > 0) {
+            auto kernel = fcmin > 0.0 ? lf::veffd_partial<true> : lf::veffd_partial<false>;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)nch, tiles), dim3(lf::VEFFD_THREADS), 0, 0, d_flux, d_ipv, d_field, d_cstart, d_clen,
+                               d_draws, (int)nf, (int)R, ratio, d_part);
+            ok(hipGetLastError());
+        }
+        ok(hipEventRecord(ev[1], 0));
+        hipLaunchKernelGGL(lf::veffd_reduce, dim3(tiles, (unsigned)nbin), dim3(lf::VEFFD_THREADS), 0, 0, d_part, d_c0, (int)nbin, (int)R, d_val);
+        ok(hipGetLastError());
+        ok(hipEventRecord(ev[2], 0));
+        const int G = lf::BANDS_SLOTS >> lg;
+        hipLaunchKernelGGL(lf::veffd_quant, dim3((unsigned)((nbin + G - 1) / G)), dim3(lf::BANDS_THREADS), 0, 0, d_val, (int)R, lg, (int)nbin,
+                           d_q, (int)nq, method == LF_Q_MEDIAN ? 1 : 0, d_out);
+        ok(hipGetLastError());
+        ok(hipEventRecord(ev[3], 0));
+        ok(hipMemcpy(out, d_out, (size_t)nq * nbin * sizeof(double), hipMemcpyDeviceToHost));
+        if (values) ok(hipMemcpy(values, d_val, (size_t)R * nbin * sizeof(double), hipMemcpyDeviceToHost));
+        for (int s = 0; s < 3 && rc == LF_OK; ++s) {
+            float ms = 0.0f;
+            if (ok(hipEventElapsedTime(&ms, ev[s], ev[s + 1]))) g_veffd_ms[s] = ms;
+        }
+        if (rc != LF_OK)
+            for (double& t : g_veffd_ms) t = -1.0;
+    }
+    for (hipEvent_t e : ev)
+        if (e) hipEventDestroy(e);
+    return rc;
+}
+
+int lf_veff_draws_ms(double* ms) {
+    if (!ms) return LF_ERR_ARG;
+    for (int s = 0; s < 3; ++s) ms[s] = g_veffd_ms[s];
+    return g_veffd_ms[0] < 0.0 ? LF_ERR_ARG : LF_OK;
+}
+
+int lf_veff_draws_chunk(void) { return lf::VEFFD_CHUNK; }
 
 int lf_last_launch(const lf_ctx* c, int32_t info[8]) {
     if (!c || !info) return LF_ERR_ARG;

@@ -744,6 +744,37 @@ class LumFuncMCMC(_Base):
         return lfintegrals.quantiles(self._variant(), kind, recs, logLmin, q=percentiles, method=method,
                                      device=self._band_device(device), device_index=self.device)
 
+    def veff_percentiles(self, percentiles=(16, 50, 84), ndraws=200, lnprobcut=7.5, method="linear", device=None):
+        """The 1/Veff points marginalised over the completeness posterior: the binned 1/Veff LF of
+        the catalogue under the Flim and alpha of each of ndraws random posterior draws (taken as lf_percentiles takes
+        them), on the bins of VeffLF.  Returns a dict: Lavg (nbins,), percentiles (nq, nbins) and values (ndraws, nbins) in
+        dn/dlogL like lfbinorig, and var_comp = np.var(values, axis=0, ddof=1) - the completeness part of the points'
+        variance, to be added to the bootstrap self.var by whoever wants a total (self.var, Flim and alpha are not
+        touched).  The volumes are VeffLF's: shared by all sources for min_comp_frac <= 0.001 (exact); otherwise each
+        source's volume out to the z_max of the object's CURRENT Flim and alpha, held fixed over the draws (z_max per source
+        and draw is not computed: only sources at the flux cut see the difference).  method and device as lf_percentiles."""
+        if self.fix_comp:
+            raise ValueError("this object was built with fix_comp=True: there is no completeness posterior to marginalise over")
+        lfbands._method(method)
+        rows = self._posterior_rows(ndraws, lnprobcut)
+        k = 2 if self.fix_sch_al else 3                        # theta's layout: set_parameters_from_list
+        draws = np.column_stack([1.0e-17 * rows[:, k:k + self.nfields], rows[:, k + self.nfields]])
+        self.getFlim()
+        if self.min_comp_frac <= 0.001:
+            zmaxval = self.zmax
+        else:
+            root = self.rootsf.ev(self.Flims_arr, self.alpha)
+            zmaxval = np.minimum(self.zmax, veff.max_redshift(10 ** self.lum, root, _cosmo))
+        vol = veff.comoving_volume(self.dVdzf, self.zmin, zmaxval)
+        field = np.repeat(np.arange(self.nfields), np.diff(self.field_ind))
+        _, Lavg, dL, idx = veff.luminosity_bins(self.lum, self.nbins)
+        out, values = veff.veff_draws_quantiles(self.flux, field, vol, sum(self.Omega_0) / hs.SQARCSEC, self.fcmin, idx, self.nbins,
+                                                draws, q=percentiles, method=method, device=self._band_device(device),
+                                                device_index=self.device)
+        values = values / dL
+        return {"Lavg": Lavg, "percentiles": out / dL, "values": values,
+                "var_comp": np.var(values, axis=0, ddof=1) if len(values) > 1 else np.zeros(self.nbins)}
+
     def VeffLF(self, device=None):
         """1/Veff weights per source and the binned LF with bootstrap errors (lumfuncmcmc.py:515-525).  device=True
         runs weights, binning and bootstrap on the GPU (lf_veff; resamples drawn with Philox instead of numpy's global

@@ -136,6 +136,52 @@ def veff_device(L, flux, flim, vol, sum_omega, alpha, fcmin, nboot=100, nbin=25,
     return phi, Lavg, sums[0] / dL, var
 
 
+def veff_draws(flux, field, vol, pref0, fcmin, bin_of, nbin, draws):
+    """Binned 1/Veff sums of the catalogue under each completeness draw (NumPy twin of lf_veff_draws):
+    values[r][b] = sum over the sources of bin b of 1 / (pref0 fleming(flux_i, Flim_r[field_i], alpha_r, fcmin) vol_i), 0 for
+    a source with vol_i <= 0.  draws (R, nf + 1): Flim per field in erg cm^-2 s^-1, then alpha; vol: scalar or per source;
+    bin_of outside [0, nbin): no bin.  One draw is lumfunc_weights + the bincount of boot_err_log, bit for bit."""
+    flux = np.asarray(flux, dtype=np.float64)
+    field = np.asarray(field, dtype=np.int64)
+    draws = np.atleast_2d(np.asarray(draws, dtype=np.float64))
+    nf = draws.shape[1] - 1
+    idx = np.asarray(bin_of, dtype=np.int64).copy()
+    idx[(idx < 0) | (idx >= nbin)] = nbin                  # overflow slot, dropped below
+    scalar = np.ndim(vol) == 0
+    ok = None if scalar else np.asarray(vol) > 0
+    values = np.zeros((draws.shape[0], nbin))
+    for r, d in enumerate(draws):
+        pref = pref0 * hs.fleming(flux, d[:nf][field], d[nf], fcmin)
+        phi = np.zeros_like(flux)
+        if scalar:
+            if vol > 0:
+                phi = 1.0 / (pref * vol)
+        else:
+            with np.errstate(divide="ignore"):
+                phi[ok] = 1.0 / (pref[ok] * np.asarray(vol)[ok])
+        values[r] = np.bincount(idx, weights=phi, minlength=nbin + 1)[:nbin]
+    return values
+
+
+def veff_draws_quantiles(flux, field, vol, pref0, fcmin, bin_of, nbin, draws, q=(16.0, 50.0, 84.0), method="linear", device=False,
+                         device_index=0):
+    """Percentiles over the draws of veff_draws's values: (out (nq, nbin), values (R, nbin)); np.percentile's rule
+    ("linear") or np.median's ("median": one row, q ignored).  device=True: one device job (lf_veff_draws), whose sums have a
+    fixed order - the same bits on every call; False: the NumPy twin."""
+    from . import lfbands
+    lfbands._method(method)
+    if device:
+        from . import capi
+        return capi.veff_draws_device(flux, field, vol, pref0, fcmin, bin_of, nbin, draws, q=q, method=lfbands.METHODS[method],
+                                      device=device_index)
+    values = veff_draws(flux, field, vol, pref0, fcmin, bin_of, nbin, draws)
+    if method == "linear":
+        out = np.percentile(values, np.atleast_1d(np.asarray(q, dtype=np.float64)), axis=0)
+    else:
+        out = np.median(values, axis=0)[None]
+    return out, values
+
+
 def boot_err_log(L, phi, nboot=100, nbin=25):
     """Binned LF dn/dlogL, and bootstrap variances (V.getBootErrLog with correct_low=False).
     Bin edges linspace(min(L)*1.001, max(L), nbin+1), half-open bins [e_j, e_j+1): the brightest
