@@ -44,6 +44,15 @@ inline double chunk_min(const std::vector<double>& a4, size_t ch, size_t size) {
     return m;
 }
 
+// the completeness ratio |a / (1 - a)|, a = (2 fcmin - 1)^2 (VmaxLumFunc.py:164)
+inline double fc_ratio(double fcmin) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double a = (2.0 * fcmin - 1.0) * (2.0 * fcmin - 1.0);
+    return std::fabs(a / (1.0 - a));
+}
+
 // ---- per-source tables, in the order the kernels read them, and the members of kc that come from the descriptor and the
 // catalogue (everything but the cells' and the grid's)
 struct Catalogue {
@@ -77,10 +86,7 @@ inline Catalogue catalogue(const lf_desc* d, KConst& kc) {
         kc.om0_grid[f] = d->omega0[f] / LF_SQARCSEC;           // integral: float (lumfuncmcmc.py:375)
         if (d->flim0) kc.flim0[f] = d->flim0[f];
     }
-    {
-        const double a = (2.0 * d->fcmin - 1.0) * (2.0 * d->fcmin - 1.0);   // VmaxLumFunc.py:164
-        kc.fc_ratio = std::fabs(a / (1.0 - a));
-    }
+    kc.fc_ratio = fc_ratio(d->fcmin);
     std::memcpy(kc.lims, d->lims, sizeof(kc.lims));
     std::memcpy(kc.pivots, d->pivots, sizeof(kc.pivots));
     kc.sch_al0 = d->sch_al0;
@@ -689,6 +695,41 @@ inline std::vector<int> make_deal(int nchC, int nbq, int grid_part, int grid_par
     std::vector<int> at_c(t.begin(), t.begin() + VF), at_b(t.begin() + DEAL_BINS, t.begin() + DEAL_BINS + VF);
     for (int i = 0; i < nchC; ++i) t[DEAL_LIST + at_c[own_c[i]]++] = i;
     for (int b = 0; b < nbq; ++b) t[DEAL_LIST + nchC + at_b[own_b[b]]++] = b;
+    return t;
+}
+
+// ---- the quantile arguments of the band entries (lf_bands.h: bands_quantiles; lf_veffdraws.h), checked and prepared: q[nq] in
+// [0, 100] with nq <= maxq (LF_Q_LINEAR), or nq == 1 and q ignored (LF_Q_MEDIAN); R draws in 2^lg slots.
+// tab holds {prev, next, gamma} per quantile:
+// numpy 2.x's np.percentile(v, q, axis=0) index arithmetic (percentile: qf = q / 100; _QuantileMethods["linear"]:
+// vi = (R - 1) qf; _get_indexes: prev = floor(vi), next = prev + 1, vi >= R - 1 -> both -1 (the last), vi < 0 -> both 0;
+// _get_gamma: gamma = vi - prev with the CLAMPED prev, so vi + 1 past the end)
+struct Quantiles {
+    bool ok = false;
+    std::vector<double> tab;
+    int lg = 0;
+};
+
+inline Quantiles quantiles(int32_t R, int32_t nq, const double* q, int32_t method, int maxq) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    Quantiles t;
+    if (method == LF_Q_MEDIAN ? nq != 1 : (method != LF_Q_LINEAR || nq < 1 || nq > maxq || !q)) return t;
+    t.tab.assign(3 * (size_t)nq, 0.0);
+    for (int i = 0; method == LF_Q_LINEAR && i < nq; ++i) {
+        if (!(q[i] >= 0.0 && q[i] <= 100.0)) return t;                       // (NaN fails both)
+        const double qf = q[i] / 100.0;
+        const double vi = (double)(R - 1) * qf;
+        double prev = std::floor(vi), next = prev + 1.0;
+        if (vi >= (double)(R - 1)) prev = next = -1.0;
+        if (vi < 0.0) prev = next = 0.0;
+        t.tab[3 * i + 2] = vi - prev;
+        t.tab[3 * i] = prev < 0.0 ? (double)(R - 1) : prev;
+        t.tab[3 * i + 1] = next < 0.0 ? (double)(R - 1) : next;
+    }
+    while ((1 << t.lg) < R) ++t.lg;
+    t.ok = true;
     return t;
 }
 

@@ -22,6 +22,7 @@
 #include "lf_diag.h"
 #include "lf_grad.h"
 #include "lf_gridbound.h"
+#include "lf_hostcall.h"
 #include "lf_hostprep.h"
 #include "lf_kernels.h"
 #include "lf_free.h"
@@ -174,30 +175,12 @@ struct lf_ctx {
 
 namespace {
 
-#define LF_HIP(ctx, call)                                                                  \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                \
-            return LF_ERR_HIP;                                                             \
-        }                                                                                  \
-    } while (0)
-
 // upload(c, buffer, vector, buffer, vector, ...): each vector to a new allocation of its size; stops at the first error
 inline int upload(lf_ctx*) { return LF_OK; }
 template <typename T, typename... Rest>
 int upload(lf_ctx* c, Buf<T>& dst, const std::vector<T>& src, Rest&... rest) {
     LF_HIP(c, dst.upload(src.data(), src.size()));
     return upload(c, rest...);
-}
-
-// Replace `b` by a new allocation of n elements (not initialised; the old contents go).  sync: launches enqueued earlier may
-// still use the old one - wait for the device first.  `o`: who takes the error (a context, a mock generator).
-template <typename Owner, typename T, bool PINNED>
-int grow(Owner* o, Buf<T, PINNED>& b, size_t n, bool sync = true) {
-    if (sync) LF_HIP(o, hipDeviceSynchronize());
-    LF_HIP(o, b.alloc(n));
-    return LF_OK;
 }
 
 // The catalogue's cells (lf_hostprep.h: build_cells), to the device.  No cells: nothing happens (kc.cells stays 0).
@@ -1342,77 +1325,38 @@ int lf_veff(int device, int64_t n, const double* flux, const double* flim, const
     Buf<int> d_bin;
     Buf<long long> d_idx;
     const size_t nb = (size_t)n * sizeof(double);
-    int rc = LF_OK;
-    auto ok = [&](hipError_t e) {
-        if (e != hipSuccess && rc == LF_OK) rc = LF_ERR_HIP;
-        return e == hipSuccess;
-    };
-    if (ok(d_flux.alloc((size_t)n)) && ok(d_flim.alloc((size_t)n)) && ok(d_phi.alloc((size_t)n)) && (!vol || ok(d_vol.alloc((size_t)n)))) {
-        ok(hipMemcpy(d_flux, flux, nb, hipMemcpyHostToDevice));
-        ok(hipMemcpy(d_flim, flim, nb, hipMemcpyHostToDevice));
-        if (vol) ok(hipMemcpy(d_vol, vol, nb, hipMemcpyHostToDevice));
-        double ratio = 0.0;
-        if (fcmin > 0.0) {
-            const double a = (2.0 * fcmin - 1.0) * (2.0 * fcmin - 1.0);      // VmaxLumFunc.py:164
-            ratio = std::fabs(a / (1.0 - a));
-        }
-        if (rc == LF_OK) {
+    HostCall hc;
+    if (hc.ok(alloc_all(d_flux, (size_t)n, d_flim, (size_t)n, d_phi, (size_t)n)) && (!vol || hc.ok(d_vol.alloc((size_t)n)))) {
+        hc.ok(hipMemcpy(d_flux, flux, nb, hipMemcpyHostToDevice));
+        hc.ok(hipMemcpy(d_flim, flim, nb, hipMemcpyHostToDevice));
+        if (vol) hc.ok(hipMemcpy(d_vol, vol, nb, hipMemcpyHostToDevice));
+        if (hc.rc == LF_OK) {
             hipLaunchKernelGGL(lf::veff_weights, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_flux, d_flim, d_vol, vol_all, pref0,
-                               alpha, ratio, fcmin > 0.0 ? 1 : 0, (long long)n, d_phi);
-            ok(hipGetLastError());
+                               alpha, fcmin > 0.0 ? lfh::fc_ratio(fcmin) : 0.0, fcmin > 0.0 ? 1 : 0, (long long)n, d_phi);
+            hc.ok(hipGetLastError());
         }
-        if (rc == LF_OK && nbin > 0) {
+        if (hc.rc == LF_OK && nbin > 0) {
             const size_t sb = (size_t)(nboot + 1) * nbin * sizeof(double);
-            if (ok(d_bin.alloc((size_t)n)) && ok(d_sums.alloc((size_t)(nboot + 1) * nbin)) && (!boot_idx || ok(d_idx.alloc((size_t)n * nboot)))) {
-                ok(hipMemcpy(d_bin, bin_of, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-                ok(hipMemset(d_sums, 0, sb));
-                if (boot_idx) ok(hipMemcpy(d_idx, boot_idx, (size_t)n * nboot * sizeof(long long), hipMemcpyHostToDevice));
-                if (rc == LF_OK) {
+            if (hc.ok(alloc_all(d_bin, (size_t)n, d_sums, (size_t)(nboot + 1) * nbin)) && (!boot_idx || hc.ok(d_idx.alloc((size_t)n * nboot)))) {
+                hc.ok(hipMemcpy(d_bin, bin_of, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+                hc.ok(hipMemset(d_sums, 0, sb));
+                if (boot_idx) hc.ok(hipMemcpy(d_idx, boot_idx, (size_t)n * nboot * sizeof(long long), hipMemcpyHostToDevice));
+                if (hc.rc == LF_OK) {
                     const unsigned gx = (unsigned)std::min<int64_t>((n + 255) / 256, 1024);
                     hipLaunchKernelGGL(lf::veff_bins, dim3(gx, (unsigned)(nboot + 1)), dim3(256), 0, 0, d_phi, d_bin, (long long)n, nbin,
                                        d_idx, (unsigned long long)seed, d_sums);
-                    ok(hipGetLastError());
-                    ok(hipMemcpy(sums, d_sums, sb, hipMemcpyDeviceToHost));
+                    hc.ok(hipGetLastError());
+                    hc.ok(hipMemcpy(sums, d_sums, sb, hipMemcpyDeviceToHost));
                 }
             }
         }
-        if (rc == LF_OK) ok(hipMemcpy(phi, d_phi, nb, hipMemcpyDeviceToHost));
+        if (hc.rc == LF_OK) hc.ok(hipMemcpy(phi, d_phi, nb, hipMemcpyDeviceToHost));
     }
-    return rc;
+    return hc.rc;
 }
 
 static double g_bands_ms = -1.0;      // device time of the last lf_lumfunc_quantiles kernel (lf_lumfunc_quantiles_ms)
 static double g_integ_ms = -1.0;      // the same of lf_lumfunc_integral_quantiles
-
-// The quantile arguments of the band entries: q[nq] in [0, 100] (LF_Q_LINEAR), or nq == 1 and q ignored (LF_Q_MEDIAN).
-static bool quantile_args_ok(int32_t nq, const double* q, int32_t method) {
-    if (method == LF_Q_MEDIAN) return nq == 1;
-    if (method != LF_Q_LINEAR || nq < 1 || nq > lf::BANDS_MAXQ || !q) return false;
-    for (int i = 0; i < nq; ++i)
-        if (!(q[i] >= 0.0 && q[i] <= 100.0)) return false;                   // (NaN fails both)
-    return true;
-}
-
-// {prev, next, gamma} per quantile for bands_quantiles (lf_bands.h):
-// numpy 2.x's np.percentile(v, q, axis=0) index arithmetic (percentile: qf = q / 100; _QuantileMethods["linear"]:
-// vi = (R - 1) qf; _get_indexes: prev = floor(vi), next = prev + 1, vi >= R - 1 -> both -1 (the last), vi < 0 -> both 0;
-// _get_gamma: gamma = vi - prev with the CLAMPED prev, so vi + 1 past the end)
-static std::vector<double> quantile_table(int32_t R, int32_t nq, const double* q, int32_t method) {
-#pragma clang fp contract(off)
-    std::vector<double> qtab(3 * (size_t)std::max(nq, 1), 0.0);
-    if (method == LF_Q_LINEAR)
-        for (int i = 0; i < nq; ++i) {
-            const double qf = q[i] / 100.0;
-            const double vi = (double)(R - 1) * qf;
-            double prev = std::floor(vi), next = prev + 1.0;
-            if (vi >= (double)(R - 1)) prev = next = -1.0;
-            if (vi < 0.0) prev = next = 0.0;
-            qtab[3 * i + 2] = vi - prev;
-            qtab[3 * i] = prev < 0.0 ? (double)(R - 1) : prev;
-            qtab[3 * i + 1] = next < 0.0 ? (double)(R - 1) : next;
-        }
-    return qtab;
-}
 
 // lf_lumfunc_quantiles (kind < 0: the differential LF, lf_bands) and lf_lumfunc_integral_quantiles (kind LF_INT_NUMBER /
 // LF_INT_LUMDENS: lf_bands_integ, logL holds the lower limits) share everything but the per-draw factors and the kernel.
@@ -1423,8 +1367,10 @@ static int bands_run(int device, int variant, int kind, int32_t R, const double*
     if (variant < LF_FREE || variant > LF_ZEVOL || R < 1 || R > lf::BANDS_SLOTS || P < 1 || P > ((int64_t)1 << 40) || !draws ||
         !logL || !out || (variant == LF_ZEVOL && !z))
         return LF_ERR_ARG;
-    if (!quantile_args_ok(nq, q, method)) return LF_ERR_ARG;
-    const int np_in = variant == LF_ZEVOL ? 7 : 3;
+    const lfh::Quantiles qt = lfh::quantiles(R, nq, q, method, lf::BANDS_MAXQ);
+    if (!qt.ok) return LF_ERR_ARG;
+    const std::vector<double>& qtab = qt.tab;
+    const int lg = qt.lg, np_in = variant == LF_ZEVOL ? 7 : 3;
     if (kind >= 0) {
         for (int r = 0; r < R; ++r) {
             const double al = draws[(size_t)r * np_in + np_in - 1];
@@ -1455,32 +1401,23 @@ static int bands_run(int device, int variant, int kind, int32_t R, const double*
         o[np_in - 1] = d[np_in - 1] + 1.0;
         if (kind > 0) o[np_in - 1] = o[np_in - 1] + 1.0;          // (alpha + 1) + 1, as lfintegrals adds them
     }
-    const std::vector<double> qtab = quantile_table(R, nq, q, method);
-    int lg = 0;
-    while ((1 << lg) < R) ++lg;
     if (hipSetDevice(device) != hipSuccess) return LF_ERR_NODEV;
     Buf<double> d_rec, d_logL, d_z, d_q, d_out, d_val;
-    hipEvent_t ev[2] = {nullptr, nullptr};
     const size_t pb = (size_t)P * sizeof(double);
-    int rc = LF_OK;
-    auto ok = [&](hipError_t e) {
-        if (e != hipSuccess && rc == LF_OK) rc = LF_ERR_HIP;
-        return e == hipSuccess;
-    };
+    HostCall hc;
     *ms_out = -1.0;
-    if (ok(d_rec.alloc(rec.size())) && ok(d_logL.alloc((size_t)P)) && (variant != LF_ZEVOL || ok(d_z.alloc((size_t)P))) &&
-        ok(d_q.alloc(qtab.size())) && ok(d_out.alloc((size_t)nq * P)) && (!values || ok(d_val.alloc((size_t)R * P))) &&
-        ok(hipEventCreate(&ev[0])) && ok(hipEventCreate(&ev[1]))) {
-        ok(hipMemcpy(d_rec, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
-        ok(hipMemcpy(d_logL, logL, pb, hipMemcpyHostToDevice));
-        if (d_z) ok(hipMemcpy(d_z, z, pb, hipMemcpyHostToDevice));
-        ok(hipMemcpy(d_q, qtab.data(), qtab.size() * sizeof(double), hipMemcpyHostToDevice));
-        if (rc == LF_OK) {
+    if (hc.ok(alloc_all(d_rec, rec.size(), d_logL, (size_t)P)) && (variant != LF_ZEVOL || hc.ok(d_z.alloc((size_t)P))) &&
+        hc.ok(alloc_all(d_q, qtab.size(), d_out, (size_t)nq * P)) && (!values || hc.ok(d_val.alloc((size_t)R * P)))) {
+        hc.ok(hipMemcpy(d_rec, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
+        hc.ok(hipMemcpy(d_logL, logL, pb, hipMemcpyHostToDevice));
+        if (d_z) hc.ok(hipMemcpy(d_z, z, pb, hipMemcpyHostToDevice));
+        hc.ok(hipMemcpy(d_q, qtab.data(), qtab.size() * sizeof(double), hipMemcpyHostToDevice));
+        if (hc.rc == LF_OK) {
             int ncu = 0;
             if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu < 1) ncu = 256;
             const int64_t G = lf::BANDS_SLOTS >> lg;
             const unsigned grid = (unsigned)std::min<int64_t>((P + G - 1) / G, (int64_t)ncu * 5);       // five 32-KiB workgroups per CU (LDS)
-            ok(hipEventRecord(ev[0], 0));
+            hc.stamp(0, 0);
             using kernel_t = void (*)(const double*, int, int, const double*, const double*, long long, const double*, int, int, double*,
                                       double*);
             const kernel_t kernels[3][2] = {{lf::lf_bands<3>, lf::lf_bands<7>},
@@ -1488,17 +1425,14 @@ static int bands_run(int device, int variant, int kind, int32_t R, const double*
                                             {lf::lf_bands_integ<3, 1>, lf::lf_bands_integ<7, 1>}};
             hipLaunchKernelGGL(kernels[kind + 1][variant == LF_ZEVOL ? 1 : 0], dim3(grid), dim3(lf::BANDS_THREADS), 0, 0, d_rec, (int)R, lg,
                                d_logL, d_z, (long long)P, d_q, (int)nq, method == LF_Q_MEDIAN ? 1 : 0, d_out, d_val);
-            ok(hipGetLastError());
-            ok(hipEventRecord(ev[1], 0));
-            ok(hipMemcpy(out, d_out, (size_t)nq * pb, hipMemcpyDeviceToHost));
-            if (values) ok(hipMemcpy(values, d_val, (size_t)R * pb, hipMemcpyDeviceToHost));
-            float ms = 0.0f;
-            if (rc == LF_OK && ok(hipEventElapsedTime(&ms, ev[0], ev[1]))) *ms_out = ms;
+            hc.ok(hipGetLastError());
+            hc.stamp(1, 0);
+            hc.ok(hipMemcpy(out, d_out, (size_t)nq * pb, hipMemcpyDeviceToHost));
+            if (values) hc.ok(hipMemcpy(values, d_val, (size_t)R * pb, hipMemcpyDeviceToHost));
+            hc.elapsed(0, 1, ms_out);
         }
     }
-    for (hipEvent_t e : ev)
-        if (e) hipEventDestroy(e);
-    return rc;
+    return hc.rc;
 }
 
 int lf_lumfunc_quantiles(int device, int variant, int32_t R, const double* draws, int64_t P, const double* logL, const double* z,
@@ -1532,8 +1466,12 @@ int lf_veff_draws(int device, int64_t n, const double* flux, const int32_t* fiel
 #pragma clang fp contract(off)
     // every argument is checked before the device is touched
     if (!flux || !field || !bin_of || !draws || !out || n <= 0 || n > (int64_t)INT32_MAX || nbin < 1 || nbin > lf::VEFF_MAXBIN || nf < 1 ||
-        nf > lf::VEFFD_MAXF || R < 1 || R > lf::BANDS_SLOTS || !(pref0 > 0.0) || !quantile_args_ok(nq, q, method))
+        nf > lf::VEFFD_MAXF || R < 1 || R > lf::BANDS_SLOTS || !(pref0 > 0.0))
         return LF_ERR_ARG;
+    const lfh::Quantiles qt = lfh::quantiles(R, nq, q, method, lf::BANDS_MAXQ);
+    if (!qt.ok) return LF_ERR_ARG;
+    const std::vector<double>& qtab = qt.tab;
+    const int lg = qt.lg;
     for (int64_t i = 0; i < n; ++i)
         if (field[i] < 0 || field[i] >= nf) return LF_ERR_ARG;
     for (int r = 0; r < R; ++r) {
@@ -1573,59 +1511,41 @@ int lf_veff_draws(int device, int64_t n, const double* flux, const int32_t* fiel
     }
     const size_t nch = cstart.size();
     bin_c0[nbin] = (int)nch;
-    double ratio = 0.0;
-    if (fcmin > 0.0) {
-        const double a = (2.0 * fcmin - 1.0) * (2.0 * fcmin - 1.0);      // VmaxLumFunc.py:164
-        ratio = std::fabs(a / (1.0 - a));
-    }
-    const std::vector<double> qtab = quantile_table(R, nq, q, method);
-    int lg = 0;
-    while ((1 << lg) < R) ++lg;
+    const double ratio = fcmin > 0.0 ? lfh::fc_ratio(fcmin) : 0.0;
     if (hipSetDevice(device) != hipSuccess) return LF_ERR_NODEV;
     Buf<double> d_flux, d_ipv, d_draws, d_part, d_val, d_q, d_out;
     Buf<int> d_field, d_clen, d_c0;
     Buf<long long> d_cstart;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    int rc = LF_OK;
-    auto ok = [&](hipError_t e) {
-        if (e != hipSuccess && rc == LF_OK) rc = LF_ERR_HIP;
-        return e == hipSuccess;
-    };
+    HostCall hc;
     for (double& t : g_veffd_ms) t = -1.0;
-    if (ok(d_flux.upload(sflux.data(), (size_t)m)) && ok(d_ipv.upload(sipv.data(), (size_t)m)) && ok(d_field.upload(sfield.data(), (size_t)m)) &&
-        ok(d_cstart.upload(cstart.data(), nch)) && ok(d_clen.upload(clen.data(), nch)) && ok(d_c0.upload(bin_c0.data(), bin_c0.size())) &&
-        ok(d_draws.upload(draws, (size_t)R * (nf + 1))) && ok(d_q.upload(qtab.data(), qtab.size())) && ok(d_part.alloc(nch * (size_t)R)) &&
-        ok(d_val.alloc((size_t)R * nbin)) && ok(d_out.alloc((size_t)nq * nbin)) && ok(hipEventCreate(&ev[0])) && ok(hipEventCreate(&ev[1])) &&
-        ok(hipEventCreate(&ev[2])) && ok(hipEventCreate(&ev[3]))) {
+    if (hc.ok(d_flux.upload(sflux.data(), (size_t)m)) && hc.ok(d_ipv.upload(sipv.data(), (size_t)m)) && hc.ok(d_field.upload(sfield.data(), (size_t)m)) &&
+        hc.ok(d_cstart.upload(cstart.data(), nch)) && hc.ok(d_clen.upload(clen.data(), nch)) && hc.ok(d_c0.upload(bin_c0.data(), bin_c0.size())) &&
+        hc.ok(d_draws.upload(draws, (size_t)R * (nf + 1))) && hc.ok(d_q.upload(qtab.data(), qtab.size())) &&
+        hc.ok(alloc_all(d_part, nch * (size_t)R, d_val, (size_t)R * nbin, d_out, (size_t)nq * nbin))) {
         const unsigned tiles = (unsigned)((R + lf::VEFFD_THREADS - 1) / lf::VEFFD_THREADS);
-        ok(hipEventRecord(ev[0], 0));
+        hc.stamp(0, 0);
         if (nch > 0) {
             auto kernel = fcmin > 0.0 ? lf::veffd_partial<true> : lf::veffd_partial<false>;
             hipLaunchKernelGGL(kernel, dim3((unsigned)nch, tiles), dim3(lf::VEFFD_THREADS), 0, 0, d_flux, d_ipv, d_field, d_cstart, d_clen,
                                d_draws, (int)nf, (int)R, ratio, d_part);
-            ok(hipGetLastError());
+            hc.ok(hipGetLastError());
         }
-        ok(hipEventRecord(ev[1], 0));
+        hc.stamp(1, 0);
         hipLaunchKernelGGL(lf::veffd_reduce, dim3(tiles, (unsigned)nbin), dim3(lf::VEFFD_THREADS), 0, 0, d_part, d_c0, (int)nbin, (int)R, d_val);
-        ok(hipGetLastError());
-        ok(hipEventRecord(ev[2], 0));
+        hc.ok(hipGetLastError());
+        hc.stamp(2, 0);
         const int G = lf::BANDS_SLOTS >> lg;
         hipLaunchKernelGGL(lf::veffd_quant, dim3((unsigned)((nbin + G - 1) / G)), dim3(lf::BANDS_THREADS), 0, 0, d_val, (int)R, lg, (int)nbin,
                            d_q, (int)nq, method == LF_Q_MEDIAN ? 1 : 0, d_out);
-        ok(hipGetLastError());
-        ok(hipEventRecord(ev[3], 0));
-        ok(hipMemcpy(out, d_out, (size_t)nq * nbin * sizeof(double), hipMemcpyDeviceToHost));
-        if (values) ok(hipMemcpy(values, d_val, (size_t)R * nbin * sizeof(double), hipMemcpyDeviceToHost));
-        for (int s = 0; s < 3 && rc == LF_OK; ++s) {
-            float ms = 0.0f;
-            if (ok(hipEventElapsedTime(&ms, ev[s], ev[s + 1]))) g_veffd_ms[s] = ms;
-        }
-        if (rc != LF_OK)
+        hc.ok(hipGetLastError());
+        hc.stamp(3, 0);
+        hc.ok(hipMemcpy(out, d_out, (size_t)nq * nbin * sizeof(double), hipMemcpyDeviceToHost));
+        if (values) hc.ok(hipMemcpy(values, d_val, (size_t)R * nbin * sizeof(double), hipMemcpyDeviceToHost));
+        for (int s = 0; s < 3; ++s) hc.elapsed(s, s + 1, &g_veffd_ms[s]);
+        if (hc.rc != LF_OK)
             for (double& t : g_veffd_ms) t = -1.0;
     }
-    for (hipEvent_t e : ev)
-        if (e) hipEventDestroy(e);
-    return rc;
+    return hc.rc;
 }
 
 int lf_veff_draws_ms(double* ms) {
@@ -1662,16 +1582,37 @@ int lf_form_counts(lf_ctx* c, int64_t counts[9]) {
 
 int lf_set_option(lf_ctx* c, const char* key, int64_t value) {
     if (!c || !key) return LF_ERR_ARG;
+    // the options that are one number of the context: a flag (value != 0), or a clamped value
+    using Set = void (*)(lf_ctx*, int64_t);
+    static const struct {
+        const char* key;
+        Set set;
+    } plain[] = {
+        {"taper", [](lf_ctx* c, int64_t v) { c->opt_taper = v != 0; }},
+        {"fuse", [](lf_ctx* c, int64_t v) { c->opt_fuse = v != 0; }},
+        {"fuse_step", [](lf_ctx* c, int64_t v) { c->opt_fuse_step = v != 0; }},
+        {"poll", [](lf_ctx* c, int64_t v) { c->opt_poll = v != 0; }},
+        {"cells", [](lf_ctx* c, int64_t v) { c->opt_cells = v != 0; c->kc.cells = c->opt_cells && c->ncell > 0; }},
+        {"tables", [](lf_ctx* c, int64_t v) { c->kc.tables = v != 0; }},
+        {"specialise", [](lf_ctx* c, int64_t v) { c->kc.specialise = v != 0; }},
+        {"grid_shortcut", [](lf_ctx* c, int64_t v) { c->opt_grid_shortcut = v != 0; }},
+        {"compress_grid", [](lf_ctx* c, int64_t v) { c->opt_compress_grid = v != 0; }},
+        {"skip_grid", [](lf_ctx* c, int64_t v) { c->opt_skip_grid = v != 0; }},
+        {"persistent", [](lf_ctx* c, int64_t v) { c->opt_persistent = v < 0 ? 0 : (v > 2 ? 2 : v); }},
+        {"profile_every", [](lf_ctx* c, int64_t v) { c->opt_profile_every = v < 1 ? 1 : v; c->prof_tick = 0; }},
+        {"profile_span", [](lf_ctx* c, int64_t v) { c->opt_profile_span = v < 1 ? 1 : v; c->prof_tick = 0; }},
+    };
+    for (const auto& o : plain)
+        if (std::strcmp(key, o.key) == 0) {
+            o.set(c, value);
+            return LF_OK;
+        }
     if (std::strcmp(key, "geometry") == 0) {
         if (value < -1 || value >= NGEO) {
             c->err = "geometry must be -1 (auto) or an index below " + std::to_string(NGEO);
             return LF_ERR_ARG;
         }
         c->opt_geometry = value;
-        return LF_OK;
-    }
-    if (std::strcmp(key, "taper") == 0) {
-        c->opt_taper = value != 0;
         return LF_OK;
     }
     if (std::strcmp(key, "compress") == 0) {
@@ -1703,28 +1644,6 @@ int lf_set_option(lf_ctx* c, const char* key, int64_t value) {
         c->kc.forms = value != 0 ? c->d_forms : nullptr;
         return LF_OK;
     }
-    if (std::strcmp(key, "fuse") == 0) {
-        c->opt_fuse = value != 0;
-        return LF_OK;
-    }
-    if (std::strcmp(key, "fuse_step") == 0) {
-        c->opt_fuse_step = value != 0;
-        return LF_OK;
-    }
-    if (std::strcmp(key, "poll") == 0) {
-        c->opt_poll = value != 0;
-        return LF_OK;
-    }
-    if (std::strcmp(key, "profile_every") == 0) {
-        c->opt_profile_every = value < 1 ? 1 : value;
-        c->prof_tick = 0;
-        return LF_OK;
-    }
-    if (std::strcmp(key, "profile_span") == 0) {
-        c->opt_profile_span = value < 1 ? 1 : value;
-        c->prof_tick = 0;
-        return LF_OK;
-    }
     if (std::strcmp(key, "free_st") == 0) {
         if (value != 0 && value != 2 && value != 4 && value != 8) {
             c->err = "free_st must be 0 (auto), 2, 4 or 8";
@@ -1733,45 +1652,18 @@ int lf_set_option(lf_ctx* c, const char* key, int64_t value) {
         c->opt_free_st = value;
         return LF_OK;
     }
-    if (std::strcmp(key, "cells") == 0) {
-        c->opt_cells = value != 0;
-        c->kc.cells = c->opt_cells && c->ncell > 0;
-        return LF_OK;
-    }
-    if (std::strcmp(key, "persistent") == 0) {
-        c->opt_persistent = value < 0 ? 0 : (value > 2 ? 2 : value);
-        return LF_OK;
-    }
-    if (std::strcmp(key, "tables") == 0) {
-        c->kc.tables = value != 0;
-        return LF_OK;
-    }
-    if (std::strcmp(key, "specialise") == 0) {
-        c->kc.specialise = value != 0;
-        return LF_OK;
-    }
-    if (std::strcmp(key, "grid_shortcut") == 0) {
-        c->opt_grid_shortcut = value != 0;
-        return LF_OK;
-    }
-    if (std::strcmp(key, "compress_grid") == 0) {
-        c->opt_compress_grid = value != 0;
-        return LF_OK;
-    }
     if (std::strcmp(key, "grid_share") == 0) {
         // value = part + parts * 65536: integrate only the node chunks c with c % parts == part (source-sharded ranks,
-        // whose lnprob values are summed); 0 or parts <= 1 = the whole grid
+        // whose lnprob values are summed); one part, or a value below 65536 (no parts at all), = the whole grid.  Where there are
+        // parts, a part that they do not have is refused, part 1 of one part included (it used to pass as the whole grid: a rank
+        // set up so would add the whole of piece B to the sum a second time)
         const int64_t parts = value >> 16, part = value & 0xffff;
-        if (value < 0 || (parts > 1 && part >= parts)) {
+        if (value < 0 || (parts >= 1 && part >= parts)) {
             c->err = "grid_share must be part + 65536 * parts with part < parts";
             return LF_ERR_ARG;
         }
         c->kc.grid_parts = parts > 1 ? (int)parts : 1;
         c->kc.grid_part = parts > 1 ? (int)part : 0;
-        return LF_OK;
-    }
-    if (std::strcmp(key, "skip_grid") == 0) {
-        c->opt_skip_grid = value != 0;
         return LF_OK;
     }
     if (std::strcmp(key, "walker_tile") == 0) {
@@ -1911,10 +1803,8 @@ lf_sampler* lf_sampler_create(lf_ctx* c, int nwalkers, double a, uint64_t seed, 
     sm->seed = seed;
     sm->cap = capacity_steps;
     const size_t W = (size_t)nwalkers, nd = (size_t)sm->ndim, cap = (size_t)capacity_steps;
-    bool ok = sm->d_pos.alloc(W * nd) == hipSuccess && sm->d_lnp.alloc(W) == hipSuccess && sm->d_prop.alloc(W * nd) == hipSuccess &&
-              sm->d_zz.alloc(W) == hipSuccess && sm->d_newlp.alloc(W) == hipSuccess && sm->d_chain.alloc(W * cap * nd) == hipSuccess &&
-              sm->d_chain_lnp.alloc(W * cap) == hipSuccess && sm->d_nacc.alloc(W) == hipSuccess;
-    if (!ok) {
+    if (alloc_all(sm->d_pos, W * nd, sm->d_lnp, W, sm->d_prop, W * nd, sm->d_zz, W, sm->d_newlp, W, sm->d_chain, W * cap * nd,
+                  sm->d_chain_lnp, W * cap, sm->d_nacc, W) != hipSuccess) {
         c->err = "lf_sampler_create: device allocation failed";
         lf_sampler_destroy(sm);
         return nullptr;
@@ -2077,10 +1967,9 @@ lf_ptsampler* lf_ptsampler_create(lf_ctx* c, int ntemps, int nwalkers, const dou
     std::vector<double> dbeta(T, 0.0);
     for (size_t i = 1; i < T; ++i) dbeta[i] = betas[i - 1] - betas[i];
     ok = sm->d_betas.upload(betas, T) == hipSuccess && sm->d_dbeta.upload(dbeta.data(), T) == hipSuccess &&
-         sm->d_pos.alloc(TW * nd) == hipSuccess && sm->d_lnl.alloc(TW) == hipSuccess && sm->d_prop.alloc(TH * nd) == hipSuccess &&
-         sm->d_zz.alloc(TH) == hipSuccess && sm->d_newl.alloc(TH) == hipSuccess && sm->d_chain.alloc(TW * cap * nd) == hipSuccess &&
-         sm->d_chain_lnl.alloc(TW * cap) == hipSuccess && sm->d_mean.alloc(T * cap) == hipSuccess && sm->d_nacc.alloc(TW) == hipSuccess &&
-         sm->d_nswap.alloc(T) == hipSuccess && sm->d_sig.alloc(std::max<size_t>(T - 1, 1) * nwalkers) == hipSuccess;
+         alloc_all(sm->d_pos, TW * nd, sm->d_lnl, TW, sm->d_prop, TH * nd, sm->d_zz, TH, sm->d_newl, TH, sm->d_chain, TW * cap * nd,
+                   sm->d_chain_lnl, TW * cap, sm->d_mean, T * cap, sm->d_nacc, TW, sm->d_nswap, T, sm->d_sig,
+                   std::max<size_t>(T - 1, 1) * nwalkers) == hipSuccess;
     // the evaluation's workspace for the T x W / 2 rows of a half-step, now rather than by a resize inside a running chain
     ok = ok && ensure_workspace(c, (int)TH, 0, 0) == LF_OK;
     if (!ok) {
@@ -2211,34 +2100,26 @@ int diag_run(std::string& err, hipStream_t st, const double* d_chain, const doub
         err = "diagnostics: at most 65535 walkers and 2^30 steps";
         return LF_ERR_ARG;
     }
-    int rc = LF_OK;
-    auto ok = [&](hipError_t e) {
-        if (e != hipSuccess && rc == LF_OK) {
-            rc = LF_ERR_HIP;
-            err = std::string("diagnostics: ") + hipGetErrorString(e);
-        }
-        return e == hipSuccess;
-    };
+    HostCall hc(&err, "diagnostics: ");
     const size_t WD = (size_t)W * D;
     Buf<double> d_mean, d_mom, d_a0, d_a, d_acf;
-    hipEvent_t ev[2] = {nullptr, nullptr};
     double ms_total = 0.0;
     auto timed = [&]() {            // closes a bracket of launches: waits for it and adds its device time
-        float ms = 0.0f;
-        if (ok(hipEventRecord(ev[1], st)) && ok(hipEventSynchronize(ev[1])) && ok(hipEventElapsedTime(&ms, ev[0], ev[1]))) ms_total += ms;
+        double ms = 0.0;
+        if (hc.stamp(1, st) && hc.wait(1) && hc.elapsed(0, 1, &ms)) ms_total += ms;
     };
     const lf::DiagSeries ser{d_chain, d_lnp, (long long)cap, ndim, D, (long long)t0, (int)n};
     std::vector<double> mom(4 * WD);
-    if (ok(d_mean.alloc(WD)) && ok(d_mom.alloc(4 * WD)) && ok(d_a0.alloc(WD)) && ok(hipEventCreate(&ev[0])) && ok(hipEventCreate(&ev[1]))) {
-        ok(hipEventRecord(ev[0], st));
+    if (hc.ok(alloc_all(d_mean, WD, d_mom, 4 * WD, d_a0, WD))) {
+        hc.stamp(0, st);
         hipLaunchKernelGGL(lf::lf_diag_moments, dim3((unsigned)W, (unsigned)D), dim3(lf::DIAG_THREADS), 0, st, ser, d_mean.get(), d_mom.get());
-        ok(hipGetLastError());
+        hc.ok(hipGetLastError());
         timed();
-        ok(hipMemcpy(mom.data(), d_mom, 4 * WD * sizeof(double), hipMemcpyDeviceToHost));
+        hc.ok(hipMemcpy(mom.data(), d_mom, 4 * WD * sizeof(double), hipMemcpyDeviceToHost));
     }
     std::vector<std::vector<double>> curve(D);
     std::vector<char> decided(D, 0);
-    if (rc == LF_OK) {
+    if (hc.rc == LF_OK) {
         for (int d = 0; d < D; ++d) {
             rhat[d] = lfd::split_rhat(mom.data() + 4 * d, W, 4 * (size_t)D, n / 2);
             if (n < 4) decided[d] = (char)(lfd::chain_window(nullptr, 0, c, n, &tau[d], &window[d]) == 0);
@@ -2249,23 +2130,23 @@ int diag_run(std::string& err, hipStream_t st, const double* d_chain, const doub
     if (acf && acf_cap > want) want = std::min<int64_t>((acf_cap + lf::DIAG_LT - 1) / lf::DIAG_LT * lf::DIAG_LT, Mmax);
     const int64_t slice = std::max<int64_t>(((int64_t)64 << 20) / (int64_t)(WD * sizeof(double)) / lf::DIAG_LT, 1) * lf::DIAG_LT;
     const unsigned groups = (unsigned)((D + lf::DIAG_DG - 1) / lf::DIAG_DG);
-    while (rc == LF_OK && n >= 4) {
-        for (int64_t lo = have; rc == LF_OK && lo < want; lo += slice) {
+    while (hc.rc == LF_OK && n >= 4) {
+        for (int64_t lo = have; hc.rc == LF_OK && lo < want; lo += slice) {
             const int64_t Mp = std::min(slice, want - lo);
             std::vector<double> part((size_t)D * Mp);
-            if (!ok(d_a.alloc(WD * Mp)) || !ok(d_acf.alloc((size_t)D * Mp))) break;
-            ok(hipEventRecord(ev[0], st));
+            if (!hc.ok(alloc_all(d_a, WD * Mp, d_acf, (size_t)D * Mp))) break;
+            hc.stamp(0, st);
             hipLaunchKernelGGL(lf::lf_diag_acf, dim3((unsigned)(Mp / lf::DIAG_LT), (unsigned)W, groups), dim3(lf::DIAG_THREADS), 0, st, ser,
                                d_mean.get(), (int)lo, d_a.get(), d_a0.get());
-            ok(hipGetLastError());
+            hc.ok(hipGetLastError());
             hipLaunchKernelGGL(lf::lf_diag_norm, dim3((unsigned)(((int64_t)D * Mp + lf::DIAG_THREADS - 1) / lf::DIAG_THREADS)),
                                dim3(lf::DIAG_THREADS), 0, st, d_a.get(), d_a0.get(), W, D, (long long)Mp, d_acf.get());
-            ok(hipGetLastError());
+            hc.ok(hipGetLastError());
             timed();
-            ok(hipMemcpy(part.data(), d_acf, part.size() * sizeof(double), hipMemcpyDeviceToHost));
-            for (int d = 0; d < D && rc == LF_OK; ++d) curve[d].insert(curve[d].end(), part.begin() + (size_t)d * Mp, part.begin() + (size_t)(d + 1) * Mp);
+            hc.ok(hipMemcpy(part.data(), d_acf, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+            for (int d = 0; d < D && hc.rc == LF_OK; ++d) curve[d].insert(curve[d].end(), part.begin() + (size_t)d * Mp, part.begin() + (size_t)(d + 1) * Mp);
         }
-        if (rc != LF_OK) break;
+        if (hc.rc != LF_OK) break;
         have = want;
         bool all = true;
         for (int d = 0; d < D; ++d) {
@@ -2275,9 +2156,7 @@ int diag_run(std::string& err, hipStream_t st, const double* d_chain, const doub
         if (all || have >= Mmax) break;
         want = std::min(2 * have, Mmax);
     }
-    for (hipEvent_t e : ev)
-        if (e) hipEventDestroy(e);
-    if (rc != LF_OK) return rc;
+    if (hc.rc != LF_OK) return hc.rc;
     for (int d = 0; d < D; ++d) {
         ess[d] = (double)W * (double)n / tau[d];
         if (acf)
@@ -2454,10 +2333,7 @@ lf_mock* lf_mock_create(const lf_desc* d) {
     mc.sch_al0 = d->sch_al0;
     const double sq = 180.0 / M_PI * 3600.0, sqarcsec = sq * sq;       // VmaxLumFunc.py:43
     for (int f = 0; f < nf; ++f) mc.om0s[f] = d->variant == LF_FREE ? d->omega0[f] / sqarcsec : 0.0;
-    if (d->variant == LF_FREE) {
-        const double a = (2.0 * d->fcmin - 1.0) * (2.0 * d->fcmin - 1.0);
-        mc.fc_ratio = std::fabs(a / (1.0 - a));
-    }
+    if (d->variant == LF_FREE) mc.fc_ratio = lfh::fc_ratio(d->fcmin);
     for (int i = 0; i < 3; ++i) mc.pivots[i] = d->pivots[i];
     const size_t SS = (size_t)S * S;
     const double* src[5] = {d->logL, d->zarr, d->variant == LF_FREE ? d->volume_part : nullptr,
@@ -2469,10 +2345,9 @@ lf_mock* lf_mock_create(const lf_desc* d) {
     bool ok = true;
     for (int i = 0; i < 5 && ok; ++i)
         if (src[i]) ok = m->d_grid[i].upload(src[i], len[i]) == hipSuccess;
-    ok = ok && m->d_theta.alloc((size_t)m->rch * mc.ndim) == hipSuccess && m->d_rid.alloc((size_t)m->rch) == hipSuccess &&
-         m->d_cdfL.alloc(nrf * SS) == hipSuccess && m->d_colm.alloc(nrf * S) == hipSuccess && m->d_cdfZ.alloc(nrf * S) == hipSuccess &&
-         m->d_mean.alloc(nrf) == hipSuccess && m->d_count.alloc(nrf) == hipSuccess && m->d_off.alloc(nrf + 1) == hipSuccess &&
-         m->d_edges.alloc(lf::MOCK_MAX_BINS + 1) == hipSuccess;
+    ok = ok && alloc_all(m->d_theta, (size_t)m->rch * mc.ndim, m->d_rid, (size_t)m->rch, m->d_cdfL, nrf * SS, m->d_colm, nrf * S,
+                         m->d_cdfZ, nrf * S, m->d_mean, nrf, m->d_count, nrf, m->d_off, nrf + 1, m->d_edges,
+                         (size_t)lf::MOCK_MAX_BINS + 1) == hipSuccess;
     if (!ok) {
         delete m;
         return bad("device allocation or copy failed");

@@ -3,39 +3,18 @@ needed): no scratch, no spills, and the LDS DESIGN.md section 3.12 states - 39 4
 CU by LDS, three waves per SIMD by registers."""
 import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
-from lumfuncmcmc_amd import build
+import lf_isalib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "lumfuncmcmc_amd", "csrc", "lfmcmc.hip")
 LDS = {"lf_diag_moments": 2048, "lf_diag_acf": 39456, "lf_diag_norm": 0}
 
 
 @pytest.fixture(scope="module")
 def remarks():
-    hipcc = build.hipcc()
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc here")
-    with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([hipcc] + build.CXXFLAGS + ["--cuda-device-only", "-c", "-o", os.path.join(d, "lf.o"), SRC,
-                            "-Rpass-analysis=kernel-resource-usage"], stderr=subprocess.PIPE, stdout=subprocess.PIPE)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    out = {}
-    name = None
-    for line in r.stderr.decode().splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and name:
-            out[name][m.group(1).strip()] = int(m.group(2))
-    return out
+    return lf_isalib.remarks()
 
 
 @pytest.mark.parametrize("kernel", sorted(LDS))

@@ -3,40 +3,14 @@ csrc/lf_gammainc.h inlined; hipcc -Rpass-analysis=kernel-resource-usage, no GPU 
 of keys of DESIGN.md section 3.9, and few enough VGPRs that the LDS (five workgroups per CU), not the registers, sets the
 occupancy.  Measured: 70 VGPRs (<3, 0>, <7, 0>, <3, 1>), 72 (<7, 1>); 80 is the next occupancy step above (six waves
 per SIMD)."""
-import os
-import re
-import subprocess
-import tempfile
-
 import pytest
 
-from lumfuncmcmc_amd import build
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "lumfuncmcmc_amd", "csrc", "lfmcmc.hip")
+import lf_isalib
 
 
 @pytest.fixture(scope="module")
 def remarks():
-    hipcc = build.hipcc()
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc here")
-    with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([hipcc] + build.CXXFLAGS + ["--cuda-device-only", "-c", "-o", os.path.join(d, "lf.o"), SRC,
-                            "-Rpass-analysis=kernel-resource-usage"], stderr=subprocess.PIPE, stdout=subprocess.PIPE)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    out = {}
-    name = None
-    for line in r.stderr.decode().splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and name:
-            out[name][m.group(1).strip()] = int(m.group(2))
-    return out
+    return lf_isalib.remarks()
 
 
 @pytest.mark.parametrize("nrec", [3, 7])

@@ -2,29 +2,16 @@
 the one-launch lf_free takes one 64-byte line of arguments (its block pointer and the FreeLaunch: lf_free.h), and every
 kernel that warms its arguments (lf_math.h: warm_kernarg) loads nothing past the end of its kernarg segment - a scalar load
 beyond it can fault the GPU when the segment ends at the end of the runtime's kernarg pool."""
-import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
-from lumfuncmcmc_amd import build
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "lumfuncmcmc_amd", "csrc", "lfmcmc.hip")
+import lf_isalib
 
 
 @pytest.fixture(scope="module")
 def code():
-    hipcc = build.hipcc()
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc here")
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "lf.s")
-        r = subprocess.run([hipcc] + build.CXXFLAGS + ["--cuda-device-only", "-S", "-o", out, SRC], stderr=subprocess.PIPE)
-        assert r.returncode == 0, r.stderr.decode()[-2000:]
-        text = open(out).read()
+    text = lf_isalib.asm()
     kern = {}
     for m in re.finditer(r"^(_ZN2lf\w+):[^\n]*\n(.*?)^\.Lfunc_end", text, re.S | re.M):
         kern[m.group(1)] = {"body": m.group(2)}

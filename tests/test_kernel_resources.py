@@ -2,40 +2,38 @@
 persistent FREE kernel is sized for four waves per SIMD (<= 128 VGPRs) and must not touch scratch - a spilled value in
 its item loop costs a `s_waitcnt vmcnt(0)` on every reload, and prologue spills were 30 MB of
 stores per launch before they were hunted down."""
-import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
-from lumfuncmcmc_amd import build
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "lumfuncmcmc_amd", "csrc", "lfmcmc.hip")
+import lf_isalib
 
 
 @pytest.fixture(scope="module")
 def remarks():
-    hipcc = build.hipcc()
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc here")
-    with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([hipcc] + build.CXXFLAGS + ["--cuda-device-only", "-c", "-o", os.path.join(d, "lf.o"), SRC,
-                            "-Rpass-analysis=kernel-resource-usage"], stderr=subprocess.PIPE, stdout=subprocess.PIPE)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    out = {}
-    name = None
-    for line in r.stderr.decode().splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and name:
-            out[name][m.group(1).strip()] = int(m.group(2))
-    return out
+    return lf_isalib.remarks()
+
+
+def test_remarks_and_assembly_come_from_one_compiler_run(monkeypatch, tmp_path):
+    """(a stand-in compiler and a unit of its own: the cached run of the real one is neither used nor lost)"""
+    import subprocess
+    import sys
+    runs = []
+
+    def fake_run(cmd, **kw):
+        runs.append(cmd)
+        open(cmd[cmd.index("-o") + 1], "w").write("_ZN2lf1kEv:\n\ts_endpgm\n")
+        return subprocess.CompletedProcess(cmd, 0, b"", b"k.h:1:1: remark: Function Name: _ZN2lf1kEv [-Rpass]\nk.h:1:1: remark:     VGPRs: 7 [-Rpass]\n")
+
+    monkeypatch.setattr(lf_isalib.build, "hipcc", lambda: sys.executable)
+    monkeypatch.setattr(lf_isalib.subprocess, "run", fake_run)
+    src = str(tmp_path / "unit.hip")
+    for _ in range(2):
+        assert lf_isalib.remarks(src) == {"_ZN2lf1kEv": {"VGPRs": 7}}
+        assert lf_isalib.asm(src).startswith("_ZN2lf1kEv:")
+        assert lf_isalib.remarks(src, "-S") == lf_isalib.remarks(src=src, emit="-S")
+    assert len(runs) == 1, runs
+    assert lf_isalib.remarks(src, "-c") == {"_ZN2lf1kEv": {"VGPRs": 7}} and len(runs) == 2
 
 
 def _find(remarks, prefix):
@@ -76,16 +74,8 @@ def test_big_geometry_of_lf_main_has_no_scratch(remarks):
 # ---------------------------------------------------------------------------------------------- the one-launch form's ISA
 @pytest.fixture(scope="module")
 def asm():
-    hipcc = build.hipcc()
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc here")
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "lf.s")
-        r = subprocess.run([hipcc] + build.CXXFLAGS + ["--cuda-device-only", "-S", "-o", out, SRC], stderr=subprocess.PIPE)
-        assert r.returncode == 0, r.stderr.decode()[-2000:]
-        text = open(out).read()
     kern = {}
-    for m in re.finditer(r"^(_ZN2lf\w+):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M):
+    for m in re.finditer(r"^(_ZN2lf\w+):[^\n]*\n(.*?)s_endpgm", lf_isalib.asm(), re.S | re.M):
         kern[m.group(1)] = [l.strip() for l in m.group(2).split("\n")]
     return kern
 

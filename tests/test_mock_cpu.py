@@ -5,12 +5,11 @@ declared, exported and free of scratch.  No GPU."""
 import math
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import lf_isalib
 import lf_oracle as O
 import lf_testlib as T
 from lumfuncmcmc_amd import mock, synth
@@ -19,7 +18,6 @@ stats = pytest.importorskip("scipy.stats")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "lfmcmc.h")
-SRC = os.path.join(ROOT, "lumfuncmcmc_amd", "csrc", "lfmcmc.hip")
 NEW_ENTRIES = ("lf_mock_create", "lf_mock_destroy", "lf_mock_counts", "lf_mock_draw", "lf_mock_hist", "lf_mock_last_error")
 
 
@@ -206,25 +204,7 @@ def test_header_declares_and_capi_exports_the_new_entries():
 
 @pytest.fixture(scope="module")
 def remarks():
-    from lumfuncmcmc_amd import build
-    hipcc = build.hipcc()
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc here")
-    with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([hipcc] + build.CXXFLAGS + ["--cuda-device-only", "-c", "-o", os.path.join(d, "lf.o"), SRC,
-                            "-Rpass-analysis=kernel-resource-usage"], stderr=subprocess.PIPE, stdout=subprocess.PIPE)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    out, name = {}, None
-    for line in r.stderr.decode().splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and name:
-            out[name][m.group(1).strip()] = int(m.group(2))
-    return out
+    return lf_isalib.remarks()
 
 
 @pytest.mark.parametrize("kernel,lds", [("lf_mock_mass", 2048), ("lf_mock_total", 2048), ("lf_mock_draw", 0),

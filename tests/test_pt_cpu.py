@@ -3,18 +3,17 @@ rule against a literal per-walker statement, the C ABI's new entries, and what t
 import os
 import re
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-from lumfuncmcmc_amd import build, capi
+import lf_isalib
+from lumfuncmcmc_amd import capi
 from lumfuncmcmc_amd.philox import draw, u53
 from lumfuncmcmc_amd.sampler import PTSampler, default_ntemps, ti_log_evidence, tmax_from_box
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "lfmcmc.h")
-SRC = os.path.join(ROOT, "lumfuncmcmc_amd", "csrc", "lfmcmc.hip")
 PT_NAMES = ("lf_ptsampler_create", "lf_ptsampler_destroy", "lf_ptsampler_start", "lf_ptsampler_run", "lf_ptsampler_read",
             "lf_ptsampler_steps")
 
@@ -159,24 +158,7 @@ def test_load_rejects_a_library_that_lacks_an_entry(tmp_path, monkeypatch):
 # ---------------------------------------------------------------------------------------------- the kernels
 @pytest.fixture(scope="module")
 def remarks():
-    hipcc = build.hipcc()
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc here")
-    with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([hipcc] + build.CXXFLAGS + ["--cuda-device-only", "-c", "-o", os.path.join(d, "lf.o"), SRC,
-                            "-Rpass-analysis=kernel-resource-usage"], stderr=subprocess.PIPE, stdout=subprocess.PIPE)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    out, name = {}, None
-    for line in r.stderr.decode().splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and name:
-            out[name][m.group(1).strip()] = int(m.group(2))
-    return out
+    return lf_isalib.remarks()
 
 
 def test_pt_kernels_use_no_scratch_and_the_stated_lds(remarks):

@@ -3,36 +3,20 @@ library's flags and its kernels use no scratch; every generator of tests/lf_prob
 NumPy binary64 figures that the caps of the GPU tests (tests/test_gpu_terms.py) rest on are measured and printed."""
 import math
 import os
-import re
-import subprocess
 
 import mpmath as mp
 import numpy as np
 import pytest
 
+import lf_isalib
 import lf_problib as L
-from lumfuncmcmc_amd import build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "term_probe.hip")
 
 
 def test_probe_unit_compiles_for_gfx950_and_its_kernels_use_no_scratch(tmp_path):
-    hipcc = build.hipcc()
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc here")
-    r = subprocess.run([hipcc] + build.CXXFLAGS + ["--cuda-device-only", "-c", "-o", str(tmp_path / "term_probe.o"), SRC,
-                        "-Rpass-analysis=kernel-resource-usage"], stderr=subprocess.PIPE, stdout=subprocess.PIPE)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    name, seen = None, {}
-    for line in r.stderr.decode().splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            continue
-        m = re.search(r"remark:\s+ScratchSize[^:]*: (\d+)", line)
-        if m and name and "probe_" in name:
-            seen[name] = int(m.group(1))
+    seen = {name: r["ScratchSize"] for name, r in lf_isalib.remarks(SRC, "-c").items() if "probe_" in name and "ScratchSize" in r}
     # 11 unary, 3 free terms, 2 z-evolving, 6 table instantiations, cell, wave, group8, reduce
     assert len(seen) == 26, sorted(seen)
     assert all(v == 0 for v in seen.values()), seen

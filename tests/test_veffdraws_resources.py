@@ -3,40 +3,14 @@
 veffd_partial 32 KiB of Flim [16 fields][256 lanes] + 2 x 2 KiB (flux, 1 / (pref0 vol)) + 1 KiB (field) = 37 KiB, which
 lets four workgroups share a CU, so the registers must allow four waves per SIMD too (128 VGPRs); veffd_reduce none;
 veffd_quant the 32 KiB of keys of the band kernels."""
-import os
-import re
-import subprocess
-import tempfile
-
 import pytest
 
-from lumfuncmcmc_amd import build
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "lumfuncmcmc_amd", "csrc", "lfmcmc.hip")
+import lf_isalib
 
 
 @pytest.fixture(scope="module")
 def remarks():
-    hipcc = build.hipcc()
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc here")
-    with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([hipcc] + build.CXXFLAGS + ["--cuda-device-only", "-c", "-o", os.path.join(d, "lf.o"), SRC,
-                            "-Rpass-analysis=kernel-resource-usage"], stderr=subprocess.PIPE, stdout=subprocess.PIPE)
-    assert r.returncode == 0, r.stderr.decode()[-2000:]
-    out = {}
-    name = None
-    for line in r.stderr.decode().splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and name:
-            out[name][m.group(1).strip()] = int(m.group(2))
-    return out
+    return lf_isalib.remarks()
 
 
 def _one(remarks, prefix):
