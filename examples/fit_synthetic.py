@@ -79,11 +79,16 @@ def main():
     ap.add_argument("--veff-band", action="store_true",
                     help="also write the 1/Veff points with their 16 / 50 / 84 %% band over the completeness posterior and "
                          "sqrt(var_comp) (veff_percentiles; DESIGN.md section 3.17; not with --fix-comp)")
+    ap.add_argument("--deconvolve", action="store_true",
+                    help="fit the likelihood convolved with the catalogue's flux errors (Eddington-bias correction, deconvolve=True; "
+                         "DESIGN.md section 3.18; host sampler: not with --until-converged or --map; errors above 0.09 dex are refused)")
     ap.add_argument("--out", default="LFMCMCOut")
     ap.add_argument("--compress", action="store_true", help="compressed catalogue and grid (DESIGN.md section 3.5)")
     args = ap.parse_args()
     if args.veff_band and args.fix_comp:
         ap.error("--veff-band needs the completeness parameters in the fit: not with --fix-comp")
+    if args.deconvolve and (args.until_converged or args.map):
+        ap.error("--deconvolve samples through fit_model: not with --until-converged or --map")
     os.makedirs(args.out, exist_ok=True)
     cpath = os.path.join(args.out, "synthetic_catalogue.dat")
     write_catalogue(cpath, args.nsrc, seed=5)
@@ -96,7 +101,7 @@ def main():
                         phistar=synth.PHISTAR, phistar_lims=synth.PHISTAR_LIMS, Lc=synth.LC, Lh=synth.LH,
                         nwalkers=args.nwalkers, nsteps=args.nsteps, fix_sch_al=False, fix_comp=args.fix_comp,
                         min_comp_frac=0.0, Flim_lims=synth.FLIM_LIMS, alpha_lims=synth.ALPHA_LIMS,
-                        field_names=field_names, field_ind=field_ind, compress=args.compress)
+                        field_names=field_names, field_ind=field_ind, compress=args.compress, deconvolve=args.deconvolve)
     print("setup %.2f s for %d sources" % (time.time() - t0, len(LFmod.lum)))
     np.random.seed(3)
     if args.map:

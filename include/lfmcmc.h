@@ -148,6 +148,43 @@ int lf_lnprob_grad_batch(lf_ctx *ctx, const double *theta, int B, double *lnprob
  * lf_lnprob_batch_device.  d_lnprob may be NULL. */
 int lf_lnprob_grad_batch_device(lf_ctx *ctx, const double *d_theta, int B, double *d_lnprob, double *d_grad, void *hip_stream);
 
+/* The flux-error-convolved likelihood (Eddington-bias correction; csrc/lf_deconv.h).  The catalogued
+ * log-luminosity of source i is its true one plus Gaussian noise of sigma[i] dex (the source's lum_e), and the completeness acts
+ * on the true flux: the expected counts (piece B) are unchanged, and each per-source term ln[phi(L_i) Omega(L_i, z_i)] becomes
+ * ln of its convolution with N(0, sigma_i^2), by K-point Gauss-Hermite quadrature.
+ * lf_set_lum_err copies sigma[N] (catalogue order, as given to lf_create; the context's own order is applied here) to the device.
+ * K: 4, 6, 8, 10, 12, 16, 20, 24 or 32.  Each order is validated (per-source quadrature error below 1e-7 over the prior box's
+ * sharpest completeness, tests/test_deconv_cpu.py) up to a largest sigma: 0.01, 0.03, 0.04, 0.05, 0.06, 0.06, 0.07, 0.08, 0.09
+ * dex; a larger sigma is refused with a message that states the limit, unless option "deconv_unchecked" = 1 was set before
+ * (tests and A/B runs: the value is then the K-point sum, whatever its distance from the integral).
+ * FIXCOMP, ZEVOL: logf[N] = log10 of the sources' fluxes (erg cm^-2 s^-1; lum - log10(4 pi DL^2), the FREE variant's
+ * lf_desc.logf), flim0[nf] (1e-17 erg cm^-2 s^-1) and alpha0 = the fixed completeness om_arr was made with; FREE: ignored
+ * (NULL; the row's own Flim_f and alpha_C are used, and the context has the fluxes).
+ * LF_ERR_ARG with a message, nothing uploaded, for: a NULL sigma, a sigma that is not finite or < 0 or above the order's limit,
+ * an unsupported K, missing logf / flim0 (FIXCOMP, ZEVOL), and a context whose grid has its own luminosity nodes per redshift
+ * column (min_comp_frac > 0.001: a cut on the observed flux would change piece B).  May be called again (synchronises). */
+int lf_set_lum_err(lf_ctx *ctx, const double *sigma, int K, const double *logf, const double *flim0, double alpha0);
+
+/* lnprob + Delta for B rows, Delta = sum_i ln sum_k (w_k / sqrt(pi)) exp(t_ik - t_i).  The plain lnprob is computed first by
+ * the path of lf_lnprob_batch, bit for bit; a row whose lnprob is -INFINITY stays -INFINITY, NaN becomes -INFINITY; a source
+ * with sigma = 0 contributes exactly 0 (all sigma 0: the output is lf_lnprob_batch's, bit for bit).  The correction is summed
+ * in one fixed order without atomics: a row's value has the same bits whatever B is and wherever the row stands.  The option
+ * "compress" is ignored by the correction.  LF_ERR_ARG with a message, before the device is touched, when no errors are set
+ * and for a context with "skip_grid" or "grid_share" set.  Host pointers, synchronous. */
+int lf_lnprob_err_batch(lf_ctx *ctx, const double *theta, int B, double *out);
+
+/* Same, with device pointers and the launches enqueued on `hip_stream` (NULL = the default stream), asynchronous like
+ * lf_lnprob_batch_device. */
+int lf_lnprob_err_batch_device(lf_ctx *ctx, const double *d_theta, int B, double *d_out, void *hip_stream);
+
+/* Host-only, exported for tests (touches no GPU): the K-point Gauss-Hermite rule (weight e^(-x^2)) the library derives in
+ * extended precision: x[K] ascending, lnw[K] = ln(w_k / sqrt(pi)).  LF_ERR_ARG for a NULL pointer or K outside 2..64. */
+int lf_gauss_hermite(int K, double *x, double *lnw);
+
+/* Host-only: the supported orders and the largest sigma each is validated for (up to cap entries; either may be NULL), the
+ * default order and the sources per chunk of the correction's fixed summation order.  Returns the number of orders. */
+int lf_deconv_info(int32_t *orders, double *sigma_max, int cap, int *default_order, int *chunk);
+
 /* Kernel timing for bench.py: level 1 brackets lf_main, level 2 every launch, with hipEvents on
  * the stream the launch runs on (0 = off; each event pair costs a few microseconds of stream time: the events are
  * barrier packets, and the next launch no longer overlaps the previous one's tail - measured 7.6 us per evaluation

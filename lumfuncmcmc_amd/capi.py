@@ -53,7 +53,8 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_mock_destroy", "lf_mock_counts", "lf_mock_draw", "lf_mock_hist", "lf_mock_last_error", "lf_chain_diag",
            "lf_sampler_diag", "lf_ptsampler_diag", "lf_chain_window", "lf_diag_last", "lf_lnprob_grad_batch",
            "lf_lnprob_grad_batch_device", "lf_lumfunc_integral_quantiles", "lf_lumfunc_integral_quantiles_ms", "lf_veff_draws", "lf_veff_draws_ms",
-           "lf_veff_draws_chunk")
+           "lf_veff_draws_chunk", "lf_set_lum_err", "lf_lnprob_err_batch", "lf_lnprob_err_batch_device", "lf_gauss_hermite",
+           "lf_deconv_info")
 
 _lib = None
 
@@ -106,6 +107,17 @@ def load():
     lib.lf_lnprob_grad_batch_device.restype = ctypes.c_int
     lib.lf_lnprob_grad_batch_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_void_p]
+    lib.lf_set_lum_err.restype = ctypes.c_int
+    lib.lf_set_lum_err.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_double]
+    lib.lf_lnprob_err_batch.restype = ctypes.c_int
+    lib.lf_lnprob_err_batch.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int, _c_double_p]
+    lib.lf_lnprob_err_batch_device.restype = ctypes.c_int
+    lib.lf_lnprob_err_batch_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    lib.lf_gauss_hermite.restype = ctypes.c_int
+    lib.lf_gauss_hermite.argtypes = [ctypes.c_int, _c_double_p, _c_double_p]
+    lib.lf_deconv_info.restype = ctypes.c_int
+    lib.lf_deconv_info.argtypes = [ctypes.POINTER(ctypes.c_int32), _c_double_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                   ctypes.POINTER(ctypes.c_int)]
     lib.lf_lnprob_pieces.restype = ctypes.c_int
     lib.lf_lnprob_pieces.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p]
     lib.lf_set_profiling.restype = ctypes.c_int
@@ -434,6 +446,26 @@ def veff_draws_chunk():
     return int(load().lf_veff_draws_chunk())
 
 
+def gauss_hermite(K):
+    """lf_gauss_hermite (include/lfmcmc.h): the library's K-point Gauss-Hermite rule, (x[K] ascending, ln(w_k / sqrt(pi))).
+    Touches no GPU."""
+    x, lnw = np.empty(int(K)), np.empty(int(K))
+    if load().lf_gauss_hermite(int(K), _ptr(x), _ptr(lnw)) != LF_OK:
+        raise ValueError("lf_gauss_hermite: K must be in 2..64")
+    return x, lnw
+
+
+def deconv_info():
+    """lf_deconv_info: dict orders, sigma_max (per order), default_order, chunk.  Touches no GPU."""
+    lib = load()
+    n = lib.lf_deconv_info(None, None, 0, None, None)
+    orders, smax = np.empty(n, dtype=np.int32), np.empty(n)
+    dflt, chunk = ctypes.c_int(0), ctypes.c_int(0)
+    lib.lf_deconv_info(orders.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(smax), n, ctypes.byref(dflt), ctypes.byref(chunk))
+    return {"orders": tuple(int(k) for k in orders), "sigma_max": tuple(float(v) for v in smax), "default_order": int(dflt.value),
+            "chunk": int(chunk.value)}
+
+
 def _ptr(a):
     return a.ctypes.data_as(_c_double_p) if a is not None else None
 
@@ -525,6 +557,11 @@ class LFContext(object):
         self.fix_sch_al = bool(d.fix_sch_al)
         self.lims = {k: (float(lims[k][0]), float(lims[k][1])) for k in LIM_ORDER}
         self.device = int(device)
+        # what lf_set_lum_err needs beyond sigma for fixed completeness: the sources' log flux and the fixed curve
+        self._logf = keep["logf"] if variant == "free" else (_f64(inp["logf"]) if inp.get("logf") is not None else
+                                                             (_f64(log_flux(lum, inp["DLz"])) if inp.get("DLz") is not None else None))
+        self._flim0 = None if variant == "free" else _f64(inp["Flim0"])
+        self._alpha0 = 0.0 if variant == "free" else float(inp["alpha0"])
 
     def prior_box(self):
         """(ndim, 2) bounds of the flat prior in theta's order (the model classes' _theta_lims)."""
@@ -579,6 +616,47 @@ class LFContext(object):
         if th.shape[0]:
             self._check(self._lib.lf_lnprob_grad_batch(self._h, _ptr(th), th.shape[0], _ptr(lp), _ptr(g)))
         return lp, g
+
+    def set_lum_err(self, sigma, K=None, unchecked=False):
+        """lf_set_lum_err: the sources' luminosity errors sigma (dex, catalogue order) and the Gauss-Hermite order K (None: the
+        library's default) of the flux-error-convolved likelihood (lnprob_err_batch).  unchecked=True
+        sets the option "deconv_unchecked" first: sigma above the order's validated range is taken as it is."""
+        sg = _f64(sigma).ravel()
+        if sg.size != self.N:
+            raise ValueError("sigma must have one value per source (%d), got %d" % (self.N, sg.size))
+        if K is None:
+            K = deconv_info()["default_order"]
+        if self.variant != "free" and self._logf is None:
+            raise ValueError("set_lum_err: the inputs of a fixed-completeness context must hold logf or DLz")
+        self.set_option("deconv_unchecked", 1 if unchecked else 0)
+        self._check(self._lib.lf_set_lum_err(self._h, _ptr(sg), int(K), None if self.variant == "free" else _ptr(self._logf),
+                                             _ptr(self._flim0), float(self._alpha0)))
+        self.deconv_order = int(K)
+
+    def lnprob_err_batch(self, theta):
+        """theta (B, ndim) or (ndim,) host array -> the flux-error-convolved lnprob (B,): lf_lnprob_err_batch."""
+        th = self._theta(theta)
+        out = np.empty(th.shape[0], dtype=np.float64)
+        if th.shape[0]:
+            self._check(self._lib.lf_lnprob_err_batch(self._h, _ptr(th), th.shape[0], _ptr(out)))
+        return out
+
+    def lnprob_err_torch(self, theta):
+        """theta: float64 device tensor (B, ndim) on this context's device; enqueues lf_lnprob_err_batch_device on torch's
+        current stream and returns a (B,) device tensor."""
+        import torch
+        if theta.dtype != torch.float64 or not theta.is_cuda or theta.dim() != 2 or theta.shape[1] != self.ndim:
+            raise ValueError("theta must be a float64 device tensor of shape (B, %d)" % self.ndim)
+        if theta.device.index != self.device:
+            raise ValueError("theta is on device %s, context is on %d" % (theta.device, self.device))
+        theta = theta.contiguous()
+        B = theta.shape[0]
+        out = torch.empty(B, dtype=torch.float64, device=theta.device)
+        if B:
+            stream = torch.cuda.current_stream(theta.device).cuda_stream
+            self._check(self._lib.lf_lnprob_err_batch_device(self._h, ctypes.c_void_p(theta.data_ptr()), int(B),
+                                                             ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)))
+        return out
 
     def lnprob_grad_torch(self, theta):
         """theta: float64 device tensor (B, ndim) on this context's device; enqueues lf_lnprob_grad_batch_device on torch's

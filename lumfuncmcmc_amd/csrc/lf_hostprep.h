@@ -663,6 +663,60 @@ inline GradConst grad_const(const KConst& kc, int64_t N, const double* z) {
     return g;
 }
 
+// ---- the Gauss-Hermite rule of the flux-error-convolved likelihood (lf_deconv.h): x[K] ascending and lnw[K] = ln(w_k / sqrt(pi))
+// for the weight e^(-x^2).  Newton iterations on the orthonormal Hermite recurrence in extended precision, the positive roots
+// from the largest down (the classic starting guesses), mirrored.  False for K outside 2..64.  (deconv.py: gauss_hermite is
+// the same routine.)
+inline bool gauss_hermite(int K, double* x, double* lnw) {
+    if (K < 2 || K > 64) return false;
+    const long double PI = 3.14159265358979323846264338327950288L;
+    const long double pim4 = 1.0L / std::sqrt(std::sqrt(PI));
+    const long double n = (long double)K;
+    std::vector<long double> xs((size_t)K, 0.0L), ws((size_t)K, 0.0L);
+    auto eval = [&](long double z, long double& pp) {
+        long double p1 = pim4, p2 = 0.0L;
+        for (int j = 1; j <= K; ++j) {
+            const long double p3 = p2;
+            p2 = p1;
+            p1 = z * std::sqrt(2.0L / j) * p2 - std::sqrt((long double)(j - 1) / j) * p3;
+        }
+        pp = std::sqrt(2.0L * n) * p2;
+        return p1;
+    };
+    long double z = 0.0L;
+    for (int i = 0; i < (K + 1) / 2; ++i) {
+        if (i == 0) z = std::sqrt(2.0L * n + 1.0L) - 1.85575L * std::pow(2.0L * n + 1.0L, -1.0L / 6.0L);
+        else if (i == 1) z -= 1.14L * std::pow(n, 0.426L) / z;
+        else if (i == 2) z = 1.86L * z - 0.86L * xs[(size_t)K - 1];
+        else if (i == 3) z = 1.91L * z - 0.91L * xs[(size_t)K - 2];
+        else z = 2.0L * z - xs[(size_t)(K - i + 1)];
+        long double pp = 1.0L;
+        for (int it = 0; it < 100; ++it) {
+            const long double p1 = eval(z, pp);
+            const long double dz = p1 / pp;
+            z -= dz;
+            if (std::fabs(dz) <= 1.0e-18L * std::fmax(std::fabs(z), 1.0L)) break;
+        }
+        if (K % 2 == 1 && i == K / 2) z = 0.0L;
+        eval(z, pp);
+        xs[(size_t)(K - 1 - i)] = z;
+        xs[(size_t)i] = -z;
+        ws[(size_t)(K - 1 - i)] = ws[(size_t)i] = 2.0L / (pp * pp);
+    }
+    for (int k = 0; k < K; ++k) {
+        x[k] = (double)xs[(size_t)k];
+        lnw[k] = (double)(std::log(ws[(size_t)k]) - 0.5L * std::log(PI));
+    }
+    return true;
+}
+
+// the largest sigma (dex) order K is validated for, < 0 for an order that is not supported
+inline double deconv_sigma_max(int K) {
+    for (int i = 0; i < DECONV_NORDERS; ++i)
+        if (DECONV_ORDERS[i] == K) return DECONV_SIGMA_MAX[i];
+    return -1.0;
+}
+
 // ---- lf_free's static deal (lf_layout.h: DEAL_*): flux bins, then cell chunks, each to the virtual workgroup that would be done
 // first - a bin costs a wave cost_b = 8 units, a cell chunk 3 (tools/stamps_fused.py), and the ranks of the younger half are
 // counted cost_h = 8 units behind (swept on one box, tools/deal_sweep.sh: 13.4 us per 128-row evaluation at 8-10, 13.75 at 0-6,

@@ -95,4 +95,19 @@ struct GradConst {
     double nsrc;                 // N
 };
 
+// The flux-error-convolved likelihood (lf_deconv.h): sources per block, the supported Gauss-Hermite
+// orders with the largest sigma (dex) each is validated for (worst per-source error below 1e-7 over the probe set of
+// tests/test_deconv_cpu.py; lf_set_lum_err refuses larger values), and the default order.
+constexpr int DECONV_CH = 1024;
+constexpr int DECONV_KMAX = 32;
+constexpr int DECONV_NORDERS = 9;
+constexpr int DECONV_ORDERS[DECONV_NORDERS] = {4, 6, 8, 10, 12, 16, 20, 24, 32};
+constexpr double DECONV_SIGMA_MAX[DECONV_NORDERS] = {0.01, 0.03, 0.04, 0.05, 0.06, 0.06, 0.07, 0.08, 0.09};
+constexpr int DECONV_DEFAULT_ORDER = 32;
+struct DeconvConst {
+    int K;                       // nodes
+    double alpha0;               // FIXCOMP, ZEVOL: the fixed completeness the model was built with
+    double flim0[MAXF];          // ... in theta's units (1e-17)
+};
+
 }  // namespace lf

@@ -20,6 +20,7 @@
 #include "lf_compress.h"
 #include "lf_devmem.h"
 #include "lf_diag.h"
+#include "lf_deconv.h"
 #include "lf_grad.h"
 #include "lf_gridbound.h"
 #include "lf_hostcall.h"
@@ -152,6 +153,17 @@ struct lf_ctx {
     bool grad_chunks_built = false;
     Buf<double> d_gpart, d_gout;
     Buf<double, true> h_gout;
+    // the flux-error-convolved likelihood (lf_deconv.h; lf_set_lum_err): the sources' order in the device tables, whether every
+    // redshift column of the grid has the same luminosity nodes, sigma (and, FIXCOMP / ZEVOL, the log flux and 10^(that + 17))
+    // in that order, the node table, the chunks and the blocks' partial sums [rows][chunks]
+    std::vector<int64_t> perm;
+    bool grid_separable = false;
+    lf::DeconvConst deconvc{};
+    bool deconv_set = false;
+    int64_t opt_deconv_unchecked = 0;   // 1: lf_set_lum_err takes sigma above the validated range of the order (tests, A/B runs)
+    Buf<double> d_sigma, d_elogf, d_eU, d_ghnodes, d_dpart;
+    ChunkTable deconv_chunks;
+    bool deconv_chunks_built = false;
     hipStream_t stream = nullptr;
     hipStream_t last_stream = nullptr;   // stream of the previous enqueue (workspace is shared)
     bool any_enqueued = false;
@@ -875,6 +887,68 @@ int grad_check(lf_ctx* c, const char* fn, const void* theta, int B, const void* 
     return LF_OK;
 }
 
+// The flux-error-convolved lnprob of B rows (lf_deconv.h): the lnprob path itself first (d_lnp: what lf_lnprob_batch_device
+// gives, bit for bit), then the blocks' partial sums of the correction and the rows' second stage, all on `s`.
+template <int VARIANT>
+void launch_deconv(const lf::DeconvArgs& da, int B, hipStream_t s) {
+    using namespace lf;
+    for (int b0 = 0; b0 < B; b0 += 32768) {
+        const int nb = std::min(32768, B - b0);
+        DeconvArgs g = da;
+        g.theta += (size_t)b0 * g.gc.ndim;
+        g.lnprob += b0;
+        g.part += (size_t)b0 * g.nch;
+        g.out += b0;
+        if (g.nch > 0) hipLaunchKernelGGL(lf_deconv_part<VARIANT>, dim3((unsigned)g.nch, (unsigned)nb), dim3(BLOCK), 0, s, g);
+        hipLaunchKernelGGL(lf_deconv_final, dim3((unsigned)nb), dim3(64), 0, s, g);
+    }
+}
+
+int enqueue_deconv(lf_ctx* c, const double* d_theta, int B, double* d_lnp, double* d_out, hipStream_t s) {
+    using namespace lf;
+    int rc;
+    if (!c->deconv_chunks_built) {
+        const lfh::Chunks h = lfh::chunk_table(c->field_ind, c->kc.nf, DECONV_CH, 0.0, 0.0, 0.0);
+        ChunkTable& t = c->deconv_chunks;
+        t.n = (int)h.start.size();
+        if ((rc = upload(c, t.d_start, h.start, t.d_len, h.len, t.d_field, h.field)) != LF_OK) return rc;
+        c->deconv_chunks_built = true;
+    }
+    const int nch = c->deconv_chunks.n;
+    const size_t need = (size_t)B * std::max(nch, 1);
+    if (need > c->d_dpart.size() && (rc = grow(c, c->d_dpart, need)) != LF_OK) return rc;
+    if ((rc = enqueue(c, d_theta, B, d_lnp, nullptr, nullptr, s)) != LF_OK) return rc;
+    const bool fr = c->kc.variant == LF_FREE;
+    const DeconvArgs da{c->gradc, c->deconvc, d_theta, d_lnp, c->d_dpart, d_out, c->d_lum, c->d_a1, c->d_P,
+                        fr ? c->d_a1.get() : c->d_elogf.get(), fr ? c->d_U.get() : c->d_eU.get(), c->d_sigma, c->d_ghnodes,
+                        c->deconv_chunks.d_start, c->deconv_chunks.d_len, c->deconv_chunks.d_field, nch};
+    switch (c->kc.variant) {
+        case LF_FREE: launch_deconv<LF_FREE>(da, B, s); break;
+        case LF_FIXCOMP: launch_deconv<LF_FIXCOMP>(da, B, s); break;
+        default: launch_deconv<LF_ZEVOL>(da, B, s);
+    }
+    LF_HIP(c, hipGetLastError());
+    return LF_OK;
+}
+
+// what both entry points refuse before the device is touched
+int deconv_check(lf_ctx* c, const char* fn, const void* theta, int B, const void* out) {
+    if (!c) return LF_ERR_ARG;
+    if (!theta || !out || B <= 0) {
+        c->err = std::string(fn) + ": NULL pointer or B <= 0";
+        return LF_ERR_ARG;
+    }
+    if (!c->deconv_set) {
+        c->err = std::string(fn) + ": no luminosity errors set (call lf_set_lum_err first)";
+        return LF_ERR_ARG;
+    }
+    if (c->opt_skip_grid || c->kc.grid_parts > 1) {
+        c->err = std::string(fn) + ": no convolved likelihood of a source-sharded context (options skip_grid, grid_share)";
+        return LF_ERR_ARG;
+    }
+    return LF_OK;
+}
+
 // Build the compressed catalogue and grid (lf_hostprep.h: compress) from the host's copy of the keys and the device's of lum.
 int build_compressed(lf_ctx* c) {
     if (c->cmp.built) return LF_OK;
@@ -1001,6 +1075,8 @@ int build(lf_ctx* c, const lf_desc* d) {
     c->field_ind.assign(d->field_ind, d->field_ind + nf + 1);
     lfh::Catalogue cat = lfh::catalogue(d, kc);
     c->gradc = lfh::grad_const(kc, d->N, d->variant == LF_ZEVOL ? cat.a1.data() : nullptr);
+    c->perm = cat.perm;
+    c->grid_separable = lfh::same_columns(d->logL, d->S);
     int rc;
     kc.cells = 0;
     kc.zcell_rho = 0.0;
@@ -1247,6 +1323,102 @@ int lf_lnprob_grad_batch(lf_ctx* c, const double* theta, int B, double* lnprob, 
     LF_HIP(c, hipStreamSynchronize(c->stream));
     if (lnprob) std::memcpy(lnprob, c->h_gout, (size_t)B * sizeof(double));
     std::memcpy(grad, c->h_gout + B, tb);
+    return LF_OK;
+}
+
+int lf_gauss_hermite(int K, double* x, double* lnw) {
+    if (!x || !lnw || !lfh::gauss_hermite(K, x, lnw)) return LF_ERR_ARG;
+    return LF_OK;
+}
+
+int lf_deconv_info(int32_t* orders, double* sigma_max, int cap, int* default_order, int* chunk) {
+    if (default_order) *default_order = lf::DECONV_DEFAULT_ORDER;
+    if (chunk) *chunk = lf::DECONV_CH;
+    for (int i = 0; i < lf::DECONV_NORDERS && i < cap; ++i) {
+        if (orders) orders[i] = lf::DECONV_ORDERS[i];
+        if (sigma_max) sigma_max[i] = lf::DECONV_SIGMA_MAX[i];
+    }
+    return lf::DECONV_NORDERS;
+}
+
+int lf_set_lum_err(lf_ctx* c, const double* sigma, int K, const double* logf, const double* flim0, double alpha0) {
+    using namespace lf;
+    if (!c) return LF_ERR_ARG;
+    auto bad = [&](const std::string& m) {
+        c->err = "lf_set_lum_err: " + m;
+        return (int)LF_ERR_ARG;
+    };
+    const int64_t N = c->N;
+    const int nf = c->kc.nf;
+    if (N > 0 && !sigma) return bad("NULL sigma");
+    const double smax = lfh::deconv_sigma_max(K);
+    if (smax < 0.0) return bad("order K = " + std::to_string(K) + " is not supported (4, 6, 8, 10, 12, 16, 20, 24, 32)");
+    if (!c->grid_separable)
+        return bad("the grid's redshift columns have their own luminosity nodes (min_comp_frac > 0.001): a cut on the observed "
+                   "flux would change the expected counts, which this model leaves as they are");
+    const bool fr = c->kc.variant == LF_FREE;
+    if (!fr) {
+        if (!flim0 || (N > 0 && !logf)) return bad("fixed completeness (FIXCOMP, ZEVOL) needs logf and flim0");
+        if (!std::isfinite(alpha0) || alpha0 == 0.0) return bad("alpha0 must be finite and not 0");
+        for (int f = 0; f < nf; ++f)
+            if (!(flim0[f] > 0.0) || !std::isfinite(flim0[f])) return bad("flim0 must be finite and > 0");
+    }
+    for (int64_t i = 0; i < N; ++i) {
+        if (!std::isfinite(sigma[i]) || sigma[i] < 0.0) return bad("sigma must be finite and >= 0 (source " + std::to_string(i) + ")");
+        if (sigma[i] > smax && !c->opt_deconv_unchecked) {
+            char msg[200];
+            std::snprintf(msg, sizeof(msg), "sigma = %.4g dex of source %lld is above %.2f dex, the largest value the order K = %d is "
+                          "validated for (per-source error below 1e-7; K = 32 reaches 0.09)", sigma[i], (long long)i, smax, K);
+            return bad(msg);
+        }
+        if (!fr && sigma[i] > 0.0 && !std::isfinite(logf[i])) return bad("logf must be finite (source " + std::to_string(i) + ")");
+    }
+    LF_HIP(c, hipSetDevice(c->device));
+    LF_HIP(c, hipDeviceSynchronize());               // (a call in flight may read the buffers replaced below)
+    c->deconv_set = false;
+    std::vector<double> sg((size_t)N), lf_, u_, nodes((size_t)2 * K);
+    for (int64_t i = 0; i < N; ++i) sg[(size_t)i] = sigma[c->perm[(size_t)i]];
+    lfh::gauss_hermite(K, nodes.data(), nodes.data() + K);
+    int rc = upload(c, c->d_sigma, sg, c->d_ghnodes, nodes);
+    if (rc != LF_OK) return rc;
+    DeconvConst dc{};
+    dc.K = K;
+    if (!fr) {
+        lf_.resize((size_t)N), u_.resize((size_t)N);
+        for (int64_t i = 0; i < N; ++i) {
+            lf_[(size_t)i] = logf[c->perm[(size_t)i]];
+            u_[(size_t)i] = std::pow(10.0, lf_[(size_t)i] - LF_FREF);
+        }
+        if ((rc = upload(c, c->d_elogf, lf_, c->d_eU, u_)) != LF_OK) return rc;
+        dc.alpha0 = alpha0;
+        for (int f = 0; f < nf; ++f) dc.flim0[f] = flim0[f];
+    }
+    c->deconvc = dc;
+    c->deconv_set = true;
+    return LF_OK;
+}
+
+int lf_lnprob_err_batch_device(lf_ctx* c, const double* d_theta, int B, double* d_out, void* hip_stream) {
+    int rc = deconv_check(c, "lf_lnprob_err_batch_device", d_theta, B, d_out);
+    if (rc != LF_OK) return rc;
+    LF_HIP(c, hipSetDevice(c->device));
+    // (the rows' plain lnprob: into the context's own buffer, sized before the lnprob path may replace it)
+    if ((rc = ensure_workspace(c, B, 0, 0)) != LF_OK) return rc;
+    return enqueue_deconv(c, d_theta, B, c->d_outB, d_out, (hipStream_t)hip_stream);
+}
+
+int lf_lnprob_err_batch(lf_ctx* c, const double* theta, int B, double* out) {
+    int rc = deconv_check(c, "lf_lnprob_err_batch", theta, B, out);
+    if (rc != LF_OK) return rc;
+    LF_HIP(c, hipSetDevice(c->device));
+    if ((rc = ensure_workspace(c, B, 0, 0)) != LF_OK) return rc;
+    const size_t tb = (size_t)B * c->kc.ndim * sizeof(double);
+    std::memcpy(c->h_theta, theta, tb);
+    LF_HIP(c, hipMemcpyAsync(c->d_theta, c->h_theta, tb, hipMemcpyHostToDevice, c->stream));
+    if ((rc = enqueue_deconv(c, c->d_theta, B, c->d_outB, c->d_outA, c->stream)) != LF_OK) return rc;
+    LF_HIP(c, hipMemcpyAsync(c->h_out, c->d_outA, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    LF_HIP(c, hipStreamSynchronize(c->stream));
+    std::memcpy(out, c->h_out, (size_t)B * sizeof(double));
     return LF_OK;
 }
 
@@ -1598,6 +1770,7 @@ int lf_set_option(lf_ctx* c, const char* key, int64_t value) {
         {"grid_shortcut", [](lf_ctx* c, int64_t v) { c->opt_grid_shortcut = v != 0; }},
         {"compress_grid", [](lf_ctx* c, int64_t v) { c->opt_compress_grid = v != 0; }},
         {"skip_grid", [](lf_ctx* c, int64_t v) { c->opt_skip_grid = v != 0; }},
+        {"deconv_unchecked", [](lf_ctx* c, int64_t v) { c->opt_deconv_unchecked = v != 0; }},
         {"persistent", [](lf_ctx* c, int64_t v) { c->opt_persistent = v < 0 ? 0 : (v > 2 ? 2 : v); }},
         {"profile_every", [](lf_ctx* c, int64_t v) { c->opt_profile_every = v < 1 ? 1 : v; c->prof_tick = 0; }},
         {"profile_span", [](lf_ctx* c, int64_t v) { c->opt_profile_span = v < 1 ? 1 : v; c->prof_tick = 0; }},

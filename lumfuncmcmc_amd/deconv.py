@@ -1,0 +1,185 @@
+"""NumPy twin of the flux-error-convolved likelihood (csrc/lf_deconv.h), no GPU.
+
+The catalogued log-luminosity of a source is its true one plus Gaussian noise of sigma_i dex (its lum_e), and the
+completeness acts on the TRUE flux.  The noise integrates out of the expected counts (piece B is unchanged); each per-source
+term ln[phi(L_i) Omega(L_i, z_i)] of piece A becomes ln of its convolution with N(0, sigma_i^2), taken by K-point
+Gauss-Hermite quadrature and written as a correction to the plain value:
+
+    lnprob_err = lnprob + Delta,   Delta = sum_i Delta_i,   Delta_i = ln sum_k (w_k / sqrt(pi)) exp(t_ik - t_i),
+    delta_ik = sqrt(2) sigma_i x_k,
+    t_ik - t_i = ln10 (alpha + 1) delta - 10^(L_i - L*) (10^delta - 1) + l(f_i 10^delta) - l(f_i),
+
+l = ln fc^(1/d) the completeness in the form without cancellation (grad.py: _completeness; FREE: the row's Flim_f and
+alpha_C, else the fixed ones), L* = L*(z_i) for the z-evolving model.  The statements below are the kernel's, written for
+arrays: expm1 for 10^delta - 1, the inner sum as a log-sum-exp with a running maximum, a source with sigma_i = 0 skipped
+(exactly 0).  The node tables are derived here (Newton on the orthonormal Hermite recurrence in extended precision), as
+lf_hostprep.h derives the device's.
+"""
+import numpy as np
+
+from . import grad as G
+
+LN10 = G.LN10
+ORDERS = (4, 6, 8, 10, 12, 16, 20, 24, 32)      # the supported quadrature orders (lf_layout.h: DECONV_ORDERS)
+# the largest sigma (dex) each order is validated for: worst per-source error below 1e-7 over the probe set of
+# tests/test_deconv_cpu.py (lf_layout.h: DECONV_SIGMA_MAX); no order up to 32 reaches 1e-7 above 0.09 dex
+SIGMA_MAX_BY_ORDER = (0.01, 0.03, 0.04, 0.05, 0.06, 0.06, 0.07, 0.08, 0.09)
+DEFAULT_ORDER = 32                              # the smallest order that reaches 1e-7 at 0.09 dex
+SIGMA_MAX = 0.09
+CHUNK = 1024                                    # sources per block of the device's fixed summation order (lf_layout.h: DECONV_CH)
+
+
+def gauss_hermite(K):
+    """(x[K] ascending, lnw[K] = ln(w_k / sqrt(pi))) of the K-point Gauss-Hermite rule (weight e^(-x^2)): Newton iterations
+    on the orthonormal recurrence in extended precision, the positive roots from the largest down, mirrored."""
+    K = int(K)
+    if K < 2 or K > 64:
+        raise ValueError("gauss_hermite: K must be in 2..64")
+    ld = np.longdouble
+    n = ld(K)
+    pim4 = ld(1.0) / np.sqrt(np.sqrt(ld(np.pi) + ld(1.2246467991473532e-16)))
+    x, w = np.zeros(K, dtype=ld), np.zeros(K, dtype=ld)
+    z = ld(0.0)
+    for i in range((K + 1) // 2):
+        if i == 0:
+            z = np.sqrt(2 * n + 1) - ld(1.85575) * (2 * n + 1) ** (ld(-1.0) / 6)
+        elif i == 1:
+            z = z - ld(1.14) * n ** ld(0.426) / z
+        elif i == 2:
+            z = ld(1.86) * z - ld(0.86) * x[K - 1]
+        elif i == 3:
+            z = ld(1.91) * z - ld(0.91) * x[K - 2]
+        else:
+            z = 2 * z - x[K - i + 1]
+        pp = ld(1.0)
+        for _ in range(100):
+            p1, p2 = pim4, ld(0.0)
+            for j in range(1, K + 1):
+                p3, p2 = p2, p1
+                p1 = z * np.sqrt(ld(2.0) / j) * p2 - np.sqrt(ld(j - 1) / j) * p3
+            pp = np.sqrt(2 * n) * p2
+            dz = p1 / pp
+            z = z - dz
+            if abs(dz) <= ld(1e-18) * max(abs(z), ld(1.0)):
+                break
+        if K % 2 == 1 and i == K // 2:
+            z = ld(0.0)
+            p1, p2 = pim4, ld(0.0)
+            for j in range(1, K + 1):
+                p3, p2 = p2, p1
+                p1 = z * np.sqrt(ld(2.0) / j) * p2 - np.sqrt(ld(j - 1) / j) * p3
+            pp = np.sqrt(2 * n) * p2
+        x[K - 1 - i], x[i] = z, -z
+        w[K - 1 - i] = w[i] = 2 / (pp * pp)
+    lnw = np.log(w) - ld(0.5) * np.log(ld(np.pi) + ld(1.2246467991473532e-16))
+    return x.astype(np.float64), lnw.astype(np.float64)
+
+
+def _lcomp(y, v, aC):
+    """l = ln fc^(1/d) at y = log10(f / Flim), v = f / f_tau (grad.py: _completeness, the value only)"""
+    num = aC * y
+    den = np.sqrt(num * num + 1.0)
+    d = -np.expm1(-v)
+    neg = num < 0.0
+    s = np.where(neg, den - num, den + num)
+    lnfc = np.where(neg, -np.log(2.0 * den * s), np.log1p(-0.5 / (den * s)))
+    return lnfc / d
+
+
+def sigma_max(K):
+    return SIGMA_MAX_BY_ORDER[ORDERS.index(int(K))]
+
+
+def check_sigma(sigma, n, K=None, unchecked=False):
+    """sigma as a float64 array [n], refused as lf_set_lum_err refuses it"""
+    s = np.ascontiguousarray(sigma, dtype=np.float64).ravel()
+    if s.size != n:
+        raise ValueError("sigma must have one value per source (%d), got %d" % (n, s.size))
+    if not np.all(np.isfinite(s)) or np.any(s < 0.0):
+        raise ValueError("sigma must be finite and >= 0")
+    if K is not None and not unchecked and np.any(s > sigma_max(K)):
+        raise ValueError("sigma = %.4g dex is above %.2f dex, the largest value the order K = %d is validated for (per-source "
+                         "error below 1e-7; K = 32 reaches 0.09)" % (s.max(), sigma_max(K), K))
+    return s
+
+
+def _row_terms(inp, sigma, th, x, lnw):
+    """Delta_i [N] of one theta row (catalogue order); no prior test: what the formulas give."""
+    v = inp["variant"]
+    p = G._split(inp, th)
+    fi = np.asarray(inp["field_ind"])
+    lum = np.asarray(inp["lum"], dtype=float)
+    N = lum.shape[0]
+    kappa = G._kappa(inp["fcmin"])
+    c1l = LN10 * (p["al"] + 1.0)
+    if v == "zevol":
+        ls = G._basis(np.asarray(inp["z"], dtype=float), inp["pivots"])
+        t = np.exp(LN10 * (lum - ls.T @ np.asarray(p["L"], dtype=float)))
+    else:
+        t = 10.0 ** (lum - 42.0) * np.exp(LN10 * (42.0 - p["L"]))
+    logf = G.log_flux(lum, inp["DLz"]) if inp.get("logf") is None else np.asarray(inp["logf"], dtype=float)
+    U = 10.0 ** (logf + 17.0)
+    if v == "free":
+        Flim, aC = np.repeat(np.asarray(p["Flim"], dtype=float), np.diff(fi)), float(p["aC"])
+    else:
+        Flim, aC = np.repeat(np.asarray(inp["Flim0"], dtype=float), np.diff(fi)), float(inp["alpha0"])
+    y0 = (logf + 17.0) - np.log10(Flim)
+    v0 = U * (np.exp(LN10 * kappa / aC) / Flim)
+    l0 = _lcomp(y0, v0, aC)
+    s2 = np.sqrt(2.0) * sigma
+    m = np.full(N, -np.inf)
+    acc = np.zeros(N)
+    for k in range(len(x)):
+        dl = s2 * x[k]
+        em = np.expm1(LN10 * dl)
+        a = lnw[k] + ((c1l * dl - t * em) + (_lcomp(y0 + dl, v0 * (em + 1.0), aC) - l0))
+        skip = a == -np.inf
+        d = a - m
+        e = np.exp(-np.abs(d))
+        up = d > 0.0
+        acc_n = np.where(up, acc * e + 1.0, acc + e)
+        m_n = np.where(up, a, m)
+        acc = np.where(skip, acc, acc_n)
+        m = np.where(skip, m, m_n)
+    out = m + np.log(acc)
+    return np.where(sigma == 0.0, 0.0, out)
+
+
+def delta(inp, sigma, theta, K=None, terms=False, unchecked=True):
+    """theta (B, ndim) or (ndim,) -> Delta[B]; with terms=True also Delta_i [B, N] (catalogue order) and S_abs[B] = sum_i
+    |Delta_i|, the scale rounding is judged by.  The sum over sources is taken in catalogue order (the device's order is its
+    own: chunks of CHUNK sources of one field).  unchecked=False: sigma above the order's validated range is refused."""
+    K = DEFAULT_ORDER if K is None else int(K)
+    if K not in ORDERS:
+        raise ValueError("deconvolve_order must be one of %s" % (ORDERS,))
+    th = np.asarray(theta, dtype=np.float64)
+    single = th.ndim == 1
+    th = np.atleast_2d(th)
+    if th.shape[1] != G.ndim_of(inp):
+        raise ValueError("theta must be (B, %d), got %s" % (G.ndim_of(inp), th.shape))
+    sigma = check_sigma(sigma, len(inp["lum"]), K, unchecked)
+    x, lnw = gauss_hermite(K)
+    D = np.empty((len(th), sigma.size))
+    with np.errstate(all="ignore"):
+        for b, row in enumerate(th):
+            D[b] = _row_terms(inp, sigma, row, x, lnw)
+    tot, sabs = D.sum(axis=1), np.abs(D).sum(axis=1)
+    if single:
+        return (tot[0], D[0], sabs[0]) if terms else tot[0]
+    return (tot, D, sabs) if terms else tot
+
+
+def lnprob_err(inp, sigma, theta, K=None, terms=False):
+    """lnprob + Delta per row, with lnprob from grad.py's twin; a row whose lnprob is -inf stays -inf, NaN becomes -inf.
+    terms=True: (value, lnprob, S_abs)."""
+    th = np.asarray(theta, dtype=np.float64)
+    single = th.ndim == 1
+    th2 = np.atleast_2d(th)
+    lp = np.atleast_1d(G.lnprob_grad(inp, th2)[0])
+    tot, _, sabs = delta(inp, sigma, th2, K, terms=True)
+    with np.errstate(all="ignore"):
+        out = np.where(np.isfinite(lp), lp + tot, -np.inf)
+    out = np.where(np.isnan(out), -np.inf, out)
+    if single:
+        return (out[0], lp[0], sabs[0]) if terms else out[0]
+    return (out, lp, sabs) if terms else out

@@ -471,13 +471,40 @@ def generator(inputs, device=True, device_index=0):
     return MockGenerator(inputs, device=device_index) if device else MockTwin(inputs)
 
 
-def catalogue_lists(z, logL, field, nf):
-    """Per-field lists in the form the model constructors take: z, lum, lum_e (zeros), field_ind."""
+NOISE_PURPOSE = 3             # the Philox purpose tag of the measurement noise (0: counts, 1 and 2: the sources; lf_mock.h)
+
+
+def lum_noise(n_per_field, row_id, seed):
+    """Standard normal deviates of the sources 0 .. n_f - 1 of every field f of one row (concatenated field by field):
+    Box-Muller on the two 53-bit uniforms of the Philox block (row_id, index, NOISE_PURPOSE, f) - a stream of its own, so the
+    noiseless draws keep their bits.  Host arithmetic for both generators."""
+    out = []
+    for f, n in enumerate(n_per_field):
+        w = _words(row_id, np.arange(int(n), dtype=np.uint64), NOISE_PURPOSE, f, seed)
+        u1, u2 = philox.u53(w[0], w[1]), philox.u53(w[2], w[3])
+        out.append(np.sqrt(-2.0 * np.log1p(-u1)) * np.cos(2.0 * np.pi * u2))         # (1 - u1 in (0, 1]: no log of 0)
+    return np.concatenate(out) if out else np.zeros(0)
+
+
+def catalogue_lists(z, logL, field, nf, lum_err=None, seed=0, row_id=0):
+    """Per-field lists in the form the model constructors take: z, lum, lum_e, field_ind.  lum_err=None: lum as drawn and
+    lum_e zeros.  lum_err a scalar or one value per field (dex): Gaussian noise of that width is added to every drawn logL
+    (after detection: the model of DESIGN.md section 3.18) from lum_noise's stream, lum_e is filled with it, and the
+    noiseless luminosities are returned as lum_true."""
     order = np.argsort(field, kind="stable")
     z, logL, field = z[order], logL[order], field[order]
     fi = np.concatenate([[0], np.cumsum(np.bincount(field, minlength=nf))]).astype(np.int64)
     split = lambda a: [a[fi[f]:fi[f + 1]].copy() for f in range(nf)]    # noqa: E731
-    return {"z": split(z), "lum": split(logL), "lum_e": [np.zeros(fi[f + 1] - fi[f]) for f in range(nf)], "field_ind": fi}
+    if lum_err is None:
+        return {"z": split(z), "lum": split(logL), "lum_e": [np.zeros(fi[f + 1] - fi[f]) for f in range(nf)], "field_ind": fi}
+    sg = np.asarray(lum_err, dtype=np.float64)
+    if sg.ndim == 0:
+        sg = np.full(nf, float(sg))
+    if sg.shape != (nf,) or not np.all(np.isfinite(sg)) or np.any(sg < 0.0):
+        raise ValueError("lum_err must be a finite scalar >= 0 or one such value per field")
+    per = np.repeat(sg, np.diff(fi))
+    noisy = logL + per * lum_noise(np.diff(fi), row_id, seed)
+    return {"z": split(z), "lum": split(noisy), "lum_e": split(per), "field_ind": fi, "lum_true": split(logL)}
 
 
 def predictive(gen, rows, edges, observed_lum, observed_fi, seed):

@@ -185,12 +185,45 @@ class _Base(object):
                 self._ctx.set_option("grid_share", rank + 65536 * world)
             if self.compress:
                 self._ctx.set_option("compress", 1)
+            if self.deconvolve:
+                self._ctx.set_lum_err(self.lum_e, self.deconvolve_order, unchecked=self.deconvolve_unchecked)
             self._ctx_key = key
         return self._ctx
+
+    # ------------------------------------------------------------------ flux-error-convolved likelihood
+    deconvolve = False             # True: lnprob is the likelihood convolved with the sources' lum_e (csrc/lf_deconv.h), opt-in
+    deconvolve_order = None        # its Gauss-Hermite order (None: the library's default)
+    deconvolve_unchecked = False   # True: lum_e above the order's validated range is taken as it is
+
+    def _init_deconvolve(self, deconvolve, deconvolve_order):
+        from . import deconv
+        self.deconvolve, self.deconvolve_order = bool(deconvolve), deconvolve_order
+        if not self.deconvolve:
+            return
+        if self.lum_e is None:
+            raise ValueError("deconvolve=True needs lum_e (or flux_e): the sources' errors are what the likelihood is convolved with")
+        if self.min_comp_frac > 0.001:
+            raise ValueError("deconvolve=True needs min_comp_frac <= 0.001: a cut on the observed flux would change the "
+                             "expected counts, which the convolved likelihood leaves as they are")
+        if self.shard != "walkers":
+            raise NotImplementedError("deconvolve=True is not implemented for shard='sources'")
+        K = deconv.DEFAULT_ORDER if deconvolve_order is None else int(deconvolve_order)
+        if K not in deconv.ORDERS:
+            raise ValueError("deconvolve_order must be one of %s" % (deconv.ORDERS,))
+        self.deconvolve_order = K
+        deconv.check_sigma(self.lum_e, len(self.lum), K, self.deconvolve_unchecked)
+
+    def _refuse_deconvolve(self, what):
+        if self.deconvolve:
+            raise NotImplementedError("%s runs on the plain likelihood's device sampler or gradient: it is not implemented "
+                                      "for deconvolve=True (use fit_model)" % what)
 
     def _evaluate(self, theta):
         th = np.asarray(theta, dtype=np.float64)
         scalar = th.ndim == 1
+        if self.deconvolve and self.lnprob_fn is None:
+            out = self.context().lnprob_err_batch(th)
+            return float(out[0]) if scalar else out
         if self.lnprob_fn is not None:
             out = np.asarray(self.lnprob_fn(np.atleast_2d(th)))
         else:
@@ -244,7 +277,9 @@ class _Base(object):
             tdist.broadcast_object_list(box, src=0)
             pos, seed = box
         self.start_pos, self.sampler_seed = np.array(pos), seed       # (start, seed) reproduce the chain
-        if self.lnprob_fn is None and getattr(self, "device_sampler", True):
+        if self.deconvolve and (world > 1 or self.lnprob_fn is not None):
+            raise NotImplementedError("fit_model with deconvolve=True runs on one GPU and cannot use lnprob_fn")
+        if self.lnprob_fn is None and getattr(self, "device_sampler", True) and not self.deconvolve:
             # the whole stretch move runs on the device (theta never leaves HBM).  With several ranks every half-step
             # is sharded - by walker (all-gather of lnprob, RCCL) or by source (all-reduce), see `shard` - and
             # accepted on every rank.
@@ -295,6 +330,7 @@ class _Base(object):
         maximum a posteriori (map_init_walkers; fit_model_map runs first when it has not) instead of the prior box."""
         if start not in ("box", "map"):
             raise ValueError('start must be "box" or "map"')
+        self._refuse_deconvolve("fit_model_converged")
         rank, world = self._dist_state()
         if world > 1:
             raise NotImplementedError("fit_model_converged runs on one GPU: diagnostics across several ranks are not implemented")
@@ -351,6 +387,7 @@ class _Base(object):
     # ------------------------------------------------------------------ maximum a posteriori (mapfit.py)
     def _grad_fn(self):
         """The batched (lnprob, gradient) callable of the current configuration: the device's (LFContext.lnprob_grad)."""
+        self._refuse_deconvolve("the gradient (fit_model_map, map_init_walkers)")
         rank, world = self._dist_state()
         if world > 1:
             raise NotImplementedError("the gradient runs on one GPU: source- or walker-sharded gradients are not implemented")
@@ -435,6 +472,7 @@ class _Base(object):
         `betas`, or geometric up to Tmax (None: tmax_from_box on the prior box) over ntemps temperatures (None:
         default_ntemps(Tmax)).  Sets self.samples from the beta = 1 chain as fit_model does, and self.pt_sampler,
         self.lnZ, self.dlnZ (fburnin: the leading fraction of steps the estimator leaves out)."""
+        self._refuse_deconvolve("fit_model_pt")
         rank, world = self._dist_state()
         if world > 1:
             raise NotImplementedError("fit_model_pt runs on one GPU: parallel tempering over several ranks is not implemented")
@@ -525,18 +563,21 @@ class _Base(object):
             self._mock_key = key
         return self._mock
 
-    def mock_catalogue(self, theta, seed=None, device=None):
+    def mock_catalogue(self, theta, seed=None, device=None, lum_err=None):
         """One catalogue drawn from the model at `theta`: the Poisson process whose likelihood
         lnprob evaluates, on this object's integration grid.  Returns the per-field lists both constructors take - z, lum,
         lum_e (zeros), field_ind - plus theta and seed.  seed=None draws one from numpy's global state (as fit_model does);
         device=True the GPU, False NumPy, None the GPU when this object already holds a device context (one GPU; with
-        several ranks call it on one)."""
+        several ranks call it on one).  lum_err (dex; a scalar or one value per field): Gaussian measurement noise of that
+        width is added to the drawn luminosities after detection - the model deconvolve=True fits -
+        from a Philox stream of its own, on the host for both generators; lum_e is then filled and lum_true holds the
+        noiseless values.  None: the output is what it was without the keyword, bit for bit."""
         if seed is None:
             seed = int(np.random.randint(0, 2 ** 31 - 1))
         theta = np.asarray(theta, dtype=np.float64).ravel()
         gen = self._mock_generator(device)
         z, lum, fld, _ = gen.draw(theta[None], seed)
-        out = mock.catalogue_lists(z, lum, fld, self.nfields)
+        out = mock.catalogue_lists(z, lum, fld, self.nfields, lum_err=lum_err, seed=seed)
         out["theta"], out["seed"] = theta.copy(), int(seed)
         return out
 
@@ -603,7 +644,8 @@ class LumFuncMCMC(_Base):
                  nboot=100, sch_al=-1.6, sch_al_lims=[-3.0, 1.0], Lstar=42.5, Lstar_lims=[40.0, 45.0],
                  phistar=-3.0, phistar_lims=[-8.0, 5.0], Lc=40.0, Lh=46.0, nwalkers=100, nsteps=1000,
                  fix_sch_al=False, fcmin=0.1, fix_comp=False, min_comp_frac=0.5,
-                 field_names=None, field_ind=None, diff_rand=True, device=0, compress=False, shard="walkers"):
+                 field_names=None, field_ind=None, diff_rand=True, device=0, compress=False, shard="walkers",
+                 deconvolve=False, deconvolve_order=None):
         self._common_init(z, flux, flux_e, lum, lum_e)
         self.device = device
         self.compress = bool(compress)
@@ -635,6 +677,7 @@ class LumFuncMCMC(_Base):
         self.size_ln = 201 if self.fix_comp else 101
         self.setlnsimple(need_integ=bool(self.fix_comp))
         self.setup_logging()
+        self._init_deconvolve(deconvolve, deconvolve_order)
 
     def getRoot(self, size=201):
         self.rootsf = hs.completeness_roots(self.Flim_lims, self.alpha_lims, self.fcmin, self.min_comp_frac, size)
@@ -813,7 +856,8 @@ class LumFuncMCMCz(_Base):
                  nboot=100, sch_al=-1.6, sch_al_lims=[-3.0, 1.0], Lstar=42.5, Lstar_lims=[41.0, 45.0],
                  phistar=-3.0, phistar_lims=[-8.0, 5.0], Lc=40.0, Lh=46.0, nwalkers=100, nsteps=1000,
                  fcmin=0.1, min_comp_frac=0.5, field_names=None,
-                 field_ind=None, z1=1.20, z2=1.53, z3=1.86, fix_sch_al=False, device=0, compress=False, shard="walkers"):
+                 field_ind=None, z1=1.20, z2=1.53, z3=1.86, fix_sch_al=False, device=0, compress=False, shard="walkers",
+                 deconvolve=False, deconvolve_order=None):
         self._common_init(z, flux, flux_e, lum, lum_e)
         self.device = device
         self.compress = bool(compress)
@@ -846,6 +890,7 @@ class LumFuncMCMCz(_Base):
         self.size_ln = 201
         self.setlnsimple(need_integ=True)
         self.setup_logging()
+        self._init_deconvolve(deconvolve, deconvolve_order)
 
     def getRoot(self):
         """Per-field flux at which the completeness equals min_comp_frac (lumfuncmcmc_z.py:292-297);
