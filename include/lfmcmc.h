@@ -94,6 +94,12 @@ int lf_abi_version(void);
  * "grid_share" option (0, 0: the whole grid). */
 int lf_deal_table(int n_cell_chunks, int n_bins, int grid_part, int grid_parts, int32_t *table, int64_t cap);
 
+/* ... and who finishes a tile of lf_free's polling hand-over under that deal: ranks[g] = the physical
+ * rank, among the 8 (g + 1) workgroups that serve a tile, with the largest dealt cost (rank r serves the virtual ranks r,
+ * r + 8 (g + 1), ...; a bin this share integrates costs 8, a cell chunk 3, the ranks of the group's younger half start 8
+ * behind; ties go to the highest rank). */
+int lf_deal_finishers(int n_cell_chunks, int n_bins, int grid_part, int grid_parts, int32_t ranks[4]);
+
 /* Replaces the read side of LumFuncMCMC.__init__ / LumFuncMCMCz.__init__ (lumfuncmcmc.py:162-177):
  * copies the catalogue and grids to HBM, derives the parameter-independent per-source and
  * per-node tables.  Returns NULL on failure; lf_last_error(NULL) then holds the reason.

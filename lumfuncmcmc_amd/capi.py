@@ -46,7 +46,7 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_lnprob_batch_device", "lf_lnprob_batch_device_n", "lf_lnprob_pieces", "lf_set_profiling", "lf_kernel_times",
            "lf_set_option", "lf_last_error", "lf_sampler_create", "lf_sampler_destroy", "lf_sampler_start",
            "lf_sampler_run", "lf_sampler_read", "lf_sampler_steps", "lf_sampler_half_eval",
-           "lf_sampler_half_accept", "lf_compress_keys", "lf_compress_grid", "lf_grid_bins", "lf_deal_table", "lf_form_counts", "lf_last_launch",
+           "lf_sampler_half_accept", "lf_compress_keys", "lf_compress_grid", "lf_grid_bins", "lf_deal_table", "lf_deal_finishers", "lf_form_counts", "lf_last_launch",
            "lf_free_block_uploads", "lf_veff",
            "lf_lumfunc_quantiles", "lf_lumfunc_quantiles_ms", "lf_ptsampler_create", "lf_ptsampler_destroy",
            "lf_ptsampler_start", "lf_ptsampler_run", "lf_ptsampler_read", "lf_ptsampler_steps", "lf_mock_create",
@@ -287,6 +287,19 @@ def deal_table(n_cell_chunks, n_bins, grid_part=0, grid_parts=0):
     cells = [lst[t[v]:t[v + 1]].tolist() for v in range(VF)]
     bins = [lst[n_cell_chunks + t[VF + 1 + v]:n_cell_chunks + t[VF + 2 + v]].tolist() for v in range(VF)]
     return cells, bins
+
+
+def deal_finishers(n_cell_chunks, n_bins, grid_part=0, grid_parts=0):
+    """Host-only: the physical rank that finishes a tile of lf_free's polling hand-over, for tiles served by 8, 16, 24 and 32
+    workgroups (csrc/lf_hostprep.h: deal_finishers) - the rank the deal of deal_table() loads most.
+    Touches no GPU."""
+    lib = load()
+    lib.lf_deal_finishers.restype = ctypes.c_int
+    lib.lf_deal_finishers.argtypes = [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int32)]
+    r = (ctypes.c_int32 * 4)()
+    if lib.lf_deal_finishers(int(n_cell_chunks), int(n_bins), int(grid_part), int(grid_parts), r) != 0:
+        raise ValueError("lf_deal_finishers: bad arguments")
+    return [int(v) for v in r]
 
 
 def grid_bins(params, L, wL, ck, Dk):
@@ -744,6 +757,8 @@ class LFContext(object):
         if d["fused"]:
             d["kind"] -= 1
         d["kernel"] = "lf_free<%d>" % d["st"] if d["kind"] == 2 else ("lf_pers" if d["kind"] == 4 else "lf_main")
+        if d["kind"] in (2, 4):                     # the persistent kernels: groups of 8 workgroups, group k on tiles k % ntiles, + tile_stride, ...
+            d["tile_stride"] = d["workgroups"] // 8
         return d
 
     def free_block_uploads(self):

@@ -63,6 +63,8 @@ struct FreeArgs {
     const int* cc_len;        // [nchC] its cells (<= 64: one per lane of a wave; the waves take one walker each)
     const int* cc_field;      // [nchC]
     int nchC;                 // cell chunks (64 cells; 0: no cells)
+    int fin_ranks;            // who finishes a polling tile: the physical rank per group size fgroup = 8, 16, 24, 32, one byte each (lf_tile.h:
+                              // tile_finisher; from the deal's costs, lf_hostprep.h: deal_finishers; FIN_LAST without a deal or with poll off)
     double* partC;            // [B][nslot]: the cells' sums, likewise
     const int* wstat;         // [B]
     // FUSED instantiation: lf_prepare's and lf_finalize's work is done here, one launch per evaluation (plain lnprob
@@ -171,6 +173,7 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
         // Only the source chunks - unequal, and only needed by walkers that cannot use the cells - are claimed from queues.
         int fgroup, frank;
         tile_ranks(tile, la.ntiles, la.tile_stride, fgroup, frank);
+        const bool finisher = FUSED && fa.poll && frank == tile_finisher(fa.fin_ranks, fgroup);      // (of this tile, if it hands over by polling)
         bool no_src = false;                       // (thread 0's view) every walker of the tile is summed over the cells
         auto grab = [&]() -> int {
             if (no_src) return -1;
@@ -296,6 +299,11 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
         t_prep = __builtin_amdgcn_s_memtime();
 #endif
         const int cellmask = __builtin_amdgcn_readfirstlane(scell);
+        // The polling tile's finisher keeps its own partial sums: lane 63 of walker v's wave puts the sum of virtual rank vr where
+        // that wave's lane vr finds it for the final addition (cells: sown[v * 128 + vr], grid: + 64) - the same wave writes and
+        // reads, and `red` past its first PB values is free in a tile without source items.
+        const bool keep_own = finisher && uni(snosrc);
+        double* __restrict__ sown = red + PB;
         // (No register prefetch of the next item: it would cost 16 VGPRs across the whole walker loop, and with 128 per
         // wave that means scratch traffic inside the loop - measured 4x slower.  The other workgroup of the CU computes
         // while this one waits for its item at switch-in.)
@@ -375,7 +383,10 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
                 acc = wave_sum_dpp(acc);          // lane 63: the wave's total
                 const int ln = fresh_tid() & 63;
                 double* __restrict__ row = fa.partC + (size_t)(w0 + v) * fa.nslot;
-                if (ln == 63) pstore<FUSED>(row + vr, acc);
+                if (ln == 63) {
+                    if (keep_own) sown[v * 128 + vr] = acc;
+                    else pstore<FUSED>(row + vr, acc);
+                }
             }
             }
         }
@@ -464,7 +475,10 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
                 bsum = wave_sum_dpp(bsum);        // lane 63: the wave's total
                 const int ln = fresh_tid() & 63;
                 double* __restrict__ row = fa.partB + (size_t)(w0 + v) * fa.nslot;
-                if (ln == 63) pstore<FUSED>(row + vr, bsum);
+                if (ln == 63) {
+                    if (keep_own) sown[v * 128 + 64 + vr] = bsum;
+                    else pstore<FUSED>(row + vr, bsum);
+                }
             }
             }
         } else
@@ -519,7 +533,10 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
                 bsum = wave_sum_dpp(bsum);        // lane 63: the wave's total
                 const int ln = fresh_tid() & 63;
                 double* __restrict__ row = fa.partB + (size_t)(w0 + v) * fa.nslot;
-                if (ln == 63) pstore<FUSED>(row + vr, bsum);
+                if (ln == 63) {
+                    if (keep_own) sown[v * 128 + 64 + vr] = bsum;
+                    else pstore<FUSED>(row + vr, bsum);
+                }
             }
             }
         }
@@ -698,13 +715,16 @@ __device__ __forceinline__ void lf_free_body(const KConst& kc, const SrcArrays& 
         }
         if (FUSED && fa.poll && uni(snosrc)) {
             // Hand-over by polling (lf_tile.h: PART_EMPTY): this workgroup's partial sums are on their way, written through; only
-            // the tile's finisher has more to do.
-            if (frank == fgroup - 1) {
+            // the tile's finisher has more to do - the workgroup expected to end last (lf_tile.h), whose own sums are in LDS: by now
+            // the others' are in memory, and one round of loads brings them.
+            if (finisher) {
                 const int t = fresh_tid(), v = t >> 6, ln = t & 63;
                 const int nB = fa.nchB > 0 ? fa.nslot : 0, nC = fa.nchC > 0 ? fa.nslot : 0;
                 if (v < nw) {
+                    const bool own = ln % fgroup == frank;      // (the slots of the virtual ranks frank, frank + fgroup, ...)
                     double pre[2] = {0.0, 0.0};
-                    poll_finish(fa.partB, fa.partC, w0 + v, fa.nslot, nB, nC, ln, fa.err, pre);
+                    if (own && ln < fa.nslot) pre[0] = sown[v * 128 + ln], pre[1] = sown[v * 128 + 64 + ln];
+                    poll_finish(fa.partB, fa.partC, w0 + v, fa.nslot, nB, nC, ln, fa.err, pre, own);
                     finalize_wave<true>(fa.partA, 0, fa.nchA, fa.partB, nB, nB, nC > 0 ? fa.partC : nullptr, nC, (int)STAT_CELLS,
                                         sstat - w0, sbase - w0, w0 + v, ln, ap, la.out, nullptr, nullptr, 0,
                                         STEP ? sprop + v * 16 : nullptr, STEP ? szz + v : nullptr, STEP ? spre + 2 * v : nullptr, pre);

@@ -6,6 +6,7 @@
 // member, by the functions that derive its members (the context's copy starts zeroed and is compared by bytes).
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -750,6 +751,37 @@ inline std::vector<int> make_deal(int nchC, int nbq, int grid_part, int grid_par
     for (int i = 0; i < nchC; ++i) t[DEAL_LIST + at_c[own_c[i]]++] = i;
     for (int b = 0; b < nbq; ++b) t[DEAL_LIST + nchC + at_b[own_b[b]]++] = b;
     return t;
+}
+
+// ---- who finishes a tile of lf_free's polling hand-over (lf_tile.h): the workgroup expected to END LAST, so that the others'
+// partial sums are in memory when it gets there.  Per group size fgroup = 8, 16, 24, 32 (entry fgroup / 8 - 1; lf_tile.h:
+// tile_ranks) the PHYSICAL rank with the largest dealt cost: rank r of fgroup serves the virtual ranks r, r + fgroup, ... of the
+// deal table t, a bin this context integrates costs cost_b, a cell chunk 3, and the ranks of the group's younger half
+// (r >= fgroup / 2: the second workgroups of their CUs) start cost_h behind - make_deal's units and make_deal's handicap.  Ties
+// go to the highest rank, the youngest.  Like the table, the ranks depend on the context only.
+inline std::array<int, 4> deal_finishers(const std::vector<int>& t, int nchC, int nbq, int grid_part, int grid_parts, int cost_h = 8,
+                                         int cost_b = 8) {
+    int vcost[VF];
+    for (int v = 0; v < VF; ++v) {
+        vcost[v] = 3 * (t[v + 1] - t[v]);
+        for (int i = t[DEAL_BINS + v]; i < t[DEAL_BINS + v + 1]; ++i) {
+            const int b = t[DEAL_LIST + nchC + i];
+            vcost[v] += grid_parts > 1 && b % grid_parts != grid_part ? 0 : cost_b;
+        }
+    }
+    (void)nbq;
+    std::array<int, 4> fin{};
+    for (int g = 0; g < 4; ++g) {
+        const int fgroup = 8 * (g + 1);
+        int best = 0, bestc = -1;
+        for (int r = 0; r < fgroup; ++r) {
+            int c = r >= fgroup / 2 ? cost_h : 0;
+            for (int v = r; v < VF; v += fgroup) c += vcost[v];
+            if (c >= bestc) best = r, bestc = c;
+        }
+        fin[(size_t)g] = best;
+    }
+    return fin;
 }
 
 // ---- the quantile arguments of the band entries (lf_bands.h: bands_quantiles; lf_veffdraws.h), checked and prepared: q[nq] in

@@ -10,10 +10,17 @@ constexpr int PTW = 8;       // walkers per tile
 constexpr int QSTRIDE = 9;   // counters per tile: [0] grid queue, [1..8] catalogue queues of XCD 0..7
 // The one-launch form's hand-over by POLLING (tiles whose walkers are all on the cells: the normal case).  The slots of partB /
 // partC hold PART_EMPTY between launches (the host fills them, every finisher leaves them so); a workgroup writes its partial
-// sums through and is done; the tile's FINISHER - the workgroup of the last physical rank, the lightest of the deal - reads the
-// slots past its caches until none is empty, adds them up and empties them again.  Against the counter (every workgroup:
-// wait for the stores' acknowledgements, count, wait for the count; the last one: load, add) the launch's critical path
-// loses two of its three trips to memory.  A partial sum is never PART_EMPTY (a NaN is made canonical before it is stored);
+// sums through and is done; the tile's FINISHER reads the slots past its caches until none is empty, adds them up and empties
+// them again.  Against the counter (every workgroup: wait for the stores' acknowledgements, count, wait for the count; the last
+// one: load, add) the launch's critical path loses two of its three trips to memory.
+// WHO finishes: lf_free - the workgroup the deal expects to END LAST (the physical rank with the largest dealt cost, from the
+// host: lf_hostprep.h deal_finishers, tile_finisher below), so that the others' sums are in memory when it gets there and the
+// launch's last sums go from its own registers straight into the final addition: its own slots it neither stores nor polls
+// nor empties (they stay PART_EMPTY), their values reach finalize_wave through LDS in the slots' positions - the order of
+// every sum is the deal's, whoever adds.  (With the last rank - the lightest of the deal, done early - as finisher the slowest
+// workgroup's store, half a poll round and the poll's way back lay between the launch's last sum and its end: DESIGN.md 3.4d.)
+// lf_pers, and lf_free without a deal or with "poll" off: the workgroup of the last physical rank.
+// A partial sum is never PART_EMPTY (a NaN is made canonical before it is stored);
 // a finisher that has polled PART_POLLS times without success writes NaN (emcee raises on NaN) and sets the error word.
 constexpr unsigned long long PART_EMPTY = 0x7ff8dead7ff8deadull;
 constexpr int PART_POLLS = 1 << 19;
@@ -27,6 +34,14 @@ __device__ __forceinline__ void tile_ranks(int tile, int ntiles, int tile_stride
         fgroup = 8 * ((tile_stride - tile + ntiles - 1) / ntiles);
         frank += 8 * ((k - tile) / ntiles);
     }
+}
+
+// lf_free's finisher of a tile served by fgroup workgroups: byte fgroup / 8 - 1 of the host's word (FreeArgs::fin_ranks), never
+// past the last rank.  The rank depends on the context and on fgroup only: a group that loops over several tiles keeps one
+// finisher, and nobody waits on a waiter.
+constexpr int FIN_LAST = 0x1f170f07;      // the last rank of every group size
+__device__ __forceinline__ int tile_finisher(int fin_ranks, int fgroup) {
+    return min((fin_ranks >> (fgroup - 8)) & 0xff, fgroup - 1);
 }
 
 // A partial sum: in the fused form it is read by a workgroup on another XCD while the launch is still running, so it is
@@ -52,31 +67,34 @@ __device__ __forceinline__ void accept_terms_ahead(const StepArgs& sp, const Acc
 }
 
 // Lane ln of walker w's wave empties the walker's slots for the next launch (visible to it: a kernel boundary lies between):
-// the first nC of partC, the first nB of partB
-__device__ __forceinline__ void empty_slots(double* partB, double* partC, int w, int nslot, int nB, int nC, int ln) {
-    if (ln < nC) __hip_atomic_store(partC + (size_t)w * nslot + ln, __longlong_as_double((long long)PART_EMPTY), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (ln < nB) __hip_atomic_store(partB + (size_t)w * nslot + ln, __longlong_as_double((long long)PART_EMPTY), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// the first nC of partC, the first nB of partB.  own: the lane's slots were never written (lf_free's finisher keeps its own sums)
+__device__ __forceinline__ void empty_slots(double* partB, double* partC, int w, int nslot, int nB, int nC, int ln, bool own = false) {
+    if (ln < nC && !own) __hip_atomic_store(partC + (size_t)w * nslot + ln, __longlong_as_double((long long)PART_EMPTY), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (ln < nB && !own) __hip_atomic_store(partB + (size_t)w * nslot + ln, __longlong_as_double((long long)PART_EMPTY), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // The polling finisher (PART_EMPTY above), lane ln of walker w's wave: reads the first nC slots of partC and nB of partB past
 // its caches until none is empty, leaves what it read in pre (pre[0] partC's slot ln, pre[1] partB's) and empties the slots
-// again.  The sum itself is the kernel's: finalize_wave with the values in hand.
-__device__ __forceinline__ void poll_finish(double* partB, double* partC, int w, int nslot, int nB, int nC, int ln, int* err, double (&pre)[2]) {
+// again.  A lane whose slots have arrived does not load again: only the lanes still empty go round (the polls of 16 finishers x 8
+// waves share the memory system with the workgroups still at work).  own: the lane's slots are this workgroup's own - pre holds
+// them already, they are neither read nor emptied.  The sum itself is the kernel's: finalize_wave with the values in hand.
+__device__ __forceinline__ void poll_finish(double* partB, double* partC, int w, int nslot, int nB, int nC, int ln, int* err, double (&pre)[2],
+                                            bool own = false) {
     double* __restrict__ pb = partB + (size_t)w * nslot;
     double* __restrict__ pc = partC + (size_t)w * nslot;
     int tries = 0;
-    bool have;
+    bool wc = ln < nC && !own, wb = ln < nB && !own;      // still empty
     do {
-        if (ln < nC) pre[0] = __hip_atomic_load(pc + ln, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (ln < nB) pre[1] = __hip_atomic_load(pb + ln, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        have = !((ln < nC && (unsigned long long)__double_as_longlong(pre[0]) == PART_EMPTY) ||
-                 (ln < nB && (unsigned long long)__double_as_longlong(pre[1]) == PART_EMPTY));
-    } while (!__all(have) && ++tries < PART_POLLS);
+        if (wc) pre[0] = __hip_atomic_load(pc + ln, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (wb) pre[1] = __hip_atomic_load(pb + ln, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        wc = wc && (unsigned long long)__double_as_longlong(pre[0]) == PART_EMPTY;
+        wb = wb && (unsigned long long)__double_as_longlong(pre[1]) == PART_EMPTY;
+    } while (__any(wc || wb) && ++tries < PART_POLLS);
     if (tries >= PART_POLLS) {        // (cannot happen while the device runs the launch's other workgroups)
         pre[0] = pre[1] = __builtin_nan("");
         if (ln == 0) atomicExch(err, 1);
     }
-    empty_slots(partB, partC, w, nslot, nB, nC, ln);
+    empty_slots(partB, partC, w, nslot, nB, nC, ln, own);
 }
 
 // This thread's number, its wave and its lane, as a kernel makes them (lf_free: anew at every use, see fresh_tid there)

@@ -86,6 +86,7 @@ struct lf_ctx {
     Buf<int> d_cc_start;                 // [ncchunk] first cell of the chunk
     Buf<int> d_deal;                     // lf_free's deal of cell chunks and flux bins to its virtual workgroups (lf_free.h: DEAL_*)
     int64_t deal_key = -1;               // ... made for this (cell chunks, bins, grid share)
+    int deal_fin = lf::FIN_LAST;         // ... and who finishes a polling tile under it, per group size (lf_tile.h: tile_finisher)
     Buf<int> d_cc_len;                   // [ncchunk] cells in the chunk (<= 64)
     Buf<int> d_cc_field;                 // [ncchunk]
     int ncell = 0, ncchunk = 0;
@@ -433,6 +434,17 @@ std::vector<int> make_deal(int nchC, int nbq, int grid_part, int grid_parts) {
     return lfh::make_deal(nchC, nbq, grid_part, grid_parts, h ? std::atoi(h) : 8, b ? std::atoi(b) : 8);
 }
 
+// ... and the finisher ranks that go with it (lf_hostprep.h: deal_finishers), packed a byte per group size as the kernel reads them.
+// A/B runs (is the computed rank the one that ends last?): LF_FIN_SHIFT moves every rank up or down, LF_FIN_RANK names it.
+int deal_finishers(const std::vector<int>& t, int nchC, int nbq, int grid_part, int grid_parts) {
+    const char *h = std::getenv("LF_DEAL_H"), *b = std::getenv("LF_DEAL_B"), *sh = std::getenv("LF_FIN_SHIFT"), *fr = std::getenv("LF_FIN_RANK");
+    const std::array<int, 4> f = lfh::deal_finishers(t, nchC, nbq, grid_part, grid_parts, h ? std::atoi(h) : 8, b ? std::atoi(b) : 8);
+    int word = 0;
+    for (int g = 0; g < 4; ++g)
+        word |= std::min(std::max((fr ? std::atoi(fr) : f[(size_t)g]) + (sh ? std::atoi(sh) : 0), 0), 8 * g + 7) << (8 * g);
+    return word;
+}
+
 int ensure_deal(lf_ctx* c, int nchC, int nbq, hipStream_t s) {
     using namespace lf;
     const int64_t key = nbq <= 0 || DEAL_LIST + nchC + nbq > DEAL_MAX || std::getenv("LF_NO_DEAL")      // (the variable: A/B runs)
@@ -443,6 +455,7 @@ int ensure_deal(lf_ctx* c, int nchC, int nbq, hipStream_t s) {
         if (!c->d_deal) LF_HIP(c, c->d_deal.alloc(DEAL_MAX));
         if (c->any_enqueued) LF_HIP(c, hipStreamSynchronize(c->last_stream));        // (a launch may still be reading the old table)
         LF_HIP(c, hipMemcpy(c->d_deal, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
+        c->deal_fin = deal_finishers(t, nchC, nbq, c->kc.grid_part, c->kc.grid_parts);
     }
     c->deal_key = key;
     return LF_OK;
@@ -513,7 +526,7 @@ int free_block(lf_ctx* c, int slot, const lf::SrcArrays& sa, const lf::NodeArray
     FreeArgs& d = b.fa;                 // (theta, out, B, ntiles, tile_stride stay zero: the kernel takes them from its FreeLaunch)
     d.nchA = fa.nchA, d.nchB = fa.nchB, d.nslot = fa.nslot, d.skip_grid = fa.skip_grid;
     d.queues = fa.queues, d.partA = fa.partA, d.partB = fa.partB, d.cells = fa.cells, d.nodes8 = fa.nodes8, d.deal = fa.deal;
-    d.cc_len = fa.cc_len, d.cc_field = fa.cc_field, d.nchC = fa.nchC, d.partC = fa.partC, d.wstat = fa.wstat;
+    d.cc_len = fa.cc_len, d.cc_field = fa.cc_field, d.nchC = fa.nchC, d.fin_ranks = fa.fin_ranks, d.partC = fa.partC, d.wstat = fa.wstat;
     d.wrec_w = fa.wrec_w, d.wmode_w = fa.wmode_w, d.wstat_w = fa.wstat_w, d.wbase_w = fa.wbase_w;
     d.gq_rec = fa.gq_rec, d.gq_omega = fa.gq_omega, d.gq_rows = fa.gq_rows, d.nbq = fa.nbq, d.poll = fa.poll, d.err = fa.err;
     static_assert(sizeof(FreeArgs) == 208 && sizeof(NodeArrays) == 56, "a field was added: copy it above");
@@ -590,7 +603,8 @@ int enqueue_free(lf_ctx* c, const double* d_theta, int B, double* d_out, double*
     const SrcArrays sa{c->d_lum, c->d_a1, c->d_P, c->d_U, nullptr, ct->d_start, ct->d_len, ct->d_field, ct->d_keys, nullptr};
     const NodeArrays na{c->d_G, c->d_PG, c->d_W, c->d_a3, c->d_a4, c->d_a4min, c->nnodes};
     FreeArgs fa{B, ntiles, nchA, nchB, nslot, g8, (int)c->opt_skip_grid, c->d_queue, c->d_partA, c->d_partB,
-                c->d_cells, c->d_nodes8, c->deal_key > 0 ? c->d_deal : nullptr, c->d_cc_len, c->d_cc_field, nchC, c->d_partR, c->d_wstat,
+                c->d_cells, c->d_nodes8, c->deal_key > 0 ? c->d_deal : nullptr, c->d_cc_len, c->d_cc_field, nchC,
+                poll && c->deal_key > 0 ? c->deal_fin : FIN_LAST, c->d_partR, c->d_wstat,
                 d_theta, d_out, c->d_wrec, c->d_wmode, c->d_wstat, c->d_wbase,
                 gq ? c->gridq.d_rec : nullptr, gq ? c->gridq.d_omega : nullptr, gq ? c->gridq.d_rows : nullptr, gq ? c->gridq.nb : 0,
                 poll ? 1 : 0, c->d_err};
@@ -1140,6 +1154,14 @@ int lf_deal_table(int n_cell_chunks, int n_bins, int grid_part, int grid_parts, 
     const std::vector<int> t = make_deal(n_cell_chunks, n_bins, grid_part, grid_parts);
     for (int64_t i = 0; i < n; ++i) table[i] = t[(size_t)i];
     return (int)n;
+}
+
+int lf_deal_finishers(int n_cell_chunks, int n_bins, int grid_part, int grid_parts, int32_t ranks[4]) {
+    using namespace lf;
+    if (n_cell_chunks < 0 || n_bins < 0 || grid_parts < 0 || grid_part < 0 || (grid_parts > 0 && grid_part >= grid_parts) || !ranks) return LF_ERR_ARG;
+    const int word = deal_finishers(make_deal(n_cell_chunks, n_bins, grid_part, grid_parts), n_cell_chunks, n_bins, grid_part, grid_parts);
+    for (int g = 0; g < 4; ++g) ranks[g] = (word >> (8 * g)) & 0xff;
+    return LF_OK;
 }
 
 int lf_abi_version(void) { return LF_ABI_VERSION; }

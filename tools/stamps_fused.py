@@ -96,6 +96,32 @@ def main():
     print("workgroups with the slowest 10%% of prologues: ids %s" % ids[slow][:40].tolist())
     print("  first start to last end %.2f us; cycles per us of life: %.0f" % ((s[:, 6].max() - rt0) / 100.0,
                                                                         np.median(life / np.maximum((s[:, 6] - s[:, 5]) / 100.0, 0.01))))
+    if len(s) == nb and ctx.last_launch()["kernel"].startswith("lf_free"):
+        # Who ends last (lf_tile.h: tile_ranks).  A workgroup's end is its last instruction: a finisher's lies behind its sums.
+        ntiles, stride = (a.rows + 7) // 8, nb // 8
+        k = ids >> 3
+        tile = k % ntiles
+        rank = (ids & 7) + (8 * ((k - tile) // ntiles) if ntiles <= stride else 0)
+        fg = 8 * ((stride - tile + ntiles - 1) // ntiles) if ntiles <= stride else np.full(len(ids), 8)
+        end = (s[:, 6] - rt0) / 100.0
+        tail = life - s[:, 7]
+        one = tile < min(ntiles, stride)                  # (the first tile of every workgroup: all of them here)
+        # ... among the workgroups that only hand their sums over: the finisher's own end says when the tile was done, not
+        # when its own sums were
+        last_any = np.zeros(64, dtype=np.int64)
+        last_work = np.zeros(64, dtype=np.int64)
+        for tl in np.unique(tile[one]):
+            m = np.nonzero(tile == tl)[0]
+            last_any[rank[m][np.argmax(end[m])]] += 1
+            work = (s[m, 5] - rt0) / 100.0 + (s[m, 6] - s[m, 5]) / 100.0 * s[m, 7] / np.maximum(life[m], 1)      # sums done (grid stamp)
+            last_work[rank[m][np.argmax(work)]] += 1
+        print("per physical rank (group sizes %s): end us median / p90, sums done (cycles of life) median / p90, behind the sums "
+              "median / max, ends last in n tiles, its sums last in n tiles" % sorted(set(np.atleast_1d(fg).tolist())))
+        for r in range(int(rank.max()) + 1):
+            m = rank == r
+            print("  rank %2d: end %6.2f / %6.2f  sums done %6.0f / %6.0f  after %6.0f / %6.0f  last %3d  sums last %3d"
+                  % (r, np.median(end[m]), np.percentile(end[m], 90), np.median(s[m, 7]), np.percentile(s[m, 7], 90),
+                     np.median(tail[m]), tail[m].max(), last_any[r], last_work[r]))
 
 
 if __name__ == "__main__":
