@@ -81,14 +81,16 @@ def main():
                          "sqrt(var_comp) (veff_percentiles; DESIGN.md section 3.17; not with --fix-comp)")
     ap.add_argument("--deconvolve", action="store_true",
                     help="fit the likelihood convolved with the catalogue's flux errors (Eddington-bias correction, deconvolve=True; "
-                         "DESIGN.md section 3.18; host sampler: not with --until-converged or --map; errors above 0.09 dex are refused)")
+                         "DESIGN.md section 3.18; host sampler: not with --until-converged; errors above 0.09 dex are refused; with --map the "
+                         "convolved and the plain maximum are both found and the difference of their L*, the catalogue's Eddington "
+                         "shift, is printed; DESIGN.md section 3.19)")
     ap.add_argument("--out", default="LFMCMCOut")
     ap.add_argument("--compress", action="store_true", help="compressed catalogue and grid (DESIGN.md section 3.5)")
     args = ap.parse_args()
     if args.veff_band and args.fix_comp:
         ap.error("--veff-band needs the completeness parameters in the fit: not with --fix-comp")
-    if args.deconvolve and (args.until_converged or args.map):
-        ap.error("--deconvolve samples through fit_model: not with --until-converged or --map")
+    if args.deconvolve and args.until_converged:
+        ap.error("--deconvolve samples through fit_model: not with --until-converged")
     os.makedirs(args.out, exist_ok=True)
     cpath = os.path.join(args.out, "synthetic_catalogue.dat")
     write_catalogue(cpath, args.nsrc, seed=5)
@@ -104,7 +106,11 @@ def main():
                         field_names=field_names, field_ind=field_ind, compress=args.compress, deconvolve=args.deconvolve)
     print("setup %.2f s for %d sources" % (time.time() - t0, len(LFmod.lum)))
     np.random.seed(3)
-    if args.map:
+    plain_map = None
+    if args.map and args.deconvolve:
+        plain_map = dict(LFmod.fit_model_map(seed=7, likelihood="plain"))
+        LFmod.fit_model_map(seed=7, likelihood="convolved")
+    elif args.map:
         LFmod.fit_model_map(seed=7)
     if args.until_converged:
         LFmod.fit_model_converged(start="map" if args.map else "box")
@@ -136,6 +142,10 @@ def main():
         for n, t, e, m in zip(names[:-1], LFmod.map_theta, sd, med):
             print("  %-22s %9.4f +/- %.4f   (median %9.4f)" % (n, t, e, m))
         print("lnprob at the maximum %.4f; lnZ_laplace %.4f %s" % (LFmod.map_lnprob, LFmod.lnZ_laplace, LFmod.map_info["lnZ_reason"]))
+        if plain_map is not None:
+            print("maximum of the plain likelihood (converged: %s): %s" % (plain_map["converged"], np.round(plain_map["theta"], 4)))
+            print("maximum of the convolved likelihood: %s" % np.round(LFmod.map_theta, 4))
+            print("Eddington shift of L* (plain - convolved): %+.4f dex" % (plain_map["theta"][0] - LFmod.map_theta[0]))
     if args.integrals:
         write_integrals(LFmod, os.path.join(args.out, "integrals_%s.dat" % tag))
     if args.veff_band:

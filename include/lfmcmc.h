@@ -183,6 +183,20 @@ int lf_lnprob_err_batch(lf_ctx *ctx, const double *theta, int B, double *out);
  * lf_lnprob_batch_device. */
 int lf_lnprob_err_batch_device(lf_ctx *ctx, const double *d_theta, int B, double *d_out, void *hip_stream);
 
+/* The convolved lnprob of lf_lnprob_err_batch and its gradient with respect to the row's own theta elements, in theta's own
+ * units (csrc/lf_deconv_grad.h): grad[B][ndim] row-major = the gradient of lf_lnprob_grad_batch plus the
+ * exact derivative of the K-point sum Delta (its phi* elements are exactly 0).  lnprob_err: [B] or NULL; where given it is what
+ * lf_lnprob_err_batch returns for the same rows, bit for bit (the same kernels run on the same plain lnprob).  A row whose plain
+ * lnprob is not finite gets NaN in every element of its gradient; a source with sigma = 0 adds exactly 0.  No atomics: a row's
+ * gradient has the same bits whatever B is and wherever the row stands.  The option "compress" is ignored.  LF_ERR_ARG with a
+ * message, before the device is touched, for a NULL theta or grad or B <= 0, when no errors are set, and for a context with
+ * "skip_grid" or "grid_share" set; the context stays usable.  Host pointers, synchronous. */
+int lf_lnprob_err_grad_batch(lf_ctx *ctx, const double *theta, int B, double *lnprob_err, double *grad);
+
+/* Same, with device pointers and the launches enqueued on `hip_stream` (NULL = the default stream), asynchronous like
+ * lf_lnprob_batch_device.  d_lnprob_err may be NULL. */
+int lf_lnprob_err_grad_batch_device(lf_ctx *ctx, const double *d_theta, int B, double *d_lnprob_err, double *d_grad, void *hip_stream);
+
 /* Host-only, exported for tests (touches no GPU): the K-point Gauss-Hermite rule (weight e^(-x^2)) the library derives in
  * extended precision: x[K] ascending, lnw[K] = ln(w_k / sqrt(pi)).  LF_ERR_ARG for a NULL pointer or K outside 2..64. */
 int lf_gauss_hermite(int K, double *x, double *lnw);

@@ -54,7 +54,7 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_sampler_diag", "lf_ptsampler_diag", "lf_chain_window", "lf_diag_last", "lf_lnprob_grad_batch",
            "lf_lnprob_grad_batch_device", "lf_lumfunc_integral_quantiles", "lf_lumfunc_integral_quantiles_ms", "lf_veff_draws", "lf_veff_draws_ms",
            "lf_veff_draws_chunk", "lf_set_lum_err", "lf_lnprob_err_batch", "lf_lnprob_err_batch_device", "lf_gauss_hermite",
-           "lf_deconv_info")
+           "lf_deconv_info", "lf_lnprob_err_grad_batch", "lf_lnprob_err_grad_batch_device")
 
 _lib = None
 
@@ -115,6 +115,11 @@ def load():
     lib.lf_lnprob_err_batch_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.lf_gauss_hermite.restype = ctypes.c_int
     lib.lf_gauss_hermite.argtypes = [ctypes.c_int, _c_double_p, _c_double_p]
+    lib.lf_lnprob_err_grad_batch.restype = ctypes.c_int
+    lib.lf_lnprob_err_grad_batch.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p]
+    lib.lf_lnprob_err_grad_batch_device.restype = ctypes.c_int
+    lib.lf_lnprob_err_grad_batch_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p]
     lib.lf_deconv_info.restype = ctypes.c_int
     lib.lf_deconv_info.argtypes = [ctypes.POINTER(ctypes.c_int32), _c_double_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                    ctypes.POINTER(ctypes.c_int)]
@@ -670,6 +675,35 @@ class LFContext(object):
             self._check(self._lib.lf_lnprob_err_batch_device(self._h, ctypes.c_void_p(theta.data_ptr()), int(B),
                                                              ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)))
         return out
+
+    def lnprob_err_grad(self, theta):
+        """theta (B, ndim) or (ndim,) host array -> (lnprob_err (B,), grad (B, ndim)): lf_lnprob_err_grad_batch.  The value is
+        lnprob_err_batch's, bit for bit; rows whose plain lnprob is not finite have NaN gradients."""
+        th = self._theta(theta)
+        lp = np.empty(th.shape[0], dtype=np.float64)
+        g = np.empty((th.shape[0], self.ndim), dtype=np.float64)
+        if th.shape[0]:
+            self._check(self._lib.lf_lnprob_err_grad_batch(self._h, _ptr(th), th.shape[0], _ptr(lp), _ptr(g)))
+        return lp, g
+
+    def lnprob_err_grad_torch(self, theta):
+        """theta: float64 device tensor (B, ndim) on this context's device; enqueues lf_lnprob_err_grad_batch_device on torch's
+        current stream and returns (lnprob_err (B,), grad (B, ndim)) device tensors."""
+        import torch
+        if theta.dtype != torch.float64 or not theta.is_cuda or theta.dim() != 2 or theta.shape[1] != self.ndim:
+            raise ValueError("theta must be a float64 device tensor of shape (B, %d)" % self.ndim)
+        if theta.device.index != self.device:
+            raise ValueError("theta is on device %s, context is on %d" % (theta.device, self.device))
+        theta = theta.contiguous()
+        B = theta.shape[0]
+        lp = torch.empty(B, dtype=torch.float64, device=theta.device)
+        g = torch.empty((B, self.ndim), dtype=torch.float64, device=theta.device)
+        if B:
+            stream = torch.cuda.current_stream(theta.device).cuda_stream
+            self._check(self._lib.lf_lnprob_err_grad_batch_device(self._h, ctypes.c_void_p(theta.data_ptr()), int(B),
+                                                                  ctypes.c_void_p(lp.data_ptr()), ctypes.c_void_p(g.data_ptr()),
+                                                                  ctypes.c_void_p(stream)))
+        return lp, g
 
     def lnprob_grad_torch(self, theta):
         """theta: float64 device tensor (B, ndim) on this context's device; enqueues lf_lnprob_grad_batch_device on torch's

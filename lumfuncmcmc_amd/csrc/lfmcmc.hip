@@ -21,6 +21,7 @@
 #include "lf_devmem.h"
 #include "lf_diag.h"
 #include "lf_deconv.h"
+#include "lf_deconv_grad.h"
 #include "lf_grad.h"
 #include "lf_gridbound.h"
 #include "lf_hostcall.h"
@@ -163,6 +164,7 @@ struct lf_ctx {
     bool deconv_set = false;
     int64_t opt_deconv_unchecked = 0;   // 1: lf_set_lum_err takes sigma above the validated range of the order (tests, A/B runs)
     Buf<double> d_sigma, d_elogf, d_eU, d_ghnodes, d_dpart;
+    Buf<double> d_dgpart;               // its gradient's partial sums [rows][chunks][DGRAD_SLOTS] (lf_deconv_grad.h)
     ChunkTable deconv_chunks;
     bool deconv_chunks_built = false;
     hipStream_t stream = nullptr;
@@ -918,28 +920,79 @@ void launch_deconv(const lf::DeconvArgs& da, int B, hipStream_t s) {
     }
 }
 
-int enqueue_deconv(lf_ctx* c, const double* d_theta, int B, double* d_lnp, double* d_out, hipStream_t s) {
+// the chunk table of the correction's kernels, made at first use
+int deconv_chunk_table(lf_ctx* c) {
     using namespace lf;
-    int rc;
-    if (!c->deconv_chunks_built) {
-        const lfh::Chunks h = lfh::chunk_table(c->field_ind, c->kc.nf, DECONV_CH, 0.0, 0.0, 0.0);
-        ChunkTable& t = c->deconv_chunks;
-        t.n = (int)h.start.size();
-        if ((rc = upload(c, t.d_start, h.start, t.d_len, h.len, t.d_field, h.field)) != LF_OK) return rc;
-        c->deconv_chunks_built = true;
-    }
-    const int nch = c->deconv_chunks.n;
-    const size_t need = (size_t)B * std::max(nch, 1);
-    if (need > c->d_dpart.size() && (rc = grow(c, c->d_dpart, need)) != LF_OK) return rc;
-    if ((rc = enqueue(c, d_theta, B, d_lnp, nullptr, nullptr, s)) != LF_OK) return rc;
+    if (c->deconv_chunks_built) return LF_OK;
+    const lfh::Chunks h = lfh::chunk_table(c->field_ind, c->kc.nf, DECONV_CH, 0.0, 0.0, 0.0);
+    ChunkTable& t = c->deconv_chunks;
+    t.n = (int)h.start.size();
+    const int rc = upload(c, t.d_start, h.start, t.d_len, h.len, t.d_field, h.field);
+    if (rc != LF_OK) return rc;
+    c->deconv_chunks_built = true;
+    return LF_OK;
+}
+
+lf::DeconvArgs deconv_args(lf_ctx* c, const double* d_theta, double* d_lnp, double* d_out) {
     const bool fr = c->kc.variant == LF_FREE;
-    const DeconvArgs da{c->gradc, c->deconvc, d_theta, d_lnp, c->d_dpart, d_out, c->d_lum, c->d_a1, c->d_P,
-                        fr ? c->d_a1.get() : c->d_elogf.get(), fr ? c->d_U.get() : c->d_eU.get(), c->d_sigma, c->d_ghnodes,
-                        c->deconv_chunks.d_start, c->deconv_chunks.d_len, c->deconv_chunks.d_field, nch};
+    return lf::DeconvArgs{c->gradc, c->deconvc, d_theta, d_lnp, c->d_dpart, d_out, c->d_lum, c->d_a1, c->d_P,
+                          fr ? c->d_a1.get() : c->d_elogf.get(), fr ? c->d_U.get() : c->d_eU.get(), c->d_sigma, c->d_ghnodes,
+                          c->deconv_chunks.d_start, c->deconv_chunks.d_len, c->deconv_chunks.d_field, c->deconv_chunks.n};
+}
+
+void launch_deconv_variant(lf_ctx* c, const lf::DeconvArgs& da, int B, hipStream_t s) {
     switch (c->kc.variant) {
         case LF_FREE: launch_deconv<LF_FREE>(da, B, s); break;
         case LF_FIXCOMP: launch_deconv<LF_FIXCOMP>(da, B, s); break;
         default: launch_deconv<LF_ZEVOL>(da, B, s);
+    }
+}
+
+int enqueue_deconv(lf_ctx* c, const double* d_theta, int B, double* d_lnp, double* d_out, hipStream_t s) {
+    using namespace lf;
+    int rc;
+    if ((rc = deconv_chunk_table(c)) != LF_OK) return rc;
+    const size_t need = (size_t)B * std::max(c->deconv_chunks.n, 1);
+    if (need > c->d_dpart.size() && (rc = grow(c, c->d_dpart, need)) != LF_OK) return rc;
+    if ((rc = enqueue(c, d_theta, B, d_lnp, nullptr, nullptr, s)) != LF_OK) return rc;
+    launch_deconv_variant(c, deconv_args(c, d_theta, d_lnp, d_out), B, s);
+    LF_HIP(c, hipGetLastError());
+    return LF_OK;
+}
+
+// The flux-error-convolved lnprob of B rows and its gradient (lf_deconv_grad.h), all on `s`: the plain lnprob and the plain
+// gradient (enqueue_grad: d_lnp, d_grad), the value's kernels as enqueue_deconv launches them on that lnprob (d_out: what
+// lf_lnprob_err_batch_device gives, bit for bit), then the correction's gradient, added to d_grad in place.
+template <int VARIANT>
+void launch_deconv_grad(const lf::DeconvGradArgs& da, int B, hipStream_t s) {
+    using namespace lf;
+    for (int b0 = 0; b0 < B; b0 += 32768) {
+        const int nb = std::min(32768, B - b0);
+        DeconvGradArgs g = da;
+        g.d.theta += (size_t)b0 * g.d.gc.ndim;
+        g.d.lnprob += b0;
+        g.gpart += (size_t)b0 * g.d.nch * DGRAD_SLOTS;
+        g.grad += (size_t)b0 * g.d.gc.ndim;
+        if (g.d.nch > 0)
+            hipLaunchKernelGGL(lf_deconv_grad_part<VARIANT>, dim3((unsigned)g.d.nch, (unsigned)nb), dim3(BLOCK), 0, s, g);
+        hipLaunchKernelGGL(lf_deconv_grad_final<VARIANT>, dim3((unsigned)nb), dim3(64), 0, s, g);
+    }
+}
+
+int enqueue_deconv_grad(lf_ctx* c, const double* d_theta, int B, double* d_lnp, double* d_out, double* d_grad, hipStream_t s) {
+    using namespace lf;
+    int rc;
+    if ((rc = deconv_chunk_table(c)) != LF_OK) return rc;
+    const size_t need = (size_t)B * std::max(c->deconv_chunks.n, 1);
+    if (need > c->d_dpart.size() && (rc = grow(c, c->d_dpart, need)) != LF_OK) return rc;
+    if (need * DGRAD_SLOTS > c->d_dgpart.size() && (rc = grow(c, c->d_dgpart, need * DGRAD_SLOTS)) != LF_OK) return rc;
+    if ((rc = enqueue_grad(c, d_theta, B, d_lnp, d_grad, s)) != LF_OK) return rc;
+    const DeconvGradArgs da{deconv_args(c, d_theta, d_lnp, d_out), c->d_dgpart, d_grad};
+    launch_deconv_variant(c, da.d, B, s);
+    switch (c->kc.variant) {
+        case LF_FREE: launch_deconv_grad<LF_FREE>(da, B, s); break;
+        case LF_FIXCOMP: launch_deconv_grad<LF_FIXCOMP>(da, B, s); break;
+        default: launch_deconv_grad<LF_ZEVOL>(da, B, s);
     }
     LF_HIP(c, hipGetLastError());
     return LF_OK;
@@ -1441,6 +1494,37 @@ int lf_lnprob_err_batch(lf_ctx* c, const double* theta, int B, double* out) {
     LF_HIP(c, hipMemcpyAsync(c->h_out, c->d_outA, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     LF_HIP(c, hipStreamSynchronize(c->stream));
     std::memcpy(out, c->h_out, (size_t)B * sizeof(double));
+    return LF_OK;
+}
+
+int lf_lnprob_err_grad_batch_device(lf_ctx* c, const double* d_theta, int B, double* d_lnprob_err, double* d_grad, void* hip_stream) {
+    int rc = deconv_check(c, "lf_lnprob_err_grad_batch_device", d_theta, B, d_grad);
+    if (rc != LF_OK) return rc;
+    LF_HIP(c, hipSetDevice(c->device));
+    // (the rows' plain lnprob, and the value when it is not asked for: into the context's own buffers, sized before the
+    // lnprob path may replace them)
+    if ((rc = ensure_workspace(c, B, 0, 0)) != LF_OK) return rc;
+    return enqueue_deconv_grad(c, d_theta, B, c->d_outB, d_lnprob_err ? d_lnprob_err : c->d_outA.get(), d_grad, (hipStream_t)hip_stream);
+}
+
+int lf_lnprob_err_grad_batch(lf_ctx* c, const double* theta, int B, double* lnprob_err, double* grad) {
+    int rc = deconv_check(c, "lf_lnprob_err_grad_batch", theta, B, grad);
+    if (rc != LF_OK) return rc;
+    LF_HIP(c, hipSetDevice(c->device));
+    if ((rc = ensure_workspace(c, B, 0, 0)) != LF_OK) return rc;
+    const size_t nd = (size_t)c->kc.ndim, no = (size_t)B * (nd + 1);
+    if (no > c->d_gout.size()) {
+        if ((rc = grow(c, c->d_gout, no)) != LF_OK) return rc;
+        LF_HIP(c, c->h_gout.alloc(no));
+    }
+    const size_t tb = (size_t)B * nd * sizeof(double);
+    std::memcpy(c->h_theta, theta, tb);
+    LF_HIP(c, hipMemcpyAsync(c->d_theta, c->h_theta, tb, hipMemcpyHostToDevice, c->stream));
+    if ((rc = enqueue_deconv_grad(c, c->d_theta, B, c->d_outB, c->d_gout, c->d_gout + B, c->stream)) != LF_OK) return rc;
+    LF_HIP(c, hipMemcpyAsync(c->h_gout, c->d_gout, no * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    LF_HIP(c, hipStreamSynchronize(c->stream));
+    if (lnprob_err) std::memcpy(lnprob_err, c->h_gout, (size_t)B * sizeof(double));
+    std::memcpy(grad, c->h_gout + B, tb);
     return LF_OK;
 }
 

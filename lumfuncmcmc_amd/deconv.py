@@ -183,3 +183,150 @@ def lnprob_err(inp, sigma, theta, K=None, terms=False):
     if single:
         return (out[0], lp[0], sabs[0]) if terms else out[0]
     return (out, lp, sabs) if terms else out
+
+
+def _lcomp_grad(y, v, aC, kappa):
+    """(l, dF, dC) at y = log10(f / Flim), v = f / f_tau: l = ln fc^(1/d), Flim d l / d Flim and d l / d alpha_C (lf_grad.h:
+    grad_comp's statements, taken at (y, v) as the kernel's nodes have them)"""
+    num = aC * y
+    den = np.sqrt(num * num + 1.0)
+    e = np.exp(-v)
+    d = -np.expm1(-v)
+    neg = num < 0.0
+    s = np.where(neg, den - num, den + num)
+    lnfc = np.where(neg, -np.log(2.0 * den * s), np.log1p(-0.5 / (den * s)))
+    gp = np.where(neg, s / (den * den), 1.0 / (den * den * s))
+    l = lnfc / d
+    lw = np.where(e > 0.0, l * (v * e / d), 0.0)
+    dF = lw - gp * (aC / LN10) / d
+    dC = lw * (LN10 * kappa / (aC * aC)) + gp * y / d
+    return l, dF, dC
+
+
+def _row_grad_terms(inp, sigma, th, x, lnw):
+    """One theta row -> (Delta_i [N], g [N, ndim], sabs [N, ndim]): every source's correction, its derivative with respect to
+    the row's elements and the scale of the derivative's terms (csrc/lf_deconv_grad.h).  One online
+    softmax per source: the running maximum m, the sum s and one weighted numerator per quantity (delta, em; FREE: dF, dC),
+    all rescaled by the same e^(-|d|) when a node raises the maximum."""
+    v, fsa = inp["variant"], bool(inp["fix_sch_al"])
+    p = G._split(inp, th)
+    fi = np.asarray(inp["field_ind"])
+    nf = len(fi) - 1
+    lum = np.asarray(inp["lum"], dtype=float)
+    N = lum.shape[0]
+    nd = G.ndim_of(inp)
+    kappa = G._kappa(inp["fcmin"])
+    c1l = LN10 * (p["al"] + 1.0)
+    ls = None
+    if v == "zevol":
+        ls = G._basis(np.asarray(inp["z"], dtype=float), inp["pivots"])
+        t = np.exp(LN10 * (lum - ls.T @ np.asarray(p["L"], dtype=float)))
+    else:
+        t = 10.0 ** (lum - 42.0) * np.exp(LN10 * (42.0 - p["L"]))
+    logf = G.log_flux(lum, inp["DLz"]) if inp.get("logf") is None else np.asarray(inp["logf"], dtype=float)
+    U = 10.0 ** (logf + 17.0)
+    free = v == "free"
+    if free:
+        Flim, aC = np.repeat(np.asarray(p["Flim"], dtype=float), np.diff(fi)), float(p["aC"])
+    else:
+        Flim, aC = np.repeat(np.asarray(inp["Flim0"], dtype=float), np.diff(fi)), float(inp["alpha0"])
+    y0 = (logf + 17.0) - np.log10(Flim)
+    v0 = U * (np.exp(LN10 * kappa / aC) / Flim)
+    l0, dF0, dC0 = _lcomp_grad(y0, v0, aC, kappa)
+    s2 = np.sqrt(2.0) * sigma
+    m = np.full(N, -np.inf)
+    acc = np.zeros(N)
+    nq = 4 if free else 2
+    num = np.zeros((nq, N))            # the weighted numerators of delta, em (, dF, dC)
+    nab = np.zeros((nq, N))            # ... of their absolute values (S_abs only: the kernel does not keep them)
+    for k in range(len(x)):
+        dl = s2 * x[k]
+        em = np.expm1(LN10 * dl)
+        lk, dFk, dCk = _lcomp_grad(y0 + dl, v0 * (em + 1.0), aC, kappa)
+        a = lnw[k] + ((c1l * dl - t * em) + (lk - l0))
+        skip = a == -np.inf
+        d = a - m
+        e = np.exp(-np.abs(d))
+        up = d > 0.0
+        acc_n = np.where(up, acc * e + 1.0, acc + e)
+        m_n = np.where(up, a, m)
+        q = (dl, em, dFk, dCk)[:nq]
+        for j in range(nq):
+            num[j] = np.where(skip, num[j], np.where(up, num[j] * e + q[j], num[j] + e * q[j]))
+            nab[j] = np.where(skip, nab[j], np.where(up, nab[j] * e + np.abs(q[j]), nab[j] + e * np.abs(q[j])))
+        acc = np.where(skip, acc, acc_n)
+        m = np.where(skip, m, m_n)
+    on = sigma > 0.0
+    D = np.where(on, m + np.log(acc), 0.0)
+    ex = [np.where(on, num[j] / acc, 0.0) for j in range(nq)]          # E_p[.]
+    ea = [np.where(on, nab[j] / acc, 0.0) for j in range(nq)]
+    g, sabs = np.zeros((N, nd)), np.zeros((N, nd))
+    gL, aL = t * ex[1], t * ea[1]
+    if v == "zevol":
+        for mm in range(3):
+            g[:, mm] = LN10 * (ls[mm] * gL)
+            sabs[:, mm] = LN10 * (np.abs(ls[mm]) * aL)
+        if not fsa:
+            g[:, 6], sabs[:, 6] = LN10 * ex[0], LN10 * ea[0]
+    else:
+        g[:, 0], sabs[:, 0] = LN10 * gL, LN10 * aL
+        if not fsa:
+            g[:, 2], sabs[:, 2] = LN10 * ex[0], LN10 * ea[0]
+        if free:
+            kF = 2 if fsa else 3
+            for f in range(nf):
+                sl = slice(fi[f], fi[f + 1])
+                inv = 1.0 / p["Flim"][f]
+                g[sl, kF + f] = inv * np.where(on[sl], ex[2][sl] - dF0[sl], 0.0)
+                sabs[sl, kF + f] = abs(inv) * np.where(on[sl], ea[2][sl] + np.abs(dF0[sl]), 0.0)
+            g[:, kF + nf] = np.where(on, ex[3] - dC0, 0.0)
+            sabs[:, kF + nf] = np.where(on, ea[3] + np.abs(dC0), 0.0)
+    return D, g, sabs
+
+
+def delta_grad(inp, sigma, theta, K=None, terms=False, per_source=False):
+    """theta (B, ndim) or (ndim,) -> (Delta[B], dDelta[B, ndim]): the correction and its derivative with respect to the row's
+    own elements, the exact derivative of the K-point sum; with terms=True also S_abs[B, ndim], per element the sum over the
+    sources of sum_k p_ik |d a_ik / d theta_e| + |the subtracted term at f_i|: the scale rounding is judged by.  The elements
+    of phi* are exactly 0; a source with sigma_i = 0 adds exactly 0 to every element.  No prior test: what the formulas give.
+    per_source=True: the per-source arrays (Delta_i [B, N], dDelta_i [B, N, ndim], S_abs_i [B, N, ndim]) instead."""
+    K = DEFAULT_ORDER if K is None else int(K)
+    if K not in ORDERS:
+        raise ValueError("deconvolve_order must be one of %s" % (ORDERS,))
+    th = np.asarray(theta, dtype=np.float64)
+    single = th.ndim == 1
+    th = np.atleast_2d(th)
+    nd = G.ndim_of(inp)
+    if th.shape[1] != nd:
+        raise ValueError("theta must be (B, %d), got %s" % (nd, th.shape))
+    sigma = check_sigma(sigma, len(inp["lum"]), K, True)
+    x, lnw = gauss_hermite(K)
+    N = sigma.size
+    D, g, s = np.empty((len(th), N)), np.empty((len(th), N, nd)), np.empty((len(th), N, nd))
+    with np.errstate(all="ignore"):
+        for b, row in enumerate(th):
+            D[b], g[b], s[b] = _row_grad_terms(inp, sigma, row, x, lnw)
+    if per_source:
+        return (D[0], g[0], s[0]) if single else (D, g, s)
+    out = (D.sum(axis=1), g.sum(axis=1), s.sum(axis=1))
+    if single:
+        out = tuple(o[0] for o in out)
+    return out if terms else out[:2]
+
+
+def lnprob_err_grad(inp, sigma, theta, K=None, terms=False):
+    """(value[B], grad[B, ndim]) of the convolved lnprob: lnprob_err's value, grad.lnprob_grad's gradient plus dDelta; a row
+    whose lnprob is not finite gets NaN in every element (the plain gradient's convention).  terms=True: also S_abs[B, ndim],
+    the sum of both parts' scales."""
+    th = np.asarray(theta, dtype=np.float64)
+    single = th.ndim == 1
+    th2 = np.atleast_2d(th)
+    lp, g0, s0 = G.lnprob_grad(inp, th2, terms=True)
+    tot, dD, s1 = delta_grad(inp, sigma, th2, K, terms=True)
+    with np.errstate(all="ignore"):
+        val = np.where(np.isfinite(lp), lp + tot, -np.inf)
+        val = np.where(np.isnan(val), -np.inf, val)
+        g, s = g0 + dD, s0 + s1                     # (g0, s0 are NaN where lnprob is not finite)
+    if single:
+        return (val[0], g[0], s[0]) if terms else (val[0], g[0])
+    return (val, g, s) if terms else (val, g)

@@ -385,26 +385,46 @@ class _Base(object):
         return tau
 
     # ------------------------------------------------------------------ maximum a posteriori (mapfit.py)
-    def _grad_fn(self):
-        """The batched (lnprob, gradient) callable of the current configuration: the device's (LFContext.lnprob_grad)."""
-        self._refuse_deconvolve("the gradient (fit_model_map, map_init_walkers)")
+    def _map_likelihood(self, likelihood):
+        """Which likelihood fit_model_map / map_init_walkers maximise: None (the plain one; refused under deconvolve=True, where
+        the choice has to be stated), "plain" or "convolved" (needs deconvolve=True)."""
+        if likelihood is None:
+            if self.deconvolve:
+                raise NotImplementedError("fit_model_map and map_init_walkers do not choose a likelihood for deconvolve=True: "
+                                          'pass likelihood="convolved" (the flux-error-convolved one, lnprob\'s) or '
+                                          'likelihood="plain"')
+            return "plain"
+        if likelihood not in ("plain", "convolved"):
+            raise ValueError('likelihood must be None, "plain" or "convolved", got %r' % (likelihood,))
+        if likelihood == "convolved" and not self.deconvolve:
+            raise ValueError('likelihood="convolved" needs an object made with deconvolve=True')
+        return likelihood
+
+    def _grad_fn(self, likelihood=None):
+        """The batched (lnprob, gradient) callable of the current configuration: the device's (LFContext.lnprob_grad, or
+        LFContext.lnprob_err_grad for the convolved likelihood)."""
+        likelihood = self._map_likelihood(likelihood)
         rank, world = self._dist_state()
         if world > 1:
             raise NotImplementedError("the gradient runs on one GPU: source- or walker-sharded gradients are not implemented")
         if self.lnprob_fn is not None:
             raise NotImplementedError("the gradient comes from the device context: it cannot use lnprob_fn")
-        return self.context().lnprob_grad
+        return self.context().lnprob_err_grad if likelihood == "convolved" else self.context().lnprob_grad
 
-    def fit_model_map(self, nstarts=16, seed=None, tol=1e-6):
+    def fit_model_map(self, nstarts=16, seed=None, tol=1e-6, likelihood=None):
         """Maximum a posteriori fit: box-constrained Newton iterations from nstarts draws of get_init_walker_values' box
         (seed: a RandomState of its own instead of numpy's global one; a start with -inf lnprob is drawn again), every
         iteration one batched gradient call on the device (mapfit.maximise).  For fixed completeness the context is
         lnprob_fix_comp's, as in fit_model.  Sets map_theta, map_lnprob, map_hessian, map_cov = (-H)^-1 (over the
         coordinates not held at a bound: rows and columns of a held coordinate are 0) and lnZ_laplace (NaN when a
         coordinate is on its bound or -H is not positive definite: map_info["lnZ_reason"] says which); returns them in a
-        dict with converged, on_bound, niter and decrement."""
+        dict with converged, on_bound, niter and decrement.  likelihood: None (the plain likelihood; an object made with
+        deconvolve=True refuses and asks for the choice), "convolved" (deconvolve=True only: the flux-error-convolved
+        likelihood, LFContext.lnprob_err_grad) or "plain" (also under deconvolve=True: the two maxima side by side give the
+        catalogue's Eddington shift); map_info["likelihood"] records which one ran."""
         from . import mapfit
-        f = self._grad_fn()
+        likelihood = self._map_likelihood(likelihood)
+        f = self._grad_fn(likelihood)
         box = self._theta_lims()
         rs = np.random.RandomState(seed) if seed is not None else np.random
         draw = lambda n: rs.rand(n, len(box)) * (box[:, 1] - box[:, 0]) + box[:, 0]    # noqa: E731
@@ -427,23 +447,24 @@ class _Base(object):
         self.map_theta, self.map_lnprob, self.map_hessian, self.map_cov, self.lnZ_laplace = r["theta"], r["lnprob"], H, cov, lnZ
         self.map_info = {"theta": r["theta"], "lnprob": r["lnprob"], "hessian": H, "cov": cov, "lnZ_laplace": lnZ,
                          "lnZ_reason": why, "converged": r["converged"], "on_bound": r["on_bound"], "niter": r["niter"],
-                         "decrement": r["decrement"], "box": r["box"]}
+                         "decrement": r["decrement"], "box": r["box"], "likelihood": likelihood}
         self.log.info("MAP fit: lnprob %.5f after %d iterations (%sconverged), Laplace lnZ %.3f %s"
                       % (r["lnprob"], r["niter"], "" if r["converged"] else "NOT ", lnZ, why))
         return self.map_info
 
-    def map_init_walkers(self, num=None, scale=1.0):
+    def map_init_walkers(self, num=None, scale=1.0, likelihood=None):
         """Start positions drawn from N(map_theta, scale^2 map_cov) (numpy's global state, like get_init_walker_values)
         instead of the prior box; a row outside the box or with a lnprob that is not finite is drawn again, so every walker
         starts with a finite lnprob.  A coordinate held at a bound has no variance in map_cov: it is scattered into the box
-        by |N(0, (1e-3 width)^2)| so that the ensemble is not degenerate there."""
+        by |N(0, (1e-3 width)^2)| so that the ensemble is not degenerate there.  likelihood: whose lnprob has to be finite
+        (as in fit_model_map)."""
         if getattr(self, "map_theta", None) is None:
             raise RuntimeError("map_init_walkers: call fit_model_map first")
         if not np.all(np.isfinite(self.map_cov)):
             raise RuntimeError("map_init_walkers: map_cov is not finite")
         num = self.nwalkers if num is None else int(num)
         box = self._theta_lims()
-        f = self._grad_fn()
+        f = self._grad_fn(likelihood)
         held = self.map_info["on_bound"]
         cov = 0.5 * (self.map_cov + self.map_cov.T) * scale ** 2
 
