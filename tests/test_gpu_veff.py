@@ -83,3 +83,76 @@ def test_resampling_indices_outside_the_catalogue_are_refused():
             capi.veff_device(flux, flim, 1.0e6, 0.04, 4.56, 0.1, bin_of=bins, nbin=10, nboot=3, boot_idx=idx)
     phi, sums = capi.veff_device(flux, flim, 1.0e6, 0.04, 4.56, 0.1, bin_of=bins, nbin=10, nboot=3, boot_idx=rng.integers(0, n, (3, n)))
     assert np.isfinite(phi).all() and sums.shape == (4, 10)
+
+
+# ---------------------------------------------------------------------------------------------- the device-drawn bootstrap, replayed
+def replayed_indices(n, nboot, seed):
+    """idx[k - 1][j] of veff_bins (csrc/lf_kernels.h) for resample k = 1 .. nboot: Philox4x32-10 with counter (j lo, j hi, k,
+    0x5eed) and key (seed lo, seed hi); floor(u53(r0, r1) n), clamped to n - 1"""
+    from lumfuncmcmc_amd import philox
+    j = np.arange(n, dtype=np.uint64)
+    out = np.empty((nboot, n), dtype=np.int64)
+    for k in range(1, nboot + 1):
+        r = philox.philox4x32(j & np.uint64(philox.MASK), j >> np.uint64(32), np.full(n, k, dtype=np.uint64),
+                              np.full(n, 0x5eed, dtype=np.uint64), seed & philox.MASK, (seed >> 32) & philox.MASK)
+        out[k - 1] = np.minimum((philox.u53(r[0], r[1]) * float(n)).astype(np.int64), n - 1)
+    return out
+
+
+@pytest.mark.parametrize("n", [3000, 300001])
+def test_device_drawn_bootstrap_is_the_replayed_one(n):
+    """lf_veff with boot_idx == NULL (the form VeffLF(device=True) uses) draws its resampling indices on the device.  The same
+    indices replayed on the host and handed back through boot_idx give the same binned sums - the order of the atomic adds
+    differs, nothing else does - and both are the bincount over the replayed indices (math.fsum), to 1e-13 sum|phi| per bin.
+    n = 300001 is past the 1024 x 256 span of the grid-stride loop; some sources have no bin and some no volume."""
+    import math
+    from lumfuncmcmc_amd import capi
+    nbin, nboot, seed = 7, 3, (0x1234 << 32) | 0x9abcdef1
+    rng = np.random.default_rng(n)
+    flim = rng.uniform(2.0e-17, 4.0e-17, n)
+    flux = flim * 10.0 ** rng.uniform(-0.3, 1.5, n)
+    vol = rng.uniform(1.0e5, 5.0e6, n)
+    vol[rng.permutation(n)[:9]] = np.repeat([0.0, -1.0, -3.5], 3)
+    bin_of = rng.integers(-1, nbin + 2, n)
+    assert (bin_of < 0).sum() > 100 and (bin_of >= nbin).sum() > 100
+    idx = replayed_indices(n, nboot, seed)
+    assert idx.min() >= 0 and idx.max() < n
+    args = (flux, flim, vol, 0.04, 4.56, 0.1)
+    phi, drawn = capi.veff_device(*args, bin_of=bin_of, nbin=nbin, nboot=nboot, seed=seed)
+    phi2, given = capi.veff_device(*args, bin_of=bin_of, nbin=nbin, nboot=nboot, boot_idx=idx, seed=99)
+    assert np.array_equal(phi, phi2) and np.all(phi[vol <= 0] == 0.0) and np.all(phi[vol > 0] > 0.0)
+    want, scale = np.zeros((nboot + 1, nbin)), np.zeros((nboot + 1, nbin))
+    for k in range(nboot + 1):
+        sel = np.arange(n) if k == 0 else idx[k - 1]
+        b, p = bin_of[sel], phi[sel]
+        for q in range(nbin):
+            want[k, q] = math.fsum(p[b == q])
+            scale[k, q] = math.fsum(np.abs(p[b == q]))
+    tol = 1e-13 * scale
+    print("n %d: max |drawn - given| / bound %.3g, |drawn - bincount| / bound %.3g" %
+          (n, (np.abs(drawn - given) / tol).max(), (np.abs(drawn - want) / tol).max()))
+    assert np.all(scale > 0) and np.all(np.abs(drawn - given) <= tol) and np.all(np.abs(drawn - want) <= tol) and np.all(np.abs(given - want) <= tol)
+    # another seed: other resamples, the catalogue's own row unchanged
+    _, other = capi.veff_device(*args, bin_of=bin_of, nbin=nbin, nboot=nboot, seed=seed + 1)
+    assert np.all(np.abs(other[0] - drawn[0]) <= tol[0]) and np.all(other[1:] != drawn[1:])
+
+
+def test_weights_element_by_element_against_40_digits():
+    """veff_weights against 40-digit values of 1 / (pref0 fleming(f, Flim, alpha, fcmin) vol) (tests/lf_gradproblib.py:
+    case_veff): f / Flim from 1e-3 to 1e3, alpha 0.6, 4.56 and 10, fcmin 0.1 and 0 (the plain Fleming curve), vol per source
+    and vol = NULL with vol_all; vol_i <= 0 gives exactly 0.  The kernel keeps the reference's 0.5 (1 + num / sqrt(1 + num^2)),
+    which cancels for num << 0: the yardstick 2^-53 |phi| (1 + 1 / fc) carries that, times 1 + |ln fc / d| for fcmin > 0.
+    Cap: max(2, 4 x the figure of hostsetup.fleming's NumPy expression), measured on the CPU by tests/test_gradterms_cpu.py
+    (1.456 on 2026-10-19: lf_gradproblib.CAPS["veff_phi"] = 5.83)."""
+    import lf_gradproblib as P
+    from lumfuncmcmc_amd import capi
+    worst = 0.0
+    for cfg in P.veff_cases():
+        c = P.case_veff(*cfg)
+        phi, _ = capi.veff_device(c["flux"], c["flim"], c["vol"], P.VEFF_PREF0, c["alpha"], c["fcmin"])
+        fig, i = P.measure(c, phi)
+        print("veff_phi alpha %-5g fcmin %-4g vol %-10s device max err / yard %7.3f (cap %g) at f / Flim = %r: got %.17g ref %.17g" %
+              (cfg[0], cfg[1], "per source" if cfg[2] else "shared", fig, P.CAPS["veff_phi"], c["flux"][i] / c["flim"][i], phi[i], c["ref"][0][i]))
+        assert np.all(phi[c["zero"]] == 0.0) and not np.any(np.signbit(phi[c["zero"]]))
+        worst = max(worst, fig)
+    assert worst <= P.CAPS["veff_phi"], worst
