@@ -607,6 +607,35 @@ class LFContext(object):
             raise ValueError("theta must be (B, %d), got %s" % (self.ndim, th.shape))
         return th
 
+    def _value_grad(self, fn, theta):
+        """A "(value, gradient)" call of the library on host arrays: fn(handle, theta, B, value (B,), grad (B, ndim))."""
+        th = self._theta(theta)
+        lp = np.empty(th.shape[0], dtype=np.float64)
+        g = np.empty((th.shape[0], self.ndim), dtype=np.float64)
+        if th.shape[0]:
+            self._check(fn(self._h, _ptr(th), th.shape[0], _ptr(lp), _ptr(g)))
+        return lp, g
+
+    def _device_theta(self, theta):
+        """Checks a float64 device tensor (B, ndim) on this context's device -> (it, contiguous; B; torch's current stream)."""
+        import torch
+        if theta.dtype != torch.float64 or not theta.is_cuda or theta.dim() != 2 or theta.shape[1] != self.ndim:
+            raise ValueError("theta must be a float64 device tensor of shape (B, %d)" % self.ndim)
+        if theta.device.index != self.device:
+            raise ValueError("theta is on device %s, context is on %d" % (theta.device, self.device))
+        return theta.contiguous(), theta.shape[0], torch.cuda.current_stream(theta.device).cuda_stream
+
+    def _value_grad_torch(self, fn, theta):
+        """The same on device tensors, enqueued on torch's current stream: fn(handle, theta, B, value, grad, stream)."""
+        import torch
+        theta, B, stream = self._device_theta(theta)
+        lp = torch.empty(B, dtype=torch.float64, device=theta.device)
+        g = torch.empty((B, self.ndim), dtype=torch.float64, device=theta.device)
+        if B:
+            self._check(fn(self._h, ctypes.c_void_p(theta.data_ptr()), int(B), ctypes.c_void_p(lp.data_ptr()),
+                           ctypes.c_void_p(g.data_ptr()), ctypes.c_void_p(stream)))
+        return lp, g
+
     def lnprob_batch(self, theta):
         """theta (B, ndim) or (ndim,) host array -> lnprob (B,) float64."""
         th = self._theta(theta)
@@ -628,12 +657,7 @@ class LFContext(object):
     def lnprob_grad(self, theta):
         """theta (B, ndim) or (ndim,) host array -> (lnprob (B,), grad (B, ndim)): lf_lnprob_grad_batch.  lnprob is
         lnprob_batch's, bit for bit; rows whose lnprob is -inf have NaN gradients."""
-        th = self._theta(theta)
-        lp = np.empty(th.shape[0], dtype=np.float64)
-        g = np.empty((th.shape[0], self.ndim), dtype=np.float64)
-        if th.shape[0]:
-            self._check(self._lib.lf_lnprob_grad_batch(self._h, _ptr(th), th.shape[0], _ptr(lp), _ptr(g)))
-        return lp, g
+        return self._value_grad(self._lib.lf_lnprob_grad_batch, theta)
 
     def set_lum_err(self, sigma, K=None, unchecked=False):
         """lf_set_lum_err: the sources' luminosity errors sigma (dex, catalogue order) and the Gauss-Hermite order K (None: the
@@ -663,15 +687,9 @@ class LFContext(object):
         """theta: float64 device tensor (B, ndim) on this context's device; enqueues lf_lnprob_err_batch_device on torch's
         current stream and returns a (B,) device tensor."""
         import torch
-        if theta.dtype != torch.float64 or not theta.is_cuda or theta.dim() != 2 or theta.shape[1] != self.ndim:
-            raise ValueError("theta must be a float64 device tensor of shape (B, %d)" % self.ndim)
-        if theta.device.index != self.device:
-            raise ValueError("theta is on device %s, context is on %d" % (theta.device, self.device))
-        theta = theta.contiguous()
-        B = theta.shape[0]
+        theta, B, stream = self._device_theta(theta)
         out = torch.empty(B, dtype=torch.float64, device=theta.device)
         if B:
-            stream = torch.cuda.current_stream(theta.device).cuda_stream
             self._check(self._lib.lf_lnprob_err_batch_device(self._h, ctypes.c_void_p(theta.data_ptr()), int(B),
                                                              ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)))
         return out
@@ -679,50 +697,17 @@ class LFContext(object):
     def lnprob_err_grad(self, theta):
         """theta (B, ndim) or (ndim,) host array -> (lnprob_err (B,), grad (B, ndim)): lf_lnprob_err_grad_batch.  The value is
         lnprob_err_batch's, bit for bit; rows whose plain lnprob is not finite have NaN gradients."""
-        th = self._theta(theta)
-        lp = np.empty(th.shape[0], dtype=np.float64)
-        g = np.empty((th.shape[0], self.ndim), dtype=np.float64)
-        if th.shape[0]:
-            self._check(self._lib.lf_lnprob_err_grad_batch(self._h, _ptr(th), th.shape[0], _ptr(lp), _ptr(g)))
-        return lp, g
+        return self._value_grad(self._lib.lf_lnprob_err_grad_batch, theta)
 
     def lnprob_err_grad_torch(self, theta):
         """theta: float64 device tensor (B, ndim) on this context's device; enqueues lf_lnprob_err_grad_batch_device on torch's
         current stream and returns (lnprob_err (B,), grad (B, ndim)) device tensors."""
-        import torch
-        if theta.dtype != torch.float64 or not theta.is_cuda or theta.dim() != 2 or theta.shape[1] != self.ndim:
-            raise ValueError("theta must be a float64 device tensor of shape (B, %d)" % self.ndim)
-        if theta.device.index != self.device:
-            raise ValueError("theta is on device %s, context is on %d" % (theta.device, self.device))
-        theta = theta.contiguous()
-        B = theta.shape[0]
-        lp = torch.empty(B, dtype=torch.float64, device=theta.device)
-        g = torch.empty((B, self.ndim), dtype=torch.float64, device=theta.device)
-        if B:
-            stream = torch.cuda.current_stream(theta.device).cuda_stream
-            self._check(self._lib.lf_lnprob_err_grad_batch_device(self._h, ctypes.c_void_p(theta.data_ptr()), int(B),
-                                                                  ctypes.c_void_p(lp.data_ptr()), ctypes.c_void_p(g.data_ptr()),
-                                                                  ctypes.c_void_p(stream)))
-        return lp, g
+        return self._value_grad_torch(self._lib.lf_lnprob_err_grad_batch_device, theta)
 
     def lnprob_grad_torch(self, theta):
         """theta: float64 device tensor (B, ndim) on this context's device; enqueues lf_lnprob_grad_batch_device on torch's
         current stream and returns (lnprob (B,), grad (B, ndim)) device tensors."""
-        import torch
-        if theta.dtype != torch.float64 or not theta.is_cuda or theta.dim() != 2 or theta.shape[1] != self.ndim:
-            raise ValueError("theta must be a float64 device tensor of shape (B, %d)" % self.ndim)
-        if theta.device.index != self.device:
-            raise ValueError("theta is on device %s, context is on %d" % (theta.device, self.device))
-        theta = theta.contiguous()
-        B = theta.shape[0]
-        lp = torch.empty(B, dtype=torch.float64, device=theta.device)
-        g = torch.empty((B, self.ndim), dtype=torch.float64, device=theta.device)
-        if B:
-            stream = torch.cuda.current_stream(theta.device).cuda_stream
-            self._check(self._lib.lf_lnprob_grad_batch_device(self._h, ctypes.c_void_p(theta.data_ptr()), int(B),
-                                                              ctypes.c_void_p(lp.data_ptr()), ctypes.c_void_p(g.data_ptr()),
-                                                              ctypes.c_void_p(stream)))
-        return lp, g
+        return self._value_grad_torch(self._lib.lf_lnprob_grad_batch_device, theta)
 
     def lnprob_batch_device(self, theta_ptr, B, out_ptr, stream=0):
         """Raw device pointers (ints) and a hipStream_t handle (int, 0 = default stream)."""
@@ -734,16 +719,10 @@ class LFContext(object):
         torch's current stream and returns a (B,) tensor.  torch is plumbing here: device memory
         and streams only."""
         import torch
-        if theta.dtype != torch.float64 or not theta.is_cuda or theta.dim() != 2 or theta.shape[1] != self.ndim:
-            raise ValueError("theta must be a float64 device tensor of shape (B, %d)" % self.ndim)
-        if theta.device.index != self.device:
-            raise ValueError("theta is on device %s, context is on %d" % (theta.device, self.device))
-        theta = theta.contiguous()
-        B = theta.shape[0]
+        theta, B, stream = self._device_theta(theta)
         if out is None:
             out = torch.empty(B, dtype=torch.float64, device=theta.device)
         if B:
-            stream = torch.cuda.current_stream(theta.device).cuda_stream
             self.lnprob_batch_device(theta.data_ptr(), B, out.data_ptr(), stream)
         return out
 

@@ -7,7 +7,7 @@
 //     lnprob_err = lnprob + Delta,   Delta = sum_i Delta_i,   Delta_i = ln sum_k (w_k / sqrt(pi)) exp(t_ik - t_i),
 //     delta = sqrt(2) sigma_i x_k,   E = 10^delta = 1 + expm1(ln10 delta),
 //     t_ik - t_i = ln10 (alpha + 1) delta - 10^(L_i - L*) (E - 1) + l(f_i E) - l(f_i),
-// L* = L*(z_i) for the z-evolving model (phi* cancels), l = ln fc^(1/d) in lf_grad.h's form without cancellation - FREE: the
+// L* = L*(z_i) for the z-evolving model (phi* cancels), l = ln fc^(1/d) by lf_grad.h's comp_form<false> - FREE: the
 // row's Flim_f and alpha_C; FIXCOMP, ZEVOL: the fixed ones the model was built with (the ratio does not depend on the row
 // then, but it is evaluated here all the same: no table of N x K values).  The inner sum is a log-sum-exp with a running
 // maximum (ratios of e^(+-hundreds) occur for faint sources at large sigma): one exponential per node.  A node whose term is
@@ -16,8 +16,8 @@
 // lf_deconv_part   grid (blocks, rows), 256 threads.  Block c: chunk c of up to DECONV_CH sources of one field (the
 //                  context's per-source arrays plus sigma; FIXCOMP, ZEVOL: plus the sources' log flux and 10^(log flux + 17)).
 //                  The node table {x_k}, {ln(w_k / sqrt(pi))} is copied to LDS; the row's constants are scalars.  Thread t
-//                  takes sources t, t + 256, ... of its chunk in that order; then the wave's 64 lanes by the shuffle tree of
-//                  wave_sum, the four waves' totals through LDS as ((w0 + w1) + w2) + w3 -> part[row][block].
+//                  takes sources t, t + 256, ... of its chunk in that order (deconv_items, the loop of lf_deconv_grad_part
+//                  too); then the block's tail (block_sum, lf_math.h) -> part[row][block].
 // lf_deconv_final  one wave per row: lane l adds blocks l, l + 64, ... in that order, then the shuffle tree; out = lnprob +
 //                  Delta.  A row whose lnprob is -inf stays -inf; NaN becomes -inf.
 // No atomics; nothing in either order depends on the batch: a row's value has the same bits at any B and any position.
@@ -47,78 +47,113 @@ struct DeconvArgs {
     int nch;
 };
 
-// l = ln fc^(1/d) at y = log10(f / Flim), v = f / f_tau (grad_comp's value, without its derivatives)
-__device__ __forceinline__ double deconv_lcomp(double aC, double y, double v) {
-    const double num = aC * y;
-    const double den = sqrt(fma(num, num, 1.0));
-    const double d = -expm1(-v);
-    double lnfc;
-    if (num < 0.0) lnfc = -log(2.0 * den * (den - num));
-    else lnfc = log1p(-0.5 / (den * (den + num)));
-    return lnfc / d;
+// l alone at (y, v): comp_form's DERIV = false instantiation under the name the probe and its tests know
+__device__ __forceinline__ double deconv_lcomp(double aC, double y, double v) { return comp_form<false>(aC, 0.0, 0.0, y, v).l; }
+
+// what a block's items share: the row's theta and what the node exponents take from it and from the block's field
+struct DeconvRow {
+    GradRow r;
+    double c1l, Q;               // ln10 (alpha + 1); 10^(42 - L*) (FREE, FIXCOMP)
+    double aC, lF, vs;           // the completeness in force: alpha_C, log10 Flim, 10^(kappa / alpha_C) / Flim
+    double aC_ln, kc2;           // grad_comp_row's (the gradient only)
+    GradPiv pv;                  // ZEVOL
+};
+template <int V>
+__device__ __forceinline__ DeconvRow deconv_row(const DeconvArgs& a, int b, int f) {
+    const GradConst& gc = a.gc;
+    DeconvRow w{};
+    w.r = grad_row<V>(gc, a.theta + (size_t)b * gc.ndim, V == LF_FREE ? f : 0);
+    w.c1l = LF_LN10 * (w.r.al + 1.0);
+    const double flim = V == LF_FREE ? w.r.flim : a.dc.flim0[f];
+    w.aC = V == LF_FREE ? w.r.aC : a.dc.alpha0;
+    w.lF = log10(flim);
+    w.vs = exp(LF_LN10 * gc.kappa / w.aC) / flim;
+    w.aC_ln = w.aC / LF_LN10, w.kc2 = LF_LN10 * gc.kappa / (w.aC * w.aC);
+    w.Q = V == LF_ZEVOL ? 0.0 : exp(LF_LN10 * (LF_LREF - w.r.L[0]));
+    if (V == LF_ZEVOL) w.pv = grad_piv(gc);
+    return w;
+}
+// t = 10^(L - L*) of source g; ZEVOL: L* at its z, and lb the Lagrange basis there (else lb stays as it is)
+template <int V>
+__device__ __forceinline__ double deconv_t(const DeconvArgs& a, const DeconvRow& w, int g, double (&lb)[3]) {
+    if (V == LF_ZEVOL) return exp(LF_LN10 * (a.lum[g] - zevol_Lstar(w.r, w.pv, a.a1[g], lb)));
+    return a.P[g] * w.Q;
 }
 
-template <int V>
-__global__ __launch_bounds__(BLOCK) void lf_deconv_part(DeconvArgs a) {
-    __shared__ double nd[2 * DECONV_KMAX];
-    __shared__ double red[4];
+// The item loop of both part kernels: block (blockIdx.x, row blockIdx.y) takes its chunk's sources as the header says and
+// leaves each thread's NS running sums in acc.  GRAD false: acc[0] = the sum of Delta_i.  GRAD true: the numerators of
+// lf_deconv_grad.h ride the same online softmax, acc = that header's slots; m and s, and so Delta_i, take the same steps
+// either way.  nd: LDS for the node table.  False when the row's lnprob is not finite: the whole block returns then, before
+// any barrier (the rows' second stages do not read the partial sums of such a row).
+template <int V, bool GRAD, int NS>
+__device__ __forceinline__ bool deconv_items(const DeconvArgs& a, double* nd, double (&acc)[NS]) {
+    constexpr bool DERIV = GRAD && V == LF_FREE;  // dF, dC: of a completeness that is the row's own
     const int b = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
-    if (!isfinite(a.lnprob[b])) return;           // (the whole block: lf_deconv_final does not read `part` then)
+    if (!isfinite(a.lnprob[b])) return false;
     const int K = a.dc.K;
     if (tid < 2 * K) nd[tid] = a.nodes[tid];
     __syncthreads();
-    const GradConst& gc = a.gc;
-    const int f = a.chunk_field[blk];
-    const GradRow r = grad_row<V>(gc, a.theta + (size_t)b * gc.ndim, V == LF_FREE ? f : 0);
-    const double c1l = LF_LN10 * (r.al + 1.0);
-    const double flim = V == LF_FREE ? r.flim : a.dc.flim0[f];
-    const double aC = V == LF_FREE ? r.aC : a.dc.alpha0;
-    const double lF = log10(flim);
-    const double vs = exp(LF_LN10 * gc.kappa / aC) / flim;
-    const double Q = V == LF_ZEVOL ? 0.0 : exp(LF_LN10 * (LF_LREF - r.L[0]));
-    GradPiv pv{};
-    if (V == LF_ZEVOL) pv = grad_piv(gc);
+    const DeconvRow w = deconv_row<V>(a, b, a.chunk_field[blk]);
     const int first = a.chunk_start[blk], len = a.chunk_len[blk];
-    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) acc[j] = 0.0;
     for (int i = tid; i < len; i += BLOCK) {
         const int g = first + i;
         const double sg = a.sigma[g];
         if (!(sg > 0.0)) continue;
-        double t;
-        if (V == LF_ZEVOL) {
-            double l[3];
-            grad_basis(pv, a.a1[g], l);
-            const double Lz = fma(l[2], r.L[2], fma(l[1], r.L[1], l[0] * r.L[0]));
-            t = exp(LF_LN10 * (a.lum[g] - Lz));
-        } else {
-            t = a.P[g] * Q;
-        }
-        const double y0 = (a.logf[g] - LF_FREF) - lF;
-        const double v0 = a.U[g] * vs;
-        const double l0 = deconv_lcomp(aC, y0, v0);
+        double lb[3] = {0.0, 0.0, 0.0};
+        const double t = deconv_t<V>(a, w, g, lb);
+        const double y0 = (a.logf[g] - LF_FREF) - w.lF;
+        const double v0 = a.U[g] * w.vs;
+        const GradComp c0 = comp_form<DERIV>(w.aC, w.aC_ln, w.kc2, y0, v0);
         const double s2 = 1.41421356237309504880 * sg;
-        double m = -HUGE_VAL, s = 0.0;
+        double m = -HUGE_VAL, s = 0.0, nD = 0.0, nE = 0.0, nF = 0.0, nC = 0.0;
         for (int k = 0; k < K; ++k) {
             const double dl = s2 * nd[k];
             const double em = expm1(LF_LN10 * dl);
-            const double av = nd[K + k] + ((c1l * dl - t * em) + (deconv_lcomp(aC, y0 + dl, v0 * (em + 1.0)) - l0));
+            const GradComp ck = comp_form<DERIV>(w.aC, w.aC_ln, w.kc2, y0 + dl, v0 * (em + 1.0));
+            const double av = nd[K + k] + ((w.c1l * dl - t * em) + (ck.l - c0.l));
             if (av == -HUGE_VAL) continue;
             const double d = av - m;
             const double e = exp(-fabs(d));
             if (d > 0.0) {
                 s = fma(s, e, 1.0);
+                if (GRAD) nD = fma(nD, e, dl), nE = fma(nE, e, em);
+                if (DERIV) nF = fma(nF, e, ck.dF), nC = fma(nC, e, ck.dC);
                 m = av;
             } else {
                 s += e;
+                if (GRAD) nD = fma(e, dl, nD), nE = fma(e, em, nE);
+                if (DERIV) nF = fma(e, ck.dF, nF), nC = fma(e, ck.dC, nC);
             }
         }
-        acc += m + log(s);
+        if constexpr (!GRAD) {
+            acc[0] += m + log(s);
+        } else if constexpr (V == LF_ZEVOL) {
+            const double gL = t * (nE / s);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) acc[q] += lb[q] * gL;
+            acc[3] += nD / s;
+        } else {
+            acc[0] += t * (nE / s);
+            acc[1] += nD / s;
+            if constexpr (DERIV) {
+                acc[2] += nF / s - c0.dF;
+                acc[3] += nC / s - c0.dC;
+            }
+        }
     }
-    const int lane = tid & 63, wv = tid >> 6;
-    const double ws = wave_sum(acc);
-    if (lane == 0) red[wv] = ws;
-    __syncthreads();
-    if (tid == 0) a.part[(size_t)b * a.nch + blk] = ((red[0] + red[1]) + red[2]) + red[3];
+    return true;
+}
+
+template <int V>
+__global__ __launch_bounds__(BLOCK) void lf_deconv_part(DeconvArgs a) {
+    __shared__ double nd[2 * DECONV_KMAX];
+    __shared__ double red[4][1];
+    double acc[1];
+    if (!deconv_items<V, false>(a, nd, acc)) return;
+    const int b = blockIdx.y, blk = blockIdx.x;
+    block_sum(acc, red, a.part + (size_t)b * a.nch + blk);
 }
 
 // grid (rows), 64 threads

@@ -22,11 +22,15 @@
 // lf_grad_part   grid (blocks, rows), 256 threads.  Block c < nchA: chunk c of up to GRAD_CH sources of one field (the context's
 //                per-source arrays, lf_hostprep.h: catalogue); block nchA + q: field q % nfB of the lattice's nodes [q / nfB
 //                GRAD_CH, + GRAD_CH) (FREE: nfB = nf; else the fields are summed in W: nfB = 1).  Thread t takes items t, t + 256,
-//                ... of its chunk in that order, GRAD_SLOTS running sums; then the wave's 64 lanes by the shuffle tree of
-//                wave_sum, the four waves' totals through LDS as ((w0 + w1) + w2) + w3 -> part[row][block][GRAD_SLOTS].
+//                ... of its chunk in that order, GRAD_SLOTS running sums; then the block's tail (block_sum, lf_math.h): the
+//                wave's 64 lanes by the shuffle tree of wave_sum, the four waves' totals through LDS as ((w0 + w1) + w2) + w3
+//                -> part[row][block][GRAD_SLOTS].
 // lf_grad_final  one wave per row: element e = scale x ((closed form + sum of the source blocks' slot) - sum of the lattice
-//                blocks' slot); lane l adds blocks l, l + 64, ... in that order, then the shuffle tree.  A row whose lnprob is
-//                not finite gets NaN in every element.
+//                blocks' slot); lane l adds blocks l, l + 64, ... in that order (final_lane_sum; the Flim_f element: its
+//                field's blocks only), then the shuffle tree; scale (grad_elem): ln10, 1 / Flim_f, 1 for alpha_C.  A row
+//                whose lnprob is not finite gets NaN in every element (final_nan_row).
+// The completeness form above is written once, comp_form<DERIV>; lf_deconv.h and lf_deconv_grad.h call it at their nodes, and
+// lf_deconv_grad_final is made of lf_grad_final's helpers.
 // No atomics; nothing in either order depends on the batch: a row's gradient has the same bits at any B and any position.
 // Slots: FREE, FIXCOMP {L*, phi*, alpha, Flim_f, alpha_C};  ZEVOL {L1, L2, L3, phi1, phi2, phi3, alpha}.
 #pragma once
@@ -96,30 +100,35 @@ __device__ __forceinline__ GradCompRow grad_comp_row(const GradRow& r, double ka
     q.kc2 = LF_LN10 * kappa / (r.aC * r.aC);
     return q;
 }
-// logf: log10 of the flux, U = 10^(logf + 17)
-__device__ __forceinline__ GradComp grad_comp(const GradCompRow& q, double logf, double U) {
-    const double y = (logf - LF_FREF) - q.lF;
-    const double num = q.aC * y;
+// The one body of the form above at y = log10(f / Flim), v = f / f_tau.  DERIV false: l only (dF = dC = 0), by the same
+// statements - l has the same bits either way.
+template <bool DERIV>
+__device__ __forceinline__ GradComp comp_form(double aC, double aC_ln, double kc2, double y, double v) {
+    const double num = aC * y;
     const double den = sqrt(fma(num, num, 1.0));
-    const double v = U * q.vs;
-    const double e = exp(-v);
+    const double e = DERIV ? exp(-v) : 0.0;
     const double d = -expm1(-v);
-    double lnfc, gp;
+    double lnfc, gp = 0.0;
     if (num < 0.0) {
         const double s = den - num;
         lnfc = -log(2.0 * den * s);
-        gp = s / (den * den);
+        if (DERIV) gp = s / (den * den);
     } else {
         const double s = den + num;
         lnfc = log1p(-0.5 / (den * s));
-        gp = 1.0 / (den * den * s);
+        if (DERIV) gp = 1.0 / (den * den * s);
     }
-    GradComp c;
-    c.l = lnfc / d;
-    const double lw = e > 0.0 ? c.l * (v * e / d) : 0.0;
-    c.dF = lw - gp * q.aC_ln / d;
-    c.dC = fma(lw, q.kc2, gp * y / d);
+    GradComp c{lnfc / d, 0.0, 0.0};
+    if (DERIV) {
+        const double lw = e > 0.0 ? c.l * (v * e / d) : 0.0;
+        c.dF = lw - gp * aC_ln / d;
+        c.dC = fma(lw, kc2, gp * y / d);
+    }
     return c;
+}
+// logf: log10 of the flux, U = 10^(logf + 17)
+__device__ __forceinline__ GradComp grad_comp(const GradCompRow& q, double logf, double U) {
+    return comp_form<true>(q.aC, q.aC_ln, q.kc2, (logf - LF_FREF) - q.lF, U * q.vs);
 }
 
 // the Lagrange basis on the pivots at z
@@ -139,6 +148,11 @@ __device__ __forceinline__ void grad_basis(const GradPiv& p, double z, double (&
     l[0] = b * c * p.i1;
     l[1] = a * c * p.i2;
     l[2] = a * b * p.i3;
+}
+// L*(z) of a z-evolving row, and the basis l at z it is made with
+__device__ __forceinline__ double zevol_Lstar(const GradRow& r, const GradPiv& p, double z, double (&l)[3]) {
+    grad_basis(p, z, l);
+    return fma(l[2], r.L[2], fma(l[1], r.L[1], l[0] * r.L[0]));
 }
 
 template <int V>
@@ -163,9 +177,7 @@ __global__ __launch_bounds__(BLOCK) void lf_grad_part(GradArgs a) {
         for (int i = tid; i < len; i += BLOCK) {
             const int g = first + i;
             double l[3];
-            grad_basis(pv, src ? a.a1[g] : a.a3[g], l);
-            const double Lz = fma(l[2], r.L[2], fma(l[1], r.L[1], l[0] * r.L[0]));
-            const double x = (src ? a.lum[g] : a.G[g]) - Lz;
+            const double x = (src ? a.lum[g] : a.G[g]) - zevol_Lstar(r, pv, src ? a.a1[g] : a.a3[g], l);
             const double t = exp(LF_LN10 * x);
             double I = 1.0;
             if (!src) {
@@ -209,15 +221,41 @@ __global__ __launch_bounds__(BLOCK) void lf_grad_part(GradArgs a) {
         }
     }
 
-    const int lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-    for (int j = 0; j < GRAD_SLOTS - 1; ++j) {
-        const double s = wave_sum(acc[j]);
-        if (lane == 0) red[wv][j] = s;
-    }
-    __syncthreads();
-    if (tid < GRAD_SLOTS - 1)
-        a.part[((size_t)b * (a.nchA + a.nchB * a.nfB) + blk) * GRAD_SLOTS + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    block_sum(acc, red, a.part + ((size_t)b * (a.nchA + a.nchB * a.nfB) + blk) * GRAD_SLOTS);
+}
+
+// ---- what the rows' second stages share (lf_grad_final, lf_deconv_grad_final: one wave per row) ----
+// A row whose lnprob is not finite: NaN in every element, and the caller returns
+__device__ __forceinline__ bool final_nan_row(double lnprob, double* __restrict__ out, int ndim) {
+    if (isfinite(lnprob)) return false;
+    if ((int)threadIdx.x < ndim) out[threadIdx.x] = __builtin_nan("");
+    return true;
+}
+// theta element e: what it is (FREE / FIXCOMP: 0 L*, 1 phi*, 2 alpha, 3 Flim_f, 4 alpha_C; ZEVOL: e itself - L1, L2, L3, phi1,
+// phi2, phi3, alpha), the field whose blocks alone count (-1: all) and the factor of the blocks' sum (ln10; 1 / Flim_f; 1)
+struct GradElem {
+    int kind, fld;
+    double scale;
+};
+template <int V>
+__device__ __forceinline__ GradElem grad_elem(const GradConst& gc, const double* __restrict__ th, int e) {
+    GradElem g{e, -1, LF_LN10};
+    const int kF = gc.fix_sch_al ? 2 : 3;         // FREE: theta index of Flim_0
+    if (V == LF_ZEVOL || e < 2) return g;
+    if (!gc.fix_sch_al && e == 2) return g;
+    if (V != LF_FREE) return g;                   // (FIXCOMP has no further element)
+    if (e < kF + gc.nf) g.kind = 3, g.fld = e - kF, g.scale = 1.0 / th[e];
+    else g.kind = 4, g.scale = 1.0;
+    return g;
+}
+// this lane's share of the sum over n blocks of part[block LD]: blocks lane, lane + 64, ... in that order, those of field fld
+// only (fld < 0: all; field_of(block): its field); wave_sum of it is the row's sum
+template <int LD, class F>
+__device__ __forceinline__ double final_lane_sum(const double* __restrict__ part, int n, int fld, F field_of) {
+    double s = 0.0;
+    for (int c = threadIdx.x; c < n; c += 64)
+        if (fld < 0 || field_of(c) == fld) s += part[(size_t)c * LD];
+    return s;
 }
 
 // grid (rows), 64 threads
@@ -226,35 +264,24 @@ __global__ __launch_bounds__(64) void lf_grad_final(GradArgs a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const GradConst& gc = a.gc;
     double* out = a.grad + (size_t)b * gc.ndim;
-    if (!isfinite(a.lnprob[b])) {
-        if (lane < gc.ndim) out[lane] = __builtin_nan("");
-        return;
-    }
+    if (final_nan_row(a.lnprob[b], out, gc.ndim)) return;
     const double* th = a.theta + (size_t)b * gc.ndim;
     const int nblkB = a.nchB * a.nfB, nblk = a.nchA + nblkB;
     const double* part = a.part + (size_t)b * nblk * GRAD_SLOTS;
-    const int kF = gc.fix_sch_al ? 2 : 3;         // FREE: theta index of Flim_0
     for (int e = 0; e < gc.ndim; ++e) {
-        int slot, fld = -1;
-        double scale = LF_LN10, closed = 0.0;
+        const GradElem el = grad_elem<V>(gc, th, e);
+        const int slot = el.kind;                 // (the slots are in the elements' order)
+        double closed = 0.0;
         if (V == LF_ZEVOL) {
-            slot = e;
             if (e >= 3 && e < 6) closed = gc.sl[e - 3];
-        } else {
-            if (e < 2) slot = e;
-            else if (!gc.fix_sch_al && e == 2) slot = 2;
-            else if (e < kF + gc.nf) slot = 3, fld = e - kF, scale = 1.0 / th[e];
-            else slot = 4, scale = 1.0;
-            if (e == 1) closed = gc.nsrc;
+        } else if (e == 1) {
+            closed = gc.nsrc;
         }
-        double sA = 0.0, sB = 0.0;
-        for (int c = lane; c < a.nchA; c += 64)
-            if (fld < 0 || a.chunk_field[c] == fld) sA += part[(size_t)c * GRAD_SLOTS + slot];
-        for (int q = lane; q < nblkB; q += 64)
-            if (fld < 0 || q % a.nfB == fld) sB += part[(size_t)(a.nchA + q) * GRAD_SLOTS + slot];
+        double sA = final_lane_sum<GRAD_SLOTS>(part + slot, a.nchA, el.fld, [&](int c) { return a.chunk_field[c]; });
+        double sB = final_lane_sum<GRAD_SLOTS>(part + (size_t)a.nchA * GRAD_SLOTS + slot, nblkB, el.fld, [&](int q) { return q % a.nfB; });
         sA = wave_sum(sA);
         sB = wave_sum(sB);
-        if (lane == 0) out[e] = scale * ((closed + sA) - sB);
+        if (lane == 0) out[e] = el.scale * ((closed + sA) - sB);
     }
 }
 

@@ -212,6 +212,20 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// The tail of a 256-thread block that keeps NS running sums per thread: each wave's 64 lanes by wave_sum, the four waves'
+// totals through red (LDS, rows of LD >= NS) as ((w0 + w1) + w2) + w3 -> dst[0 .. NS).  Every thread of the block calls it.
+template <int NS, int LD>
+__device__ __forceinline__ void block_sum(const double (&acc)[NS], double (&red)[4][LD], double* __restrict__ dst) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const double s = wave_sum(acc[j]);
+        if (lane == 0) red[wv][j] = s;
+    }
+    __syncthreads();
+    if (tid < NS) dst[tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
 // ----------------------------------------------------------------------------------------------
 // Kernel arguments: one round trip instead of a dozen.  A launch's kernarg segment is freshly written memory - nothing of
 // it is in the scalar cache or in L2 - and these kernels take ~1.5 KB of arguments (KConst alone is 1360 bytes) which the

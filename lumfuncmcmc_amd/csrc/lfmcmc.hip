@@ -14,6 +14,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "lf_bands.h"
@@ -148,16 +149,17 @@ struct lf_ctx {
     Buf<int> d_wstat, d_wmode;
     Buf<double> d_wbase;
     Buf<double, true> h_theta, h_out;   // pinned staging
-    // the gradient (lf_grad.h): its constants, its chunks of the catalogue (made at first use), the blocks' partial sums
-    // [rows][blocks][GRAD_SLOTS], and the host form's results {lnprob [B], grad [B][ndim]} with their pinned staging
+    // the gradient (lf_grad.h): its constants, the chunks of the catalogue its source blocks and those of lf_deconv.h and
+    // lf_deconv_grad.h take (made at first use), the blocks' partial sums [rows][blocks][GRAD_SLOTS], and the host forms'
+    // results {value [B], grad [B][ndim]} with their pinned staging
     lf::GradConst gradc{};
-    ChunkTable grad_chunks;
-    bool grad_chunks_built = false;
+    ChunkTable src_chunks;
+    bool src_chunks_built = false;
     Buf<double> d_gpart, d_gout;
     Buf<double, true> h_gout;
     // the flux-error-convolved likelihood (lf_deconv.h; lf_set_lum_err): the sources' order in the device tables, whether every
     // redshift column of the grid has the same luminosity nodes, sigma (and, FIXCOMP / ZEVOL, the log flux and 10^(that + 17))
-    // in that order, the node table, the chunks and the blocks' partial sums [rows][chunks]
+    // in that order, the node table and the blocks' partial sums [rows][chunks]
     std::vector<int64_t> perm;
     bool grid_separable = false;
     lf::DeconvConst deconvc{};
@@ -165,8 +167,6 @@ struct lf_ctx {
     int64_t opt_deconv_unchecked = 0;   // 1: lf_set_lum_err takes sigma above the validated range of the order (tests, A/B runs)
     Buf<double> d_sigma, d_elogf, d_eU, d_ghnodes, d_dpart;
     Buf<double> d_dgpart;               // its gradient's partial sums [rows][chunks][DGRAD_SLOTS] (lf_deconv_grad.h)
-    ChunkTable deconv_chunks;
-    bool deconv_chunks_built = false;
     hipStream_t stream = nullptr;
     hipStream_t last_stream = nullptr;   // stream of the previous enqueue (workspace is shared)
     bool any_enqueued = false;
@@ -842,120 +842,122 @@ int enqueue(lf_ctx* c, const double* d_theta, int B, double* d_out, double* d_ou
     return LF_OK;
 }
 
-// The gradient of lnprob for B rows (lf_grad.h): the lnprob path itself first (d_lnp: what lf_lnprob_batch_device gives, and what
-// decides which rows get NaN), then the blocks' partial sums and the rows' second stage, all on `s`.
-template <int VARIANT>
-void launch_grad(const lf::GradArgs& ga, int nblk, int B, hipStream_t s) {
-    using namespace lf;
-    // (a grid's second dimension holds 65 535 rows)
-    for (int b0 = 0; b0 < B; b0 += 32768) {
-        const int nb = std::min(32768, B - b0);
-        GradArgs g = ga;
-        g.theta += (size_t)b0 * g.gc.ndim;
-        g.lnprob += b0;
-        g.part += (size_t)b0 * nblk * GRAD_SLOTS;
-        g.grad += (size_t)b0 * g.gc.ndim;
-        if (nblk > 0) hipLaunchKernelGGL(lf_grad_part<VARIANT>, dim3((unsigned)nblk, (unsigned)nb), dim3(BLOCK), 0, s, g);
-        hipLaunchKernelGGL(lf_grad_final<VARIANT>, dim3((unsigned)nb), dim3(64), 0, s, g);
+// The three families below (lf_grad.h, lf_deconv.h, lf_deconv_grad.h) launch a part kernel on a grid (blocks, rows) and a
+// second stage on (rows), the context's variant as the template argument.  A grid's second dimension holds 65 535 rows:
+// launch(V, b0, nb) for rows [b0, b0 + nb) in chunks of 32 768, V the variant as a std::integral_constant.
+template <class F>
+void launch_rows(int variant, int B, F launch) {
+    const auto rows = [&](auto v) {
+        for (int b0 = 0; b0 < B; b0 += 32768) launch(v, b0, std::min(32768, B - b0));
+    };
+    switch (variant) {
+        case LF_FREE: rows(std::integral_constant<int, LF_FREE>{}); break;
+        case LF_FIXCOMP: rows(std::integral_constant<int, LF_FIXCOMP>{}); break;
+        default: rows(std::integral_constant<int, LF_ZEVOL>{});
     }
 }
 
+// the chunks of the catalogue that the three families' source blocks take, made and uploaded at first use
+static_assert(lf::GRAD_CH == lf::DECONV_CH, "lf_grad_part and the lf_deconv*_part kernels share one chunk table");
+int src_chunk_table(lf_ctx* c) {
+    if (c->src_chunks_built) return LF_OK;
+    const lfh::Chunks h = lfh::chunk_table(c->field_ind, c->kc.nf, lf::GRAD_CH, 0.0, 0.0, 0.0);
+    ChunkTable& t = c->src_chunks;
+    t.n = (int)h.start.size();
+    const int rc = upload(c, t.d_start, h.start, t.d_len, h.len, t.d_field, h.field);
+    if (rc != LF_OK) return rc;
+    c->src_chunks_built = true;
+    return LF_OK;
+}
+
+// The gradient of lnprob for B rows (lf_grad.h): the lnprob path itself first (d_lnp: what lf_lnprob_batch_device gives, and what
+// decides which rows get NaN), then the blocks' partial sums and the rows' second stage, all on `s`.
 int enqueue_grad(lf_ctx* c, const double* d_theta, int B, double* d_lnp, double* d_grad, hipStream_t s) {
     using namespace lf;
     int rc;
-    if (!c->grad_chunks_built) {
-        const lfh::Chunks h = lfh::chunk_table(c->field_ind, c->kc.nf, GRAD_CH, 0.0, 0.0, 0.0);
-        ChunkTable& t = c->grad_chunks;
-        t.n = (int)h.start.size();
-        if ((rc = upload(c, t.d_start, h.start, t.d_len, h.len, t.d_field, h.field)) != LF_OK) return rc;
-        c->grad_chunks_built = true;
-    }
-    const int nchA = c->grad_chunks.n;
+    if ((rc = src_chunk_table(c)) != LF_OK) return rc;
+    const ChunkTable& t = c->src_chunks;
+    const int nchA = t.n;
     const int nchB = (c->nnodes + GRAD_CH - 1) / GRAD_CH;
     const int nfB = c->kc.variant == LF_FREE ? c->kc.nf : 1;
     const int nblk = nchA + nchB * nfB;
     const size_t need = (size_t)B * std::max(nblk, 1) * GRAD_SLOTS;
     if (need > c->d_gpart.size() && (rc = grow(c, c->d_gpart, need)) != LF_OK) return rc;
     if ((rc = enqueue(c, d_theta, B, d_lnp, nullptr, nullptr, s)) != LF_OK) return rc;
-    const GradArgs ga{c->gradc, d_theta, d_lnp, c->d_gpart, d_grad, c->d_lum, c->d_a1, c->d_P, c->d_U,
-                      c->grad_chunks.d_start, c->grad_chunks.d_len, c->grad_chunks.d_field,
+    const GradArgs ga{c->gradc, d_theta, d_lnp, c->d_gpart, d_grad, c->d_lum, c->d_a1, c->d_P, c->d_U, t.d_start, t.d_len, t.d_field,
                       c->d_G, c->d_PG, c->d_W, c->d_a3, c->d_a4, c->nnodes, nchA, nchB, nfB};
-    switch (c->kc.variant) {
-        case LF_FREE: launch_grad<LF_FREE>(ga, nblk, B, s); break;
-        case LF_FIXCOMP: launch_grad<LF_FIXCOMP>(ga, nblk, B, s); break;
-        default: launch_grad<LF_ZEVOL>(ga, nblk, B, s);
-    }
+    launch_rows(c->kc.variant, B, [&](auto v, int b0, int nb) {
+        GradArgs g = ga;
+        g.theta += (size_t)b0 * g.gc.ndim;
+        g.lnprob += b0;
+        g.part += (size_t)b0 * nblk * GRAD_SLOTS;
+        g.grad += (size_t)b0 * g.gc.ndim;
+        if (nblk > 0) hipLaunchKernelGGL(lf_grad_part<v()>, dim3((unsigned)nblk, (unsigned)nb), dim3(BLOCK), 0, s, g);
+        hipLaunchKernelGGL(lf_grad_final<v()>, dim3((unsigned)nb), dim3(64), 0, s, g);
+    });
     LF_HIP(c, hipGetLastError());
     return LF_OK;
 }
 
-// what both gradient entry points refuse before the device is touched
-int grad_check(lf_ctx* c, const char* fn, const void* theta, int B, const void* grad) {
+// what the entry points of the three families refuse before the device is touched; err: those of the convolved likelihood
+int family_check(lf_ctx* c, const char* fn, bool err, const void* theta, int B, const void* out) {
     if (!c) return LF_ERR_ARG;
-    if (!theta || !grad || B <= 0) {
+    if (!theta || !out || B <= 0) {
         c->err = std::string(fn) + ": NULL pointer or B <= 0";
         return LF_ERR_ARG;
     }
+    if (err && !c->deconv_set) {
+        c->err = std::string(fn) + ": no luminosity errors set (call lf_set_lum_err first)";
+        return LF_ERR_ARG;
+    }
     if (c->opt_skip_grid || c->kc.grid_parts > 1) {
-        c->err = std::string(fn) + ": no gradient of a source-sharded context (options skip_grid, grid_share)";
+        c->err = std::string(fn) + ": no " + (err ? "convolved likelihood" : "gradient") +
+                 " of a source-sharded context (options skip_grid, grid_share)";
         return LF_ERR_ARG;
     }
     return LF_OK;
 }
 
-// The flux-error-convolved lnprob of B rows (lf_deconv.h): the lnprob path itself first (d_lnp: what lf_lnprob_batch_device
-// gives, bit for bit), then the blocks' partial sums of the correction and the rows' second stage, all on `s`.
-template <int VARIANT>
-void launch_deconv(const lf::DeconvArgs& da, int B, hipStream_t s) {
-    using namespace lf;
-    for (int b0 = 0; b0 < B; b0 += 32768) {
-        const int nb = std::min(32768, B - b0);
-        DeconvArgs g = da;
-        g.theta += (size_t)b0 * g.gc.ndim;
-        g.lnprob += b0;
-        g.part += (size_t)b0 * g.nch;
-        g.out += b0;
-        if (g.nch > 0) hipLaunchKernelGGL(lf_deconv_part<VARIANT>, dim3((unsigned)g.nch, (unsigned)nb), dim3(BLOCK), 0, s, g);
-        hipLaunchKernelGGL(lf_deconv_final, dim3((unsigned)nb), dim3(64), 0, s, g);
-    }
-}
-
-// the chunk table of the correction's kernels, made at first use
-int deconv_chunk_table(lf_ctx* c) {
-    using namespace lf;
-    if (c->deconv_chunks_built) return LF_OK;
-    const lfh::Chunks h = lfh::chunk_table(c->field_ind, c->kc.nf, DECONV_CH, 0.0, 0.0, 0.0);
-    ChunkTable& t = c->deconv_chunks;
-    t.n = (int)h.start.size();
-    const int rc = upload(c, t.d_start, h.start, t.d_len, h.len, t.d_field, h.field);
-    if (rc != LF_OK) return rc;
-    c->deconv_chunks_built = true;
+// What the correction's kernels need before anything is enqueued: the chunk table and the blocks' partial sums [rows][chunks]
+// (grad: and [rows][chunks][DGRAD_SLOTS]).
+int deconv_prepare(lf_ctx* c, int B, bool grad) {
+    int rc;
+    if ((rc = src_chunk_table(c)) != LF_OK) return rc;
+    const size_t need = (size_t)B * std::max(c->src_chunks.n, 1);
+    if (need > c->d_dpart.size() && (rc = grow(c, c->d_dpart, need)) != LF_OK) return rc;
+    if (grad && need * lf::DGRAD_SLOTS > c->d_dgpart.size() && (rc = grow(c, c->d_dgpart, need * lf::DGRAD_SLOTS)) != LF_OK) return rc;
     return LF_OK;
 }
 
 lf::DeconvArgs deconv_args(lf_ctx* c, const double* d_theta, double* d_lnp, double* d_out) {
     const bool fr = c->kc.variant == LF_FREE;
+    const ChunkTable& t = c->src_chunks;
     return lf::DeconvArgs{c->gradc, c->deconvc, d_theta, d_lnp, c->d_dpart, d_out, c->d_lum, c->d_a1, c->d_P,
                           fr ? c->d_a1.get() : c->d_elogf.get(), fr ? c->d_U.get() : c->d_eU.get(), c->d_sigma, c->d_ghnodes,
-                          c->deconv_chunks.d_start, c->deconv_chunks.d_len, c->deconv_chunks.d_field, c->deconv_chunks.n};
+                          t.d_start, t.d_len, t.d_field, t.n};
 }
 
-void launch_deconv_variant(lf_ctx* c, const lf::DeconvArgs& da, int B, hipStream_t s) {
-    switch (c->kc.variant) {
-        case LF_FREE: launch_deconv<LF_FREE>(da, B, s); break;
-        case LF_FIXCOMP: launch_deconv<LF_FIXCOMP>(da, B, s); break;
-        default: launch_deconv<LF_ZEVOL>(da, B, s);
-    }
-}
-
-int enqueue_deconv(lf_ctx* c, const double* d_theta, int B, double* d_lnp, double* d_out, hipStream_t s) {
+// the value's two kernels on the plain lnprob of B rows (da.lnprob)
+void launch_deconv(lf_ctx* c, const lf::DeconvArgs& da, int B, hipStream_t s) {
     using namespace lf;
+    launch_rows(c->kc.variant, B, [&](auto v, int b0, int nb) {
+        DeconvArgs g = da;
+        g.theta += (size_t)b0 * g.gc.ndim;
+        g.lnprob += b0;
+        g.part += (size_t)b0 * g.nch;
+        g.out += b0;
+        if (g.nch > 0) hipLaunchKernelGGL(lf_deconv_part<v()>, dim3((unsigned)g.nch, (unsigned)nb), dim3(BLOCK), 0, s, g);
+        hipLaunchKernelGGL(lf_deconv_final, dim3((unsigned)nb), dim3(64), 0, s, g);
+    });
+}
+
+// The flux-error-convolved lnprob of B rows (lf_deconv.h): the lnprob path itself first (d_lnp: what lf_lnprob_batch_device
+// gives, bit for bit), then the blocks' partial sums of the correction and the rows' second stage, all on `s`.
+int enqueue_deconv(lf_ctx* c, const double* d_theta, int B, double* d_lnp, double* d_out, hipStream_t s) {
     int rc;
-    if ((rc = deconv_chunk_table(c)) != LF_OK) return rc;
-    const size_t need = (size_t)B * std::max(c->deconv_chunks.n, 1);
-    if (need > c->d_dpart.size() && (rc = grow(c, c->d_dpart, need)) != LF_OK) return rc;
+    if ((rc = deconv_prepare(c, B, false)) != LF_OK) return rc;
     if ((rc = enqueue(c, d_theta, B, d_lnp, nullptr, nullptr, s)) != LF_OK) return rc;
-    launch_deconv_variant(c, deconv_args(c, d_theta, d_lnp, d_out), B, s);
+    launch_deconv(c, deconv_args(c, d_theta, d_lnp, d_out), B, s);
     LF_HIP(c, hipGetLastError());
     return LF_OK;
 }
@@ -963,56 +965,56 @@ int enqueue_deconv(lf_ctx* c, const double* d_theta, int B, double* d_lnp, doubl
 // The flux-error-convolved lnprob of B rows and its gradient (lf_deconv_grad.h), all on `s`: the plain lnprob and the plain
 // gradient (enqueue_grad: d_lnp, d_grad), the value's kernels as enqueue_deconv launches them on that lnprob (d_out: what
 // lf_lnprob_err_batch_device gives, bit for bit), then the correction's gradient, added to d_grad in place.
-template <int VARIANT>
-void launch_deconv_grad(const lf::DeconvGradArgs& da, int B, hipStream_t s) {
+int enqueue_deconv_grad(lf_ctx* c, const double* d_theta, int B, double* d_lnp, double* d_out, double* d_grad, hipStream_t s) {
     using namespace lf;
-    for (int b0 = 0; b0 < B; b0 += 32768) {
-        const int nb = std::min(32768, B - b0);
+    int rc;
+    if ((rc = deconv_prepare(c, B, true)) != LF_OK) return rc;
+    if ((rc = enqueue_grad(c, d_theta, B, d_lnp, d_grad, s)) != LF_OK) return rc;
+    const DeconvGradArgs da{deconv_args(c, d_theta, d_lnp, d_out), c->d_dgpart, d_grad};
+    launch_deconv(c, da.d, B, s);
+    launch_rows(c->kc.variant, B, [&](auto v, int b0, int nb) {
         DeconvGradArgs g = da;
         g.d.theta += (size_t)b0 * g.d.gc.ndim;
         g.d.lnprob += b0;
         g.gpart += (size_t)b0 * g.d.nch * DGRAD_SLOTS;
         g.grad += (size_t)b0 * g.d.gc.ndim;
-        if (g.d.nch > 0)
-            hipLaunchKernelGGL(lf_deconv_grad_part<VARIANT>, dim3((unsigned)g.d.nch, (unsigned)nb), dim3(BLOCK), 0, s, g);
-        hipLaunchKernelGGL(lf_deconv_grad_final<VARIANT>, dim3((unsigned)nb), dim3(64), 0, s, g);
-    }
-}
-
-int enqueue_deconv_grad(lf_ctx* c, const double* d_theta, int B, double* d_lnp, double* d_out, double* d_grad, hipStream_t s) {
-    using namespace lf;
-    int rc;
-    if ((rc = deconv_chunk_table(c)) != LF_OK) return rc;
-    const size_t need = (size_t)B * std::max(c->deconv_chunks.n, 1);
-    if (need > c->d_dpart.size() && (rc = grow(c, c->d_dpart, need)) != LF_OK) return rc;
-    if (need * DGRAD_SLOTS > c->d_dgpart.size() && (rc = grow(c, c->d_dgpart, need * DGRAD_SLOTS)) != LF_OK) return rc;
-    if ((rc = enqueue_grad(c, d_theta, B, d_lnp, d_grad, s)) != LF_OK) return rc;
-    const DeconvGradArgs da{deconv_args(c, d_theta, d_lnp, d_out), c->d_dgpart, d_grad};
-    launch_deconv_variant(c, da.d, B, s);
-    switch (c->kc.variant) {
-        case LF_FREE: launch_deconv_grad<LF_FREE>(da, B, s); break;
-        case LF_FIXCOMP: launch_deconv_grad<LF_FIXCOMP>(da, B, s); break;
-        default: launch_deconv_grad<LF_ZEVOL>(da, B, s);
-    }
+        if (g.d.nch > 0) hipLaunchKernelGGL(lf_deconv_grad_part<v()>, dim3((unsigned)g.d.nch, (unsigned)nb), dim3(BLOCK), 0, s, g);
+        hipLaunchKernelGGL(lf_deconv_grad_final<v()>, dim3((unsigned)nb), dim3(64), 0, s, g);
+    });
     LF_HIP(c, hipGetLastError());
     return LF_OK;
 }
 
-// what both entry points refuse before the device is touched
-int deconv_check(lf_ctx* c, const char* fn, const void* theta, int B, const void* out) {
-    if (!c) return LF_ERR_ARG;
-    if (!theta || !out || B <= 0) {
-        c->err = std::string(fn) + ": NULL pointer or B <= 0";
-        return LF_ERR_ARG;
+// The host forms' way in and out.  stage_theta: the workspace for B rows, theta through the pinned staging to d_theta on the
+// context's stream.  fetch: n doubles of d through the pinned h, on that stream, and the wait for them.
+int stage_theta(lf_ctx* c, const double* theta, int B) {
+    int rc;
+    LF_HIP(c, hipSetDevice(c->device));
+    if ((rc = ensure_workspace(c, B, 0, 0)) != LF_OK) return rc;
+    const size_t tb = (size_t)B * c->kc.ndim * sizeof(double);
+    std::memcpy(c->h_theta, theta, tb);
+    LF_HIP(c, hipMemcpyAsync(c->d_theta, c->h_theta, tb, hipMemcpyHostToDevice, c->stream));
+    return LF_OK;
+}
+int fetch(lf_ctx* c, double* h, const double* d, size_t n) {
+    LF_HIP(c, hipMemcpyAsync(h, d, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    LF_HIP(c, hipStreamSynchronize(c->stream));
+    return LF_OK;
+}
+// a "(value, gradient)" call on host arrays: enq(d_value [B], d_grad [B][ndim]) enqueues it on the context's stream
+template <class F>
+int host_value_grad(lf_ctx* c, const double* theta, int B, double* value, double* grad, F enq) {
+    int rc;
+    if ((rc = stage_theta(c, theta, B)) != LF_OK) return rc;
+    const size_t no = (size_t)B * (c->kc.ndim + 1);
+    if (no > c->d_gout.size()) {
+        if ((rc = grow(c, c->d_gout, no)) != LF_OK) return rc;
+        LF_HIP(c, c->h_gout.alloc(no));
     }
-    if (!c->deconv_set) {
-        c->err = std::string(fn) + ": no luminosity errors set (call lf_set_lum_err first)";
-        return LF_ERR_ARG;
-    }
-    if (c->opt_skip_grid || c->kc.grid_parts > 1) {
-        c->err = std::string(fn) + ": no convolved likelihood of a source-sharded context (options skip_grid, grid_share)";
-        return LF_ERR_ARG;
-    }
+    if ((rc = enq(c->d_gout.get(), c->d_gout + B)) != LF_OK) return rc;
+    if ((rc = fetch(c, c->h_gout, c->d_gout, no)) != LF_OK) return rc;
+    if (value) std::memcpy(value, c->h_gout, (size_t)B * sizeof(double));
+    std::memcpy(grad, c->h_gout + B, (no - B) * sizeof(double));
     return LF_OK;
 }
 
@@ -1369,7 +1371,7 @@ int lf_lnprob_pieces(lf_ctx* c, const double* theta, int B, double* outA, double
 }
 
 int lf_lnprob_grad_batch_device(lf_ctx* c, const double* d_theta, int B, double* d_lnprob, double* d_grad, void* hip_stream) {
-    int rc = grad_check(c, "lf_lnprob_grad_batch_device", d_theta, B, d_grad);
+    int rc = family_check(c, "lf_lnprob_grad_batch_device", false, d_theta, B, d_grad);
     if (rc != LF_OK) return rc;
     LF_HIP(c, hipSetDevice(c->device));
     if (!d_lnprob) {
@@ -1381,24 +1383,11 @@ int lf_lnprob_grad_batch_device(lf_ctx* c, const double* d_theta, int B, double*
 }
 
 int lf_lnprob_grad_batch(lf_ctx* c, const double* theta, int B, double* lnprob, double* grad) {
-    int rc = grad_check(c, "lf_lnprob_grad_batch", theta, B, grad);
+    const int rc = family_check(c, "lf_lnprob_grad_batch", false, theta, B, grad);
     if (rc != LF_OK) return rc;
-    LF_HIP(c, hipSetDevice(c->device));
-    if ((rc = ensure_workspace(c, B, 0, 0)) != LF_OK) return rc;
-    const size_t nd = (size_t)c->kc.ndim, no = (size_t)B * (nd + 1);
-    if (no > c->d_gout.size()) {
-        if ((rc = grow(c, c->d_gout, no)) != LF_OK) return rc;
-        LF_HIP(c, c->h_gout.alloc(no));
-    }
-    const size_t tb = (size_t)B * nd * sizeof(double);
-    std::memcpy(c->h_theta, theta, tb);
-    LF_HIP(c, hipMemcpyAsync(c->d_theta, c->h_theta, tb, hipMemcpyHostToDevice, c->stream));
-    if ((rc = enqueue_grad(c, c->d_theta, B, c->d_gout, c->d_gout + B, c->stream)) != LF_OK) return rc;
-    LF_HIP(c, hipMemcpyAsync(c->h_gout, c->d_gout, no * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    LF_HIP(c, hipStreamSynchronize(c->stream));
-    if (lnprob) std::memcpy(lnprob, c->h_gout, (size_t)B * sizeof(double));
-    std::memcpy(grad, c->h_gout + B, tb);
-    return LF_OK;
+    return host_value_grad(c, theta, B, lnprob, grad, [&](double* d_lnp, double* d_grad) {
+        return enqueue_grad(c, c->d_theta, B, d_lnp, d_grad, c->stream);
+    });
 }
 
 int lf_gauss_hermite(int K, double* x, double* lnw) {
@@ -1474,7 +1463,7 @@ int lf_set_lum_err(lf_ctx* c, const double* sigma, int K, const double* logf, co
 }
 
 int lf_lnprob_err_batch_device(lf_ctx* c, const double* d_theta, int B, double* d_out, void* hip_stream) {
-    int rc = deconv_check(c, "lf_lnprob_err_batch_device", d_theta, B, d_out);
+    int rc = family_check(c, "lf_lnprob_err_batch_device", true, d_theta, B, d_out);
     if (rc != LF_OK) return rc;
     LF_HIP(c, hipSetDevice(c->device));
     // (the rows' plain lnprob: into the context's own buffer, sized before the lnprob path may replace it)
@@ -1483,22 +1472,17 @@ int lf_lnprob_err_batch_device(lf_ctx* c, const double* d_theta, int B, double* 
 }
 
 int lf_lnprob_err_batch(lf_ctx* c, const double* theta, int B, double* out) {
-    int rc = deconv_check(c, "lf_lnprob_err_batch", theta, B, out);
+    int rc = family_check(c, "lf_lnprob_err_batch", true, theta, B, out);
     if (rc != LF_OK) return rc;
-    LF_HIP(c, hipSetDevice(c->device));
-    if ((rc = ensure_workspace(c, B, 0, 0)) != LF_OK) return rc;
-    const size_t tb = (size_t)B * c->kc.ndim * sizeof(double);
-    std::memcpy(c->h_theta, theta, tb);
-    LF_HIP(c, hipMemcpyAsync(c->d_theta, c->h_theta, tb, hipMemcpyHostToDevice, c->stream));
+    if ((rc = stage_theta(c, theta, B)) != LF_OK) return rc;
     if ((rc = enqueue_deconv(c, c->d_theta, B, c->d_outB, c->d_outA, c->stream)) != LF_OK) return rc;
-    LF_HIP(c, hipMemcpyAsync(c->h_out, c->d_outA, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    LF_HIP(c, hipStreamSynchronize(c->stream));
+    if ((rc = fetch(c, c->h_out, c->d_outA, (size_t)B)) != LF_OK) return rc;
     std::memcpy(out, c->h_out, (size_t)B * sizeof(double));
     return LF_OK;
 }
 
 int lf_lnprob_err_grad_batch_device(lf_ctx* c, const double* d_theta, int B, double* d_lnprob_err, double* d_grad, void* hip_stream) {
-    int rc = deconv_check(c, "lf_lnprob_err_grad_batch_device", d_theta, B, d_grad);
+    int rc = family_check(c, "lf_lnprob_err_grad_batch_device", true, d_theta, B, d_grad);
     if (rc != LF_OK) return rc;
     LF_HIP(c, hipSetDevice(c->device));
     // (the rows' plain lnprob, and the value when it is not asked for: into the context's own buffers, sized before the
@@ -1508,24 +1492,11 @@ int lf_lnprob_err_grad_batch_device(lf_ctx* c, const double* d_theta, int B, dou
 }
 
 int lf_lnprob_err_grad_batch(lf_ctx* c, const double* theta, int B, double* lnprob_err, double* grad) {
-    int rc = deconv_check(c, "lf_lnprob_err_grad_batch", theta, B, grad);
+    const int rc = family_check(c, "lf_lnprob_err_grad_batch", true, theta, B, grad);
     if (rc != LF_OK) return rc;
-    LF_HIP(c, hipSetDevice(c->device));
-    if ((rc = ensure_workspace(c, B, 0, 0)) != LF_OK) return rc;
-    const size_t nd = (size_t)c->kc.ndim, no = (size_t)B * (nd + 1);
-    if (no > c->d_gout.size()) {
-        if ((rc = grow(c, c->d_gout, no)) != LF_OK) return rc;
-        LF_HIP(c, c->h_gout.alloc(no));
-    }
-    const size_t tb = (size_t)B * nd * sizeof(double);
-    std::memcpy(c->h_theta, theta, tb);
-    LF_HIP(c, hipMemcpyAsync(c->d_theta, c->h_theta, tb, hipMemcpyHostToDevice, c->stream));
-    if ((rc = enqueue_deconv_grad(c, c->d_theta, B, c->d_outB, c->d_gout, c->d_gout + B, c->stream)) != LF_OK) return rc;
-    LF_HIP(c, hipMemcpyAsync(c->h_gout, c->d_gout, no * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    LF_HIP(c, hipStreamSynchronize(c->stream));
-    if (lnprob_err) std::memcpy(lnprob_err, c->h_gout, (size_t)B * sizeof(double));
-    std::memcpy(grad, c->h_gout + B, tb);
-    return LF_OK;
+    return host_value_grad(c, theta, B, lnprob_err, grad, [&](double* d_val, double* d_grad) {
+        return enqueue_deconv_grad(c, c->d_theta, B, c->d_outB, d_val, d_grad, c->stream);
+    });
 }
 
 int lf_set_profiling(lf_ctx* c, int enabled) {

@@ -55,9 +55,9 @@ int blocks_for(long long threads) { return (int)((threads + TPB - 1) / TPB); }
 // ---------------------------------------------------------------------------------------------- completeness forms
 enum { COMP_GRAD = 0, COMP_DGRAD = 1, COMP_LCOMP = 2 };
 // COMP_GRAD:  p = Flim, q = logf, r = U:  grad_comp(grad_comp_row(row, kappa), logf, U)
-// COMP_DGRAD: q = y, r = v:               dgrad_comp(aC, aC_ln, kc2, y, v), aC_ln and kc2 out of grad_comp_row (the statements
-//                                         lf_deconv_grad_part forms them with)
-// COMP_LCOMP: q = y, r = v:               deconv_lcomp(aC, y, v)
+// COMP_DGRAD: q = y, r = v:               dgrad_comp(aC, aC_ln, kc2, y, v) = comp_form<true>, aC_ln and kc2 out of grad_comp_row
+//                                         (the statements deconv_row forms them with)
+// COMP_LCOMP: q = y, r = v:               deconv_lcomp(aC, y, v) = comp_form<false>(...).l
 // out: {l, dF, dC} per element (COMP_LCOMP: l only, the other two stay 0)
 template <int WHICH>
 __global__ __launch_bounds__(TPB) void probe_comp(const double* __restrict__ aC, const double* __restrict__ kappa,
