@@ -6,7 +6,7 @@
     -> set_median_fit (median LF + 1/Veff estimate) -> the reference's output tables.
 
     python examples/fit_synthetic.py [--nsrc 20000] [--nwalkers 64] [--nsteps 300] [--fix-comp] [--until-converged] [--map]
-                                     [--integrals]
+                                     [--integrals] [--pt] [--deconvolve [--deconvolve-tile]]
 """
 import argparse
 import os
@@ -81,16 +81,23 @@ def main():
                          "sqrt(var_comp) (veff_percentiles; DESIGN.md section 3.17; not with --fix-comp)")
     ap.add_argument("--deconvolve", action="store_true",
                     help="fit the likelihood convolved with the catalogue's flux errors (Eddington-bias correction, deconvolve=True; "
-                         "DESIGN.md section 3.18; host sampler: not with --until-converged; errors above 0.09 dex are refused; with --map the "
+                         "DESIGN.md section 3.18; errors above 0.09 dex are refused; --until-converged and --pt run the device "
+                         "samplers on the convolved likelihood, DESIGN.md section 3.20, a plain run the host sampler; with --map the "
                          "convolved and the plain maximum are both found and the difference of their L*, the catalogue's Eddington "
                          "shift, is printed; DESIGN.md section 3.19)")
+    ap.add_argument("--deconvolve-tile", action="store_true",
+                    help="with --deconvolve and --fix-comp: the correction by tiles of rows (deconvolve_tile=True; DESIGN.md section "
+                         "3.20; no effect with free completeness)")
+    ap.add_argument("--pt", action="store_true",
+                    help="parallel-tempered fit and the evidence by thermodynamic integration (fit_model_pt; DESIGN.md section "
+                         "3.10) instead of fit_model")
     ap.add_argument("--out", default="LFMCMCOut")
     ap.add_argument("--compress", action="store_true", help="compressed catalogue and grid (DESIGN.md section 3.5)")
     args = ap.parse_args()
     if args.veff_band and args.fix_comp:
         ap.error("--veff-band needs the completeness parameters in the fit: not with --fix-comp")
-    if args.deconvolve and args.until_converged:
-        ap.error("--deconvolve samples through fit_model: not with --until-converged")
+    if args.pt and args.until_converged:
+        ap.error("--pt and --until-converged are two fits: choose one")
     os.makedirs(args.out, exist_ok=True)
     cpath = os.path.join(args.out, "synthetic_catalogue.dat")
     write_catalogue(cpath, args.nsrc, seed=5)
@@ -103,7 +110,8 @@ def main():
                         phistar=synth.PHISTAR, phistar_lims=synth.PHISTAR_LIMS, Lc=synth.LC, Lh=synth.LH,
                         nwalkers=args.nwalkers, nsteps=args.nsteps, fix_sch_al=False, fix_comp=args.fix_comp,
                         min_comp_frac=0.0, Flim_lims=synth.FLIM_LIMS, alpha_lims=synth.ALPHA_LIMS,
-                        field_names=field_names, field_ind=field_ind, compress=args.compress, deconvolve=args.deconvolve)
+                        field_names=field_names, field_ind=field_ind, compress=args.compress, deconvolve=args.deconvolve,
+                        deconvolve_tile=args.deconvolve_tile)
     print("setup %.2f s for %d sources" % (time.time() - t0, len(LFmod.lum)))
     np.random.seed(3)
     plain_map = None
@@ -112,10 +120,14 @@ def main():
         LFmod.fit_model_map(seed=7, likelihood="convolved")
     elif args.map:
         LFmod.fit_model_map(seed=7)
+    like = "convolved" if args.deconvolve else None
     if args.until_converged:
-        LFmod.fit_model_converged(start="map" if args.map else "box")
+        LFmod.fit_model_converged(start="map" if args.map else "box", likelihood=like)
         print("converged: %s after %d steps; tau per parameter %s" % (LFmod.converged, LFmod.tau_history[-1][0],
                                                                      np.array2string(LFmod.tau_history[-1][1], precision=1)))
+    elif args.pt:
+        LFmod.fit_model_pt(likelihood=like)
+        print("lnZ = %.3f +/- %.3f (thermodynamic integration over %d temperatures)" % (LFmod.lnZ, LFmod.dlnZ, LFmod.pt_sampler.ntemps))
     else:
         LFmod.fit_model()
     LFmod.set_median_fit()

@@ -175,8 +175,11 @@ int lf_set_lum_err(lf_ctx *ctx, const double *sigma, int K, const double *logf, 
  * the path of lf_lnprob_batch, bit for bit; a row whose lnprob is -INFINITY stays -INFINITY, NaN becomes -INFINITY; a source
  * with sigma = 0 contributes exactly 0 (all sigma 0: the output is lf_lnprob_batch's, bit for bit).  The correction is summed
  * in one fixed order without atomics: a row's value has the same bits whatever B is and wherever the row stands.  The option
- * "compress" is ignored by the correction.  LF_ERR_ARG with a message, before the device is touched, when no errors are set
- * and for a context with "skip_grid" or "grid_share" set.  Host pointers, synchronous. */
+ * "compress" is ignored by the correction.  Option "deconv_tile" = 1 (default 0; FIXCOMP, ZEVOL): the correction's first stage
+ * takes a tile of 8 rows per block and makes what depends on the source and the node only once for them
+ * (csrc/lf_deconv_tile.h): the same guarantees, values within rounding of the default's; accepted and
+ * without effect on a FREE context, and ignored by the gradient entries below.  LF_ERR_ARG with a message, before the device
+ * is touched, when no errors are set and for a context with "skip_grid" or "grid_share" set.  Host pointers, synchronous. */
 int lf_lnprob_err_batch(lf_ctx *ctx, const double *theta, int B, double *out);
 
 /* Same, with device pointers and the launches enqueued on `hip_stream` (NULL = the default stream), asynchronous like
@@ -338,6 +341,16 @@ int64_t lf_sampler_steps(const lf_sampler *s);
  * Same random numbers and arithmetic as lf_sampler_run: the chain is identical for any sharding. */
 int lf_sampler_half_eval(lf_sampler *s, int half, int lo, int hi, double *d_newlp, void *hip_stream);
 int lf_sampler_half_accept(lf_sampler *s, int half, const double *d_newlp, void *hip_stream);
+/* Which likelihood the sampler's target is: convolved = 0 the plain lnprob (the default), 1 the flux-error-convolved one
+ * (lf_lnprob_err_batch).  With 1 a half-step is lf_propose, the plain evaluation of the proposals,
+ * the correction's kernels on them (per the context's option "deconv_tile") and lf_accept, all on the stream and without a
+ * host round trip (the option "fuse_step" does not apply); lf_sampler_start with lnprob0 == NULL evaluates the convolved value
+ * of the start; lf_sampler_half_eval / lf_sampler_half_accept follow the same setting.  The chain equals the host replay over
+ * lf_lnprob_err_batch bit for bit.  Valid before lf_sampler_start, or between a start and the first step (a start whose
+ * lnprob0 was NULL is evaluated again; one that was given has to be the chosen likelihood's): LF_ERR_ARG with a message
+ * otherwise, and when no errors are set (lf_set_lum_err) or the context is source-sharded.  What the correction needs for the
+ * sampler's rows is allocated here, not inside the running chain. */
+int lf_sampler_set_likelihood(lf_sampler *s, int convolved);
 
 /* Parallel-tempered device sampler (emcee 2.x's PTSampler: thermodynamic-integration evidence).
  * ntemps T <= 64 temperatures with inverse temperatures betas[0] == 1 > betas[1] > ... > betas[T-1] > 0, nwalkers W
@@ -363,6 +376,10 @@ int lf_ptsampler_read(lf_ptsampler *s, double *chain, double *chain_lnlike, doub
                       int64_t *nswap, double *pos, double *lnlike);
 /* Steps recorded so far. */
 int64_t lf_ptsampler_steps(const lf_ptsampler *s);
+/* lf_sampler_set_likelihood for the tempered sampler: with convolved = 1 the tempered target is beta x the
+ * flux-error-convolved lnprob - the correction's kernels run between lf_pt_propose's plain evaluation and lf_pt_accept, and
+ * lf_ptsampler_start with lnlike0 == NULL evaluates the convolved value.  The same validity and refusals. */
+int lf_ptsampler_set_likelihood(lf_ptsampler *s, int convolved);
 
 /* Chain diagnostics on the device (csrc/lf_diag.h).  Replace the read-back behind
  *     tau = np.max(sampler.acor); burnin_step = int(tau * 3), at most nsteps // 2          lumfuncmcmc.py:499-501

@@ -54,7 +54,8 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_sampler_diag", "lf_ptsampler_diag", "lf_chain_window", "lf_diag_last", "lf_lnprob_grad_batch",
            "lf_lnprob_grad_batch_device", "lf_lumfunc_integral_quantiles", "lf_lumfunc_integral_quantiles_ms", "lf_veff_draws", "lf_veff_draws_ms",
            "lf_veff_draws_chunk", "lf_set_lum_err", "lf_lnprob_err_batch", "lf_lnprob_err_batch_device", "lf_gauss_hermite",
-           "lf_deconv_info", "lf_lnprob_err_grad_batch", "lf_lnprob_err_grad_batch_device")
+           "lf_deconv_info", "lf_lnprob_err_grad_batch", "lf_lnprob_err_grad_batch_device", "lf_sampler_set_likelihood",
+           "lf_ptsampler_set_likelihood")
 
 _lib = None
 
@@ -178,6 +179,10 @@ def load():
     lib.lf_sampler_half_eval.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.lf_sampler_half_accept.restype = ctypes.c_int
     lib.lf_sampler_half_accept.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    lib.lf_sampler_set_likelihood.restype = ctypes.c_int
+    lib.lf_sampler_set_likelihood.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    lib.lf_ptsampler_set_likelihood.restype = ctypes.c_int
+    lib.lf_ptsampler_set_likelihood.argtypes = [ctypes.c_void_p, ctypes.c_int]
     lib.lf_ptsampler_create.restype = ctypes.c_void_p
     lib.lf_ptsampler_create.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_double, ctypes.c_uint64,
                                         ctypes.c_int64]

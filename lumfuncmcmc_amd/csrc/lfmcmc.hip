@@ -23,6 +23,7 @@
 #include "lf_diag.h"
 #include "lf_deconv.h"
 #include "lf_deconv_grad.h"
+#include "lf_deconv_tile.h"
 #include "lf_grad.h"
 #include "lf_gridbound.h"
 #include "lf_hostcall.h"
@@ -165,6 +166,7 @@ struct lf_ctx {
     lf::DeconvConst deconvc{};
     bool deconv_set = false;
     int64_t opt_deconv_unchecked = 0;   // 1: lf_set_lum_err takes sigma above the validated range of the order (tests, A/B runs)
+    int64_t opt_deconv_tile = 0;        // 1: FIXCOMP, ZEVOL: the value's first stage by tiles of rows (lf_deconv_tile.h); FREE: no effect
     Buf<double> d_sigma, d_elogf, d_eU, d_ghnodes, d_dpart;
     Buf<double> d_dgpart;               // its gradient's partial sums [rows][chunks][DGRAD_SLOTS] (lf_deconv_grad.h)
     hipStream_t stream = nullptr;
@@ -937,16 +939,25 @@ lf::DeconvArgs deconv_args(lf_ctx* c, const double* d_theta, double* d_lnp, doub
                           t.d_start, t.d_len, t.d_field, t.n};
 }
 
-// the value's two kernels on the plain lnprob of B rows (da.lnprob)
-void launch_deconv(lf_ctx* c, const lf::DeconvArgs& da, int B, hipStream_t s) {
+// the value's two kernels on the plain lnprob of B rows (da.lnprob).  tile: the first stage by tiles of DECONV_RT rows where the
+// variant has that kernel (a chunk of launch_rows is a whole number of tiles, except the last)
+void launch_deconv(lf_ctx* c, const lf::DeconvArgs& da, int B, hipStream_t s, bool tile) {
     using namespace lf;
+    static_assert(32768 % DECONV_RT == 0, "launch_rows' chunks are whole tiles");
     launch_rows(c->kc.variant, B, [&](auto v, int b0, int nb) {
         DeconvArgs g = da;
         g.theta += (size_t)b0 * g.gc.ndim;
         g.lnprob += b0;
         g.part += (size_t)b0 * g.nch;
         g.out += b0;
-        if (g.nch > 0) hipLaunchKernelGGL(lf_deconv_part<v()>, dim3((unsigned)g.nch, (unsigned)nb), dim3(BLOCK), 0, s, g);
+        bool tiled = false;
+        if constexpr (v() != LF_FREE) {
+            tiled = tile && g.nch > 0;
+            if (tiled)
+                hipLaunchKernelGGL(lf_deconv_tile<v()>, dim3((unsigned)g.nch, (unsigned)((nb + DECONV_RT - 1) / DECONV_RT)), dim3(BLOCK),
+                                   0, s, g, nb);
+        }
+        if (g.nch > 0 && !tiled) hipLaunchKernelGGL(lf_deconv_part<v()>, dim3((unsigned)g.nch, (unsigned)nb), dim3(BLOCK), 0, s, g);
         hipLaunchKernelGGL(lf_deconv_final, dim3((unsigned)nb), dim3(64), 0, s, g);
     });
 }
@@ -957,7 +968,7 @@ int enqueue_deconv(lf_ctx* c, const double* d_theta, int B, double* d_lnp, doubl
     int rc;
     if ((rc = deconv_prepare(c, B, false)) != LF_OK) return rc;
     if ((rc = enqueue(c, d_theta, B, d_lnp, nullptr, nullptr, s)) != LF_OK) return rc;
-    launch_deconv(c, deconv_args(c, d_theta, d_lnp, d_out), B, s);
+    launch_deconv(c, deconv_args(c, d_theta, d_lnp, d_out), B, s, c->opt_deconv_tile != 0);
     LF_HIP(c, hipGetLastError());
     return LF_OK;
 }
@@ -971,7 +982,7 @@ int enqueue_deconv_grad(lf_ctx* c, const double* d_theta, int B, double* d_lnp, 
     if ((rc = deconv_prepare(c, B, true)) != LF_OK) return rc;
     if ((rc = enqueue_grad(c, d_theta, B, d_lnp, d_grad, s)) != LF_OK) return rc;
     const DeconvGradArgs da{deconv_args(c, d_theta, d_lnp, d_out), c->d_dgpart, d_grad};
-    launch_deconv(c, da.d, B, s);
+    launch_deconv(c, da.d, B, s, false);          // (the gradient's value: the per-row kernels whatever "deconv_tile" says)
     launch_rows(c->kc.variant, B, [&](auto v, int b0, int nb) {
         DeconvGradArgs g = da;
         g.d.theta += (size_t)b0 * g.d.gc.ndim;
@@ -1848,6 +1859,7 @@ int lf_set_option(lf_ctx* c, const char* key, int64_t value) {
         {"compress_grid", [](lf_ctx* c, int64_t v) { c->opt_compress_grid = v != 0; }},
         {"skip_grid", [](lf_ctx* c, int64_t v) { c->opt_skip_grid = v != 0; }},
         {"deconv_unchecked", [](lf_ctx* c, int64_t v) { c->opt_deconv_unchecked = v != 0; }},
+        {"deconv_tile", [](lf_ctx* c, int64_t v) { c->opt_deconv_tile = v != 0; }},
         {"persistent", [](lf_ctx* c, int64_t v) { c->opt_persistent = v < 0 ? 0 : (v > 2 ? 2 : v); }},
         {"profile_every", [](lf_ctx* c, int64_t v) { c->opt_profile_every = v < 1 ? 1 : v; c->prof_tick = 0; }},
         {"profile_span", [](lf_ctx* c, int64_t v) { c->opt_profile_span = v < 1 ? 1 : v; c->prof_tick = 0; }},
@@ -2006,9 +2018,37 @@ struct lf_sampler {
     Buf<double> d_chain, d_chain_lnp;
     Buf<long long> d_nacc;
     bool started = false;
+    // lf_sampler_set_likelihood: the flux-error-convolved likelihood, the plain lnprob of the rows it evaluates [W], whether
+    // the start's lnprob was the sampler's own evaluation, whether a step has been taken since the start
+    bool convolved = false, own_start = false, moved = false;
+    Buf<double> d_plain;
 };
 
 namespace {
+
+// A sampler's evaluation of B rows on `s`: the plain lnprob (the three-piece form), or with convolved the plain lnprob into
+// d_plain and the correction's kernels on it, per the context's "deconv_tile" (enqueue_deconv) - d_out either way.
+int sampler_eval(lf_ctx* c, bool convolved, const double* d_theta, int B, double* d_plain, double* d_out, hipStream_t s) {
+    if (!convolved) return enqueue(c, d_theta, B, d_out, nullptr, nullptr, s);
+    return enqueue_deconv(c, d_theta, B, d_plain, d_out, s);
+}
+
+// What both samplers' set_likelihood entries check and prepare: family_check's refusals, the call's place (before a step),
+// and with convolved everything the correction needs for `rows` rows (d_plain, the evaluation's workspace, deconv_prepare),
+// now rather than by a resize inside a running chain.
+int sampler_likelihood(lf_ctx* c, const char* fn, int convolved, bool moved, int rows, Buf<double>& d_plain) {
+    if (moved) {
+        c->err = std::string(fn) + ": the chain has taken a step (valid before the start, or between a start and the first step)";
+        return LF_ERR_ARG;
+    }
+    if (!convolved) return LF_OK;
+    int rc = family_check(c, fn, true, c, 1, c);
+    if (rc != LF_OK) return rc;
+    LF_HIP(c, hipSetDevice(c->device));
+    if (d_plain.size() < (size_t)rows) LF_HIP(c, d_plain.alloc((size_t)rows));
+    if ((rc = ensure_workspace(c, rows, 0, 0)) != LF_OK) return rc;
+    return deconv_prepare(c, rows, false);
+}
 
 // A sampler's chains on the device are [rows][cap][width], the caller's [rows][t][width] (t steps taken): packed on the device
 // first, then ONE copy to the host (a strided copy into pageable host memory goes row by row).  parts[0] is the widest.
@@ -2081,13 +2121,30 @@ int lf_sampler_start(lf_sampler* sm, const double* pos, const double* lnprob0) {
     if (lnprob0) {
         LF_HIP(c, hipMemcpy(sm->d_lnp, lnprob0, W * 8, hipMemcpyHostToDevice));
     } else {
-        int rc = enqueue(c, sm->d_pos, sm->W, sm->d_lnp, nullptr, nullptr, c->stream);
+        int rc = sampler_eval(c, sm->convolved, sm->d_pos, sm->W, sm->d_plain, sm->d_lnp, c->stream);
         if (rc != LF_OK) return rc;
         LF_HIP(c, hipStreamSynchronize(c->stream));
     }
+    sm->own_start = !lnprob0;
+    sm->moved = false;
     sm->step = 0;
     sm->t = 0;
     sm->started = true;
+    return LF_OK;
+}
+
+int lf_sampler_set_likelihood(lf_sampler* sm, int convolved) {
+    if (!sm) return LF_ERR_ARG;
+    lf_ctx* c = sm->ctx;
+    int rc = sampler_likelihood(c, "lf_sampler_set_likelihood", convolved, sm->moved, sm->W, sm->d_plain);
+    if (rc != LF_OK) return rc;
+    const bool changed = sm->convolved != (convolved != 0);
+    sm->convolved = convolved != 0;
+    if (changed && sm->started && sm->own_start) {
+        // the start's lnprob was this sampler's evaluation, of the other likelihood: once more
+        if ((rc = sampler_eval(c, sm->convolved, sm->d_pos, sm->W, sm->d_plain, sm->d_lnp, c->stream)) != LF_OK) return rc;
+        LF_HIP(c, hipStreamSynchronize(c->stream));
+    }
     return LF_OK;
 }
 
@@ -2105,12 +2162,23 @@ int lf_sampler_run(lf_sampler* sm, int64_t nsteps, void* hip_stream) {
     LF_HIP(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     const int halfW = sm->W / 2;
+    if (nsteps > 0) sm->moved = true;
     for (int64_t it = 0; it < nsteps; ++it) {
         for (int half = 0; half < 2; ++half) {
             lf::StepArgs sp{1, half, halfW, sm->ndim, sm->step, sm->seed, sm->a, sm->d_pos, sm->d_prop, sm->d_zz};
             lf::AcceptArgs ap{1, half, halfW, sm->ndim, sm->step, sm->seed, (long long)sm->t, (long long)sm->cap,
                               sm->d_pos, sm->d_lnp, sm->d_prop, sm->d_zz, sm->d_nacc, sm->d_chain, sm->d_chain_lnp};
-            int rc = enqueue(c, nullptr, halfW, sm->d_newlp, nullptr, nullptr, s, &sp, &ap);
+            int rc;
+            if (sm->convolved) {
+                // propose, the plain evaluation, the correction's kernels, accept: the option "fuse_step" does not apply
+                hipLaunchKernelGGL(lf::lf_propose, dim3((halfW + 7) / 8), dim3(64), 0, s, sp);
+                LF_HIP(c, hipGetLastError());
+                if ((rc = sampler_eval(c, true, sm->d_prop, halfW, sm->d_plain, sm->d_newlp, s)) != LF_OK) return rc;
+                hipLaunchKernelGGL(lf::lf_accept, dim3(halfW), dim3(64), 0, s, ap, (const double*)sm->d_newlp);
+                LF_HIP(c, hipGetLastError());
+                continue;
+            }
+            rc = enqueue(c, nullptr, halfW, sm->d_newlp, nullptr, nullptr, s, &sp, &ap);
             if (rc != LF_OK) return rc;
         }
         sm->step += 1;
@@ -2150,7 +2218,7 @@ int lf_sampler_half_eval(lf_sampler* sm, int half, int lo, int hi, double* d_new
     hipLaunchKernelGGL(lf::lf_propose, dim3((halfW + 7) / 8), dim3(64), 0, s, sp);
     LF_HIP(c, hipGetLastError());
     if (hi > lo)
-        return enqueue(c, sm->d_prop + (size_t)lo * sm->ndim, hi - lo, d_newlp + lo, nullptr, nullptr, s);
+        return sampler_eval(c, sm->convolved, sm->d_prop + (size_t)lo * sm->ndim, hi - lo, sm->d_plain + lo, d_newlp + lo, s);
     return LF_OK;
 }
 
@@ -2168,6 +2236,7 @@ int lf_sampler_half_accept(lf_sampler* sm, int half, const double* d_newlp, void
                       sm->d_pos, sm->d_lnp, sm->d_prop, sm->d_zz, sm->d_nacc, sm->d_chain, sm->d_chain_lnp};
     hipLaunchKernelGGL(lf::lf_accept, dim3(halfW), dim3(64), 0, s, ap, d_newlp);
     LF_HIP(c, hipGetLastError());
+    sm->moved = true;
     if (half == 1) {
         sm->step += 1;
         sm->t += 1;
@@ -2190,6 +2259,9 @@ struct lf_ptsampler {
     Buf<long long> d_nacc, d_nswap;
     Buf<int> d_sig;
     bool started = false;
+    // lf_ptsampler_set_likelihood: as lf_sampler's (d_plain: [T x W])
+    bool convolved = false, own_start = false, moved = false;
+    Buf<double> d_plain;
 };
 
 lf_ptsampler* lf_ptsampler_create(lf_ctx* c, int ntemps, int nwalkers, const double* betas, double a, uint64_t seed,
@@ -2249,7 +2321,7 @@ int lf_ptsampler_start(lf_ptsampler* sm, const double* pos, const double* lnlike
         std::copy(lnlike0, lnlike0 + TW, l.begin());
     } else {
         LF_HIP(c, hipMemcpy(sm->d_pos, pos, TW * nd * 8, hipMemcpyHostToDevice));
-        int rc = enqueue(c, sm->d_pos, (int)TW, sm->d_lnl, nullptr, nullptr, c->stream);
+        int rc = sampler_eval(c, sm->convolved, sm->d_pos, (int)TW, sm->d_plain, sm->d_lnl, c->stream);
         if (rc != LF_OK) return rc;
         LF_HIP(c, hipStreamSynchronize(c->stream));
         LF_HIP(c, hipMemcpy(l.data(), sm->d_lnl, TW * 8, hipMemcpyDeviceToHost));
@@ -2264,9 +2336,36 @@ int lf_ptsampler_start(lf_ptsampler* sm, const double* pos, const double* lnlike
     LF_HIP(c, hipMemcpy(sm->d_lnl, l.data(), TW * 8, hipMemcpyHostToDevice));
     LF_HIP(c, hipMemset(sm->d_nacc, 0, TW * sizeof(long long)));
     LF_HIP(c, hipMemset(sm->d_nswap, 0, (size_t)sm->T * sizeof(long long)));
+    sm->own_start = !lnlike0;
+    sm->moved = false;
     sm->step = 0;
     sm->t = 0;
     sm->started = true;
+    return LF_OK;
+}
+
+int lf_ptsampler_set_likelihood(lf_ptsampler* sm, int convolved) {
+    if (!sm) return LF_ERR_ARG;
+    lf_ctx* c = sm->ctx;
+    const int TW = sm->T * sm->W;
+    int rc = sampler_likelihood(c, "lf_ptsampler_set_likelihood", convolved, sm->moved, TW, sm->d_plain);
+    if (rc != LF_OK) return rc;
+    const bool changed = sm->convolved != (convolved != 0);
+    sm->convolved = convolved != 0;
+    if (changed && sm->started && sm->own_start) {
+        // the start's lnlike was this sampler's evaluation, of the other likelihood: once more (it has to stay finite)
+        std::vector<double> l((size_t)TW);
+        if ((rc = sampler_eval(c, sm->convolved, sm->d_pos, TW, sm->d_plain, sm->d_lnl, c->stream)) != LF_OK) return rc;
+        LF_HIP(c, hipStreamSynchronize(c->stream));
+        LF_HIP(c, hipMemcpy(l.data(), sm->d_lnl, l.size() * 8, hipMemcpyDeviceToHost));
+        for (double v : l) {
+            if (!std::isfinite(v)) {
+                sm->started = false;
+                c->err = "lf_ptsampler_set_likelihood: every start position needs a finite lnprob (start again)";
+                return LF_ERR_ARG;
+            }
+        }
+    }
     return LF_OK;
 }
 
@@ -2285,13 +2384,14 @@ int lf_ptsampler_run(lf_ptsampler* sm, int64_t nsteps, void* hip_stream) {
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     const int halfW = sm->W / 2, rows = sm->T * halfW;
     const dim3 grid((rows * 8 + 63) / 64);
+    if (nsteps > 0) sm->moved = true;
     for (int64_t it = 0; it < nsteps; ++it) {
         for (int half = 0; half < 2; ++half) {
             lf::PtArgs p{sm->T, sm->W, halfW, sm->ndim, half, sm->step, sm->seed, sm->a, sm->d_betas, sm->d_pos, sm->d_lnl,
                          sm->d_prop, sm->d_zz, sm->d_newl, sm->d_nacc};
             hipLaunchKernelGGL(lf::lf_pt_propose, grid, dim3(64), 0, s, p);
             LF_HIP(c, hipGetLastError());
-            int rc = enqueue(c, sm->d_prop, rows, sm->d_newl, nullptr, nullptr, s);
+            int rc = sampler_eval(c, sm->convolved, sm->d_prop, rows, sm->d_plain, sm->d_newl, s);
             if (rc != LF_OK) return rc;
             hipLaunchKernelGGL(lf::lf_pt_accept, grid, dim3(64), 0, s, p);
             LF_HIP(c, hipGetLastError());

@@ -187,6 +187,8 @@ class _Base(object):
                 self._ctx.set_option("compress", 1)
             if self.deconvolve:
                 self._ctx.set_lum_err(self.lum_e, self.deconvolve_order, unchecked=self.deconvolve_unchecked)
+            if self.deconvolve_tile:
+                self._ctx.set_option("deconv_tile", 1)
             self._ctx_key = key
         return self._ctx
 
@@ -194,10 +196,12 @@ class _Base(object):
     deconvolve = False             # True: lnprob is the likelihood convolved with the sources' lum_e (csrc/lf_deconv.h), opt-in
     deconvolve_order = None        # its Gauss-Hermite order (None: the library's default)
     deconvolve_unchecked = False   # True: lum_e above the order's validated range is taken as it is
+    deconvolve_tile = False        # True: the context option "deconv_tile" (csrc/lf_deconv_tile.h; no effect with free completeness)
 
-    def _init_deconvolve(self, deconvolve, deconvolve_order):
+    def _init_deconvolve(self, deconvolve, deconvolve_order, deconvolve_tile=False):
         from . import deconv
         self.deconvolve, self.deconvolve_order = bool(deconvolve), deconvolve_order
+        self.deconvolve_tile = bool(deconvolve_tile)
         if not self.deconvolve:
             return
         if self.lum_e is None:
@@ -212,11 +216,6 @@ class _Base(object):
             raise ValueError("deconvolve_order must be one of %s" % (deconv.ORDERS,))
         self.deconvolve_order = K
         deconv.check_sigma(self.lum_e, len(self.lum), K, self.deconvolve_unchecked)
-
-    def _refuse_deconvolve(self, what):
-        if self.deconvolve:
-            raise NotImplementedError("%s runs on the plain likelihood's device sampler or gradient: it is not implemented "
-                                      "for deconvolve=True (use fit_model)" % what)
 
     def _evaluate(self, theta):
         th = np.asarray(theta, dtype=np.float64)
@@ -317,7 +316,7 @@ class _Base(object):
         self.log.info("Median lnprob: %.5f; Max lnprob: %.5f" % (np.median(sampler.lnprobability),
                                                                 np.amax(sampler.lnprobability)))
 
-    def fit_model_converged(self, max_steps=None, check_every=None, ntau=50, rtol=0.01, start="box"):
+    def fit_model_converged(self, max_steps=None, check_every=None, ntau=50, rtol=0.01, start="box", likelihood=None):
         """fit_model that runs until the chain is long enough instead of for a number of steps guessed beforehand: one
         device sampler with room for max_steps (default 10 * self.nsteps) runs check_every steps at a time (default
         max(100, self.nsteps // 10)) and asks the chain where it is for its autocorrelation times
@@ -327,10 +326,14 @@ class _Base(object):
         once, at the end.  Sets what fit_model sets (samples, chain, sampler, start_pos, sampler_seed; burn-in =
         min(int(3 max tau), steps // 2) with the device's tau) plus self.converged and self.tau_history = [(steps, tau), ...];
         returns the last tau.  One GPU, device sampler only.  start="map": the walkers start in a Gaussian ball around the
-        maximum a posteriori (map_init_walkers; fit_model_map runs first when it has not) instead of the prior box."""
+        maximum a posteriori (map_init_walkers; fit_model_map runs first when it has not) instead of the prior box.
+        likelihood: what the device sampler samples, with fit_model_map's semantics - None (the plain likelihood; an object made
+        with deconvolve=True refuses and asks for the choice), "convolved" (deconvolve=True only: the flux-error-convolved
+        likelihood) or "plain" (also under deconvolve=True); start="map" uses the same one.
+        self.sampler_likelihood records which one ran."""
         if start not in ("box", "map"):
             raise ValueError('start must be "box" or "map"')
-        self._refuse_deconvolve("fit_model_converged")
+        likelihood = self._map_likelihood(likelihood, "fit_model_converged does")
         rank, world = self._dist_state()
         if world > 1:
             raise NotImplementedError("fit_model_converged runs on one GPU: diagnostics across several ranks are not implemented")
@@ -341,14 +344,15 @@ class _Base(object):
         if max_steps < 1 or check_every < 1:
             raise ValueError("max_steps and check_every must be positive")
         self.log.info('Fitting Schechter model to true luminosity function until the chain has converged')
-        if start == "map" and getattr(self, "map_theta", None) is None:
-            self.fit_model_map()
-        pos = self.get_init_walker_values() if start == "box" else self.map_init_walkers()
+        if start == "map" and (getattr(self, "map_theta", None) is None or getattr(self, "map_info", {}).get("likelihood", likelihood) != likelihood):
+            self.fit_model_map(likelihood=likelihood)
+        pos = self.get_init_walker_values() if start == "box" else self.map_init_walkers(likelihood=likelihood)
         ndim = pos.shape[1]
         start = time.time()
         seed = int(np.random.randint(0, 2 ** 31 - 1))
         self.start_pos, self.sampler_seed = np.array(pos), seed       # (start, seed, steps) reproduce the chain
-        sampler = DeviceEnsembleSampler(self.context(), self.nwalkers, seed=seed, capacity=max_steps)
+        self.sampler_likelihood = likelihood
+        sampler = DeviceEnsembleSampler(self.context(), self.nwalkers, seed=seed, capacity=max_steps, likelihood=likelihood)
         steps, tau, tau_prev = 0, None, None
         self.converged, self.tau_history = False, []
         while steps < max_steps and not self.converged:
@@ -385,14 +389,15 @@ class _Base(object):
         return tau
 
     # ------------------------------------------------------------------ maximum a posteriori (mapfit.py)
-    def _map_likelihood(self, likelihood):
-        """Which likelihood fit_model_map / map_init_walkers maximise: None (the plain one; refused under deconvolve=True, where
-        the choice has to be stated), "plain" or "convolved" (needs deconvolve=True)."""
+    def _map_likelihood(self, likelihood, who="fit_model_map and map_init_walkers do"):
+        """Which likelihood fit_model_map / map_init_walkers maximise and fit_model_converged / fit_model_pt sample: None (the
+        plain one; refused under deconvolve=True, where the choice has to be stated), "plain" or "convolved" (needs
+        deconvolve=True; DESIGN.md sections 3.19 and 3.20)."""
         if likelihood is None:
             if self.deconvolve:
-                raise NotImplementedError("fit_model_map and map_init_walkers do not choose a likelihood for deconvolve=True: "
+                raise NotImplementedError("%s not choose a likelihood for deconvolve=True: "
                                           'pass likelihood="convolved" (the flux-error-convolved one, lnprob\'s) or '
-                                          'likelihood="plain"')
+                                          'likelihood="plain"' % who)
             return "plain"
         if likelihood not in ("plain", "convolved"):
             raise ValueError('likelihood must be None, "plain" or "convolved", got %r' % (likelihood,))
@@ -486,14 +491,15 @@ class _Base(object):
             pos[bad] = draw(int(bad.sum()))
         raise RuntimeError("map_init_walkers: could not draw %d walkers with finite lnprob around the maximum" % num)
 
-    def fit_model_pt(self, ntemps=None, Tmax=None, betas=None, fburnin=0.1):
+    def fit_model_pt(self, ntemps=None, Tmax=None, betas=None, fburnin=0.1, likelihood=None):
         """Parallel-tempered fit (DevicePTSampler, sampler.py) and the Bayesian evidence of this model by thermodynamic
         integration, for comparing the models the classes offer.  self.nwalkers walkers per temperature, self.nsteps
         steps; every temperature starts from get_init_walker_values (a start with -inf lnprob is drawn again).  Ladder:
         `betas`, or geometric up to Tmax (None: tmax_from_box on the prior box) over ntemps temperatures (None:
         default_ntemps(Tmax)).  Sets self.samples from the beta = 1 chain as fit_model does, and self.pt_sampler,
-        self.lnZ, self.dlnZ (fburnin: the leading fraction of steps the estimator leaves out)."""
-        self._refuse_deconvolve("fit_model_pt")
+        self.lnZ, self.dlnZ (fburnin: the leading fraction of steps the estimator leaves out).  likelihood: as in
+        fit_model_converged - the starts' lnlike, Tmax from the box and the tempered target are all the chosen likelihood's."""
+        likelihood = self._map_likelihood(likelihood, "fit_model_pt does")
         rank, world = self._dist_state()
         if world > 1:
             raise NotImplementedError("fit_model_pt runs on one GPU: parallel tempering over several ranks is not implemented")
@@ -501,30 +507,32 @@ class _Base(object):
             raise NotImplementedError("fit_model_pt runs the device sampler: it cannot use lnprob_fn")
         self.log.info('Fitting Schechter model with parallel tempering (evidence by thermodynamic integration)')
         ctx = self.context()
+        lnlike = ctx.lnprob_err_batch if likelihood == "convolved" else ctx.lnprob_batch
         lims = self._theta_lims()
         if betas is not None:
             ntemps = len(betas)
         else:
             if Tmax is None:
-                Tmax = tmax_from_box(ctx.lnprob_batch, lims)
+                Tmax = tmax_from_box(lnlike, lims)
             if ntemps is None:
                 ntemps = default_ntemps(Tmax)
         W, ndim = self.nwalkers, len(lims)
         pos = np.array([self.get_init_walker_values() for _ in range(ntemps)])
-        ll = ctx.lnprob_batch(pos.reshape(-1, ndim)).reshape(ntemps, W)
+        ll = lnlike(pos.reshape(-1, ndim)).reshape(ntemps, W)
         for _ in range(100):
             bad = ~np.isfinite(ll)
             if not bad.any():
                 break
             fresh = self.get_init_walker_values(int(bad.sum()))
             pos[bad] = fresh
-            ll[bad] = ctx.lnprob_batch(fresh)
+            ll[bad] = lnlike(fresh)
         else:
             raise RuntimeError("fit_model_pt: no finite start in 100 draws of the prior box")
         seed = int(np.random.randint(0, 2 ** 31 - 1))
         self.start_pos, self.sampler_seed = pos.copy(), seed
         start = time.time()
-        sampler = DevicePTSampler(ctx, ntemps, W, betas=betas, Tmax=Tmax, seed=seed, capacity=self.nsteps)
+        self.sampler_likelihood = likelihood
+        sampler = DevicePTSampler(ctx, ntemps, W, betas=betas, Tmax=Tmax, seed=seed, capacity=self.nsteps, likelihood=likelihood)
         sampler.run_mcmc(pos, self.nsteps, lnlike0=ll)
         elapsed = time.time() - start
         self.log.info("Total time taken: %0.2f s" % elapsed)
@@ -647,6 +655,10 @@ class _Base(object):
             self.Lavg = self.lfbinorig = self.var = None
 
     def close(self):
+        # (a device sampler holds its context's handle: it goes first; what it read back stays on it)
+        for s in (getattr(self, "sampler", None), getattr(self, "pt_sampler", None)):
+            if hasattr(s, "close"):
+                s.close()
         if self._ctx is not None:
             self._ctx.close()
             self._ctx = None
@@ -666,7 +678,7 @@ class LumFuncMCMC(_Base):
                  phistar=-3.0, phistar_lims=[-8.0, 5.0], Lc=40.0, Lh=46.0, nwalkers=100, nsteps=1000,
                  fix_sch_al=False, fcmin=0.1, fix_comp=False, min_comp_frac=0.5,
                  field_names=None, field_ind=None, diff_rand=True, device=0, compress=False, shard="walkers",
-                 deconvolve=False, deconvolve_order=None):
+                 deconvolve=False, deconvolve_order=None, deconvolve_tile=False):
         self._common_init(z, flux, flux_e, lum, lum_e)
         self.device = device
         self.compress = bool(compress)
@@ -698,7 +710,7 @@ class LumFuncMCMC(_Base):
         self.size_ln = 201 if self.fix_comp else 101
         self.setlnsimple(need_integ=bool(self.fix_comp))
         self.setup_logging()
-        self._init_deconvolve(deconvolve, deconvolve_order)
+        self._init_deconvolve(deconvolve, deconvolve_order, deconvolve_tile)
 
     def getRoot(self, size=201):
         self.rootsf = hs.completeness_roots(self.Flim_lims, self.alpha_lims, self.fcmin, self.min_comp_frac, size)
@@ -878,7 +890,7 @@ class LumFuncMCMCz(_Base):
                  phistar=-3.0, phistar_lims=[-8.0, 5.0], Lc=40.0, Lh=46.0, nwalkers=100, nsteps=1000,
                  fcmin=0.1, min_comp_frac=0.5, field_names=None,
                  field_ind=None, z1=1.20, z2=1.53, z3=1.86, fix_sch_al=False, device=0, compress=False, shard="walkers",
-                 deconvolve=False, deconvolve_order=None):
+                 deconvolve=False, deconvolve_order=None, deconvolve_tile=False):
         self._common_init(z, flux, flux_e, lum, lum_e)
         self.device = device
         self.compress = bool(compress)
@@ -911,7 +923,7 @@ class LumFuncMCMCz(_Base):
         self.size_ln = 201
         self.setlnsimple(need_integ=True)
         self.setup_logging()
-        self._init_deconvolve(deconvolve, deconvolve_order)
+        self._init_deconvolve(deconvolve, deconvolve_order, deconvolve_tile)
 
     def getRoot(self):
         """Per-field flux at which the completeness equals min_comp_frac (lumfuncmcmc_z.py:292-297);

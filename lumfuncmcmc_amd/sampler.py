@@ -271,6 +271,13 @@ class EnsembleSampler(object):
         return self.get_autocorr_time()
 
 
+def _likelihood_flag(likelihood):
+    """("plain", 0) or ("convolved", 1): the device samplers' `likelihood` keyword, checked before any library is touched."""
+    if likelihood not in ("plain", "convolved"):
+        raise ValueError('likelihood must be "plain" or "convolved", got %r' % (likelihood,))
+    return likelihood, int(likelihood == "convolved")
+
+
 class DeviceEnsembleSampler(object):
     """The same read-back surface, with the whole stretch move on the GPU (lf_sampler_* of
     include/lfmcmc.h): positions, lnprob and the chain stay in HBM, a step is two kernel launches
@@ -278,10 +285,14 @@ class DeviceEnsembleSampler(object):
     ctx.last_launch() reports as fused; six with the option "fuse_step" 0 or where lf_main serves)
     - and no host round trip.  Parallel stretch move with two fixed half-ensembles (emcee 2.x form);
     Philox4x32-10 random numbers keyed by `seed`, so (seed, start) determines the chain
-    (tests/test_gpu_sampler.py and tests/test_gpu_sampler_shapes.py replay it on the host)."""
+    (tests/test_gpu_sampler.py and tests/test_gpu_sampler_shapes.py replay it on the host).
+    likelihood="convolved": the target is the flux-error-convolved likelihood (ctx.set_lum_err first; lf_sampler_set_likelihood,
+    DESIGN.md section 3.20) - a half-step is then proposal, plain evaluation, the correction's kernels and accept step, still
+    without a host round trip, and the chain is the host replay over ctx.lnprob_err_batch."""
 
-    def __init__(self, ctx, nwalkers, a=2.0, seed=0, capacity=1000):
+    def __init__(self, ctx, nwalkers, a=2.0, seed=0, capacity=1000, likelihood="plain"):
         import ctypes
+        self.likelihood = _likelihood_flag(likelihood)[0]
         if nwalkers < 2 * ctx.ndim or nwalkers % 2:
             raise ValueError("nwalkers must be even and at least 2*ndim (got %d for ndim %d)" % (nwalkers, ctx.ndim))
         self._ct = ctypes
@@ -292,6 +303,18 @@ class DeviceEnsembleSampler(object):
             raise RuntimeError("lf_sampler_create failed: %s" % ctx._lib.lf_last_error(ctx._h).decode())
         self._h = ctypes.c_void_p(h)
         self._started = False
+        if self.likelihood == "convolved":
+            try:
+                self.set_likelihood("convolved")
+            except Exception:
+                self.close()
+                raise
+
+    def set_likelihood(self, likelihood):
+        """"plain" or "convolved" (lf_sampler_set_likelihood): before the start, or between a start and the first step."""
+        name, flag = _likelihood_flag(likelihood)
+        self.ctx._check(self.ctx._lib.lf_sampler_set_likelihood(self._h, flag))
+        self.likelihood = name
 
     def _p(self, a):
         return a.ctypes.data_as(self._ct.POINTER(self._ct.c_double)) if a is not None else None
@@ -635,16 +658,19 @@ class PTSampler(_PTSurface):
 class DevicePTSampler(_PTSurface):
     """PTSampler on the GPU (lf_ptsampler_* of include/lfmcmc.h): positions, lnlike and the chain stay in HBM, a step is
     three launches and one evaluation of T x W/2 rows per half plus one swap launch.  ntemps x nwalkers walkers; the
-    ladder is `betas`, or geometric up to Tmax (Tmax=None: tmax_from_box on the context's prior box)."""
+    ladder is `betas`, or geometric up to Tmax (Tmax=None: tmax_from_box on the context's prior box, over the likelihood
+    being sampled).  likelihood="convolved": the tempered target is beta x the flux-error-convolved likelihood
+    (lf_ptsampler_set_likelihood; see DeviceEnsembleSampler)."""
 
-    def __init__(self, ctx, ntemps, nwalkers, betas=None, Tmax=None, a=2.0, seed=0, capacity=1000):
+    def __init__(self, ctx, ntemps, nwalkers, betas=None, Tmax=None, a=2.0, seed=0, capacity=1000, likelihood="plain"):
         import ctypes
+        self.likelihood, flag = _likelihood_flag(likelihood)
         if nwalkers < 2 or nwalkers % 2:
             raise ValueError("nwalkers must be even and >= 2")
         self._ct = ctypes
         self.ctx, self.ntemps, self.nwalkers, self.ndim = ctx, int(ntemps), int(nwalkers), ctx.ndim
         self.a, self.seed, self.capacity = float(a), int(seed), int(capacity)
-        self.betas = self._ladder(self.ntemps, betas, Tmax, ctx.lnprob_batch, ctx.prior_box())
+        self.betas = self._ladder(self.ntemps, betas, Tmax, ctx.lnprob_err_batch if flag else ctx.lnprob_batch, ctx.prior_box())
         self._betas_c = np.ascontiguousarray(self.betas)
         h = ctx._lib.lf_ptsampler_create(ctx._h, self.ntemps, self.nwalkers, self._p(self._betas_c), self.a,
                                          ctypes.c_uint64(self.seed), self.capacity)
@@ -653,6 +679,11 @@ class DevicePTSampler(_PTSurface):
         self._h = ctypes.c_void_p(h)
         self._started = False
         self.iterations = 0
+        if flag:
+            rc = ctx._lib.lf_ptsampler_set_likelihood(self._h, flag)
+            if rc != 0:
+                self.close()
+                ctx._check(rc)
 
     def _p(self, a):
         return a.ctypes.data_as(self._ct.POINTER(self._ct.c_double)) if a is not None else None
