@@ -6,7 +6,7 @@
     -> set_median_fit (median LF + 1/Veff estimate) -> the reference's output tables.
 
     python examples/fit_synthetic.py [--nsrc 20000] [--nwalkers 64] [--nsteps 300] [--fix-comp] [--until-converged] [--map]
-                                     [--integrals] [--pt] [--deconvolve [--deconvolve-tile]]
+                                     [--integrals] [--pt] [--deconvolve [--deconvolve-tile] [--deconvolve-wide]]
 """
 import argparse
 import os
@@ -88,6 +88,9 @@ def main():
     ap.add_argument("--deconvolve-tile", action="store_true",
                     help="with --deconvolve and --fix-comp: the correction by tiles of rows (deconvolve_tile=True; DESIGN.md section "
                          "3.20; no effect with free completeness)")
+    ap.add_argument("--deconvolve-wide", action="store_true",
+                    help="with --deconvolve: errors above 0.09 dex, up to 0.30 dex, are integrated by the wide rule instead of "
+                         "being refused (deconvolve_wide=True; DESIGN.md section 3.21)")
     ap.add_argument("--pt", action="store_true",
                     help="parallel-tempered fit and the evidence by thermodynamic integration (fit_model_pt; DESIGN.md section "
                          "3.10) instead of fit_model")
@@ -111,7 +114,7 @@ def main():
                         nwalkers=args.nwalkers, nsteps=args.nsteps, fix_sch_al=False, fix_comp=args.fix_comp,
                         min_comp_frac=0.0, Flim_lims=synth.FLIM_LIMS, alpha_lims=synth.ALPHA_LIMS,
                         field_names=field_names, field_ind=field_ind, compress=args.compress, deconvolve=args.deconvolve,
-                        deconvolve_tile=args.deconvolve_tile)
+                        deconvolve_tile=args.deconvolve_tile, deconvolve_wide=args.deconvolve_wide)
     print("setup %.2f s for %d sources" % (time.time() - t0, len(LFmod.lum)))
     np.random.seed(3)
     plain_map = None

@@ -208,6 +208,24 @@ int lf_gauss_hermite(int K, double *x, double *lnw);
  * default order and the sources per chunk of the correction's fixed summation order.  Returns the number of orders. */
 int lf_deconv_info(int32_t *orders, double *sigma_max, int cap, int *default_order, int *chunk);
 
+/* The wide rule (csrc/lf_deconv_wide.h): option "deconv_wide" = 1 (default 0), set BEFORE lf_set_lum_err.
+ * Without it nothing changes: sigma above the order's limit is refused (or, with "deconv_unchecked", summed by the order as it
+ * is).  With it lf_set_lum_err accepts sigma up to 0.30 dex and refuses larger values with that limit in the message.  A source
+ * at or below the order's limit keeps the Gauss-Hermite sum and its bits (no source above it: every result is the one without
+ * the option, bit for bit).  A source above it falls into a sigma class (upper edges 0.10, 0.15, 0.20, 0.25, 0.30 dex: the
+ * first edge that is not below its sigma) and is integrated by that class's composite Gauss-Legendre rule - panels of 8 nodes,
+ * at most 0.25 dex wide, over +-7.5 sigma; 48 to 144 nodes; per-source error below 1e-7 - by kernels of their own whose partial
+ * sums enter the same fixed-order second stages: every entry above and both device samplers take it, and a row's bits still
+ * depend neither on B nor on its position.  With "deconv_tile" the narrow part is tiled, the wide part is not.  Still refused:
+ * source-sharded contexts and min_comp_frac > 0.001.
+ * lf_deconv_wide_info: host-only (touches no GPU).  The classes' upper edges and node counts (up to cap entries), the sources
+ * per wide chunk, T, the nodes per panel and the widest panel h in dex - any of them may be NULL; with x and lnw the table of
+ * class cls in the kernels' form (x_k with delta = sqrt(2) sigma x_k, and the log of the whole weight, the Gaussian density
+ * included; nodes[cls] entries each).  Returns the number of classes; LF_ERR_ARG when only one of x, lnw is given or cls is not
+ * a class. */
+int lf_deconv_wide_info(double *edges, int32_t *nodes, int cap, int *chunk, double *T, int *npanel, double *h, int cls, double *x,
+                        double *lnw);
+
 /* Kernel timing for bench.py: level 1 brackets lf_main, level 2 every launch, with hipEvents on
  * the stream the launch runs on (0 = off; each event pair costs a few microseconds of stream time: the events are
  * barrier packets, and the next launch no longer overlaps the previous one's tail - measured 7.6 us per evaluation

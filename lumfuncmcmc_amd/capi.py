@@ -54,7 +54,7 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_sampler_diag", "lf_ptsampler_diag", "lf_chain_window", "lf_diag_last", "lf_lnprob_grad_batch",
            "lf_lnprob_grad_batch_device", "lf_lumfunc_integral_quantiles", "lf_lumfunc_integral_quantiles_ms", "lf_veff_draws", "lf_veff_draws_ms",
            "lf_veff_draws_chunk", "lf_set_lum_err", "lf_lnprob_err_batch", "lf_lnprob_err_batch_device", "lf_gauss_hermite",
-           "lf_deconv_info", "lf_lnprob_err_grad_batch", "lf_lnprob_err_grad_batch_device", "lf_sampler_set_likelihood",
+           "lf_deconv_info", "lf_deconv_wide_info", "lf_lnprob_err_grad_batch", "lf_lnprob_err_grad_batch_device", "lf_sampler_set_likelihood",
            "lf_ptsampler_set_likelihood")
 
 _lib = None
@@ -121,6 +121,9 @@ def load():
     lib.lf_lnprob_err_grad_batch_device.restype = ctypes.c_int
     lib.lf_lnprob_err_grad_batch_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                     ctypes.c_void_p]
+    lib.lf_deconv_wide_info.restype = ctypes.c_int
+    lib.lf_deconv_wide_info.argtypes = [_c_double_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                        _c_double_p, ctypes.POINTER(ctypes.c_int), _c_double_p, ctypes.c_int, _c_double_p, _c_double_p]
     lib.lf_deconv_info.restype = ctypes.c_int
     lib.lf_deconv_info.argtypes = [ctypes.POINTER(ctypes.c_int32), _c_double_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                    ctypes.POINTER(ctypes.c_int)]
@@ -489,6 +492,30 @@ def deconv_info():
             "chunk": int(chunk.value)}
 
 
+def deconv_wide_info(tables=False):
+    """lf_deconv_wide_info: dict edges (the sigma classes' upper edges, dex), nodes (per class), chunk, T, nodes_per_panel, h
+    of the wide rule; tables=True: also "tables", per class (x, lnw) in the kernels' form.  Touches no
+    GPU."""
+    lib = load()
+    n = lib.lf_deconv_wide_info(None, None, 0, None, None, None, None, 0, None, None)
+    edges, nodes = np.empty(n), np.empty(n, dtype=np.int32)
+    chunk, npan = ctypes.c_int(0), ctypes.c_int(0)
+    T, h = ctypes.c_double(0.0), ctypes.c_double(0.0)
+    lib.lf_deconv_wide_info(_ptr(edges), nodes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n, ctypes.byref(chunk), ctypes.byref(T),
+                            ctypes.byref(npan), ctypes.byref(h), 0, None, None)
+    out = {"edges": tuple(float(v) for v in edges), "nodes": tuple(int(k) for k in nodes), "chunk": int(chunk.value),
+           "T": float(T.value), "nodes_per_panel": int(npan.value), "h": float(h.value)}
+    if tables:
+        tabs = []
+        for c in range(n):
+            x, lnw = np.empty(out["nodes"][c]), np.empty(out["nodes"][c])
+            if lib.lf_deconv_wide_info(None, None, 0, None, None, None, None, c, _ptr(x), _ptr(lnw)) != n:
+                raise ValueError("lf_deconv_wide_info: class %d" % c)
+            tabs.append((x, lnw))
+        out["tables"] = tabs
+    return out
+
+
 def _ptr(a):
     return a.ctypes.data_as(_c_double_p) if a is not None else None
 
@@ -664,10 +691,11 @@ class LFContext(object):
         lnprob_batch's, bit for bit; rows whose lnprob is -inf have NaN gradients."""
         return self._value_grad(self._lib.lf_lnprob_grad_batch, theta)
 
-    def set_lum_err(self, sigma, K=None, unchecked=False):
+    def set_lum_err(self, sigma, K=None, unchecked=False, wide=False):
         """lf_set_lum_err: the sources' luminosity errors sigma (dex, catalogue order) and the Gauss-Hermite order K (None: the
         library's default) of the flux-error-convolved likelihood (lnprob_err_batch).  unchecked=True
-        sets the option "deconv_unchecked" first: sigma above the order's validated range is taken as it is."""
+        sets the option "deconv_unchecked" first: sigma above the order's validated range is taken as it is.  wide=True sets
+        the option "deconv_wide" first: sigma above that range, up to 0.30 dex, goes to the wide rule."""
         sg = _f64(sigma).ravel()
         if sg.size != self.N:
             raise ValueError("sigma must have one value per source (%d), got %d" % (self.N, sg.size))
@@ -676,6 +704,7 @@ class LFContext(object):
         if self.variant != "free" and self._logf is None:
             raise ValueError("set_lum_err: the inputs of a fixed-completeness context must hold logf or DLz")
         self.set_option("deconv_unchecked", 1 if unchecked else 0)
+        self.set_option("deconv_wide", 1 if wide else 0)
         self._check(self._lib.lf_set_lum_err(self._h, _ptr(sg), int(K), None if self.variant == "free" else _ptr(self._logf),
                                              _ptr(self._flim0), float(self._alpha0)))
         self.deconv_order = int(K)

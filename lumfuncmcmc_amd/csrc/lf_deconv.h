@@ -17,7 +17,7 @@
 //                  context's per-source arrays plus sigma; FIXCOMP, ZEVOL: plus the sources' log flux and 10^(log flux + 17)).
 //                  The node table {x_k}, {ln(w_k / sqrt(pi))} is copied to LDS; the row's constants are scalars.  Thread t
 //                  takes sources t, t + 256, ... of its chunk in that order (deconv_items, the loop of lf_deconv_grad_part
-//                  too); then the block's tail (block_sum, lf_math.h) -> part[row][block].
+//                  too; a source's nodes: deconv_source, lf_deconv_wide.h's too); then the block's tail (block_sum, lf_math.h) -> part[row][block].
 // lf_deconv_final  one wave per row: lane l adds blocks l, l + 64, ... in that order, then the shuffle tree; out = lnprob +
 //                  Delta.  A row whose lnprob is -inf stays -inf; NaN becomes -inf.
 // No atomics; nothing in either order depends on the batch: a row's value has the same bits at any B and any position.
@@ -80,14 +80,63 @@ __device__ __forceinline__ double deconv_t(const DeconvArgs& a, const DeconvRow&
     return a.P[g] * w.Q;
 }
 
+// One source of both part kernels and of lf_deconv_wide.h's: source g of the arrays in `a` (sigma sg > 0) against the K nodes
+// {x_k}, {ln of the whole weight} at nd[0 .. 2K), added to the thread's NS running sums.  GRAD false: acc[0] += Delta_i.
+// GRAD true: the numerators of lf_deconv_grad.h ride the same online softmax, acc = that header's slots; m and s, and so
+// Delta_i, take the same steps either way.
+template <int V, bool GRAD, int NS>
+__device__ __forceinline__ void deconv_source(const DeconvArgs& a, const DeconvRow& w, int g, double sg, int K, const double* nd,
+                                              double (&acc)[NS]) {
+    constexpr bool DERIV = GRAD && V == LF_FREE;  // dF, dC: of a completeness that is the row's own
+    double lb[3] = {0.0, 0.0, 0.0};
+    const double t = deconv_t<V>(a, w, g, lb);
+    const double y0 = (a.logf[g] - LF_FREF) - w.lF;
+    const double v0 = a.U[g] * w.vs;
+    const GradComp c0 = comp_form<DERIV>(w.aC, w.aC_ln, w.kc2, y0, v0);
+    const double s2 = 1.41421356237309504880 * sg;
+    double m = -HUGE_VAL, s = 0.0, nD = 0.0, nE = 0.0, nF = 0.0, nC = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const double dl = s2 * nd[k];
+        const double em = expm1(LF_LN10 * dl);
+        const GradComp ck = comp_form<DERIV>(w.aC, w.aC_ln, w.kc2, y0 + dl, v0 * (em + 1.0));
+        const double av = nd[K + k] + ((w.c1l * dl - t * em) + (ck.l - c0.l));
+        if (av == -HUGE_VAL) continue;
+        const double d = av - m;
+        const double e = exp(-fabs(d));
+        if (d > 0.0) {
+            s = fma(s, e, 1.0);
+            if (GRAD) nD = fma(nD, e, dl), nE = fma(nE, e, em);
+            if (DERIV) nF = fma(nF, e, ck.dF), nC = fma(nC, e, ck.dC);
+            m = av;
+        } else {
+            s += e;
+            if (GRAD) nD = fma(e, dl, nD), nE = fma(e, em, nE);
+            if (DERIV) nF = fma(e, ck.dF, nF), nC = fma(e, ck.dC, nC);
+        }
+    }
+    if constexpr (!GRAD) {
+        acc[0] += m + log(s);
+    } else if constexpr (V == LF_ZEVOL) {
+        const double gL = t * (nE / s);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) acc[q] += lb[q] * gL;
+        acc[3] += nD / s;
+    } else {
+        acc[0] += t * (nE / s);
+        acc[1] += nD / s;
+        if constexpr (DERIV) {
+            acc[2] += nF / s - c0.dF;
+            acc[3] += nC / s - c0.dC;
+        }
+    }
+}
+
 // The item loop of both part kernels: block (blockIdx.x, row blockIdx.y) takes its chunk's sources as the header says and
-// leaves each thread's NS running sums in acc.  GRAD false: acc[0] = the sum of Delta_i.  GRAD true: the numerators of
-// lf_deconv_grad.h ride the same online softmax, acc = that header's slots; m and s, and so Delta_i, take the same steps
-// either way.  nd: LDS for the node table.  False when the row's lnprob is not finite: the whole block returns then, before
-// any barrier (the rows' second stages do not read the partial sums of such a row).
+// leaves each thread's NS running sums in acc (deconv_source).  nd: LDS for the node table.  False when the row's lnprob is
+// not finite: the whole block returns then, before any barrier (the rows' second stages do not read the partial sums of such a
+// row).
 template <int V, bool GRAD, int NS>
 __device__ __forceinline__ bool deconv_items(const DeconvArgs& a, double* nd, double (&acc)[NS]) {
-    constexpr bool DERIV = GRAD && V == LF_FREE;  // dF, dC: of a completeness that is the row's own
     const int b = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
     if (!isfinite(a.lnprob[b])) return false;
     const int K = a.dc.K;
@@ -101,47 +150,7 @@ __device__ __forceinline__ bool deconv_items(const DeconvArgs& a, double* nd, do
         const int g = first + i;
         const double sg = a.sigma[g];
         if (!(sg > 0.0)) continue;
-        double lb[3] = {0.0, 0.0, 0.0};
-        const double t = deconv_t<V>(a, w, g, lb);
-        const double y0 = (a.logf[g] - LF_FREF) - w.lF;
-        const double v0 = a.U[g] * w.vs;
-        const GradComp c0 = comp_form<DERIV>(w.aC, w.aC_ln, w.kc2, y0, v0);
-        const double s2 = 1.41421356237309504880 * sg;
-        double m = -HUGE_VAL, s = 0.0, nD = 0.0, nE = 0.0, nF = 0.0, nC = 0.0;
-        for (int k = 0; k < K; ++k) {
-            const double dl = s2 * nd[k];
-            const double em = expm1(LF_LN10 * dl);
-            const GradComp ck = comp_form<DERIV>(w.aC, w.aC_ln, w.kc2, y0 + dl, v0 * (em + 1.0));
-            const double av = nd[K + k] + ((w.c1l * dl - t * em) + (ck.l - c0.l));
-            if (av == -HUGE_VAL) continue;
-            const double d = av - m;
-            const double e = exp(-fabs(d));
-            if (d > 0.0) {
-                s = fma(s, e, 1.0);
-                if (GRAD) nD = fma(nD, e, dl), nE = fma(nE, e, em);
-                if (DERIV) nF = fma(nF, e, ck.dF), nC = fma(nC, e, ck.dC);
-                m = av;
-            } else {
-                s += e;
-                if (GRAD) nD = fma(e, dl, nD), nE = fma(e, em, nE);
-                if (DERIV) nF = fma(e, ck.dF, nF), nC = fma(e, ck.dC, nC);
-            }
-        }
-        if constexpr (!GRAD) {
-            acc[0] += m + log(s);
-        } else if constexpr (V == LF_ZEVOL) {
-            const double gL = t * (nE / s);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) acc[q] += lb[q] * gL;
-            acc[3] += nD / s;
-        } else {
-            acc[0] += t * (nE / s);
-            acc[1] += nD / s;
-            if constexpr (DERIV) {
-                acc[2] += nF / s - c0.dF;
-                acc[3] += nC / s - c0.dC;
-            }
-        }
+        deconv_source<V, GRAD>(a, w, g, sg, K, nd, acc);
     }
     return true;
 }

@@ -718,6 +718,87 @@ inline double deconv_sigma_max(int K) {
     return -1.0;
 }
 
+// ---- the wide rule of the flux-error-convolved likelihood (lf_deconv_wide.h) ----
+// The n-point Gauss-Legendre rule on [-1, 1], x ascending: Newton iterations on the Legendre recurrence in extended precision,
+// the positive roots mirrored.  False for n outside 1..64.  (deconv.py: gauss_legendre is the same routine.)
+inline bool gauss_legendre(int n, long double* x, long double* w) {
+    if (n < 1 || n > 64) return false;
+    const long double PI = 3.14159265358979323846264338327950288L;
+    auto eval = [&](long double z, long double& pp) {
+        long double p1 = 1.0L, p2 = 0.0L;
+        for (int j = 1; j <= n; ++j) {
+            const long double p3 = p2;
+            p2 = p1;
+            p1 = ((2 * j - 1) * z * p2 - (j - 1) * p3) / j;
+        }
+        pp = n * (z * p1 - p2) / (z * z - 1.0L);
+        return p1;
+    };
+    for (int i = 0; i < (n + 1) / 2; ++i) {
+        long double z = std::cos(PI * (i + 0.75L) / (n + 0.5L)), pp = 1.0L;
+        for (int it = 0; it < 100; ++it) {
+            const long double dz = eval(z, pp) / pp;
+            z -= dz;
+            if (std::fabs(dz) <= 1.0e-19L) break;
+        }
+        if (n % 2 == 1 && i == n / 2) z = 0.0L;
+        eval(z, pp);
+        x[i] = -z, x[n - 1 - i] = z;
+        w[i] = w[n - 1 - i] = 2.0L / ((1.0L - z * z) * pp * pp);
+    }
+    return true;
+}
+
+// The table of sigma class cls in the kernel's form: K = DECONV_WIDE_PANELS[cls] * DECONV_WIDE_NPAN nodes, x[K] ascending with
+// delta = sqrt(2) sigma x, and lnw[K] = ln[w_j (T / panels) exp(-u^2 / 2) / sqrt(2 pi)] at u = sqrt(2) x - equal panels on
+// [-T, T] sigma.  Returns K.  (deconv.py: composite_table.)
+inline int wide_table(int cls, double* x, double* lnw) {
+    const int panels = DECONV_WIDE_PANELS[cls], np_ = DECONV_WIDE_NPAN;
+    long double gx[64], gw[64];
+    gauss_legendre(np_, gx, gw);
+    const long double PI = 3.14159265358979323846264338327950288L;
+    const long double T = (long double)DECONV_WIDE_T, half = T / panels;
+    for (int p = 0; p < panels; ++p)
+        for (int j = 0; j < np_; ++j) {
+            const long double u = -T + (2 * p + 1) * half + half * gx[j];
+            x[p * np_ + j] = (double)(u / std::sqrt(2.0L));
+            lnw[p * np_ + j] = (double)(std::log(gw[j] * half) - 0.5L * u * u - 0.5L * std::log(2.0L * PI));
+        }
+    return panels * np_;
+}
+inline int wide_nodes(int cls) { return DECONV_WIDE_PANELS[cls] * DECONV_WIDE_NPAN; }
+
+// the class of a sigma above the narrow limit: the first whose upper edge is not below it; -1 above the top edge
+inline int wide_class(double sigma) {
+    for (int c = 0; c < DECONV_WIDE_NCLASS; ++c)
+        if (sigma <= DECONV_WIDE_EDGE[c]) return c;
+    return -1;
+}
+
+// The wide list of a catalogue in the context's order (sigma[i], the fields' ranges field_ind): the indices of the sources with
+// sigma above smax sorted by field, then class, then index, and its chunks of up to DECONV_WIDE_CH sources of one field and
+// one class.
+struct WideList {
+    std::vector<int64_t> src;                     // indices into the context's order
+    std::vector<int> start, len, field, cls;      // the chunks, into src
+};
+inline WideList wide_list(const std::vector<double>& sigma, const std::vector<int64_t>& field_ind, int nf, double smax) {
+    WideList wl;
+    for (int f = 0; f < nf; ++f)
+        for (int c = 0; c < DECONV_WIDE_NCLASS; ++c) {
+            const size_t first = wl.src.size();
+            for (int64_t i = field_ind[f]; i < field_ind[f + 1]; ++i)
+                if (sigma[(size_t)i] > smax && wide_class(sigma[(size_t)i]) == c) wl.src.push_back(i);
+            for (size_t s = first; s < wl.src.size(); s += DECONV_WIDE_CH) {
+                wl.start.push_back((int)s);
+                wl.len.push_back((int)std::min<size_t>(DECONV_WIDE_CH, wl.src.size() - s));
+                wl.field.push_back(f);
+                wl.cls.push_back(c);
+            }
+        }
+    return wl;
+}
+
 // ---- lf_free's static deal (lf_layout.h: DEAL_*): flux bins, then cell chunks, each to the virtual workgroup that would be done
 // first - a bin costs a wave cost_b = 8 units, a cell chunk 3 (tools/stamps_fused.py), and the ranks of the younger half are
 // counted cost_h = 8 units behind (swept on one box, tools/deal_sweep.sh: 13.4 us per 128-row evaluation at 8-10, 13.75 at 0-6,

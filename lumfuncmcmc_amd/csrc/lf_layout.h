@@ -104,6 +104,17 @@ constexpr int DECONV_NORDERS = 9;
 constexpr int DECONV_ORDERS[DECONV_NORDERS] = {4, 6, 8, 10, 12, 16, 20, 24, 32};
 constexpr double DECONV_SIGMA_MAX[DECONV_NORDERS] = {0.01, 0.03, 0.04, 0.05, 0.06, 0.06, 0.07, 0.08, 0.09};
 constexpr int DECONV_DEFAULT_ORDER = 32;
+// Its wide rule (lf_deconv_wide.h), for sigma above the order's limit: the classes' upper edges (dex;
+// the last is the largest sigma accepted), per class the panels of the composite Gauss-Legendre rule on [-T, T] sigma - the
+// fewest that are at most DECONV_WIDE_H dex wide at the class's upper edge - the nodes per panel, and the sources per block.
+constexpr int DECONV_WIDE_CH = 256;
+constexpr int DECONV_WIDE_NCLASS = 5;
+constexpr double DECONV_WIDE_EDGE[DECONV_WIDE_NCLASS] = {0.10, 0.15, 0.20, 0.25, 0.30};
+constexpr int DECONV_WIDE_PANELS[DECONV_WIDE_NCLASS] = {6, 9, 12, 15, 18};
+constexpr int DECONV_WIDE_NPAN = 8;
+constexpr double DECONV_WIDE_T = 7.5;
+constexpr double DECONV_WIDE_H = 0.25;
+constexpr int DECONV_WIDE_KMAX = DECONV_WIDE_PANELS[DECONV_WIDE_NCLASS - 1] * DECONV_WIDE_NPAN;    // 144 nodes
 struct DeconvConst {
     int K;                       // nodes
     double alpha0;               // FIXCOMP, ZEVOL: the fixed completeness the model was built with

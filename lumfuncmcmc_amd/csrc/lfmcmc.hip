@@ -24,6 +24,7 @@
 #include "lf_deconv.h"
 #include "lf_deconv_grad.h"
 #include "lf_deconv_tile.h"
+#include "lf_deconv_wide.h"
 #include "lf_grad.h"
 #include "lf_gridbound.h"
 #include "lf_hostcall.h"
@@ -169,6 +170,16 @@ struct lf_ctx {
     int64_t opt_deconv_tile = 0;        // 1: FIXCOMP, ZEVOL: the value's first stage by tiles of rows (lf_deconv_tile.h); FREE: no effect
     Buf<double> d_sigma, d_elogf, d_eU, d_ghnodes, d_dpart;
     Buf<double> d_dgpart;               // its gradient's partial sums [rows][chunks][DGRAD_SLOTS] (lf_deconv_grad.h)
+    // the wide rule (lf_deconv_wide.h): the sources above the order's limit in arrays of their own (lf_set_lum_err; their
+    // entries of d_sigma are 0), their chunks, the classes' tables, and the field of every block of a row - the narrow chunks',
+    // then the wide ones' (what the second stages read when n > 0)
+    int64_t opt_deconv_wide = 0;        // 1: lf_set_lum_err takes sigma up to the wide rule's top edge
+    struct {
+        int n = 0;                      // wide chunks
+        Buf<double> d_lum, d_a1, d_P, d_logf, d_U, d_sigma, d_tables;
+        Buf<int> d_start, d_len, d_class, d_field_all;
+        int K[lf::DECONV_WIDE_NCLASS] = {}, off[lf::DECONV_WIDE_NCLASS] = {};
+    } wide;
     hipStream_t stream = nullptr;
     hipStream_t last_stream = nullptr;   // stream of the previous enqueue (workspace is shared)
     bool any_enqueued = false;
@@ -921,11 +932,11 @@ int family_check(lf_ctx* c, const char* fn, bool err, const void* theta, int B, 
 }
 
 // What the correction's kernels need before anything is enqueued: the chunk table and the blocks' partial sums [rows][chunks]
-// (grad: and [rows][chunks][DGRAD_SLOTS]).
+// (grad: and [rows][chunks][DGRAD_SLOTS]); chunks: the narrow ones and behind them those of the wide list.
 int deconv_prepare(lf_ctx* c, int B, bool grad) {
     int rc;
     if ((rc = src_chunk_table(c)) != LF_OK) return rc;
-    const size_t need = (size_t)B * std::max(c->src_chunks.n, 1);
+    const size_t need = (size_t)B * std::max(c->src_chunks.n + c->wide.n, 1);
     if (need > c->d_dpart.size() && (rc = grow(c, c->d_dpart, need)) != LF_OK) return rc;
     if (grad && need * lf::DGRAD_SLOTS > c->d_dgpart.size() && (rc = grow(c, c->d_dgpart, need * lf::DGRAD_SLOTS)) != LF_OK) return rc;
     return LF_OK;
@@ -936,7 +947,23 @@ lf::DeconvArgs deconv_args(lf_ctx* c, const double* d_theta, double* d_lnp, doub
     const ChunkTable& t = c->src_chunks;
     return lf::DeconvArgs{c->gradc, c->deconvc, d_theta, d_lnp, c->d_dpart, d_out, c->d_lum, c->d_a1, c->d_P,
                           fr ? c->d_a1.get() : c->d_elogf.get(), fr ? c->d_U.get() : c->d_eU.get(), c->d_sigma, c->d_ghnodes,
-                          t.d_start, t.d_len, t.d_field, t.n};
+                          t.d_start, t.d_len, c->wide.n ? c->wide.d_field_all.get() : t.d_field.get(), t.n + c->wide.n};
+}
+
+// lf_deconv_wide.h's arguments from the narrow kernels' (da: the rows of one launch): the wide list's arrays and chunks, the
+// partial sums advanced past the narrow blocks' slots
+lf::DeconvWideArgs deconv_wide_args(lf_ctx* c, const lf::DeconvArgs& da) {
+    const auto& w = c->wide;
+    const int n0 = c->src_chunks.n;
+    lf::DeconvWideArgs wa{};
+    wa.d = da;
+    wa.d.part = da.part + n0;
+    wa.d.lum = w.d_lum, wa.d.a1 = w.d_a1, wa.d.P = w.d_P, wa.d.logf = w.d_logf, wa.d.U = w.d_U, wa.d.sigma = w.d_sigma;
+    wa.d.chunk_start = w.d_start, wa.d.chunk_len = w.d_len, wa.d.chunk_field = w.d_field_all + n0;
+    wa.chunk_class = w.d_class;
+    wa.tables = w.d_tables;
+    for (int k = 0; k < lf::DECONV_WIDE_NCLASS; ++k) wa.K[k] = w.K[k], wa.off[k] = w.off[k];
+    return wa;
 }
 
 // the value's two kernels on the plain lnprob of B rows (da.lnprob).  tile: the first stage by tiles of DECONV_RT rows where the
@@ -950,14 +977,16 @@ void launch_deconv(lf_ctx* c, const lf::DeconvArgs& da, int B, hipStream_t s, bo
         g.lnprob += b0;
         g.part += (size_t)b0 * g.nch;
         g.out += b0;
+        const int n0 = c->src_chunks.n, nw = c->wide.n;     // the narrow blocks of a row and the wide ones (g.nch = n0 + nw)
         bool tiled = false;
         if constexpr (v() != LF_FREE) {
-            tiled = tile && g.nch > 0;
+            tiled = tile && n0 > 0;
             if (tiled)
-                hipLaunchKernelGGL(lf_deconv_tile<v()>, dim3((unsigned)g.nch, (unsigned)((nb + DECONV_RT - 1) / DECONV_RT)), dim3(BLOCK),
+                hipLaunchKernelGGL(lf_deconv_tile<v()>, dim3((unsigned)n0, (unsigned)((nb + DECONV_RT - 1) / DECONV_RT)), dim3(BLOCK),
                                    0, s, g, nb);
         }
-        if (g.nch > 0 && !tiled) hipLaunchKernelGGL(lf_deconv_part<v()>, dim3((unsigned)g.nch, (unsigned)nb), dim3(BLOCK), 0, s, g);
+        if (n0 > 0 && !tiled) hipLaunchKernelGGL(lf_deconv_part<v()>, dim3((unsigned)n0, (unsigned)nb), dim3(BLOCK), 0, s, g);
+        if (nw > 0) hipLaunchKernelGGL(lf_deconv_wide_part<v()>, dim3((unsigned)nw, (unsigned)nb), dim3(BLOCK), 0, s, deconv_wide_args(c, g));
         hipLaunchKernelGGL(lf_deconv_final, dim3((unsigned)nb), dim3(64), 0, s, g);
     });
 }
@@ -989,7 +1018,11 @@ int enqueue_deconv_grad(lf_ctx* c, const double* d_theta, int B, double* d_lnp, 
         g.d.lnprob += b0;
         g.gpart += (size_t)b0 * g.d.nch * DGRAD_SLOTS;
         g.grad += (size_t)b0 * g.d.gc.ndim;
-        if (g.d.nch > 0) hipLaunchKernelGGL(lf_deconv_grad_part<v()>, dim3((unsigned)g.d.nch, (unsigned)nb), dim3(BLOCK), 0, s, g);
+        const int n0 = c->src_chunks.n, nw = c->wide.n;
+        if (n0 > 0) hipLaunchKernelGGL(lf_deconv_grad_part<v()>, dim3((unsigned)n0, (unsigned)nb), dim3(BLOCK), 0, s, g);
+        if (nw > 0)
+            hipLaunchKernelGGL(lf_deconv_wide_grad_part<v()>, dim3((unsigned)nw, (unsigned)nb), dim3(BLOCK), 0, s,
+                               DeconvWideGradArgs{deconv_wide_args(c, g.d), g.gpart + (size_t)n0 * DGRAD_SLOTS});
         hipLaunchKernelGGL(lf_deconv_grad_final<v()>, dim3((unsigned)nb), dim3(64), 0, s, g);
     });
     LF_HIP(c, hipGetLastError());
@@ -1416,6 +1449,23 @@ int lf_deconv_info(int32_t* orders, double* sigma_max, int cap, int* default_ord
     return lf::DECONV_NORDERS;
 }
 
+int lf_deconv_wide_info(double* edges, int32_t* nodes, int cap, int* chunk, double* T, int* npanel, double* h, int cls, double* x,
+                        double* lnw) {
+    if (chunk) *chunk = lf::DECONV_WIDE_CH;
+    if (T) *T = lf::DECONV_WIDE_T;
+    if (npanel) *npanel = lf::DECONV_WIDE_NPAN;
+    if (h) *h = lf::DECONV_WIDE_H;
+    for (int i = 0; i < lf::DECONV_WIDE_NCLASS && i < cap; ++i) {
+        if (edges) edges[i] = lf::DECONV_WIDE_EDGE[i];
+        if (nodes) nodes[i] = lfh::wide_nodes(i);
+    }
+    if (x || lnw) {
+        if (!x || !lnw || cls < 0 || cls >= lf::DECONV_WIDE_NCLASS) return LF_ERR_ARG;
+        lfh::wide_table(cls, x, lnw);
+    }
+    return lf::DECONV_WIDE_NCLASS;
+}
+
 int lf_set_lum_err(lf_ctx* c, const double* sigma, int K, const double* logf, const double* flim0, double alpha0) {
     using namespace lf;
     if (!c) return LF_ERR_ARG;
@@ -1438,9 +1488,17 @@ int lf_set_lum_err(lf_ctx* c, const double* sigma, int K, const double* logf, co
         for (int f = 0; f < nf; ++f)
             if (!(flim0[f] > 0.0) || !std::isfinite(flim0[f])) return bad("flim0 must be finite and > 0");
     }
+    const double top = DECONV_WIDE_EDGE[DECONV_WIDE_NCLASS - 1];
     for (int64_t i = 0; i < N; ++i) {
         if (!std::isfinite(sigma[i]) || sigma[i] < 0.0) return bad("sigma must be finite and >= 0 (source " + std::to_string(i) + ")");
-        if (sigma[i] > smax && !c->opt_deconv_unchecked) {
+        if (c->opt_deconv_wide) {
+            if (sigma[i] > top) {
+                char msg[200];
+                std::snprintf(msg, sizeof(msg), "sigma = %.4g dex of source %lld is above %.2f dex, the largest value the wide rule "
+                              "(option deconv_wide) is validated for", sigma[i], (long long)i, top);
+                return bad(msg);
+            }
+        } else if (sigma[i] > smax && !c->opt_deconv_unchecked) {
             char msg[200];
             std::snprintf(msg, sizeof(msg), "sigma = %.4g dex of source %lld is above %.2f dex, the largest value the order K = %d is "
                           "validated for (per-source error below 1e-7; K = 32 reaches 0.09)", sigma[i], (long long)i, smax, K);
@@ -1454,6 +1512,12 @@ int lf_set_lum_err(lf_ctx* c, const double* sigma, int K, const double* logf, co
     std::vector<double> sg((size_t)N), lf_, u_, nodes((size_t)2 * K);
     for (int64_t i = 0; i < N; ++i) sg[(size_t)i] = sigma[c->perm[(size_t)i]];
     lfh::gauss_hermite(K, nodes.data(), nodes.data() + K);
+    // the wide list (option "deconv_wide"): the sources above the order's limit; the narrow kernels find sigma = 0 for them
+    c->wide.n = 0;
+    lfh::WideList wl;
+    if (c->opt_deconv_wide) wl = lfh::wide_list(sg, c->field_ind, nf, smax);
+    const std::vector<double> sg_all = sg;
+    for (int64_t i : wl.src) sg[(size_t)i] = 0.0;
     int rc = upload(c, c->d_sigma, sg, c->d_ghnodes, nodes);
     if (rc != LF_OK) return rc;
     DeconvConst dc{};
@@ -1467,6 +1531,38 @@ int lf_set_lum_err(lf_ctx* c, const double* sigma, int K, const double* logf, co
         if ((rc = upload(c, c->d_elogf, lf_, c->d_eU, u_)) != LF_OK) return rc;
         dc.alpha0 = alpha0;
         for (int f = 0; f < nf; ++f) dc.flim0[f] = flim0[f];
+    }
+    if (!wl.src.empty()) {
+        // what the terms read per source, as the context's own arrays hold it (FREE: the log flux is a1, 10^(that + 17) is U)
+        std::vector<double> h[4];
+        const double* dev[4] = {c->d_lum, c->d_a1, c->d_P, c->d_U};
+        for (int k = 0; k < 4; ++k) {
+            h[k].resize((size_t)N);
+            LF_HIP(c, hipMemcpy(h[k].data(), dev[k], (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        const std::vector<double>&hl = fr ? h[1] : lf_, &hu = fr ? h[3] : u_;
+        const size_t nw = wl.src.size();
+        std::vector<double> wlum(nw), wa1(nw), wP(nw), wlogf(nw), wU(nw), wsg(nw);
+        for (size_t j = 0; j < nw; ++j) {
+            const size_t i = (size_t)wl.src[j];
+            wlum[j] = h[0][i], wa1[j] = h[1][i], wP[j] = h[2][i], wlogf[j] = hl[i], wU[j] = hu[i], wsg[j] = sg_all[i];
+        }
+        auto& w = c->wide;
+        std::vector<double> tables;
+        for (int k = 0; k < DECONV_WIDE_NCLASS; ++k) {
+            w.K[k] = lfh::wide_nodes(k);
+            w.off[k] = (int)tables.size();
+            tables.resize(tables.size() + 2 * (size_t)w.K[k]);
+            lfh::wide_table(k, tables.data() + w.off[k], tables.data() + w.off[k] + w.K[k]);
+        }
+        // the field of every block of a row: the chunks the narrow kernels take (src_chunk_table's), then the wide ones
+        std::vector<int> field_all = lfh::chunk_table(c->field_ind, nf, GRAD_CH, 0.0, 0.0, 0.0).field;
+        field_all.insert(field_all.end(), wl.field.begin(), wl.field.end());
+        if ((rc = src_chunk_table(c)) != LF_OK) return rc;
+        if ((rc = upload(c, w.d_lum, wlum, w.d_a1, wa1, w.d_P, wP, w.d_logf, wlogf, w.d_U, wU, w.d_sigma, wsg, w.d_tables, tables)) != LF_OK)
+            return rc;
+        if ((rc = upload(c, w.d_start, wl.start, w.d_len, wl.len, w.d_class, wl.cls, w.d_field_all, field_all)) != LF_OK) return rc;
+        w.n = (int)wl.start.size();
     }
     c->deconvc = dc;
     c->deconv_set = true;
@@ -1860,6 +1956,7 @@ int lf_set_option(lf_ctx* c, const char* key, int64_t value) {
         {"skip_grid", [](lf_ctx* c, int64_t v) { c->opt_skip_grid = v != 0; }},
         {"deconv_unchecked", [](lf_ctx* c, int64_t v) { c->opt_deconv_unchecked = v != 0; }},
         {"deconv_tile", [](lf_ctx* c, int64_t v) { c->opt_deconv_tile = v != 0; }},
+        {"deconv_wide", [](lf_ctx* c, int64_t v) { c->opt_deconv_wide = v != 0; }},
         {"persistent", [](lf_ctx* c, int64_t v) { c->opt_persistent = v < 0 ? 0 : (v > 2 ? 2 : v); }},
         {"profile_every", [](lf_ctx* c, int64_t v) { c->opt_profile_every = v < 1 ? 1 : v; c->prof_tick = 0; }},
         {"profile_span", [](lf_ctx* c, int64_t v) { c->opt_profile_span = v < 1 ? 1 : v; c->prof_tick = 0; }},

@@ -15,6 +15,8 @@ arrays: expm1 for 10^delta - 1, the inner sum as a log-sum-exp with a running ma
 (exactly 0).  The node tables are derived here (Newton on the orthonormal Hermite recurrence in extended precision), as
 lf_hostprep.h derives the device's.
 """
+import functools
+
 import numpy as np
 
 from . import grad as G
@@ -27,6 +29,17 @@ SIGMA_MAX_BY_ORDER = (0.01, 0.03, 0.04, 0.05, 0.06, 0.06, 0.07, 0.08, 0.09)
 DEFAULT_ORDER = 32                              # the smallest order that reaches 1e-7 at 0.09 dex
 SIGMA_MAX = 0.09
 CHUNK = 1024                                    # sources per block of the device's fixed summation order (lf_layout.h: DECONV_CH)
+# The wide rule (csrc/lf_deconv_wide.h; lf_layout.h: DECONV_WIDE_*), for sigma above the order's limit:
+# sigma classes by their upper edges, per class a composite Gauss-Legendre rule on [-T, T] sigma of WIDE_PANELS[c] equal panels
+# (the fewest that are at most WIDE_H dex wide at the class's upper edge) with WIDE_NPANEL nodes each.  Chosen against 30-digit
+# integration on the probe set of tests/test_deconv_wide_cpu.py: worst per-source error below 1e-7 at every class's upper edge.
+WIDE_EDGES = (0.10, 0.15, 0.20, 0.25, 0.30)
+WIDE_PANELS = (6, 9, 12, 15, 18)
+WIDE_NPANEL = 8
+WIDE_T = 7.5
+WIDE_H = 0.25
+WIDE_SIGMA_MAX = WIDE_EDGES[-1]
+WIDE_CHUNK = 256                                # sources per block of the wide kernels (lf_layout.h: DECONV_WIDE_CH)
 
 
 def gauss_hermite(K):
@@ -73,6 +86,102 @@ def gauss_hermite(K):
         w[K - 1 - i] = w[i] = 2 / (pp * pp)
     lnw = np.log(w) - ld(0.5) * np.log(ld(np.pi) + ld(1.2246467991473532e-16))
     return x.astype(np.float64), lnw.astype(np.float64)
+
+
+def gauss_legendre(n):
+    """(x[n] ascending, w[n]) of the n-point Gauss-Legendre rule on [-1, 1]: Newton iterations on the Legendre recurrence in
+    extended precision, the positive roots mirrored (lf_hostprep.h: gauss_legendre is the same routine)."""
+    n = int(n)
+    if n < 1 or n > 64:
+        raise ValueError("gauss_legendre: n must be in 1..64")
+    ld = np.longdouble
+    pi = ld(np.pi) + ld(1.2246467991473532e-16)
+    x, w = np.zeros(n, dtype=ld), np.zeros(n, dtype=ld)
+    for i in range((n + 1) // 2):
+        z = np.cos(pi * (ld(i) + ld(0.75)) / (ld(n) + ld(0.5)))
+        pp = ld(1.0)
+        for _ in range(100):
+            p1, p2 = ld(1.0), ld(0.0)
+            for j in range(1, n + 1):
+                p3, p2 = p2, p1
+                p1 = ((2 * j - 1) * z * p2 - (j - 1) * p3) / j
+            pp = n * (z * p1 - p2) / (z * z - 1)
+            dz = p1 / pp
+            z = z - dz
+            if abs(dz) <= ld(1e-19):
+                break
+        if n % 2 == 1 and i == n // 2:
+            z = ld(0.0)
+        p1, p2 = ld(1.0), ld(0.0)
+        for j in range(1, n + 1):
+            p3, p2 = p2, p1
+            p1 = ((2 * j - 1) * z * p2 - (j - 1) * p3) / j
+        pp = n * (z * p1 - p2) / (z * z - 1)
+        x[i], x[n - 1 - i] = -z, z
+        w[i] = w[n - 1 - i] = 2 / ((1 - z * z) * pp * pp)
+    return x, w
+
+
+def composite_table(panels, npan, T):
+    """(x[panels * npan] ascending, lnw) of the composite Gauss-Legendre rule of `panels` equal panels with npan nodes each on
+    [-T, T] in units of sigma, in the kernel's form: delta = sqrt(2) sigma x, and lnw the log of the whole weight, the
+    Gaussian density included - ln[w_j (T / panels) exp(-u^2 / 2) / sqrt(2 pi)] at u = sqrt(2) x.  Extended precision, as
+    lf_hostprep.h: wide_table derives the device's."""
+    ld = np.longdouble
+    gx, gw = gauss_legendre(npan)
+    pi = ld(np.pi) + ld(1.2246467991473532e-16)
+    half = ld(T) / ld(panels)
+    x, lnw = np.empty(panels * npan), np.empty(panels * npan)
+    for p in range(panels):
+        u = -ld(T) + (2 * p + 1) * half + half * gx
+        x[p * npan:(p + 1) * npan] = (u / np.sqrt(ld(2.0))).astype(np.float64)
+        lnw[p * npan:(p + 1) * npan] = (np.log(gw * half) - ld(0.5) * u * u - ld(0.5) * np.log(2 * pi)).astype(np.float64)
+    return x, lnw
+
+
+@functools.lru_cache(maxsize=None)
+def wide_table(c):
+    """(x, lnw) of sigma class c, WIDE_PANELS[c] * WIDE_NPANEL nodes in the kernel's form"""
+    return composite_table(WIDE_PANELS[c], WIDE_NPANEL, WIDE_T)
+
+
+def wide_class(sigma, K=None):
+    """The rule of every source: -1 for the Gauss-Hermite order (sigma at or below sigma_max(K); sigma = 0 among them), else
+    the first class whose upper edge is not below sigma.  Sigma above the top edge is refused with the limit stated, as
+    lf_set_lum_err with "deconv_wide" refuses it."""
+    K = DEFAULT_ORDER if K is None else int(K)
+    s = np.asarray(sigma, dtype=np.float64)
+    if np.any(s > WIDE_SIGMA_MAX):
+        raise ValueError("sigma = %.4g dex is above %.2f dex, the largest value the wide rule (option deconv_wide) is validated "
+                         "for" % (s.max(), WIDE_SIGMA_MAX))
+    cls = np.searchsorted(np.asarray(WIDE_EDGES), s, side="left").astype(np.int64)
+    return np.where(s > sigma_max(K), cls, -1)
+
+
+def _subset(inp, idx):
+    """the kernel inputs of the sources idx (ascending, catalogue order) alone"""
+    fi = np.asarray(inp["field_ind"])
+    sub = dict(inp)
+    for k in ("lum", "z", "DLz", "logf", "Om_arr"):
+        if inp.get(k) is not None:
+            sub[k] = np.asarray(inp[k])[idx]
+    sub["field_ind"] = np.searchsorted(idx, fi, side="left").astype(np.int64)
+    return sub
+
+
+def _rules(inp, sigma, K, wide):
+    """[(inputs, the sources' places in the catalogue or None for all, x, lnw)]: the Gauss-Hermite order for every source, or
+    with wide=True for those at or below its limit, and the classes' tables for the others"""
+    x, lnw = gauss_hermite(K)
+    if not wide:
+        return [(inp, None, x, lnw)]
+    cls = wide_class(sigma, K)
+    out = []
+    for c in range(-1, len(WIDE_EDGES)):
+        idx = np.flatnonzero(cls == c)
+        if idx.size:
+            out.append((_subset(inp, idx), idx) + ((x, lnw) if c < 0 else wide_table(c)))
+    return out
 
 
 def _lcomp(y, v, aC):
@@ -145,10 +254,11 @@ def _row_terms(inp, sigma, th, x, lnw):
     return np.where(sigma == 0.0, 0.0, out)
 
 
-def delta(inp, sigma, theta, K=None, terms=False, unchecked=True):
+def delta(inp, sigma, theta, K=None, terms=False, unchecked=True, wide=False):
     """theta (B, ndim) or (ndim,) -> Delta[B]; with terms=True also Delta_i [B, N] (catalogue order) and S_abs[B] = sum_i
     |Delta_i|, the scale rounding is judged by.  The sum over sources is taken in catalogue order (the device's order is its
-    own: chunks of CHUNK sources of one field).  unchecked=False: sigma above the order's validated range is refused."""
+    own: chunks of CHUNK sources of one field).  unchecked=False: sigma above the order's validated range is refused.
+    wide=True: sources above that range, up to WIDE_SIGMA_MAX, are taken by their class's composite rule (wide_class)."""
     K = DEFAULT_ORDER if K is None else int(K)
     if K not in ORDERS:
         raise ValueError("deconvolve_order must be one of %s" % (ORDERS,))
@@ -157,26 +267,27 @@ def delta(inp, sigma, theta, K=None, terms=False, unchecked=True):
     th = np.atleast_2d(th)
     if th.shape[1] != G.ndim_of(inp):
         raise ValueError("theta must be (B, %d), got %s" % (G.ndim_of(inp), th.shape))
-    sigma = check_sigma(sigma, len(inp["lum"]), K, unchecked)
-    x, lnw = gauss_hermite(K)
-    D = np.empty((len(th), sigma.size))
+    sigma = check_sigma(sigma, len(inp["lum"]), K, unchecked or wide)
+    D = np.zeros((len(th), sigma.size))
     with np.errstate(all="ignore"):
-        for b, row in enumerate(th):
-            D[b] = _row_terms(inp, sigma, row, x, lnw)
+        for sub, idx, x, lnw in _rules(inp, sigma, K, wide):
+            idx = slice(None) if idx is None else idx
+            for b, row in enumerate(th):
+                D[b, idx] = _row_terms(sub, sigma[idx], row, x, lnw)
     tot, sabs = D.sum(axis=1), np.abs(D).sum(axis=1)
     if single:
         return (tot[0], D[0], sabs[0]) if terms else tot[0]
     return (tot, D, sabs) if terms else tot
 
 
-def lnprob_err(inp, sigma, theta, K=None, terms=False):
+def lnprob_err(inp, sigma, theta, K=None, terms=False, wide=False):
     """lnprob + Delta per row, with lnprob from grad.py's twin; a row whose lnprob is -inf stays -inf, NaN becomes -inf.
     terms=True: (value, lnprob, S_abs)."""
     th = np.asarray(theta, dtype=np.float64)
     single = th.ndim == 1
     th2 = np.atleast_2d(th)
     lp = np.atleast_1d(G.lnprob_grad(inp, th2)[0])
-    tot, _, sabs = delta(inp, sigma, th2, K, terms=True)
+    tot, _, sabs = delta(inp, sigma, th2, K, terms=True, wide=wide)
     with np.errstate(all="ignore"):
         out = np.where(np.isfinite(lp), lp + tot, -np.inf)
     out = np.where(np.isnan(out), -np.inf, out)
@@ -284,12 +395,13 @@ def _row_grad_terms(inp, sigma, th, x, lnw):
     return D, g, sabs
 
 
-def delta_grad(inp, sigma, theta, K=None, terms=False, per_source=False):
+def delta_grad(inp, sigma, theta, K=None, terms=False, per_source=False, wide=False):
     """theta (B, ndim) or (ndim,) -> (Delta[B], dDelta[B, ndim]): the correction and its derivative with respect to the row's
     own elements, the exact derivative of the K-point sum; with terms=True also S_abs[B, ndim], per element the sum over the
     sources of sum_k p_ik |d a_ik / d theta_e| + |the subtracted term at f_i|: the scale rounding is judged by.  The elements
     of phi* are exactly 0; a source with sigma_i = 0 adds exactly 0 to every element.  No prior test: what the formulas give.
-    per_source=True: the per-source arrays (Delta_i [B, N], dDelta_i [B, N, ndim], S_abs_i [B, N, ndim]) instead."""
+    per_source=True: the per-source arrays (Delta_i [B, N], dDelta_i [B, N, ndim], S_abs_i [B, N, ndim]) instead.
+    wide=True: as delta's (the exact derivative of each source's own sum, whichever rule takes it)."""
     K = DEFAULT_ORDER if K is None else int(K)
     if K not in ORDERS:
         raise ValueError("deconvolve_order must be one of %s" % (ORDERS,))
@@ -300,12 +412,13 @@ def delta_grad(inp, sigma, theta, K=None, terms=False, per_source=False):
     if th.shape[1] != nd:
         raise ValueError("theta must be (B, %d), got %s" % (nd, th.shape))
     sigma = check_sigma(sigma, len(inp["lum"]), K, True)
-    x, lnw = gauss_hermite(K)
     N = sigma.size
-    D, g, s = np.empty((len(th), N)), np.empty((len(th), N, nd)), np.empty((len(th), N, nd))
+    D, g, s = np.zeros((len(th), N)), np.zeros((len(th), N, nd)), np.zeros((len(th), N, nd))
     with np.errstate(all="ignore"):
-        for b, row in enumerate(th):
-            D[b], g[b], s[b] = _row_grad_terms(inp, sigma, row, x, lnw)
+        for sub, idx, x, lnw in _rules(inp, sigma, K, wide):
+            idx = slice(None) if idx is None else idx
+            for b, row in enumerate(th):
+                D[b, idx], g[b, idx], s[b, idx] = _row_grad_terms(sub, sigma[idx], row, x, lnw)
     if per_source:
         return (D[0], g[0], s[0]) if single else (D, g, s)
     out = (D.sum(axis=1), g.sum(axis=1), s.sum(axis=1))
@@ -314,7 +427,7 @@ def delta_grad(inp, sigma, theta, K=None, terms=False, per_source=False):
     return out if terms else out[:2]
 
 
-def lnprob_err_grad(inp, sigma, theta, K=None, terms=False):
+def lnprob_err_grad(inp, sigma, theta, K=None, terms=False, wide=False):
     """(value[B], grad[B, ndim]) of the convolved lnprob: lnprob_err's value, grad.lnprob_grad's gradient plus dDelta; a row
     whose lnprob is not finite gets NaN in every element (the plain gradient's convention).  terms=True: also S_abs[B, ndim],
     the sum of both parts' scales."""
@@ -322,7 +435,7 @@ def lnprob_err_grad(inp, sigma, theta, K=None, terms=False):
     single = th.ndim == 1
     th2 = np.atleast_2d(th)
     lp, g0, s0 = G.lnprob_grad(inp, th2, terms=True)
-    tot, dD, s1 = delta_grad(inp, sigma, th2, K, terms=True)
+    tot, dD, s1 = delta_grad(inp, sigma, th2, K, terms=True, wide=wide)
     with np.errstate(all="ignore"):
         val = np.where(np.isfinite(lp), lp + tot, -np.inf)
         val = np.where(np.isnan(val), -np.inf, val)

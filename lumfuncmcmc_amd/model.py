@@ -186,7 +186,8 @@ class _Base(object):
             if self.compress:
                 self._ctx.set_option("compress", 1)
             if self.deconvolve:
-                self._ctx.set_lum_err(self.lum_e, self.deconvolve_order, unchecked=self.deconvolve_unchecked)
+                self._ctx.set_lum_err(self.lum_e, self.deconvolve_order, unchecked=self.deconvolve_unchecked,
+                                       wide=self.deconvolve_wide)
             if self.deconvolve_tile:
                 self._ctx.set_option("deconv_tile", 1)
             self._ctx_key = key
@@ -197,11 +198,12 @@ class _Base(object):
     deconvolve_order = None        # its Gauss-Hermite order (None: the library's default)
     deconvolve_unchecked = False   # True: lum_e above the order's validated range is taken as it is
     deconvolve_tile = False        # True: the context option "deconv_tile" (csrc/lf_deconv_tile.h; no effect with free completeness)
+    deconvolve_wide = False        # True: lum_e above the order's range, up to 0.30 dex, by the wide rule (csrc/lf_deconv_wide.h)
 
-    def _init_deconvolve(self, deconvolve, deconvolve_order, deconvolve_tile=False):
+    def _init_deconvolve(self, deconvolve, deconvolve_order, deconvolve_tile=False, deconvolve_wide=False):
         from . import deconv
         self.deconvolve, self.deconvolve_order = bool(deconvolve), deconvolve_order
-        self.deconvolve_tile = bool(deconvolve_tile)
+        self.deconvolve_tile, self.deconvolve_wide = bool(deconvolve_tile), bool(deconvolve_wide)
         if not self.deconvolve:
             return
         if self.lum_e is None:
@@ -215,7 +217,9 @@ class _Base(object):
         if K not in deconv.ORDERS:
             raise ValueError("deconvolve_order must be one of %s" % (deconv.ORDERS,))
         self.deconvolve_order = K
-        deconv.check_sigma(self.lum_e, len(self.lum), K, self.deconvolve_unchecked)
+        sg = deconv.check_sigma(self.lum_e, len(self.lum), K, self.deconvolve_unchecked or self.deconvolve_wide)
+        if self.deconvolve_wide:
+            deconv.wide_class(sg, K)                 # (refuses lum_e above the wide rule's top edge)
 
     def _evaluate(self, theta):
         th = np.asarray(theta, dtype=np.float64)
@@ -678,7 +682,7 @@ class LumFuncMCMC(_Base):
                  phistar=-3.0, phistar_lims=[-8.0, 5.0], Lc=40.0, Lh=46.0, nwalkers=100, nsteps=1000,
                  fix_sch_al=False, fcmin=0.1, fix_comp=False, min_comp_frac=0.5,
                  field_names=None, field_ind=None, diff_rand=True, device=0, compress=False, shard="walkers",
-                 deconvolve=False, deconvolve_order=None, deconvolve_tile=False):
+                 deconvolve=False, deconvolve_order=None, deconvolve_tile=False, deconvolve_wide=False):
         self._common_init(z, flux, flux_e, lum, lum_e)
         self.device = device
         self.compress = bool(compress)
@@ -710,7 +714,7 @@ class LumFuncMCMC(_Base):
         self.size_ln = 201 if self.fix_comp else 101
         self.setlnsimple(need_integ=bool(self.fix_comp))
         self.setup_logging()
-        self._init_deconvolve(deconvolve, deconvolve_order, deconvolve_tile)
+        self._init_deconvolve(deconvolve, deconvolve_order, deconvolve_tile, deconvolve_wide)
 
     def getRoot(self, size=201):
         self.rootsf = hs.completeness_roots(self.Flim_lims, self.alpha_lims, self.fcmin, self.min_comp_frac, size)
@@ -890,7 +894,7 @@ class LumFuncMCMCz(_Base):
                  phistar=-3.0, phistar_lims=[-8.0, 5.0], Lc=40.0, Lh=46.0, nwalkers=100, nsteps=1000,
                  fcmin=0.1, min_comp_frac=0.5, field_names=None,
                  field_ind=None, z1=1.20, z2=1.53, z3=1.86, fix_sch_al=False, device=0, compress=False, shard="walkers",
-                 deconvolve=False, deconvolve_order=None, deconvolve_tile=False):
+                 deconvolve=False, deconvolve_order=None, deconvolve_tile=False, deconvolve_wide=False):
         self._common_init(z, flux, flux_e, lum, lum_e)
         self.device = device
         self.compress = bool(compress)
@@ -923,7 +927,7 @@ class LumFuncMCMCz(_Base):
         self.size_ln = 201
         self.setlnsimple(need_integ=True)
         self.setup_logging()
-        self._init_deconvolve(deconvolve, deconvolve_order, deconvolve_tile)
+        self._init_deconvolve(deconvolve, deconvolve_order, deconvolve_tile, deconvolve_wide)
 
     def getRoot(self):
         """Per-field flux at which the completeness equals min_comp_frac (lumfuncmcmc_z.py:292-297);
