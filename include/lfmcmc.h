@@ -226,6 +226,22 @@ int lf_deconv_info(int32_t *orders, double *sigma_max, int cap, int *default_ord
 int lf_deconv_wide_info(double *edges, int32_t *nodes, int cap, int *chunk, double *T, int *npanel, double *h, int cls, double *x,
                         double *lnw);
 
+/* The per-source posterior of the TRUE log-luminosity under the convolved model (csrc/lf_lumpost.h),
+ * marginalised over R rows of theta: for source i with sigma_i > 0 and row r the nodes delta_k = sqrt(2) sigma_i x_k of the
+ * source's rule (the order of lf_set_lum_err, or its wide class under "deconv_wide") carry the weights p_k proportional to
+ * exp(ln w_k + t_ik - t_i), the terms of lf_lnprob_err_batch, and
+ *     m1[i] = mean over the used rows of sum_k p_k delta_k,   m2[i] = mean of sum_k p_k delta_k^2      (dex, dex^2)
+ * in the CALLER's source order: the true value is lum_i + m1[i], its spread sqrt(max(m2[i] - m1[i]^2, 0)).  A row is used when
+ * its plain lnprob (lf_lnprob_batch's) is finite; *n_used = R', their number.  A source with sigma_i = 0 gets exactly 0 and 0;
+ * with R' = 0 every source with sigma_i > 0 gets NaN.  theta[R][ndim], m1[N], m2[N]: host pointers; synchronous; 1 <= R <= 4096.
+ * The summation order is fixed (rows in row order inside tiles of row_tile rows, the tiles' sums in tile order, then one
+ * division) and there are no atomics: the same inputs give the same bits, and R = 1 gives that row's own moments exactly.  The
+ * workspace does not depend on R.  LF_ERR_ARG with a message, before the device is touched, for a NULL pointer, R outside
+ * 1..4096, when no errors are set, and for a context with "skip_grid" or "grid_share" set; the context stays usable.
+ * lf_lum_posterior_info: host-only; the rows of a tile and the largest R (either may be NULL). */
+int lf_lum_posterior(lf_ctx *ctx, const double *theta, int R, double *m1, double *m2, int *n_used);
+int lf_lum_posterior_info(int *row_tile, int *max_rows);
+
 /* Kernel timing for bench.py: level 1 brackets lf_main, level 2 every launch, with hipEvents on
  * the stream the launch runs on (0 = off; each event pair costs a few microseconds of stream time: the events are
  * barrier packets, and the next launch no longer overlaps the previous one's tail - measured 7.6 us per evaluation

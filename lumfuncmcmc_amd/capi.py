@@ -55,7 +55,7 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_lnprob_grad_batch_device", "lf_lumfunc_integral_quantiles", "lf_lumfunc_integral_quantiles_ms", "lf_veff_draws", "lf_veff_draws_ms",
            "lf_veff_draws_chunk", "lf_set_lum_err", "lf_lnprob_err_batch", "lf_lnprob_err_batch_device", "lf_gauss_hermite",
            "lf_deconv_info", "lf_deconv_wide_info", "lf_lnprob_err_grad_batch", "lf_lnprob_err_grad_batch_device", "lf_sampler_set_likelihood",
-           "lf_ptsampler_set_likelihood")
+           "lf_ptsampler_set_likelihood", "lf_lum_posterior", "lf_lum_posterior_info")
 
 _lib = None
 
@@ -121,6 +121,10 @@ def load():
     lib.lf_lnprob_err_grad_batch_device.restype = ctypes.c_int
     lib.lf_lnprob_err_grad_batch_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                     ctypes.c_void_p]
+    lib.lf_lum_posterior.restype = ctypes.c_int
+    lib.lf_lum_posterior.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int)]
+    lib.lf_lum_posterior_info.restype = ctypes.c_int
+    lib.lf_lum_posterior_info.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.lf_deconv_wide_info.restype = ctypes.c_int
     lib.lf_deconv_wide_info.argtypes = [_c_double_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                         _c_double_p, ctypes.POINTER(ctypes.c_int), _c_double_p, ctypes.c_int, _c_double_p, _c_double_p]
@@ -516,6 +520,14 @@ def deconv_wide_info(tables=False):
     return out
 
 
+def lum_posterior_info():
+    """lf_lum_posterior_info: dict row_tile (rows summed in row order before the tiles' sums are added), max_rows.  Touches no
+    GPU."""
+    rt, mr = ctypes.c_int(0), ctypes.c_int(0)
+    load().lf_lum_posterior_info(ctypes.byref(rt), ctypes.byref(mr))
+    return {"row_tile": rt.value, "max_rows": mr.value}
+
+
 def _ptr(a):
     return a.ctypes.data_as(_c_double_p) if a is not None else None
 
@@ -716,6 +728,16 @@ class LFContext(object):
         if th.shape[0]:
             self._check(self._lib.lf_lnprob_err_batch(self._h, _ptr(th), th.shape[0], _ptr(out)))
         return out
+
+    def lum_posterior(self, theta):
+        """theta (R, ndim) or (ndim,) host array, 1 <= R <= 4096 -> (m1 (N,), m2 (N,), n_used): lf_lum_posterior, the per-source
+        posterior mean and second moment of (true - catalogued) log-luminosity under the convolved model, averaged over the
+        rows whose plain lnprob is finite, in catalogue order.  Needs set_lum_err."""
+        th = self._theta(theta)
+        m1, m2 = np.empty(self.N, dtype=np.float64), np.empty(self.N, dtype=np.float64)
+        used = ctypes.c_int(0)
+        self._check(self._lib.lf_lum_posterior(self._h, _ptr(th), th.shape[0], _ptr(m1), _ptr(m2), ctypes.byref(used)))
+        return m1, m2, used.value
 
     def lnprob_err_torch(self, theta):
         """theta: float64 device tensor (B, ndim) on this context's device; enqueues lf_lnprob_err_batch_device on torch's

@@ -120,5 +120,14 @@ struct DeconvConst {
     double alpha0;               // FIXCOMP, ZEVOL: the fixed completeness the model was built with
     double flim0[MAXF];          // ... in theta's units (1e-17)
 };
+// The per-source posterior of the true luminosity (lf_lumpost.h).  LUMPOST_RT: rows of a tile, summed in
+// row order; the tiles' sums are added in tile order.  A tile's rows share nothing but the node table and one 16-byte store
+// per source, against K exponents each, so the height buys no arithmetic; 2 keeps the sum of LUMPOST_RT + 1 equal addends to
+// one rounding (x + x is exact), which is what bounds the mean of equal rows to 2 ulp of the row's own value.  LUMPOST_SLABS:
+// tiles of one launch, each with a slab of 2 doubles per source - the workspace is (LUMPOST_SLABS + 1) * 16 bytes per source
+// whatever the number of rows; LUMPOST_MAX_ROWS: the rows of a call (the posterior bands' limit).
+constexpr int LUMPOST_RT = 2;
+constexpr int LUMPOST_SLABS = 16;
+constexpr int LUMPOST_MAX_ROWS = 4096;
 
 }  // namespace lf

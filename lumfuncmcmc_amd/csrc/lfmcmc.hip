@@ -25,6 +25,7 @@
 #include "lf_deconv_grad.h"
 #include "lf_deconv_tile.h"
 #include "lf_deconv_wide.h"
+#include "lf_lumpost.h"
 #include "lf_grad.h"
 #include "lf_gridbound.h"
 #include "lf_hostcall.h"
@@ -180,6 +181,11 @@ struct lf_ctx {
         Buf<int> d_start, d_len, d_class, d_field_all;
         int K[lf::DECONV_WIDE_NCLASS] = {}, off[lf::DECONV_WIDE_NCLASS] = {};
     } wide;
+    // the per-source posterior of the true luminosity (lf_lumpost.h): every slot's source in the caller's order - the context's
+    // sources, then those of the wide list (lf_set_lum_err) - and the workspace: the slabs, the running sums, m1 and m2
+    Buf<int> d_lp_caller;
+    int lp_nslots = 0;
+    Buf<double> d_lumpost;
     hipStream_t stream = nullptr;
     hipStream_t last_stream = nullptr;   // stream of the previous enqueue (workspace is shared)
     bool any_enqueued = false;
@@ -1564,6 +1570,12 @@ int lf_set_lum_err(lf_ctx* c, const double* sigma, int K, const double* logf, co
         if ((rc = upload(c, w.d_start, wl.start, w.d_len, wl.len, w.d_class, wl.cls, w.d_field_all, field_all)) != LF_OK) return rc;
         w.n = (int)wl.start.size();
     }
+    // lf_lumpost.h's slots: where each source of the device's arrays stands in the caller's catalogue
+    std::vector<int> caller((size_t)N + wl.src.size());
+    for (int64_t i = 0; i < N; ++i) caller[(size_t)i] = (int)c->perm[(size_t)i];
+    for (size_t j = 0; j < wl.src.size(); ++j) caller[(size_t)N + j] = (int)c->perm[(size_t)wl.src[j]];
+    if ((rc = upload(c, c->d_lp_caller, caller)) != LF_OK) return rc;
+    c->lp_nslots = (int)caller.size();
     c->deconvc = dc;
     c->deconv_set = true;
     return LF_OK;
@@ -1604,6 +1616,63 @@ int lf_lnprob_err_grad_batch(lf_ctx* c, const double* theta, int B, double* lnpr
     return host_value_grad(c, theta, B, lnprob_err, grad, [&](double* d_val, double* d_grad) {
         return enqueue_deconv_grad(c, c->d_theta, B, c->d_outB, d_val, d_grad, c->stream);
     });
+}
+
+int lf_lum_posterior_info(int* row_tile, int* max_rows) {
+    if (row_tile) *row_tile = lf::LUMPOST_RT;
+    if (max_rows) *max_rows = lf::LUMPOST_MAX_ROWS;
+    return LF_OK;
+}
+
+int lf_lum_posterior(lf_ctx* c, const double* theta, int R, double* m1, double* m2, int* n_used) {
+    using namespace lf;
+    int rc = family_check(c, "lf_lum_posterior", true, theta, R, m1);
+    if (rc != LF_OK) return rc;
+    if (!m2 || !n_used || R > LUMPOST_MAX_ROWS) {
+        c->err = "lf_lum_posterior: NULL pointer or R outside 1.." + std::to_string(LUMPOST_MAX_ROWS);
+        return LF_ERR_ARG;
+    }
+    if ((rc = stage_theta(c, theta, R)) != LF_OK) return rc;
+    if ((rc = src_chunk_table(c)) != LF_OK) return rc;
+    const size_t N = (size_t)c->N, ns = (size_t)c->lp_nslots;
+    const size_t need = std::max<size_t>((2 * LUMPOST_SLABS + 2) * ns + 2 * N, 1);
+    if (need > c->d_lumpost.size() && (rc = grow(c, c->d_lumpost, need)) != LF_OK) return rc;
+    // the rows' plain lnprob decides which are used: R' is counted here, the kernels read the same array
+    double* d_lnp = c->d_outB;
+    if ((rc = enqueue(c, c->d_theta, R, d_lnp, nullptr, nullptr, c->stream)) != LF_OK) return rc;
+    if ((rc = fetch(c, c->h_out, d_lnp, (size_t)R)) != LF_OK) return rc;
+    int used = 0;
+    for (int r = 0; r < R; ++r) used += std::isfinite(c->h_out[r]) ? 1 : 0;
+    *n_used = used;
+    if (N == 0) return LF_OK;
+    LumPostArgs x{};
+    x.d = deconv_args(c, c->d_theta, d_lnp, nullptr);
+    if (c->wide.n) x.w = deconv_wide_args(c, x.d);
+    x.n0 = c->src_chunks.n, x.nw = c->wide.n, x.N = (int)N, x.nslots = (int)ns;
+    x.slab = c->d_lumpost;
+    x.run = x.slab + 2 * LUMPOST_SLABS * ns;
+    x.m1 = x.run + 2 * ns, x.m2 = x.m1 + N;
+    x.caller = c->d_lp_caller;
+    LF_HIP(c, hipMemsetAsync(x.m1, 0, 2 * N * sizeof(double), c->stream));
+    // groups of LUMPOST_SLABS tiles: the tiles' sums, then their fold into the running sums; no used row: the fold alone (NaN)
+    constexpr int GROUP = LUMPOST_RT * LUMPOST_SLABS;
+    const int ngroups = used > 0 ? (R + GROUP - 1) / GROUP : 1;
+    const unsigned fblocks = (unsigned)((ns + BLOCK - 1) / BLOCK);
+    launch_rows(c->kc.variant, 1, [&](auto v, int, int) {
+        for (int g = 0; g < ngroups; ++g) {
+            const int row0 = g * GROUP;
+            const int ntiles = used > 0 ? std::min(LUMPOST_SLABS, (R - row0 + LUMPOST_RT - 1) / LUMPOST_RT) : 0;
+            if (ntiles > 0)
+                hipLaunchKernelGGL(lf_lumpost_part<v()>, dim3((unsigned)(x.n0 + x.nw), (unsigned)ntiles), dim3(BLOCK), 0, c->stream, x, row0, R);
+            hipLaunchKernelGGL(lf_lumpost_fold, dim3(fblocks), dim3(BLOCK), 0, c->stream, x, ntiles, g == 0 ? 1 : 0,
+                               g == ngroups - 1 ? 1 : 0, used);
+        }
+    });
+    LF_HIP(c, hipGetLastError());
+    LF_HIP(c, hipMemcpyAsync(m1, x.m1, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    LF_HIP(c, hipMemcpyAsync(m2, x.m2, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    LF_HIP(c, hipStreamSynchronize(c->stream));
+    return LF_OK;
 }
 
 int lf_set_profiling(lf_ctx* c, int enabled) {

@@ -212,8 +212,10 @@ def check_sigma(sigma, n, K=None, unchecked=False):
     return s
 
 
-def _row_terms(inp, sigma, th, x, lnw):
-    """Delta_i [N] of one theta row (catalogue order); no prior test: what the formulas give."""
+def _row_terms(inp, sigma, th, x, lnw, moments=False):
+    """Delta_i [N] of one theta row (catalogue order); no prior test: what the formulas give.  moments=True: instead the
+    posterior moments of delta over the nodes (csrc/lf_lumpost.h), (e1 [N], e2 [N], e1_abs [N]) = sum_k p_k delta_k, sum_k p_k
+    delta_k^2 and sum_k p_k |delta_k|, their numerators carried by the same running maximum; 0 where sigma = 0."""
     v = inp["variant"]
     p = G._split(inp, th)
     fi = np.asarray(inp["field_ind"])
@@ -238,6 +240,7 @@ def _row_terms(inp, sigma, th, x, lnw):
     s2 = np.sqrt(2.0) * sigma
     m = np.full(N, -np.inf)
     acc = np.zeros(N)
+    num = np.zeros((3, N))             # moments: the weighted numerators of delta, delta^2, |delta|
     for k in range(len(x)):
         dl = s2 * x[k]
         em = np.expm1(LN10 * dl)
@@ -248,8 +251,14 @@ def _row_terms(inp, sigma, th, x, lnw):
         up = d > 0.0
         acc_n = np.where(up, acc * e + 1.0, acc + e)
         m_n = np.where(up, a, m)
+        if moments:
+            for j, q in enumerate((dl, dl * dl, np.abs(dl))):
+                num[j] = np.where(skip, num[j], np.where(up, num[j] * e + q, num[j] + e * q))
         acc = np.where(skip, acc, acc_n)
         m = np.where(skip, m, m_n)
+    if moments:
+        on = sigma > 0.0
+        return tuple(np.where(on, num[j] / acc, 0.0) for j in range(3))
     out = m + np.log(acc)
     return np.where(sigma == 0.0, 0.0, out)
 
@@ -294,6 +303,32 @@ def lnprob_err(inp, sigma, theta, K=None, terms=False, wide=False):
     if single:
         return (out[0], lp[0], sabs[0]) if terms else out[0]
     return (out, lp, sabs) if terms else out
+
+
+def lum_posterior(inp, sigma, theta, K=None, wide=False, terms=False):
+    """The per-source posterior of the true log-luminosity under the convolved model, marginalised over the rows of theta
+    (csrc/lf_lumpost.h): theta (R, ndim) or (ndim,) -> (m1 [N], m2 [N], n_used).  Per source and row
+    the nodes delta_k = sqrt(2) sigma_i x_k of the source's rule (the one delta takes it by: _rules) carry the weights p_k
+    proportional to exp(ln w_k + t_ik - t_i); m1 and m2 are the means over the used rows of sum_k p_k delta_k and sum_k p_k
+    delta_k^2 (dex, dex^2): true = catalogued + m1, spread sqrt(max(m2 - m1^2, 0)).  A row is used when its plain lnprob
+    (grad.py's twin) is finite; n_used = 0: NaN for every source with sigma > 0.  A source with sigma = 0: exactly 0, 0.
+    terms=True: also s1_abs [N], the mean over the used rows of sum_k p_k |delta_k|, the scale of m1's rounding."""
+    K = DEFAULT_ORDER if K is None else int(K)
+    if K not in ORDERS:
+        raise ValueError("deconvolve_order must be one of %s" % (ORDERS,))
+    th = np.atleast_2d(np.asarray(theta, dtype=np.float64))
+    if th.shape[1] != G.ndim_of(inp):
+        raise ValueError("theta must be (R, %d), got %s" % (G.ndim_of(inp), th.shape))
+    sigma = check_sigma(sigma, len(inp["lum"]), K, True)
+    used = th[np.isfinite(np.atleast_1d(G.lnprob_grad(inp, th)[0]))]
+    tot = np.zeros((3, sigma.size))
+    with np.errstate(all="ignore"):
+        for sub, idx, x, lnw in _rules(inp, sigma, K, wide):
+            idx = slice(None) if idx is None else idx
+            for row in used:                                   # (rows in row order, as the device adds them)
+                tot[:, idx] += _row_terms(sub, sigma[idx], row, x, lnw, moments=True)
+        out = np.where(sigma > 0.0, tot / len(used) if len(used) else np.full_like(tot, np.nan), 0.0)
+    return (out[0], out[1], len(used)) + ((out[2],) if terms else ())
 
 
 def _lcomp_grad(y, v, aC, kappa):

@@ -585,6 +585,27 @@ class _Base(object):
     def _band_device(self, device):
         return self._ctx is not None if device is None else bool(device)
 
+    def deconvolved_luminosities(self, ndraws=200, lnprobcut=7.5, device=None):
+        """Every source's posterior of its TRUE log-luminosity under the flux-error-convolved model, marginalised over
+        ndraws random posterior draws (taken as lf_percentiles takes them; at most 4096): DESIGN.md section 3.22.  Returns a
+        dict: lum_true = self.lum + shift, lum_true_e = sqrt(max(m2 - shift^2, 0)) - the spread of the mixture over the draws
+        - shift = m1, the mean of (true - catalogued) in dex, and n_used, the draws whose plain lnprob is finite (0: NaN for
+        every source with lum_e > 0); a source with lum_e = 0 keeps its luminosity with spread 0.  Needs deconvolve=True.
+        device=True: the GPU (lf_lum_posterior), False: NumPy (deconv.lum_posterior); None = the GPU when this object
+        already holds a device context.  self.lum and the tables are not touched."""
+        if not self.deconvolve:
+            raise ValueError("deconvolved_luminosities needs an object made with deconvolve=True")
+        from . import deconv
+        rows = self._posterior_rows(ndraws, lnprobcut)[:, :-1]
+        if self._band_device(device):
+            m1, m2, used = self.context().lum_posterior(rows)
+        else:
+            m1, m2, used = deconv.lum_posterior(self.kernel_inputs(), np.asarray(self.lum_e, dtype=np.float64), rows,
+                                                K=self.deconvolve_order, wide=self.deconvolve_wide)
+        with np.errstate(invalid="ignore"):
+            spread = np.sqrt(np.maximum(m2 - m1 * m1, 0.0))
+        return {"lum_true": np.asarray(self.lum, dtype=np.float64) + m1, "lum_true_e": spread, "shift": m1, "n_used": int(used)}
+
     def _mock_generator(self, device):
         """MockGenerator (GPU) or MockTwin (NumPy) over this object's unsharded kernel_inputs(); device=None = the GPU when
         this object already holds a context.  The device generator is kept for the object's configuration."""
