@@ -109,6 +109,11 @@ def main():
                     help="with --deconvolve: every source's posterior mean and spread of its TRUE luminosity over 200 posterior "
                          "draws (deconvolved_luminosities; DESIGN.md section 3.22) written to FILE: ID, lum, lum_e, lum_true, "
                          "lum_true_e")
+    ap.add_argument("--predictive-noise", choices=("none", "catalogue"), default=None,
+                    help="posterior predictive check of the luminosity histogram over 200 posterior draws (posterior_predictive; "
+                         "DESIGN.md sections 3.11, 3.23), p-values per field printed: `none` bins the replicates' true "
+                         "luminosities (the comparison for a plain fit), `catalogue` their observed ones under the catalogue's own "
+                         "error model (the comparison for --deconvolve)")
     ap.add_argument("--pt", action="store_true",
                     help="parallel-tempered fit and the evidence by thermodynamic integration (fit_model_pt; DESIGN.md section "
                          "3.10) instead of fit_model")
@@ -185,6 +190,15 @@ def main():
         write_integrals(LFmod, os.path.join(args.out, "integrals_%s.dat" % tag))
     if args.deconvolved_lums:
         write_deconvolved_lums(LFmod, args.deconvolved_lums)
+    if args.predictive_noise:
+        pp = LFmod.posterior_predictive(seed=11, noise=None if args.predictive_noise == "none" else "catalogue")
+        bright = pp["edges"].size // 2
+        print("posterior predictive check (noise: %s), per field: observed total, median replicated total, P(rep >= obs), and the "
+              "same for the brighter half of the bins" % pp["noise"])
+        for f in range(pp["nf"]):
+            ob, rb = pp["observed"][f, bright:].sum(), pp["replicated"][:, f, bright:].sum(axis=1)
+            print("  field %d: %6d %8.1f %.3f   bright: %6d %8.1f %.3f" % (f, pp["observed_total"][f], np.median(pp["replicated_total"][:, f]),
+                                                                         pp["p_upper_total"][f], ob, np.median(rb), np.mean(rb >= ob)))
     if args.veff_band:
         write_veff_band(LFmod, os.path.join(args.out, "veffband_%s.dat" % tag))
     print("wrote", sorted(os.listdir(args.out)))

@@ -572,6 +572,26 @@ int lf_mock_draw(lf_mock *m, const double *theta, int32_t R, const int64_t *row_
  * edges [nbins + 1], hist [R][nf][nbins + 2] */
 int lf_mock_hist(lf_mock *m, const double *theta, int32_t R, const int64_t *row_ids, uint64_t seed, int32_t nbins,
                  const double *edges, int64_t *hist);
+/* The observation step of the mocks (csrc/lf_mock_noise.h): the catalogue records
+ * L_obs = L_true + sigma n, n ~ N(0, 1), after detection (the generative model of section 3.18), with sigma in dex a function
+ * of the field and of the source's true log10 flux (cgs): M nodes logf_nodes [M], strictly ascending and shared by the
+ * fields, sigma [nf][M] >= 0, linear between the nodes and constant outside them (M = 1: one value per field).  The flux of a
+ * source at (z, L) is log10 f = L - ld2(z), ld2 the linear interpolant over zarr of log10(4 pi (3.086e24 dl_zarr[k])^2);
+ * dl_zarr [S] is read by every variant here (lf_mock_create keeps it for FREE only).  n is Box-Muller on the Philox block
+ * (row_id, index, purpose 3, field): a block of its own, the true draws keep their bits, and sigma = 0 leaves L_obs ==
+ * L_true bit for bit.  M = 0 clears the model (the pointers are not read).  LF_ERR_ARG, with lf_mock_last_error saying why,
+ * for: a NULL pointer, M outside 0..64, nodes that are not finite or not strictly ascending, a sigma that is negative or
+ * not finite (the message names the field and the node), a dl_zarr entry that is not finite or not > 0.  An error leaves
+ * the model that was set in place and the handle usable. */
+int lf_mock_set_error_model(lf_mock *m, int32_t M, const double *logf_nodes, const double *sigma, const double *dl_zarr);
+/* lf_mock_draw with the observation step: z, logL_true (what lf_mock_draw writes as logL, bit for bit), logL_obs, sigma,
+ * field of length sum(count).  Arguments, limits and refusals of lf_mock_draw; LF_ERR_ARG when no error model is set. */
+int lf_mock_draw_err(lf_mock *m, const double *theta, int32_t R, const int64_t *row_ids, uint64_t seed, const int64_t *count,
+                     double *z, double *logL_true, double *logL_obs, double *sigma, int32_t *field);
+/* lf_mock_hist of logL_obs.  Arguments, limits and refusals of lf_mock_hist; LF_ERR_ARG when no error model is set.  With
+ * an all-zero sigma the histogram is lf_mock_hist's. */
+int lf_mock_hist_err(lf_mock *m, const double *theta, int32_t R, const int64_t *row_ids, uint64_t seed, int32_t nbins,
+                     const double *edges, int64_t *hist);
 /* Last error of this handle; m == NULL: of the last failed lf_mock_create.  Never NULL. */
 const char *lf_mock_last_error(const lf_mock *m);
 

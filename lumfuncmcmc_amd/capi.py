@@ -55,7 +55,8 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_lnprob_grad_batch_device", "lf_lumfunc_integral_quantiles", "lf_lumfunc_integral_quantiles_ms", "lf_veff_draws", "lf_veff_draws_ms",
            "lf_veff_draws_chunk", "lf_set_lum_err", "lf_lnprob_err_batch", "lf_lnprob_err_batch_device", "lf_gauss_hermite",
            "lf_deconv_info", "lf_deconv_wide_info", "lf_lnprob_err_grad_batch", "lf_lnprob_err_grad_batch_device", "lf_sampler_set_likelihood",
-           "lf_ptsampler_set_likelihood", "lf_lum_posterior", "lf_lum_posterior_info")
+           "lf_ptsampler_set_likelihood", "lf_lum_posterior", "lf_lum_posterior_info",
+           "lf_mock_set_error_model", "lf_mock_draw_err", "lf_mock_hist_err")
 
 _lib = None
 
@@ -216,6 +217,13 @@ def load():
     lib.lf_mock_hist.restype = ctypes.c_int
     lib.lf_mock_hist.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int32, _c_int64_p, ctypes.c_uint64, ctypes.c_int32, _c_double_p,
                                  _c_int64_p]
+    lib.lf_mock_set_error_model.restype = ctypes.c_int
+    lib.lf_mock_set_error_model.argtypes = [ctypes.c_void_p, ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p]
+    lib.lf_mock_draw_err.restype = ctypes.c_int
+    lib.lf_mock_draw_err.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int32, _c_int64_p, ctypes.c_uint64, _c_int64_p, _c_double_p,
+                                     _c_double_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int32)]
+    lib.lf_mock_hist_err.restype = ctypes.c_int
+    lib.lf_mock_hist_err.argtypes = lib.lf_mock_hist.argtypes
     lib.lf_mock_last_error.restype = ctypes.c_char_p
     lib.lf_mock_last_error.argtypes = [ctypes.c_void_p]
     lib.lf_compress_keys.restype = ctypes.c_int64

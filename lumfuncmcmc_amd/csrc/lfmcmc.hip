@@ -33,6 +33,7 @@
 #include "lf_kernels.h"
 #include "lf_free.h"
 #include "lf_mock.h"
+#include "lf_mock_noise.h"
 #include "lf_pers.h"
 #include "lf_pt.h"
 #include "lf_veffdraws.h"
@@ -2750,6 +2751,9 @@ struct lf_mock {
     Buf<double> d_z, d_L, d_edges;        // d_z, d_L, d_fld: the sources of the largest chunk drawn so far
     Buf<int> d_fld;
     Buf<unsigned long long> d_hist;
+    lf::MockNoise mn{};                   // the error model (section 3.23); mn.M == 0: none set
+    Buf<double> d_nodes, d_sigma, d_ld2n; // its tables
+    Buf<double> d_Lobs, d_sg;             // as d_z: the observed luminosities and sigmas of the largest chunk drawn so far
     std::string err;
 };
 
@@ -2977,6 +2981,130 @@ int lf_mock_hist(lf_mock* m, const double* theta, int32_t R, const int64_t* row_
             LF_HIP(m, hipMemcpy(m->d_off, blk.data(), blk.size() * sizeof(long long), hipMemcpyHostToDevice));
             hipLaunchKernelGGL(lf::lf_mock_hist, dim3((unsigned)blk[(size_t)nrf]), dim3(lf::MOCK_THREADS), 0, 0, m->mc, nrf, m->d_off,
                                m->d_count, m->d_rid, (unsigned long long)seed, m->d_cdfL, m->d_cdfZ, nbins, m->d_edges, m->d_hist);
+            LF_HIP(m, hipGetLastError());
+        }
+        LF_HIP(m, hipMemcpy(hist + (size_t)r0 * nf * ns, m->d_hist, (size_t)nrf * ns * sizeof(int64_t), hipMemcpyDeviceToHost));
+    }
+    return LF_OK;
+}
+
+// The error model of the observation step (csrc/lf_mock_noise.h).
+int lf_mock_set_error_model(lf_mock* m, int32_t M, const double* logf_nodes, const double* sigma, const double* dl_zarr) {
+    static const char* fn = "lf_mock_set_error_model";
+    if (!m) return LF_ERR_ARG;
+    m->err.clear();
+    if (M == 0) {
+        m->mn.M = 0;
+        return LF_OK;
+    }
+    if (M < 0 || M > lf::MOCK_MAX_NODES) return mock_fail(m, fn, "M must be in 0.." + std::to_string(lf::MOCK_MAX_NODES));
+    if (!logf_nodes || !sigma || !dl_zarr) return mock_fail(m, fn, "logf_nodes, sigma or dl_zarr is NULL");
+    const int nf = m->mc.nf, S = m->mc.S;
+    for (int i = 0; i < M; ++i)
+        if (!std::isfinite(logf_nodes[i]) || (i > 0 && !(logf_nodes[i] > logf_nodes[i - 1])))
+            return mock_fail(m, fn, "node " + std::to_string(i) + ": logf_nodes must be finite and strictly ascending");
+    for (int f = 0; f < nf; ++f)
+        for (int i = 0; i < M; ++i)
+            if (!std::isfinite(sigma[(size_t)f * M + i]) || sigma[(size_t)f * M + i] < 0.0)
+                return mock_fail(m, fn, "field " + std::to_string(f) + " node " + std::to_string(i) + ": sigma must be finite and >= 0");
+    std::vector<double> ld2n((size_t)S);
+    for (int k = 0; k < S; ++k) {
+        if (!std::isfinite(dl_zarr[k]) || !(dl_zarr[k] > 0.0))
+            return mock_fail(m, fn, "dl_zarr[" + std::to_string(k) + "] must be finite and > 0");
+        const double dl = 3.086e24 * dl_zarr[k];
+        ld2n[(size_t)k] = std::log10(4.0 * 3.141592653589793 * (dl * dl));
+    }
+    LF_HIP(m, hipSetDevice(m->device));
+    m->mn.M = 0;                          // (a failed upload leaves no model)
+    LF_HIP(m, m->d_nodes.upload(logf_nodes, (size_t)M));
+    LF_HIP(m, m->d_sigma.upload(sigma, (size_t)nf * M));
+    LF_HIP(m, m->d_ld2n.upload(ld2n.data(), (size_t)S));
+    m->mn.nodes = m->d_nodes;
+    m->mn.sigma = m->d_sigma;
+    m->mn.ld2n = m->d_ld2n;
+    m->mn.M = M;
+    return LF_OK;
+}
+
+int lf_mock_draw_err(lf_mock* m, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed, const int64_t* count, double* z,
+                     double* logL_true, double* logL_obs, double* sigma, int32_t* field) {
+    static const char* fn = "lf_mock_draw_err";
+    if (!m) return LF_ERR_ARG;
+    int rc = mock_check(m, fn, theta, R);
+    if (rc != LF_OK) return rc;
+    if (m->mn.M == 0) return mock_fail(m, fn, "no error model is set (lf_mock_set_error_model)");
+    if (!count) return mock_fail(m, fn, "count is NULL");
+    const int nf = m->mc.nf;
+    int64_t total = 0;
+    for (int64_t i = 0; i < (int64_t)R * nf; ++i) {
+        if (count[i] < 0 || count[i] > (int64_t)UINT32_MAX)
+            return mock_fail(m, fn, "row " + std::to_string(i / nf) + " field " + std::to_string(i % nf) + ": count out of range");
+        total += count[i];
+    }
+    if (total > 0 && (!z || !logL_true || !logL_obs || !sigma || !field))
+        return mock_fail(m, fn, "z, logL_true, logL_obs, sigma or field is NULL");
+    LF_HIP(m, hipSetDevice(m->device));
+    std::vector<double> mu;
+    std::vector<long long> n, off;
+    int64_t done = 0;
+    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
+        const int rows = std::min<int32_t>(m->rch, R - r0);
+        const int nrf = rows * nf;
+        off.assign((size_t)nrf + 1, 0);
+        for (int i = 0; i < nrf; ++i) off[(size_t)i + 1] = off[(size_t)i] + count[(size_t)r0 * nf + i];
+        const int64_t tot = off[(size_t)nrf];
+        if (tot == 0) continue;
+        if ((rc = mock_masses(m, fn, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
+        if ((size_t)tot > m->d_z.size() && (rc = grow(m, m->d_z, (size_t)tot, false)) != LF_OK) return rc;
+        if ((size_t)tot > m->d_L.size() && (rc = grow(m, m->d_L, (size_t)tot, false)) != LF_OK) return rc;
+        if ((size_t)tot > m->d_Lobs.size() && (rc = grow(m, m->d_Lobs, (size_t)tot, false)) != LF_OK) return rc;
+        if ((size_t)tot > m->d_sg.size() && (rc = grow(m, m->d_sg, (size_t)tot, false)) != LF_OK) return rc;
+        if ((size_t)tot > m->d_fld.size() && (rc = grow(m, m->d_fld, (size_t)tot, false)) != LF_OK) return rc;
+        LF_HIP(m, hipMemcpy(m->d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(lf::lf_mock_draw_err, dim3((unsigned)((tot + lf::MOCK_THREADS - 1) / lf::MOCK_THREADS)), dim3(lf::MOCK_THREADS), 0,
+                           0, m->mc, m->mn, nrf, m->d_off, m->d_rid, (unsigned long long)seed, m->d_cdfL, m->d_cdfZ, m->d_z, m->d_L, m->d_Lobs,
+                           m->d_sg, m->d_fld);
+        LF_HIP(m, hipGetLastError());
+        LF_HIP(m, hipMemcpy(z + done, m->d_z, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
+        LF_HIP(m, hipMemcpy(logL_true + done, m->d_L, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
+        LF_HIP(m, hipMemcpy(logL_obs + done, m->d_Lobs, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
+        LF_HIP(m, hipMemcpy(sigma + done, m->d_sg, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
+        LF_HIP(m, hipMemcpy(field + done, m->d_fld, (size_t)tot * sizeof(int), hipMemcpyDeviceToHost));
+        done += tot;
+    }
+    return LF_OK;
+}
+
+int lf_mock_hist_err(lf_mock* m, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed, int32_t nbins,
+                     const double* edges, int64_t* hist) {
+    static const char* fn = "lf_mock_hist_err";
+    if (!m) return LF_ERR_ARG;
+    int rc = mock_check(m, fn, theta, R);
+    if (rc != LF_OK) return rc;
+    if (m->mn.M == 0) return mock_fail(m, fn, "no error model is set (lf_mock_set_error_model)");
+    if (nbins < 1 || nbins > lf::MOCK_MAX_BINS)
+        return mock_fail(m, fn, "nbins must be in 1.." + std::to_string(lf::MOCK_MAX_BINS));
+    if (!edges || !hist) return mock_fail(m, fn, "edges or hist is NULL");
+    for (int i = 0; i <= nbins; ++i)
+        if (!std::isfinite(edges[i]) || (i > 0 && !(edges[i] >= edges[i - 1])))
+            return mock_fail(m, fn, "edges must be finite and non-decreasing");
+    LF_HIP(m, hipSetDevice(m->device));
+    LF_HIP(m, hipMemcpy(m->d_edges, edges, (size_t)(nbins + 1) * sizeof(double), hipMemcpyHostToDevice));
+    const int nf = m->mc.nf, ns = nbins + 2;
+    std::vector<double> mu;
+    std::vector<long long> n, blk;
+    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
+        const int rows = std::min<int32_t>(m->rch, R - r0);
+        const int nrf = rows * nf;
+        if ((rc = mock_masses(m, fn, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
+        if ((size_t)nrf * ns > m->d_hist.size() && (rc = grow(m, m->d_hist, (size_t)nrf * ns, false)) != LF_OK) return rc;
+        blk.assign((size_t)nrf + 1, 0);
+        for (int i = 0; i < nrf; ++i) blk[(size_t)i + 1] = blk[(size_t)i] + (n[(size_t)i] + lf::MOCK_HIST_CHUNK - 1) / lf::MOCK_HIST_CHUNK;
+        LF_HIP(m, hipMemset(m->d_hist, 0, (size_t)nrf * ns * sizeof(unsigned long long)));
+        if (blk[(size_t)nrf] > 0) {
+            LF_HIP(m, hipMemcpy(m->d_off, blk.data(), blk.size() * sizeof(long long), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(lf::lf_mock_hist_err, dim3((unsigned)blk[(size_t)nrf]), dim3(lf::MOCK_THREADS), 0, 0, m->mc, m->mn, nrf,
+                               m->d_off, m->d_count, m->d_rid, (unsigned long long)seed, m->d_cdfL, m->d_cdfZ, nbins, m->d_edges, m->d_hist);
             LF_HIP(m, hipGetLastError());
         }
         LF_HIP(m, hipMemcpy(hist + (size_t)r0 * nf * ns, m->d_hist, (size_t)nrf * ns * sizeof(int64_t), hipMemcpyDeviceToHost));

@@ -227,6 +227,8 @@ class MockTwin(object):
             self.ip = _integ_part(inp, self.nf, S)
         self.wz = trapz_weights(self.zarr)
         self.wL = trapz_weights(self.logL, axis=0)
+        self.dl_zarr = inp.get("DL_zarr")     # every variant's kernel_inputs() has it; only the error model needs it
+        self.noise = None
 
     # ---------------------------------------------------------------- the density
     def lam(self, theta):
@@ -334,6 +336,144 @@ class MockTwin(object):
         R = np.atleast_2d(thetas).shape[0]
         return bin_sources(L, off, edges).reshape(R, self.nf, edges.size + 1)
 
+    # ---------------------------------------------------------------- the observation step (lf_mock_noise.h)
+    def set_error_model(self, nodes, sigma):
+        """sigma(field, log10 flux) of L_obs = L_true + sigma n: `nodes` (M,) log10 flux, `sigma` (nf, M); None clears it."""
+        if nodes is None:
+            self.noise = None
+            return
+        nodes, sigma = check_error_model(nodes, sigma, self.nf)
+        if self.dl_zarr is None:
+            raise MockError("the inputs hold no DL_zarr: the error model needs it for the sources' fluxes")
+        dl = np.asarray(self.dl_zarr, dtype=np.float64)
+        if dl.shape != (self.S,) or not np.isfinite(dl).all() or (dl <= 0.0).any():
+            raise MockError("DL_zarr must hold S finite values > 0")
+        self.noise = (nodes, sigma, ld2_nodes(dl))
+
+    def _observe(self, z, L, fld, off, rid, seed):
+        if self.noise is None:
+            raise MockError("no error model is set (set_error_model)")
+        nodes, sigma, ld2n = self.noise
+        sg = np.empty(L.size)
+        for f in range(self.nf):
+            sel = fld == f
+            sg[sel] = sigma_lookup(nodes, sigma[f], log_flux(self.zarr, ld2n, z[sel], L[sel]))
+        n = np.diff(off).reshape(-1, self.nf)
+        dev = np.concatenate([lum_noise(n[r], rid[r], seed) for r in range(n.shape[0])]) if L.size else np.zeros(0)
+        return L + sg * dev, sg
+
+    def draw_noisy(self, thetas, seed, row_ids=None, count=None):
+        """(z, L_true, L_obs, sigma, field, offsets): draw()'s sources and what the catalogue records of them."""
+        th = _rows(thetas, self.ndim)
+        rid = _row_ids(row_ids, th.shape[0])
+        z, L, fld, off = self.draw(th, seed, rid, count)
+        Lobs, sg = self._observe(z, L, fld, off, rid, seed)
+        return z, L, Lobs, sg, fld, off
+
+    def hist_noisy(self, thetas, edges, seed, row_ids=None):
+        """hist() of the observed luminosities."""
+        edges = _edges(edges)
+        z, L, Lobs, sg, fld, off = self.draw_noisy(thetas, seed, row_ids)
+        R = np.atleast_2d(thetas).shape[0]
+        return bin_sources(Lobs, off, edges).reshape(R, self.nf, edges.size + 1)
+
+
+MAX_NODES = 64                # lf_mock_noise.h: MOCK_MAX_NODES
+
+
+def check_error_model(nodes, sigma, nf):
+    """(nodes (M,), sigma (nf, M)) as float64, or MockError naming what lf_mock_set_error_model refuses."""
+    x = np.ascontiguousarray(np.asarray(nodes, dtype=np.float64).ravel())
+    M = x.size
+    if M < 1 or M > MAX_NODES:
+        raise MockError("M must be in 1..%d, got %d nodes" % (MAX_NODES, M))
+    s = np.asarray(sigma, dtype=np.float64)
+    if s.ndim == 1 and M == 1:
+        s = s[:, None]
+    if s.shape != (nf, M):
+        raise MockError("sigma must be (nf, M) = (%d, %d), got %s" % (nf, M, s.shape))
+    bad = ~np.isfinite(x)
+    bad[1:] |= ~(np.diff(x) > 0)
+    if bad.any():
+        raise MockError("node %d: logf_nodes must be finite and strictly ascending" % int(np.flatnonzero(bad)[0]))
+    bad = ~np.isfinite(s) | (s < 0.0)
+    if bad.any():
+        f, i = np.argwhere(bad)[0]
+        raise MockError("field %d node %d: sigma must be finite and >= 0" % (f, i))
+    return x, np.ascontiguousarray(s)
+
+
+def ld2_nodes(dl_zarr):
+    """log10(4 pi (Mpc DL_zarr)^2) at the redshift nodes (lf_mock_set_error_model's host arithmetic)."""
+    dl = hs.MPC_CM * np.asarray(dl_zarr, dtype=np.float64)
+    return np.log10(4.0 * 3.141592653589793 * (dl * dl))
+
+
+def log_flux(zarr, ld2n, z, L):
+    """log10 flux (cgs) of sources (z, L): L - ld2(z), ld2 linear between the nodes (lf_mock_noise.h: mock_logflux)."""
+    i = np.clip(np.searchsorted(zarr, z, side="right") - 1, 0, zarr.size - 2)
+    ld2 = ld2n[i] + (z - zarr[i]) * ((ld2n[i + 1] - ld2n[i]) / (zarr[i + 1] - zarr[i]))
+    return L - ld2
+
+
+def sigma_lookup(nodes, sig, t):
+    """One field's sigma at log10 flux t: linear between the nodes, constant outside (lf_mock_noise.h: mock_sigma)."""
+    t = np.asarray(t, dtype=np.float64)
+    M = nodes.size
+    if M == 1:
+        return np.full(t.shape, sig[0])
+    i = np.clip(np.searchsorted(nodes, t, side="right") - 1, 0, M - 2)
+    mid = sig[i] + (t - nodes[i]) * ((sig[i + 1] - sig[i]) / (nodes[i + 1] - nodes[i]))
+    return np.where(~(t > nodes[0]), sig[0], np.where(t >= nodes[-1], sig[-1], mid))
+
+
+def error_model_from_catalogue(logf, sigma, field_ind, nodes=16):
+    """The error model a catalogue shows: (nodes (M,), sigma (nf, M)) for set_error_model.  The pooled log10 fluxes are cut
+    into `nodes` equal-count bins (in sorted order, ties by position: deterministic); a node is the pooled median log flux
+    of its bin, its value for field f the median sigma of f's sources in the bin.  A bin empty for a field takes the value
+    of that field's nearest filled bin (the lower one at equal distance), a field without sources the pooled medians;
+    nodes that coincide are merged (their sources pooled)."""
+    logf = np.asarray(logf, dtype=np.float64).ravel()
+    sigma = np.asarray(sigma, dtype=np.float64).ravel()
+    fi = np.asarray(field_ind, dtype=np.int64).ravel()
+    nf, N = fi.size - 1, logf.size
+    if sigma.size != N or fi[-1] != N or fi[0] != 0 or (np.diff(fi) < 0).any():
+        raise ValueError("logf, sigma and field_ind do not describe one catalogue")
+    if N < 1:
+        raise ValueError("the catalogue is empty")
+    if not (np.isfinite(logf).all() and np.isfinite(sigma).all() and (sigma >= 0).all()):
+        raise ValueError("logf must be finite and sigma finite and >= 0")
+    nb = int(min(max(int(nodes), 1), MAX_NODES, N))
+    fld = np.repeat(np.arange(nf), np.diff(fi))
+    order = np.argsort(logf, kind="stable")
+    cut = (np.arange(nb + 1) * N) // nb
+    x = np.array([np.median(logf[order[cut[b]:cut[b + 1]]]) for b in range(nb)])
+    # merge bins whose nodes coincide
+    groups = [[0]]
+    for b in range(1, nb):
+        if x[b] > x[groups[-1][0]]:
+            groups.append([b])
+        else:
+            groups[-1].append(b)
+    M = len(groups)
+    xs, pooled, val = np.empty(M), np.empty(M), np.full((nf, M), np.nan)
+    for g, bins in enumerate(groups):
+        idx = order[cut[bins[0]]:cut[bins[-1] + 1]]
+        xs[g] = np.median(logf[idx])
+        pooled[g] = np.median(sigma[idx])
+        for f in range(nf):
+            own = idx[fld[idx] == f]
+            if own.size:
+                val[f, g] = np.median(sigma[own])
+    for f in range(nf):
+        have = np.flatnonzero(~np.isnan(val[f]))
+        if have.size == 0:
+            val[f] = pooled
+            continue
+        for g in np.flatnonzero(np.isnan(val[f])):
+            val[f, g] = val[f, have[np.argmin(np.abs(have - g))]]       # (argmin: the first, i.e. lower, at a tie)
+    return xs, val
+
 
 def _edges(edges):
     e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).ravel())
@@ -402,6 +542,7 @@ class MockGenerator(object):
             raise capi.LFError(lib.lf_mock_last_error(None).decode())
         self._h = ctypes.c_void_p(h)
         self.device = int(device)
+        self._dl_zarr = inp.get("DL_zarr")    # every variant's kernel_inputs() has it; only the error model needs it
 
     def _check(self, rc):
         from . import capi
@@ -452,6 +593,53 @@ class MockGenerator(object):
         out = np.empty((R, self.nf, nb + 2), dtype=np.int64)
         self._check(self._lib.lf_mock_hist(self._h, capi._ptr(th), R, rid.ctypes.data_as(capi._c_int64_p), ctypes.c_uint64(int(seed)), nb,
                                            capi._ptr(e), out.ctypes.data_as(capi._c_int64_p)))
+        return out
+
+    # ---------------------------------------------------------------- the observation step (lf_mock_noise.h)
+    def set_error_model(self, nodes, sigma):
+        """As MockTwin.set_error_model, uploaded through lf_mock_set_error_model (which validates again)."""
+        from . import capi
+        if nodes is None:
+            self._check(self._lib.lf_mock_set_error_model(self._h, 0, None, None, None))
+            return
+        x, s = check_error_model(nodes, sigma, self.nf)
+        if self._dl_zarr is None:
+            raise MockError("the inputs hold no DL_zarr: the error model needs it for the sources' fluxes")
+        dl = capi._f64(self._dl_zarr)
+        if dl.shape != (self.S,):
+            raise MockError("DL_zarr must hold S finite values > 0")
+        self._check(self._lib.lf_mock_set_error_model(self._h, x.size, capi._ptr(x), capi._ptr(s), capi._ptr(dl)))
+
+    def draw_noisy(self, thetas, seed, row_ids=None, count=None):
+        """(z, L_true, L_obs, sigma, field, offsets): draw()'s sources and what the catalogue records of them, the noise
+        added on the device (lf_mock_draw_err)."""
+        from . import capi
+        th = _rows(thetas, self.ndim)
+        R = th.shape[0]
+        rid = _row_ids(row_ids, R)
+        if count is None:
+            count = self.counts(th, seed, rid)[1]
+        cnt = np.ascontiguousarray(np.asarray(count, dtype=np.int64).reshape(R, self.nf))
+        total = int(cnt.sum())
+        z, L, Lobs, sg = np.empty(total), np.empty(total), np.empty(total), np.empty(total)
+        fld = np.empty(total, dtype=np.int32)
+        self._check(self._lib.lf_mock_draw_err(self._h, capi._ptr(th), R, rid.ctypes.data_as(capi._c_int64_p), ctypes.c_uint64(int(seed)),
+                                               cnt.ctypes.data_as(capi._c_int64_p), capi._ptr(z), capi._ptr(L), capi._ptr(Lobs),
+                                               capi._ptr(sg), fld.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        off = np.concatenate([[0], np.cumsum(cnt.ravel())]).astype(np.int64)
+        return z, L, Lobs, sg, fld, off
+
+    def hist_noisy(self, thetas, edges, seed, row_ids=None):
+        """hist() of the observed luminosities (lf_mock_hist_err)."""
+        from . import capi
+        th = _rows(thetas, self.ndim)
+        R = th.shape[0]
+        rid = _row_ids(row_ids, R)
+        e = _edges(edges)
+        nb = e.size - 1
+        out = np.empty((R, self.nf, nb + 2), dtype=np.int64)
+        self._check(self._lib.lf_mock_hist_err(self._h, capi._ptr(th), R, rid.ctypes.data_as(capi._c_int64_p), ctypes.c_uint64(int(seed)),
+                                               nb, capi._ptr(e), out.ctypes.data_as(capi._c_int64_p)))
         return out
 
     def close(self):
@@ -507,13 +695,22 @@ def catalogue_lists(z, logL, field, nf, lum_err=None, seed=0, row_id=0):
     return {"z": split(z), "lum": split(noisy), "lum_e": split(per), "field_ind": fi, "lum_true": split(logL)}
 
 
-def predictive(gen, rows, edges, observed_lum, observed_fi, seed):
+def observed_lists(z, logL_true, logL_obs, sigma, field, nf):
+    """catalogue_lists for one row of draw_noisy: lum the observed luminosities, lum_e the per-source sigma, lum_true the
+    noiseless values."""
+    fi = np.concatenate([[0], np.cumsum(np.bincount(field, minlength=nf))]).astype(np.int64)     # (a row is in field order)
+    split = lambda a: [a[fi[f]:fi[f + 1]].copy() for f in range(nf)]    # noqa: E731
+    return {"z": split(z), "lum": split(logL_obs), "lum_e": split(sigma), "field_ind": fi, "lum_true": split(logL_true)}
+
+
+def predictive(gen, rows, edges, observed_lum, observed_fi, seed, noisy=False):
     """Posterior predictive check of the logL histogram per field: `rows` (R, ndim) posterior draws, `edges` (B + 1),
-    the observed catalogue's lum and field_ind.  Returns the dict of _Base.posterior_predictive."""
+    the observed catalogue's lum and field_ind.  noisy: the replicates are binned by their observed luminosities under
+    the generator's error model (hist_noisy).  Returns the dict of _Base.posterior_predictive."""
     edges = _edges(edges)
     nf = len(observed_fi) - 1
     obs = bin_sources(np.asarray(observed_lum, dtype=np.float64), np.asarray(observed_fi, dtype=np.int64), edges)
-    rep = gen.hist(rows, edges, seed)
+    rep = gen.hist_noisy(rows, edges, seed) if noisy else gen.hist(rows, edges, seed)
     expected = gen.counts(rows, seed)[0]
     obs_tot, rep_tot = obs.sum(axis=1), rep.sum(axis=2)
     return {"edges": edges, "observed": obs, "replicated": rep, "expected": expected,

@@ -617,6 +617,22 @@ class _Base(object):
             self._mock_key = key
         return self._mock
 
+    def error_model(self, nodes=16):
+        """The error model this catalogue shows: (log10 flux nodes (M,), sigma (nf, M)) from
+        mock.error_model_from_catalogue on log10(self.flux), self.lum_e and self.field_ind."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            logf = np.log10(np.asarray(self.flux, dtype=np.float64))
+        return mock.error_model_from_catalogue(logf, self.lum_e, self.field_ind, nodes=nodes)
+
+    def _noise_model(self, spec):
+        """(nodes, sigma) of "catalogue" (self.error_model()) or of a (nodes, sigma) pair."""
+        if isinstance(spec, str):
+            if spec != "catalogue":
+                raise ValueError("the error model must be \"catalogue\" or a (nodes, sigma) pair, got %r" % (spec,))
+            return self.error_model()
+        nodes, sigma = spec
+        return mock.check_error_model(nodes, sigma, self.nfields)
+
     def mock_catalogue(self, theta, seed=None, device=None, lum_err=None):
         """One catalogue drawn from the model at `theta`: the Poisson process whose likelihood
         lnprob evaluates, on this object's integration grid.  Returns the per-field lists both constructors take - z, lum,
@@ -625,31 +641,56 @@ class _Base(object):
         several ranks call it on one).  lum_err (dex; a scalar or one value per field): Gaussian measurement noise of that
         width is added to the drawn luminosities after detection - the model deconvolve=True fits -
         from a Philox stream of its own, on the host for both generators; lum_e is then filled and lum_true holds the
-        noiseless values.  None: the output is what it was without the keyword, bit for bit."""
+        noiseless values.  None: the output is what it was without the keyword, bit for bit.  lum_err="catalogue" (this
+        catalogue's self.error_model()) or a (nodes, sigma) pair: the width is a function of the field and of the source's
+        true log10 flux (section 3.23), lum_e holds every source's own sigma, and on the device path the noise is added on
+        the GPU (the same stream and expression: the NumPy path agrees to the rounding of the device's cos and log1p)."""
         if seed is None:
             seed = int(np.random.randint(0, 2 ** 31 - 1))
         theta = np.asarray(theta, dtype=np.float64).ravel()
         gen = self._mock_generator(device)
-        z, lum, fld, _ = gen.draw(theta[None], seed)
-        out = mock.catalogue_lists(z, lum, fld, self.nfields, lum_err=lum_err, seed=seed)
+        # (a pair's sigma is two-dimensional, (nf, M): a sequence of two numbers stays one value per field)
+        if isinstance(lum_err, str) or (isinstance(lum_err, (tuple, list)) and len(lum_err) == 2 and np.ndim(lum_err[1]) == 2):
+            gen.set_error_model(*self._noise_model(lum_err))
+            z, lum, lobs, sg, fld, _ = gen.draw_noisy(theta[None], seed)
+            out = mock.observed_lists(z, lum, lobs, sg, fld, self.nfields)
+        else:
+            z, lum, fld, _ = gen.draw(theta[None], seed)
+            out = mock.catalogue_lists(z, lum, fld, self.nfields, lum_err=lum_err, seed=seed)
         out["theta"], out["seed"] = theta.copy(), int(seed)
         return out
 
-    def posterior_predictive(self, edges=None, ndraws=200, lnprobcut=7.5, seed=None, device=None):
+    def posterior_predictive(self, edges=None, ndraws=200, lnprobcut=7.5, seed=None, device=None, noise=None):
         """Posterior predictive check of the observed luminosities per field: ndraws posterior rows (drawn as
         set_median_fit draws them), one mock catalogue each, binned in logL with `edges` (default: 20 equal bins over
         [min(lum), max(lum)]) by searchsorted(edges, x, side="right") - slot 0 below edges[0], slot B + 1 at or above
         edges[B].  Returns a dict: edges, observed [nf, B + 2], replicated [R, nf, B + 2], expected [R, nf] (the mocks'
         expected counts), percentiles (16, 50, 84) of replicated, p_upper = mean(rep >= obs) and p_lower = mean(rep <= obs)
         per bin, and the same for the per-field totals (observed_total, replicated_total, p_upper_total, p_lower_total).
-        seed and device as mock_catalogue."""
+        seed and device as mock_catalogue.
+
+        noise: which luminosities of the replicates are binned.  None: the noiseless ones - the
+        result without the keyword, bit for bit.  That is the right comparison for a plain fit (deconvolve=False), whose
+        likelihood takes the catalogued luminosities for the true ones.  "catalogue" (self.error_model()) or a
+        (nodes, sigma) pair: the replicates' observed luminosities, L_true + sigma n.  A deconvolve=True (or
+        deconvolve_wide=True) posterior describes the true luminosities; the catalogue holds the observed ones, so its
+        replicates are to be compared with the catalogue under noise="catalogue" - without it the check reports a
+        bright-end excess that is only the Eddington bias the fit removed.  The dict also holds `noise` (None, "catalogue"
+        or "model") and `sigma_model` (None or the (nodes, sigma) used)."""
         rows = self._posterior_rows(ndraws, lnprobcut)[:, :-1]
         if edges is None:
             edges = np.linspace(np.min(self.lum), np.max(self.lum), 21)
         if seed is None:
             seed = int(np.random.randint(0, 2 ** 31 - 1))
         gen = self._mock_generator(device)
-        return mock.predictive(gen, rows, edges, self.lum, np.asarray(self.field_ind, dtype=np.int64), seed)
+        model = None
+        if noise is not None:
+            model = self._noise_model(noise)
+            gen.set_error_model(*model)
+        out = mock.predictive(gen, rows, edges, self.lum, np.asarray(self.field_ind, dtype=np.int64), seed, noisy=noise is not None)
+        out["noise"] = None if noise is None else ("catalogue" if isinstance(noise, str) else "model")
+        out["sigma_model"] = model
+        return out
 
     def add_fitinfo_to_table(self, percentiles, start_value=1, lnprobcut=7.5):
         """Percentiles of each parameter into the last row of self.table (lumfuncmcmc.py:653-667)."""
