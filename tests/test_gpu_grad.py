@@ -33,6 +33,24 @@ def rows37(inp, seed):
     return th
 
 
+def compare(lp_d, g_d, lp_b, g_t, s_t, label):
+    """the device's (lnprob, gradient) of one call against lnprob_batch's value of the same rows (lp_b) and the twin's gradient
+    and scale (g_t, s_t); returns the largest |dev - twin| / S_abs"""
+    assert np.array_equal(lp_d, lp_b), "%s: lnprob of the gradient call differs from lnprob_batch" % label
+    fin = np.isfinite(lp_b)
+    assert np.array_equal(np.isnan(g_d), np.isnan(g_t)), "%s: NaN pattern" % label
+    assert np.array_equal(np.isnan(g_d).all(axis=1), ~fin) and not np.isnan(g_d[fin]).any(), "%s: NaN rows" % label
+    assert np.all(np.isfinite(g_d[fin])), "%s: a finite row with a non-finite gradient" % label
+    err, scale = np.abs(g_d[fin] - g_t[fin]), s_t[fin]
+    # (an element nothing contributes to - the Flim of a field without sources on a lattice of zero width - is exactly 0)
+    assert np.all(err[scale == 0.0] == 0.0), "%s: an element without contributions is not 0" % label
+    ratio = np.where(scale > 0.0, err / np.where(scale > 0.0, scale, 1.0), 0.0)
+    worst = float(np.max(ratio)) if ratio.size else 0.0
+    print("grad %-28s rows %2d finite, max |dev - twin| / S_abs = %.3e" % (label, int(fin.sum()), worst))
+    assert worst <= TOL, (label, worst, np.unravel_index(np.argmax(ratio), ratio.shape))
+    return worst
+
+
 def check_case(inp, seed, label):
     from lumfuncmcmc_amd.capi import LFContext
     th = rows37(inp, seed)
@@ -43,20 +61,8 @@ def check_case(inp, seed, label):
         lp_b = ctx.lnprob_batch(th)
     finally:
         ctx.close()
-    assert np.array_equal(lp_d, lp_b), "%s: lnprob of the gradient call differs from lnprob_batch" % label
-    fin = np.isfinite(lp_b)
-    assert np.array_equal(np.isnan(g_d), np.isnan(g_t)), "%s: NaN pattern" % label
-    assert np.array_equal(np.isnan(g_d).all(axis=1), ~fin) and not np.isnan(g_d[fin]).any(), "%s: NaN rows" % label
-    assert np.all(np.isfinite(g_d[fin])), "%s: a finite row with a non-finite gradient" % label
-    assert len(inp["lum"]) < 60 or (~fin).sum() >= 3, "%s: the outside and underflowing rows are not -inf" % label
-    err, scale = np.abs(g_d[fin] - g_t[fin]), s_t[fin]
-    # (an element nothing contributes to - the Flim of a field without sources on a lattice of zero width - is exactly 0)
-    assert np.all(err[scale == 0.0] == 0.0), "%s: an element without contributions is not 0" % label
-    ratio = np.where(scale > 0.0, err / np.where(scale > 0.0, scale, 1.0), 0.0)
-    worst = float(np.max(ratio)) if ratio.size else 0.0
-    print("grad %-28s rows %2d finite, max |dev - twin| / S_abs = %.3e" % (label, int(fin.sum()), worst))
-    assert worst <= TOL, (label, worst, np.unravel_index(np.argmax(ratio), ratio.shape))
-    return worst
+    assert len(inp["lum"]) < 60 or (~np.isfinite(lp_b)).sum() >= 3, "%s: the outside and underflowing rows are not -inf" % label
+    return compare(lp_d, g_d, lp_b, g_t, s_t, label)
 
 
 @pytest.mark.parametrize("name,variant", GOLDENS)
