@@ -5,7 +5,8 @@
 //
 // Domain: real a in [GI_A_MIN, GI_A_MAX] = [-5, 7] (alpha + 1 and alpha + 2 for alpha in [-6, 5]), x >= 0.  x = 0 gives
 // Gamma(a) for a > 0 and +inf otherwise; x = +inf, and every x whose exp(-x / 2) is 0, gives 0.  A NaN, a negative x or an a
-// outside the domain gives NaN before any loop is entered.
+// outside the domain gives NaN before any loop is entered; inside the domain the result is never NaN, and a Gamma(a, x) above
+// the largest double (a < 0, x below 1e-61 and less) is +inf.
 //
 // With m = rint(a), a0 = a - m in [-1/2, 1/2] (exact), w(a0) the polynomial of lf_gammainc_coef.h and
 // r = 1 + a0 w = 1 / Gamma(1 + a0):
@@ -17,6 +18,13 @@
 //       whose bracket is Gamma(a0) - x^a0 / a0 without its cancellation and tends to -euler - ln x as a0 -> 0 (taken
 //       below |a0| = GI_A0_TINY); then -m steps of Gamma(c - 1, x) = (Gamma(c, x) - x^(c-1) e^-x) / (c - 1), which never
 //       divides by 0 (c - 1 <= -1/2) and is stable for x < 1.  a = 0, -1, -2, .. take this path with a0 = 0 exactly.
+//       Where |a0 ln x| > GI_AL_POW = 1 the bracket takes (x^a0 - 1) / a0 from the pow the series needs anyway: expm1 would
+//       amplify the rounding of the product a0 ln x by |a0 ln x|, up to 370 at the smallest doubles, while x^a0 is then
+//       outside [1 / e, e] and the difference loses a factor of 1.6 at the most.  The recurrence runs on
+//       GI_REC_SCALE = 2^-8 of its two terms (exact: both stay normal numbers) and a step whose x^(c-1) e^-x is +inf even
+//       so gives +inf: Gamma(c - 1, x) = (x^(c-1) e^-x - Gamma(c, x)) / (1 - c), 1 - c <= 5 and Gamma(c, x) smaller by a
+//       factor x < 1e-61, is above 2^8 / 5 of the largest double there, and the next step would otherwise take inf - inf.
+//       The product with 2^8 at the end overflows exactly when the result does.
 //   x >= 1:  Legendre's continued fraction x^c e^-x / (x + 1 - c - 1 (1 - c) / (x + 3 - c - 2 (2 - c) / ..)) evaluated
 //       bottom-up from term N = GI_CF_N0 + int(GI_CF_K / x) (one division per term; its error falls like exp(-4 sqrt(N x)),
 //       N x >= 120 leaves 1e-19), at c = a for m <= 0 (every partial denominator positive) or at c = b followed by the
@@ -43,6 +51,8 @@ constexpr int GI_CF_CAP = 136;
 constexpr int GI_REC_CAP = 6;
 constexpr double GI_EPS = 0x1p-54;
 constexpr double GI_A0_TINY = 0x1p-500;
+constexpr double GI_AL_POW = 1.0;
+constexpr double GI_REC_SCALE = 0x1p-8, GI_REC_UNSCALE = 0x1p8;
 
 // 10^t from IEEE operations alone (lfintegrals.exp10 is the same to the bit): Gamma(a, x) ~ e^-x turns one ulp of
 // x = 10^t into x ulp of the result, more than the device and the C library's exp10 may differ by.
@@ -108,15 +118,17 @@ __device__ __forceinline__ double gammainc_upper(double a, double x) {
             if (!(fabs(term) > fabs(tot) * GI_EPS)) break;
         }
         const double lx = log(x);
-        const double sing = fabs(a0) < GI_A0_TINY ? -GI_W[0] - lx : -w / r - expm1(a0 * lx) / a0;
-        double g = sing - pw * tot;
-        double f = pw * eh;
+        const double al = a0 * lx;
+        const double brk = fabs(al) > GI_AL_POW ? (pw - 1.0) / a0 : expm1(al) / a0;
+        const double sing = fabs(a0) < GI_A0_TINY ? -GI_W[0] - lx : -w / r - brk;
+        double g = (sing - pw * tot) * GI_REC_SCALE;
+        double f = (pw * eh) * GI_REC_SCALE;
         for (int k = 1; k <= GI_REC_CAP; ++k)
             if (k <= -mi) {
                 f = f / x;
-                g = (g - f) / (a + (-m - (double)k));
+                g = f == __builtin_inf() ? __builtin_inf() : (g - f) / (a + (-m - (double)k));
             }
-        return g;
+        return g * GI_REC_UNSCALE;
     }
     const double c = up ? b : a;
     int nt = GI_CF_N0 + (int)(GI_CF_K / x);

@@ -31,6 +31,8 @@ GI_CF_CAP = 136                     # its trip cap
 GI_REC_CAP = 6                      # recurrence steps: |round(a)| <= 7
 GI_EPS = 2.0 ** -54
 GI_A0_TINY = 2.0 ** -500            # below it the singular part takes its limit -euler - ln x
+GI_AL_POW = 1.0                     # |a0 ln x| above it: the bracket takes x^a0 - 1 in the place of expm1(a0 ln x)
+GI_REC_SCALE, GI_REC_UNSCALE = 2.0 ** -8, 2.0 ** 8  # the downward recurrence runs on 2^-8 of its terms (exact)
 
 
 def _kind(kind):
@@ -56,7 +58,8 @@ def exp10(t):
 
 def gammainc_upper(a, x, counts=False):
     """Gamma(a, x) = int_x^inf t^(a-1) e^-t dt in fp64 for real a in [-5, 7] and x >= 0 (x = 0: Gamma(a) for a > 0, +inf
-    otherwise; x = +inf: 0).  NaN for a NaN or anything outside the domain.  counts=True also returns the trip counts of
+    otherwise; x = +inf: 0).  NaN for a NaN or anything outside the domain; inside it never NaN, and +inf where Gamma(a, x)
+    is above the largest double (a < 0 and x below 1e-61 and less).  counts=True also returns the trip counts of
     the element's loops, (series, continued fraction, recurrence), as three int arrays."""
     a, x = np.broadcast_arrays(np.asarray(a, dtype=np.float64), np.asarray(x, dtype=np.float64))
     shape = a.shape
@@ -135,15 +138,17 @@ def gammainc_upper(a, x, counts=False):
                 if not live.any():
                     break
             lx = np.log(xs)
-            sing = np.where(np.abs(a0s) < GI_A0_TINY, -GI_W[0] - lx, -w[i] / r[i] - np.expm1(a0s * lx) / a0s)
             p = np.power(xs, a0s)
-            g = sing - p * tot
-            f = p * np.exp(-xs)
+            al = a0s * lx
+            brk = np.where(np.abs(al) > GI_AL_POW, (p - 1.0) / a0s, np.expm1(al) / a0s)
+            sing = np.where(np.abs(a0s) < GI_A0_TINY, -GI_W[0] - lx, -w[i] / r[i] - brk)
+            g = (sing - p * tot) * GI_REC_SCALE
+            f = (p * np.exp(-xs)) * GI_REC_SCALE
             for k in range(1, GI_REC_CAP + 1):
                 act = k <= -mi[i]
                 f = np.where(act, f / xs, f)
-                g = np.where(act, (g - f) / (as_ + (-m[i] - k)), g)
-            res[i] = g
+                g = np.where(act, np.where(f == np.inf, np.inf, (g - f) / (as_ + (-m[i] - k))), g)
+            res[i] = g * GI_REC_UNSCALE
             nser[i] = cnt
             nrec[i] = -mi[i]
 

@@ -1,9 +1,11 @@
 """The integrated LF on the device (lf_lumfunc_integral_quantiles, lf_bands_integ in csrc/lf_bands.h, Gamma(a, x) of
 csrc/lf_gammainc.h): the values against the NumPy twin, the quantiles bit for bit against np.percentile / np.median of the
-device's own values, the special points, the unchanged differential kernel and the model classes' device paths."""
+device's own values, the special points, the unchanged differential kernel, the model classes' device paths, and Gamma(a, x),
+10^t and the band sort over the entry's whole accepted domain (inputs of tests/lf_integlib.py)."""
 import numpy as np
 import pytest
 
+import lf_integlib
 from lf_testlib import synth
 from lumfuncmcmc_amd import capi, lfbands, lfintegrals as li
 
@@ -164,3 +166,67 @@ def test_z_model_device_path_agrees_with_the_host_path():
             res[dev] = m.lf_integrals(kind, device=dev)
         assert res[True].shape == (3, 100)
         _values_close(res[True], res[False], "LumFuncMCMCz %s:" % kind)
+
+
+# ------------------------------------------------------------------- the entry's whole accepted domain (lf_integlib.py)
+@pytest.mark.parametrize("kind", KINDS)
+def test_gamma_over_the_whole_accepted_domain(kind):
+    """Gamma(alpha + 1 + kind, gi_exp10(logLmin)) itself: draws with the prefactor 1 and logL* = 0, one per lattice order
+    (a over [-5, 6] and [-4, 7]), at 88 limits from x = 0 over the subnormals, the overflow edge of x^-5, both neighbours of
+    the switch and [512, 1490) to x = +inf; both template instances.  tests/test_integrals_cpu.py holds the twin to mpmath on
+    the same domain and checks what these inputs reach."""
+    lmin = lf_integlib.lattice_points()
+    x = li.exp10(lmin)
+    host = None
+    for variant in ("free", "zevol"):
+        draws, z = lf_integlib.lattice_draws(variant, kind)
+        out, v = capi.lumfunc_integral_quantiles(variant, li.KINDS[kind], draws, lmin, z=z, q=Q7, values=True)
+        if host is None:
+            host = li.integral_values(variant, kind, draws, lmin, z)
+            assert not np.isnan(host).any() and np.isinf(host).any() and (host == 0.0).any()
+        else:
+            np.testing.assert_array_equal(host, li.integral_values(variant, kind, draws, lmin, z))
+        assert v.shape == host.shape == (draws.shape[0], lmin.size)
+        with np.errstate(all="ignore"):
+            _bits_equal(out, np.percentile(v, Q7, axis=0))
+        fin = np.isfinite(v) & np.isfinite(host) & (np.abs(host) >= TINY) & (np.abs(v) >= TINY)
+        with np.errstate(all="ignore"):
+            rel = np.where(fin, np.abs(v - host) / np.abs(host), 0.0)
+        for label, cols in lf_integlib.lattice_regions(x).items():
+            assert cols.any()
+            print("%s %s, x in %s: largest relative difference device - twin %.3e over %d values"
+                  % (variant, kind, label, rel[:, cols].max(), fin[:, cols].sum()))
+        assert not np.isnan(v).any()
+        _values_close(v, host, "%s %s, whole domain:" % (variant, kind))
+
+
+def test_exp10_bit_for_bit():
+    """gi_exp10 against lfintegrals.exp10 through the entry: one "zevol" draw with logphi* = z and Gamma(1, 0) = 1, so that
+    values[0][p] = gi_exp10(z_p) ("number"), or gi_exp10(z_p) gi_exp10(z_p / 2) ("lumdens", on 200 of the values)."""
+    t = lf_integlib.exp10_lattice()
+    for kind, tt in (("number", t), ("lumdens", np.concatenate([t[:193], t[-7:]]))):
+        draws, lmin, z, want = lf_integlib.exp10_case(kind, tt)
+        _, v = _check_bitwise("zevol", kind, draws, lmin, z, q=(50.0,))
+        assert v.shape == (1, tt.size) and np.isinf(want).any() and (want == 0.0).any()
+        _bits_equal(v[0], want)
+        if kind == "number":
+            assert ((want > 0.0) & (want < TINY)).any()
+            _bits_equal(v[0], li.exp10(tt))
+
+
+@pytest.mark.parametrize("R", lf_integlib.SORT_R)
+def test_the_band_sort_on_ordered_inputs(R):
+    """Ascending, descending, all equal, organ-pipe, two interleaved runs and "+inf first, rest ascending" columns at every
+    draw count around the powers of two, through lf_bands_integ<7, 0> (values gi_exp10(t_r), bit for bit) and lf_bands<7>."""
+    z = np.array([0.0, 1.0, 2.0])
+    for name in lf_integlib.SORT_PATTERNS:
+        tr = lf_integlib.sort_pattern(name, R)
+        _, v = _check_bitwise("zevol", "number", lf_integlib.sort_draws(tr), np.full(3, -np.inf), z)
+        _bits_equal(v, np.repeat(li.exp10(tr)[:, None], 3, axis=1))
+        draws, logL = lf_integlib.sort_draws(tr, alpha=-1.5), np.array([-1.0, 0.0, 0.5])
+        out, w = capi.lumfunc_quantiles("zevol", draws, logL, z=z, q=Q7, values=True)
+        with np.errstate(all="ignore"):
+            _bits_equal(out, np.percentile(w, Q7, axis=0))
+            _bits_equal(capi.lumfunc_quantiles("zevol", draws, logL, z=z, method=capi.LF_Q_MEDIAN), np.median(w, axis=0)[None])
+        assert w.shape == (R, 3) and not np.isnan(w).any()
+        np.testing.assert_array_equal(np.argsort(w[:, 1], kind="stable"), np.argsort(v[:, 1], kind="stable"))    # the same order

@@ -5,6 +5,7 @@ import mpmath as mp
 import numpy as np
 import pytest
 
+import lf_integlib
 from lf_testlib import synth
 from lumfuncmcmc_amd import capi, hostsetup as hs, lfbands, lfintegrals as li
 
@@ -12,18 +13,13 @@ from lumfuncmcmc_amd import capi, hostsetup as hs, lfbands, lfintegrals as li
 # x just below the switch, where the series' difference loses most).  The tests assert twice that.
 TWIN_MAX_REL = 3.0e-15
 TINY = np.finfo(np.float64).tiny
+DMAX = np.finfo(np.float64).max
 
 
 def _lattice():
-    rng = np.random.default_rng(20240)
-    a = list(np.arange(-5.0, 6.01, 0.5))
-    for c in (0.0, -1.0, -2.0, -3.0):
-        for d in (0.0, 1e-12, 1e-9, 1e-6, 1e-3):
-            a += [c + d, c - d]
-    a += list(rng.uniform(-5.0, 6.0, 200))
-    a += [6.5, 7.0]                                        # alpha + 2 at the upper end of alpha's range
-    x = list(10.0 ** np.arange(-6.0, 6.01, 0.25)) + [0.0, np.nextafter(li.GI_XSW, 0.0), li.GI_XSW]
-    return np.unique(np.array(a)), np.unique(np.array(x))
+    """270 orders less their duplicates and 91 arguments (lf_integlib): the whole accepted domain of the order, and every
+    scale of x from the smallest subnormal to past the last x whose exp(-x / 2) is not 0."""
+    return lf_integlib.orders(), lf_integlib.arguments()
 
 
 @pytest.fixture(scope="module")
@@ -38,20 +34,32 @@ def lattice():
 
 
 def test_twin_against_mpmath_on_the_lattice(lattice):
+    """Truth at the doubles the twin received.  A truth above the largest double must come out +inf, nothing inside the
+    domain is NaN, and below the smallest normal double the absolute bound holds.  Before the bracket took x^a0 - 1 for
+    |a0 ln x| > 1 and the downward recurrence its scale and its +inf, this lattice gave NaN at 1384 points (a = -5, x = 1e-100
+    among them: inf - inf one step after x^(c-1) e^-x overflowed), +inf for a truth of 0.65 of the largest double at
+    a = -4.4102, x = 1e-70, and 4.4e-14 at a = -0.461, x = 4.9e-324."""
     a, x, truth, got, _ = lattice
     worst = (0.0, None, None)
+    region = {}
+    nan = [(ai, xj) for i, ai in enumerate(a) for j, xj in enumerate(x) if np.isnan(got[i, j])]
+    assert not nan, (len(nan), nan[:5])
     for i, ai in enumerate(a):
         for j, xj in enumerate(x):
             t, g = truth[i][j], got[i, j]
-            if t == mp.inf:
+            if t > DMAX:
                 assert g == np.inf, (ai, xj, g)
             elif abs(t) < TINY:
                 assert abs(g - float(t)) <= 1e-300, (ai, xj, g)
             else:
+                assert np.isfinite(g), (ai, xj, g, float(t / DMAX))
                 rel = float(abs((mp.mpf(float(g)) - t) / t))
                 if rel > worst[0]:
                     worst = (rel, ai, xj)
+                key = "x < 1e-6" if xj < 1e-6 else "[1e-6, 1)" if xj < 1.0 else "[1, 512)" if xj < 512.0 else "[512, 1490)"
+                region[key] = max(region.get(key, 0.0), rel)
     print("largest relative error of the twin: %.3e at a = %r, x = %r" % worst)
+    print("by region: " + ", ".join("%s %.2e" % kv for kv in region.items()))
     assert worst[0] <= 2.0 * TWIN_MAX_REL, worst
 
 
@@ -83,6 +91,95 @@ def test_exp10_of_the_twin():
     assert rel <= 2.0 ** -52                               # one ulp at the most
     np.testing.assert_array_equal(li.exp10(np.array([-np.inf, -331.0, 0.0, 1.0, 309.0, np.inf])), [0.0, 0.0, 1.0, 10.0, np.inf, np.inf])
     assert np.isnan(li.exp10(np.nan))
+    # the lattice the device is held to bit for bit (lf_integlib.exp10_lattice: down to -330, and the edges): one ulp where
+    # the truth is a normal number, one spacing of the subnormals (ldexp rounds once more there) below, +inf above
+    t = lf_integlib.exp10_lattice()
+    v = li.exp10(t)
+    sub = 0
+    for vi, ti in zip(v, t):
+        truth = mp.power(10, mp.mpf(float(ti)))
+        if truth > DMAX:
+            assert vi == np.inf, (ti, vi)
+        elif truth < TINY:
+            sub += 1
+            assert abs(mp.mpf(float(vi)) - truth) <= mp.mpf(2) ** -1074, (ti, vi)
+        else:
+            assert abs(mp.mpf(float(vi)) / truth - 1) <= 2.0 ** -52, (ti, vi)
+    assert sub >= 5 and np.isinf(v).any() and (v == 0.0).sum() >= 2        # each of the three rules met something
+    e = dict(zip(lf_integlib.EXP10_EDGES, li.exp10(np.array(lf_integlib.EXP10_EDGES))))
+    assert e[-331.0] == 0.0 and e[-330.0] == 0.0 and e[-323.3] == 5e-324 and 0.0 < e[-307.7] < TINY and e[0.0] == 1.0
+    assert TINY < e[308.25] < np.inf and e[309.0] == np.inf
+
+
+def test_the_device_lattice_holds_what_it_claims():
+    """tests/test_gpu_integrals.py runs lf_integlib's orders and points through the entry; here, that they reach every
+    branch, edge and recurrence depth of Gamma(a, x), and that the draws give the prefactor 1 and logLmin - logL* = logLmin."""
+    t = lf_integlib.lattice_points()
+    x = li.exp10(t)
+    assert not np.isnan(t).any() and t.size <= 100
+    one = 1.0
+    assert (x == 0.0).sum() >= 3 and (x == one).any() and (x == np.nextafter(one, 0.0)).any() and (x == np.nextafter(one, 2.0)).any()
+    assert ((x > 0.0) & (x < TINY)).sum() >= 3 and (x == 5e-324).any()
+    assert ((x >= 512.0) & (x < 745.0)).any() and ((x >= 745.0) & (x < 1490.0)).any()
+    with np.errstate(all="ignore"):
+        assert ((np.exp(-0.5 * x) == 0.0) & np.isfinite(x)).any() and np.isinf(x).any()
+    assert ((x > 0.0) & (x < 1e-6)).sum() >= 30 and (x == li.exp10(-62.0)).any() and (x == li.exp10(-63.0)).any()
+    up, down = set(), set()
+    for kind, k in li.KINDS.items():
+        al = lf_integlib.lattice_alpha(kind)
+        assert al.min() == li.ALPHA_MIN and al.max() == li.ALPHA_MAX
+        a = al + 1.0 + k
+        assert a.min() == li.GI_A_MIN + k and a.max() == li.GI_A_MAX - 1 + k
+        aa, xx = np.meshgrid(a, x, indexing="ij")
+        v, (nser, ncf, nrec) = li.gammainc_upper(aa, xx, counts=True)
+        assert not np.isnan(v).any()
+        m = np.rint(aa)
+        for b, branch in ((1, nser > 0), (2, ncf > 0)):    # the series (0 < x < 1) and the continued fraction (x >= 1)
+            up |= set(10 * b + int(d) for d in np.unique(nrec[branch & (m >= 1)]))
+        down |= set(int(d) for d in np.unique(nrec[(nser > 0) & (m <= 0)]))
+        for variant in ("free", "zevol"):
+            draws, z = lf_integlib.lattice_draws(variant, kind)
+            np.testing.assert_array_equal(li.integral_values(variant, kind, draws, t, z), v)
+    # upward 1 .. 6 steps (m = 2 .. 7) below and above the switch; downward 1 .. 5: m = -5 is the lowest order the domain has
+    # (GI_REC_CAP = 6 is the upward side's)
+    assert up >= set(10 * b + d for b in (1, 2) for d in range(1, 7)), up
+    assert down >= set(range(1, 6)), down
+
+
+def test_the_exp10_and_sort_inputs_are_what_they_claim():
+    """The one-draw "zevol" call of lf_integlib.exp10_case returns exp10(t_p) (logphi* = 0 (z z) + 1 z + 0 = z exactly,
+    Gamma(1, 0) = 1 exactly), and the columns of lf_integlib.sort_draws are exp10(t_r) in the order of the pattern."""
+    t = lf_integlib.exp10_lattice()
+    assert t.size == 2507
+    for kind, tt in (("number", t), ("lumdens", np.concatenate([t[:193], t[-7:]]))):
+        draws, lmin, z, want = lf_integlib.exp10_case(kind, tt)
+        d = draws[0]
+        np.testing.assert_array_equal(d[3] * z ** 2 + d[4] * z + d[5], tt)
+        assert li.gammainc_upper(d[6] + 1.0 + li.KINDS[kind], 0.0) == 1.0
+        v = li.integral_values("zevol", kind, draws, lmin, z)
+        np.testing.assert_array_equal(v[0], want)
+        if kind == "number":
+            np.testing.assert_array_equal(v[0], li.exp10(tt))
+    for R in lf_integlib.SORT_R:
+        asc = li.exp10(lf_integlib.sort_pattern("ascending", R))
+        assert np.all(np.diff(asc) > 0.0)
+        for name in lf_integlib.SORT_PATTERNS:
+            tr = lf_integlib.sort_pattern(name, R)
+            assert tr.shape == (R,)
+            v = li.integral_values("zevol", "number", lf_integlib.sort_draws(tr), np.full(3, -np.inf), np.array([0.0, 1.0, 2.0]))
+            np.testing.assert_array_equal(v, np.repeat(li.exp10(tr)[:, None], 3, axis=1))
+            col = v[:, 0]
+            if name == "descending":
+                assert np.all(np.diff(col) < 0.0)
+            elif name == "equal":
+                assert np.all(col == col[0])
+            elif name == "inf first":
+                assert col[0] == np.inf and np.all(np.diff(col[1:]) > 0.0)
+            elif name == "organ-pipe" and R >= 3:
+                k = int(np.argmax(col))
+                assert np.all(np.diff(col[:k + 1]) > 0.0) and np.all(np.diff(col[k:]) < 0.0)
+            elif name == "two runs" and R >= 4:
+                assert np.all(np.diff(col[0::2]) > 0.0) and np.all(np.diff(col[1::2]) > 0.0) and col[1] > col[2]
 
 
 @pytest.mark.parametrize("kind", ["number", "lumdens"])
