@@ -117,16 +117,19 @@ def split_rhat(x):
     """Split-R-hat (Gelman et al. 2013) of a (nwalkers, n) series: every walker's range cut into [0, n/2) and [n - n/2, n),
     2 W sequences of length h; Wv = mean of their variances, B / h = variance of their means, sqrt(((h-1)/h Wv + B/h) / Wv).
     The walkers of an ensemble are not independent chains, so this is a sanity check (a stuck or drifting ensemble shows),
-    not a convergence proof: the stopping rule of fit_model_converged is built on tau."""
+    not a convergence proof: the stopping rule of fit_model_converged is built on tau.
+    The 2 W halves are added one by one in the order of lfd::split_rhat (csrc/lf_diag.h): walker by walker, first half then
+    second, so that exact moments give the device's bits."""
     W, n = x.shape
     h = n // 2
     if h < 2:
         return float("nan")
-    halves = np.concatenate([x[:, :h], x[:, n - h:]], axis=0)
+    halves = np.stack([x[:, :h], x[:, n - h:]], axis=1).reshape(2 * W, h)
     mean = _twin_mean(halves)
     s2 = ((halves - mean[:, None]) ** 2).sum(axis=1) / (h - 1)
-    Wv = s2.sum() / (2 * W)
-    Bh = ((mean - mean.sum() / (2 * W)) ** 2).sum() / (2 * W - 1)
+    seq = lambda v: np.cumsum(v)[-1]                # np.sum adds eight or more terms in another order
+    Wv = seq(s2) / (2 * W)
+    Bh = seq((mean - seq(mean) / (2 * W)) ** 2) / (2 * W - 1)
     with np.errstate(all="ignore"):
         return float(np.sqrt(((h - 1.0) / h * Wv + Bh) / Wv))
 

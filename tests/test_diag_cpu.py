@@ -5,12 +5,17 @@ literal NumPy, and every argument error (refused before a device is touched).
 Bounds.  Twin ACF against the FFT form: 1e-12 absolute on the normalised curve - direct summation of n terms errs by about
 sqrt(n) eps a[0] (2e-14 at n = 2e4), never more than n eps a[0] (2e-12); the FFT form's own error is of order eps log2(n); the
 cases have n <= 2e4.  tau with equal windows: 2 (window + 1) 1e-12, the sum of window + 1 such terms, doubled.  Windows are
-compared only where the host's own curve keeps every m <= window further than 1e-6 from m = c taus[m] (asserted per case)."""
+compared only where the host's own curve keeps every m <= window further than 1e-6 from m = c taus[m] (asserted per case).
+
+The second half asserts everything tests/test_gpu_diag.py presupposes of its exact inputs and references (lf_diaglib.py):
+on integer series whose range and half sums are divisible by their lengths the twin equals exact_acf bit for bit; on real
+series it stays inside truth_bound of a direct sum in extended precision."""
 import ctypes
 
 import numpy as np
 import pytest
 
+import lf_diaglib as dl
 from lf_diaglib import CASES, ar1, fft_acf, fft_window, rhat_numpy, shifted
 
 F64P = ctypes.POINTER(ctypes.c_double)
@@ -174,3 +179,185 @@ def test_argument_errors_without_a_device(lib):
     assert lib.lf_chain_window(_p(acf), 0, 5.0, 8, ctypes.byref(t), ctypes.byref(w)) == capi.LF_ERR_ARG
     assert lib.lf_chain_window(_p(acf), 8, 5.0, 0, ctypes.byref(t), ctypes.byref(w)) == capi.LF_ERR_ARG
     assert lib.lf_diag_last(None, None) == capi.LF_ERR_ARG
+
+
+# --------------------------------------------------------------------- what the device tests presuppose (lf_diaglib.py)
+def _twin(x_int, **kw):
+    from lumfuncmcmc_amd.sampler import chain_diagnostics_twin
+    return chain_diagnostics_twin(np.asarray(x_int, dtype=np.float64)[:, :, None], **kw)
+
+
+def _same(a, b):
+    return a == b or (np.isnan(a) and np.isnan(b))
+
+
+def test_lattice_series_are_exact_inputs():
+    for n in dl.EXACT_N + [1, 2, 3]:
+        x = dl.lattice(n, 3, n)
+        h = n // 2
+        assert x.dtype == np.int64 and x.shape == (3, n) and np.all(x.sum(axis=1) % n == 0)
+        assert h == 0 or (np.all(x[:, :h].sum(axis=1) % h == 0) and np.all(x[:, n - h:].sum(axis=1) % h == 0))
+        assert 30000 < x.min() and x.max() < 50000                   # sums and squares far below 2^53
+        assert n < 4 or np.all(dl.exact_lag_sums(x, 1)[:, 0] > 0)    # no walker is constant by accident
+        assert not np.array_equal(x, dl.lattice(n + 1, 3, n))        # the seed matters
+    # exact_acf on a series small enough to do by hand: y = (-1, 1, 1, -1) and (-3, -1, 1, 3)
+    x = np.array([[4, 6, 6, 4], [2, 4, 6, 8]], dtype=np.int64)
+    np.testing.assert_array_equal(dl.exact_lag_sums(x, 5), [[4, -1, -2, 1, 0], [20, 5, -6, -9, 0]])
+    want = [(1.0 + 1.0) / 2, (-1.0 / 4.0 + 5.0 / 20.0) / 2, (-2.0 / 4.0 + -6.0 / 20.0) / 2, (1.0 / 4.0 + -9.0 / 20.0) / 2, 0.0]
+    np.testing.assert_array_equal(dl.exact_acf(x, 5), want)
+    with pytest.raises(AssertionError):
+        dl.exact_acf(x + np.array([[0, 0, 0, 1], [0, 0, 0, 0]]), 5)  # a sum that n does not divide is refused
+
+
+def test_twin_equals_exact_acf_at_every_length():
+    """Lists (a): bit for bit, whole lag tiles past n, for W = 1 and 3; and R-hat in the device's order of the halves."""
+    for n in dl.EXACT_N:
+        nl = dl.lags_past(n)
+        assert nl % 512 == 0 and nl - 512 > n >= nl - 1024
+        for W in (1, 3):
+            x = dl.lattice(n, W, n)
+            r = _twin(x, nlags=nl)
+            want = dl.exact_acf(x, nl)
+            np.testing.assert_array_equal(r.acf[0], want)
+            assert np.all(want[n:] == 0.0) and want[0] == 1.0
+            assert r.ess[0] == W * n / r.tau[0]
+            assert abs(r.rhat[0] - rhat_numpy(x.astype(np.float64))) <= 1e-12 * r.rhat[0]
+
+
+def test_twin_rhat_adds_the_halves_in_the_device_order():
+    """lfd::split_rhat restated term by term on exact moments (integer means and sums of squares): the twin has its bits.
+    n = 7, W = 3 is where adding all first halves before the second halves gives another last bit."""
+    from lumfuncmcmc_amd.sampler import split_rhat
+    for n, W in [(7, 3), (4, 1), (257, 2), (513, 3), (1100, 4), (300, 9)]:
+        x = dl.lattice(n, W, n)
+        h = n // 2
+        sm = sv = 0.0
+        mom = []
+        for w in range(W):
+            for half in (x[w, :h], x[w, n - h:]):
+                m = int(half.sum()) // h
+                mom.append((float(m), float(int(((half - m) ** 2).sum()))))
+        for m, q in mom:
+            sm += m
+            sv += q / float(h - 1)
+        gm, Wv = sm / (2 * W), sv / (2 * W)
+        bs = 0.0
+        for m, q in mom:
+            bs += (m - gm) * (m - gm)
+        want = float(np.sqrt((float(h - 1) / float(h) * Wv + bs / (2 * W - 1)) / Wv))
+        assert split_rhat(x.astype(np.float64)) == want, (n, W)
+
+
+def test_twin_equals_exact_acf_in_every_group_slot():
+    """List (b): the D series of a batch are different series, each equal to its own exact curve."""
+    nl = dl.lags_past(dl.GROUP_N)
+    x = dl.group_series(max(dl.GROUP_D))
+    assert x.shape == (9, dl.GROUP_W, dl.GROUP_N)
+    curves = [dl.exact_acf(x[d], nl) for d in range(9)]
+    for d in range(9):
+        np.testing.assert_array_equal(_twin(x[d], nlags=nl).acf[0], curves[d])
+        for e in range(d):
+            assert not np.array_equal(curves[d][:dl.GROUP_N], curves[e][:dl.GROUP_N])
+
+
+def test_drift_series_need_later_passes(lib):
+    """List (c): under c = 50 the window lies past the first 512 lags, far from a rounding error, and the lags diag_run has
+    computed when it decides are 1024, 1024, 1024 and 1536; the twin has the FFT form's window and the exact curve."""
+    windows = {}
+    for n in dl.DRIFT_N:
+        x = dl.drift(n, 4, n)
+        assert np.all(np.abs(x - 8 * np.arange(n)) <= 3 + n)         # 8 t + noise; the few adjusted elements moved by < n
+        tau, win, margin = fft_window(fft_acf(x.astype(np.float64)), c=50.0)
+        print("drift n %d: window %d tau %.4f margin %.3g -> %d lags" % (n, win, tau, margin, dl.passes(win, n)))
+        windows[n] = win
+        assert win > 512 and margin > 1e-6 and margin > 1.0
+        assert dl.passes(win, n) == dl.DRIFT_LAGS[n]
+        r = _twin(x, c=50.0)
+        assert r.window[0] == win
+        full = _twin(x, c=50.0, nlags=1536)
+        want = dl.exact_acf(x, 1536)
+        np.testing.assert_array_equal(full.acf[0], want)
+        assert (full.tau[0], full.window[0]) == (r.tau[0], r.window[0])
+        rc, ctau, cwin = c_window(lib, want[:min(n, 1536)], 50.0, n)  # the C rule on the exact curve: what the device must give
+        assert rc == 0 and cwin == win and abs(ctau - r.tau[0]) <= 1e-15 * abs(ctau)
+    assert windows == {600: 550, 700: 642, 1100: 1009, 1200: 1101}
+    assert dl.passes(511, 600) == 512 and dl.passes(512, 600) == 1024 and dl.passes(1023, 1100) == 1024
+    assert dl.passes(1024, 1100) == 1536 and dl.passes(1024, 3000) == 2048
+
+
+def test_slice_arithmetic_and_pattern_curves():
+    """List (d): W D 1024 doubles exceed 64 MiB, so a pass of 1024 lags takes two slices of 512; and the expected curve of
+    the pattern chain equals exact_acf of the chain itself (shown on its first 23 walkers)."""
+    W, D, n, nlags = dl.SLICE_SHAPE
+    assert W * D * nlags * 8 > dl.SLICE_BYTES and dl.slices(W, D, nlags) == (512, 2)
+    assert dl.slices(32, 3, 2048)[1] == 1 and dl.slices(W, D - 1, nlags) == (1024, 1)
+    assert nlags == -(-n // 512) * 512 and n > 512                  # both slices hold lags below n
+    pat = dl.slice_patterns()
+    live, ratio = dl.exact_ratios(pat, nlags)
+    assert list(live) == [True, True, True, True, False] and np.all(ratio[4] == 0.0)
+    for d in range(D):
+        idx = [dl.slice_pattern_of(w, d) for w in range(23)]
+        np.testing.assert_array_equal(dl.slice_expected(pat, d, 23, nlags), dl.exact_acf(pat[idx], nlags))
+        np.testing.assert_array_equal(_twin(pat[idx], nlags=nlags).acf[0], dl.exact_acf(pat[idx], nlags))
+    full = dl.slice_expected(pat, 0, W, nlags)
+    assert full[0] == sum(1.0 for w in range(W) if w % 5 != 4) / W and np.all(full[n:] == 0.0) and np.any(full[512:n] != 0.0)
+    # one constant walker among 8: acf[0] is 7/8 exactly
+    x = dl.lattice(300, 8, 400)
+    x[3] = 40000
+    want = dl.exact_acf(x, 512)
+    assert want[0] == 7.0 / 8.0
+    np.testing.assert_array_equal(_twin(x, nlags=512).acf[0], want)
+
+
+def test_constant_series_and_short_series_on_the_twin():
+    """List (f): a constant that is not representable centres to exactly 0 (the two-pass mean of a constant is exact), so
+    a[0] = 0, the ACF is 0, tau 1.0 and window 0 - where the host's integrated_time, whose one-pass mean may miss the
+    constant by an ulp, can return tau = n; and n < 4."""
+    from lumfuncmcmc_amd.sampler import chain_diagnostics_twin, integrated_time
+    host = {}
+    for v in dl.CONSTANTS:
+        assert float(np.float32(v)) != v                             # not a short binary fraction
+        for n in dl.CONSTANT_N:
+            x = np.full((3, n, 1), v)
+            r = chain_diagnostics_twin(x, nlags=dl.lags_past(n))
+            assert np.all(r.acf == 0.0) and r.tau[0] == 1.0 and r.window[0] == 0 and r.ess[0] == 3 * n, (v, n)
+            host[(v, n)] = integrated_time(x[:, :, 0].T)
+    print("host integrated_time on constants:", host)
+    # either its mean hits the constant (a[0] = 0, tau 1.0) or misses it by an ulp: then y is a constant, acf[k] = (n - k) / n
+    # and tau comes out as n
+    assert all(t == 1.0 or abs(t - n) <= 1e-12 * n for (v, n), t in host.items())
+    for n in (1, 2, 3):
+        r = _twin(dl.lattice(n, 3, n), nlags=512)
+        assert r.tau[0] == 1.0 and r.window[0] == 0 and np.isnan(r.rhat[0]) and np.all(r.acf == 0.0) and r.ess[0] == 3 * n
+    # the widest ensemble the device takes, n = 4: the exact reference handles it
+    x = dl.lattice(4, 65535, 4)
+    want = dl.exact_acf(x, 4)
+    assert want[0] == 1.0 and np.all(np.abs(want) <= 1.0)
+
+
+def test_truth_and_its_bound_hold_the_twin():
+    """List (g): the twin against direct sums in extended precision stays inside 2 ((n + 16) 2^-53 + S); so does the FFT
+    form.  The figures are printed (DESIGN.md section 3.12 quotes them)."""
+    from lumfuncmcmc_amd.sampler import chain_diagnostics_twin
+    assert np.finfo(np.longdouble).eps <= 1.1e-19 or dl._extended() is None
+    for name, x in dl.real_cases().items():
+        W, n = x.shape
+        truth, S = dl.truth_acf(x, n)
+        bound = dl.truth_bound(n, S)
+        assert bound <= 1e-12 and truth[0] == 1.0
+        twin = np.max(np.abs(chain_diagnostics_twin(x[:, :, None], nlags=n).acf[0] - truth))
+        fft = np.max(np.abs(fft_acf(x) - truth))
+        print("%-22s W %2d n %4d S %.3g bound %.3g twin err / bound %.4f FFT err / bound %.4f" % (name, W, n, S, bound, twin / bound, fft / bound))
+        assert twin <= bound and fft <= bound
+    assert {x.shape[1] for x in dl.real_cases().values()} == {300, 1100, 1025}
+
+
+def test_truth_in_mpmath_equals_truth_in_long_double(monkeypatch):
+    """The fall-back of truth_acf (40 digits) on a short series, against the extended-precision form where there is one."""
+    if dl._extended() is None:
+        pytest.skip("no extended precision to compare with")
+    x = ar1(0)[:2, :24]
+    a, Sa = dl.truth_acf(x, 30)
+    monkeypatch.setattr(dl, "_extended", lambda: None)
+    b, Sb = dl.truth_acf(x, 30)
+    assert np.max(np.abs(a - b)) <= 4e-16 and abs(Sa - Sb) <= 1e-18 + 1e-3 * Sb and np.all(b[24:] == 0.0)    # long double resolves S to about eps
