@@ -13,14 +13,29 @@
 // picks node (j, k) with probability m / M_f and inverts the two hats with one uniform each.
 //
 // Node order (the cumulative sums): column k major, then j.  cdfZ[k] = column masses summed over k' <= k; cdfL[k][j] =
-// masses of column k summed over j' <= j.  Both prefix sums run in tiles of 256: a Hillis-Steele scan of the tile in LDS
-// (step d = 1, 2, .. 128: x[t] = x[t - d] + x[t]) plus the running total of the tiles before it - one fixed order, whatever
-// the batch.  A source with uniform u takes t = u M_f, the first column with cdfZ[k] > t, then the first j with
-// cdfL[k][j] > t - cdfZ[k - 1] (0 for k = 0): nodes of zero mass are never chosen.  If rounding leaves no such entry (t at
-// the very top), the first entry that reaches the total is taken instead (>= the last element): the last node with mass.
+// masses of column k summed over j' <= j.  Both are made by mock_cdf in two steps.  The prefix sums s run in tiles of 256: a
+// Hillis-Steele scan of the tile in LDS (step d = 1, 2, .. 128: x[t] = x[t - d] + x[t]) plus the running total of the
+// tiles before it - one fixed order, whatever the batch.  That gives every prefix its own summation tree, so s alone may
+// go down by an ulp from one node to the next and may step at a node of mass 0.  What is stored is therefore the running
+// maximum over the nodes with mass,
+//     c[j] = max(0, s[i] for i <= j with m[i] > 0)
+// (the same tiles with max for +; max is exact and associative, so c is a function of s alone).  Guaranteed of cdfZ and of
+// every column of cdfL, on the device and in the host twin (mock.scan) alike:
+//     c is non-decreasing;   c[j] == c[j - 1] (0 for j = 0) wherever m[j] == 0;   c[j] is s at some node i <= j with mass,
+//     so it keeps s's error bound against the exact sum, (9 + tiles before j) 2^-53 relative.
+// A source with uniform u takes t = u cdfZ[S - 1], the first column with cdfZ[k] > t, then the first j with
+// cdfL[k][j] > t - cdfZ[k - 1] (0 for k = 0).  On such sums bisection (mock_search) and a linear search find the same index
+// for every t, and a node of zero mass is never chosen.  Not guaranteed: a node whose mass is positive but too small to
+// lift its rounded sum above the maximum before it (below about one ulp of the running sum) owns no part of the range
+// and cannot be drawn.  If rounding leaves no entry above t (t at the very top, or the remainder above a column's last
+// sum), the first entry that reaches the last one is taken instead (>=): the last node that raised the sum.  The
+// reported mean M_f is the sum scan's running total.  It and cdfZ[S - 1] are two roundings of one exact sum and may differ
+// by a few units of 2^-53 (each is within (9 + tiles) 2^-53 of the exact sum, relative).
 //
 // Hat inversion, left width a, right width b, peak x0 (a width of zero: no mass on that side):
 //     u < a / (a + b):  x = x0 - a (1 - sqrt(u (a + b) / a))       else:  x = x0 + b (1 - sqrt((1 - u) (a + b) / b))
+// with each root capped at 1: next to the branch point the rounded quotient can exceed 1 by an ulp, which would put x on
+// the wrong side of x0.  With the cap x stays in [x0 - a, x0 + b] (as rounded) and never decreases as u grows.
 //
 // Random numbers: Philox4x32-10 (lf_kernels.h), key = seed, counter = (row_id lo, row_id hi, index, MOCK_TAG | purpose << 8 |
 // field).  purpose 0: the count, index = rejection round; purpose 1: source `index` of the (row, field) - words 0-1 the
@@ -33,9 +48,9 @@
 // that is not finite, negative or above MOCK_MAX_MEAN gives count -1 (the host reports LF_ERR_ARG naming the row).
 //
 // Kernels (256 threads, no scratch):
-//   lf_mock_mass   grid (S columns, rows x nf): one column of one (row, field): lambda, m, the column's prefix sum
-//                  (cdfL) and its total (colm).  LDS: 2 KiB (the scan tile).
-//   lf_mock_total  grid (rows x nf): prefix sum of the column totals (cdfZ), M_f, the Poisson count.  LDS: 2 KiB.
+//   lf_mock_mass   grid (S columns, rows x nf): one column of one (row, field): lambda, m, the column's cumulative sums
+//                  (cdfL) and its total (colm).  LDS: 2 KiB (one tile, shared by the sum scan and the max scan).
+//   lf_mock_total  grid (rows x nf): cumulative sums of the column totals (cdfZ), M_f, the Poisson count.  LDS: 2 KiB.
 //   lf_mock_draw   one thread per source: (row, field) from the offsets by binary search, node search, two hat
 //                  inversions, plain vector stores of z, logL, field.  No LDS.
 //   lf_mock_hist   the same draw binned by logL: a workgroup takes up to MOCK_HIST_CHUNK sources of one (row, field),
@@ -71,10 +86,10 @@ __device__ __forceinline__ double mock_hat(double x0, double a, double b, double
 #pragma clang fp contract(off)
     const double ab = a + b;
     if (u < a / ab) {
-        const double s = sqrt(u * ab / a);
+        const double s = fmin(sqrt(u * ab / a), 1.0);
         return x0 - a * (1.0 - s);
     }
-    const double s = sqrt((1.0 - u) * ab / b);
+    const double s = fmin(sqrt((1.0 - u) * ab / b), 1.0);
     return x0 + b * (1.0 - s);
 }
 
@@ -243,6 +258,43 @@ __device__ __forceinline__ double mock_scan_tile(double* __restrict__ buf, doubl
     return out;
 }
 
+// running maximum of one tile of 256 values >= 0 in LDS (the same tree with max for +), continued from `top`; returns this
+// thread's maximum and leaves the tile's (top included) in `top` for every thread.  Max is exact: the order is immaterial.
+__device__ __forceinline__ double mock_max_tile(double* __restrict__ buf, double v, double& top) {
+    const int t = threadIdx.x;
+    buf[t] = v;
+    __syncthreads();
+#pragma unroll
+    for (int d = 1; d < MOCK_THREADS; d <<= 1) {
+        const double o = t >= d ? buf[t - d] : 0.0;
+        __syncthreads();
+        if (t >= d) buf[t] = fmax(o, buf[t]);
+        __syncthreads();
+    }
+    const double out = fmax(top, buf[t]);
+    const double tot = fmax(top, buf[MOCK_THREADS - 1]);
+    __syncthreads();
+    top = tot;
+    return out;
+}
+
+// The cumulative sums of the file comment for n masses mass(0) .. mass(n - 1) >= 0, one workgroup of 256, tile by tile:
+// out[j] = the largest prefix sum at a node i <= j with mass(i) > 0 (0 if there is none); returns the sum scan's running
+// total (all threads).  buf: the 2 KiB tile, used by both scans in turn.  lf_mock_mass, lf_mock_total and the tests' probe
+// (tests/mock_probe.hip) all run this one loop.
+template <class Mass>
+__device__ __forceinline__ double mock_cdf(double* __restrict__ buf, int n, Mass mass, double* __restrict__ out) {
+    double carry = 0.0, top = 0.0;
+    for (int base = 0; base < n; base += MOCK_THREADS) {
+        const int j = base + (int)threadIdx.x;
+        const double m = j < n ? mass(j) : 0.0;
+        const double s = mock_scan_tile(buf, m, carry);
+        const double c = mock_max_tile(buf, m > 0.0 ? s : 0.0, top);
+        if (j < n) out[j] = c;
+    }
+    return carry;
+}
+
 // trapezoid weight of node i of n nodes x[i * stride]: half the spacing to each neighbour
 __device__ __forceinline__ double mock_weight(const double* __restrict__ x, int stride, int i, int n) {
 #pragma clang fp contract(off)
@@ -262,18 +314,12 @@ __global__ __launch_bounds__(MOCK_THREADS) void lf_mock_mass(MockConst mc, const
     const double wz = mock_weight(mc.zarr, 1, k, S);
     const MockColumn col = mock_column(mc, th, f, k);
     double* out = cdfL + ((size_t)rf * S + k) * S;
-    double carry = 0.0;
-    for (int base = 0; base < S; base += MOCK_THREADS) {
-        const int j = base + (int)threadIdx.x;
-        double m = 0.0;
-        if (j < S) {
-            const double wl = mock_weight(mc.logL + k, S, j, S);
-            m = (wz * wl) * mock_lambda(mc, col, f, j, k);
-        }
-        const double c = mock_scan_tile(buf, m, carry);
-        if (j < S) out[j] = c;
-    }
-    if (threadIdx.x == 0) colm[(size_t)rf * S + k] = carry;
+    const double total = mock_cdf(buf, S, [&](int j) {
+#pragma clang fp contract(off)
+        const double wl = mock_weight(mc.logL + k, S, j, S);
+        return (wz * wl) * mock_lambda(mc, col, f, j, k);
+    }, out);
+    if (threadIdx.x == 0) colm[(size_t)rf * S + k] = total;
 }
 
 // blockIdx.x = rf.  cdfZ: [rows * nf][S]; mean, count: [rows * nf]
@@ -283,17 +329,12 @@ __global__ __launch_bounds__(MOCK_THREADS) void lf_mock_total(int S, int nf, con
                                                               long long* __restrict__ count) {
     __shared__ double buf[MOCK_THREADS];
     const int rf = blockIdx.x;
-    double carry = 0.0;
-    for (int base = 0; base < S; base += MOCK_THREADS) {
-        const int k = base + (int)threadIdx.x;
-        const double v = k < S ? colm[(size_t)rf * S + k] : 0.0;
-        const double c = mock_scan_tile(buf, v, carry);
-        if (k < S) cdfZ[(size_t)rf * S + k] = c;
-    }
+    const double* cm = colm + (size_t)rf * S;
+    const double total = mock_cdf(buf, S, [&](int k) { return cm[k]; }, cdfZ + (size_t)rf * S);
     if (threadIdx.x == 0) {
         const int row = rf / nf, f = rf - row * nf;
-        mean[rf] = carry;
-        count[rf] = mock_poisson(carry, (unsigned long long)row_ids[row], f, seed);
+        mean[rf] = total;
+        count[rf] = mock_poisson(total, (unsigned long long)row_ids[row], f, seed);
     }
 }
 

@@ -67,10 +67,17 @@ def _row_ids(row_ids, R):
 
 # ----------------------------------------------------------------------------------------------------------- NumPy pieces
 def scan(x):
-    """Inclusive prefix sums along the last axis in lf_mock.h's order: tiles of 256, a Hillis-Steele scan of each tile
-    (x[t] = x[t - d] + x[t], d = 1, 2, .., 128) plus the total of the tiles before it.  Returns (prefix sums, total);
-    the total is the running sum of the tile totals (the scan's last lane), which may differ from the last prefix sum
-    in the last bit."""
+    """The cumulative sums of lf_mock.h (mock_cdf) along the last axis, for masses x >= 0.  First the inclusive prefix sums
+    in the device's order: tiles of 256, a Hillis-Steele scan of each tile (x[t] = x[t - d] + x[t], d = 1, 2, .., 128)
+    plus the total of the tiles before it.  Every prefix has its own summation tree, so these sums alone may decrease by
+    an ulp and may step at a node of zero mass.  Then a running maximum over the nodes with x > 0:
+        c[j] = max(0, s[i] for i <= j with x[i] > 0)
+    (max is exact: any order gives the same bits).  So c is non-decreasing and c[j] == c[j - 1] (0 for j = 0) wherever
+    x[j] == 0: a first-above search never lands on a node of zero mass, and bisection and a linear search agree for every
+    threshold.  A positive mass too small to lift its rounded sum above the maximum before it (below about one ulp of
+    the running sum) leaves c flat too and cannot be drawn.  Returns (c, total); the total is the running sum of the
+    tile totals (the scan's last lane).  It and c[-1] are two roundings of one exact sum and may differ by a few units
+    of 2^-53 (each is within (9 + tiles) 2^-53 of the exact sum, relative)."""
     x = np.asarray(x, dtype=np.float64)
     n = x.shape[-1]
     out = np.empty_like(x)
@@ -85,7 +92,7 @@ def scan(x):
             d <<= 1
         out[..., base:base + w] = carry[..., None] + t[..., :w]
         carry = carry + t[..., SCAN_TILE - 1]
-    return out, carry
+    return np.maximum.accumulate(np.where(x > 0.0, out, 0.0), axis=-1), carry
 
 
 def trapz_weights(x, axis=0):
@@ -99,13 +106,14 @@ def trapz_weights(x, axis=0):
 
 
 def hat_inverse(x0, a, b, u):
-    """Inverse CDF of the unit hat with left width a, right width b, peak x0 (a width of 0: no mass on that side)."""
+    """Inverse CDF of the unit hat with left width a, right width b, peak x0 (a width of 0: no mass on that side).  Each
+    root is capped at 1 (lf_mock.h: mock_hat): x stays on its side of x0 and never decreases as u grows."""
     x0, a, b, u = (np.asarray(v, dtype=np.float64) for v in (x0, a, b, u))
     with np.errstate(all="ignore"):
         ab = a + b
         left = u < a / ab
-        xl = x0 - a * (1.0 - np.sqrt(u * ab / a))
-        xr = x0 + b * (1.0 - np.sqrt((1.0 - u) * ab / b))
+        xl = x0 - a * (1.0 - np.minimum(np.sqrt(u * ab / a), 1.0))
+        xr = x0 + b * (1.0 - np.minimum(np.sqrt((1.0 - u) * ab / b), 1.0))
     return np.where(left, xl, xr)
 
 
@@ -261,7 +269,8 @@ class MockTwin(object):
         return (self.wz[None, None, :] * self.wL[None]) * self.lam(theta)
 
     def _cdfs(self, theta):
-        """cdfL (nf, S_k, S_j): column k's masses summed over j; cdfZ (nf, S): column totals summed over k; M (nf)."""
+        """cdfL (nf, S_k, S_j): column k's masses summed over j; cdfZ (nf, S): column totals summed over k; M (nf).  Both are
+        scan()'s cumulative sums: non-decreasing, flat across zero masses.  M is the sum scan's carry (the reported mean)."""
         cdfL, colm = scan(np.swapaxes(self.masses(theta), 1, 2))
         cdfZ, M = scan(colm)
         return cdfL, cdfZ, M

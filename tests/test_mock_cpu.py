@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import lf_isalib
+import lf_mockproblib
 import lf_oracle as O
 import lf_testlib as T
 from lumfuncmcmc_amd import mock, synth
@@ -55,39 +56,13 @@ def test_expected_counts_are_piece_b(variant, fix_sch_al, grid):
     assert (mean >= 0).all() and (cnt >= 0).all()
 
 
-def _pmf(mu, k):
-    return np.exp(-mu + k * math.log(mu) - np.array([math.lgamma(x + 1.0) for x in k]))
-
-
 @pytest.mark.parametrize("mu", [1e-3, 0.5, 5.0, 9.99, 10.0, 37.0, 1e4, 1e6])
 def test_poisson_draws_follow_the_exact_pmf(mu):
     n = 40000
     k = mock.poisson(np.full(n, mu), np.arange(n, dtype=np.int64), 3, seed=20260101)
     assert k.dtype == np.int64 and (k >= 0).all()
-    sd = math.sqrt(mu)
-    lo, hi = max(0, int(mu - 6 * sd) - 1), int(mu + 6 * sd) + 2
-    support = np.arange(lo, hi)
-    p = _pmf(mu, support.astype(np.float64))
-    obs = np.bincount(np.clip(k - lo, 0, hi - lo - 1), minlength=hi - lo)[:hi - lo].astype(float)
-    # merge neighbours until every class expects >= 5 draws (both tails go into their edge classes)
-    exp_, got, acc_e, acc_o = [], [], 0.0, 0.0
-    for e, o in zip(n * p, obs):
-        acc_e += e
-        acc_o += o
-        if acc_e >= 5.0:
-            exp_.append(acc_e)
-            got.append(acc_o)
-            acc_e = acc_o = 0.0
-    if exp_:
-        exp_[-1] += acc_e
-        got[-1] += acc_o
-    exp_, got = np.array(exp_), np.array(got)
-    exp_ *= got.sum() / exp_.sum()
-    if len(exp_) < 2:                  # mu = 1e-3: almost every draw is 0
-        assert abs((k > 0).sum() - n * (1.0 - math.exp(-mu))) < 5 * math.sqrt(n * mu) + 1
-        return
-    chi2 = float(((got - exp_) ** 2 / exp_).sum())
-    assert stats.chi2.sf(chi2, len(exp_) - 1) > 1e-4, (mu, chi2, len(exp_))
+    # chi^2 against the exact pmf, classes merged to >= 5 expected draws, p > 1e-4 (mu = 1e-3: the count of non-zero draws)
+    lf_mockproblib.poisson_fit(k, mu)
 
 
 def test_poisson_special_means():
