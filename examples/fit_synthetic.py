@@ -74,6 +74,15 @@ def write_deconvolved_lums(LFmod, path):
           % (res["n_used"], np.mean(res["shift"][order[:k]]), np.mean(res["shift"][order[-k:]])))
 
 
+def print_veff_deconvolved(LFmod):
+    """the deconvolved 1/Veff points (veff_deconvolved) next to the plain ones"""
+    np.random.seed(6)
+    res = LFmod.veff_deconvolved(percentiles=(16, 50, 84))
+    print("1/Veff points over %d draws: Lavg, plain dn/dlogL, deconvolved 16 / 50 / 84 %%" % res["n_used"])
+    for b in range(len(res["Lavg"])):
+        print("  %8.4f  %12.5e  %12.5e %12.5e %12.5e" % ((res["Lavg"][b], LFmod.lfbinorig[b]) + tuple(res["percentiles"][:, b])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nsrc", type=int, default=20000)
@@ -109,6 +118,10 @@ def main():
                     help="with --deconvolve: every source's posterior mean and spread of its TRUE luminosity over 200 posterior "
                          "draws (deconvolved_luminosities; DESIGN.md section 3.22) written to FILE: ID, lum, lum_e, lum_true, "
                          "lum_true_e")
+    ap.add_argument("--veff-deconvolved", action="store_true",
+                    help="with --deconvolve: print the deconvolved 1/Veff points - the sources' posteriors of the true luminosity "
+                         "binned with the completeness at the true flux, 16 / 50 / 84 %% over 200 posterior draws - next to the "
+                         "plain ones (veff_deconvolved; DESIGN.md section 3.26)")
     ap.add_argument("--predictive-noise", choices=("none", "catalogue"), default=None,
                     help="posterior predictive check of the luminosity histogram over 200 posterior draws (posterior_predictive; "
                          "DESIGN.md sections 3.11, 3.23), p-values per field printed: `none` bins the replicates' true "
@@ -124,6 +137,8 @@ def main():
         ap.error("--veff-band needs the completeness parameters in the fit: not with --fix-comp")
     if args.deconvolved_lums and not args.deconvolve:
         ap.error("--deconvolved-lums needs --deconvolve")
+    if args.veff_deconvolved and not args.deconvolve:
+        ap.error("--veff-deconvolved needs --deconvolve")
     if args.pt and args.until_converged:
         ap.error("--pt and --until-converged are two fits: choose one")
     os.makedirs(args.out, exist_ok=True)
@@ -190,6 +205,8 @@ def main():
         write_integrals(LFmod, os.path.join(args.out, "integrals_%s.dat" % tag))
     if args.deconvolved_lums:
         write_deconvolved_lums(LFmod, args.deconvolved_lums)
+    if args.veff_deconvolved:
+        print_veff_deconvolved(LFmod)
     if args.predictive_noise:
         pp = LFmod.posterior_predictive(seed=11, noise=None if args.predictive_noise == "none" else "catalogue")
         bright = pp["edges"].size // 2

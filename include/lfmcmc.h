@@ -242,6 +242,28 @@ int lf_deconv_wide_info(double *edges, int32_t *nodes, int cap, int *chunk, doub
 int lf_lum_posterior(lf_ctx *ctx, const double *theta, int R, double *m1, double *m2, int *n_used);
 int lf_lum_posterior_info(int *row_tile, int *max_rows);
 
+/* The deconvolved 1/Veff points (csrc/lf_vefftrue.h): the sources' posteriors of the TRUE luminosity
+ * (lf_lum_posterior's node weights p_irk) binned in luminosity with the completeness at the node's TRUE flux, per row of theta,
+ *     values[r][b] = sum_i sum_k [edges[b] <= lum_i + dl_ik < edges[b + 1]] p_irk / (pref0 fc(f_i 10^dl_ik) vol),
+ * dl_ik = (sqrt(2) sigma_i) x_k (one rounded product, one rounded add), the bin of a node searchsorted(edges, L, "right") - 1,
+ * nodes outside [edges[0], edges[nbin]) dropped; a source with sigma_i = 0 is one node at dl = 0 with p = 1 (lf_veff_draws'
+ * term).  FREE takes the row's Flim_f and alpha_C, FIXCOMP and ZEVOL those of lf_set_lum_err.  A row is used when its plain
+ * lnprob is finite: *n_used = R'; an unused row gets NaN in values; out[nq][nbin] holds NumPy's percentiles (method, q: as
+ * lf_lumfunc_quantiles) of every bin over the R' used rows, NaN when R' = 0.  theta[R][ndim], edges[nbin + 1], out, values
+ * (may be NULL): host pointers; synchronous.  No atomics and one fixed order of summation: the same inputs give the same bits,
+ * and a row's values do not depend on R, on its place in the batch or on the other rows; the workspace does not grow with R
+ * (the rows run in groups of lf_veff_true_info's return value).  LF_ERR_ARG with a message, before the device is touched, for a
+ * NULL required pointer, R outside 1..4096, nbin outside 1..1024, edges not finite and strictly ascending, pref0 <= 0 or
+ * vol <= 0, a bad nq, q or method, when no errors are set, and for a context with "skip_grid" or "grid_share" set; the
+ * context stays usable.
+ * lf_veff_true_info: host-only; the largest R and nbin (either may be NULL); returns the rows of a launch group.
+ * lf_veff_true_ms: the device times of the last successful call's stages - the node kernel, the chunk sums, the quantiles
+ * (hipEvents; summed over the groups); LF_ERR_ARG when there is none. */
+int lf_veff_true(lf_ctx *ctx, const double *theta, int R, const double *edges, int nbin, double pref0, double vol, int nq,
+                 const double *q, int method, double *out, double *values, int *n_used);
+int lf_veff_true_info(int *max_rows, int *max_bins);
+int lf_veff_true_ms(double ms[3]);
+
 /* Kernel timing for bench.py: level 1 brackets lf_main, level 2 every launch, with hipEvents on
  * the stream the launch runs on (0 = off; each event pair costs a few microseconds of stream time: the events are
  * barrier packets, and the next launch no longer overlaps the previous one's tail - measured 7.6 us per evaluation

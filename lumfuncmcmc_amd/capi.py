@@ -56,6 +56,7 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_veff_draws_chunk", "lf_set_lum_err", "lf_lnprob_err_batch", "lf_lnprob_err_batch_device", "lf_gauss_hermite",
            "lf_deconv_info", "lf_deconv_wide_info", "lf_lnprob_err_grad_batch", "lf_lnprob_err_grad_batch_device", "lf_sampler_set_likelihood",
            "lf_ptsampler_set_likelihood", "lf_lum_posterior", "lf_lum_posterior_info",
+           "lf_veff_true", "lf_veff_true_info", "lf_veff_true_ms",
            "lf_mock_set_error_model", "lf_mock_draw_err", "lf_mock_hist_err")
 
 _lib = None
@@ -126,6 +127,13 @@ def load():
     lib.lf_lum_posterior.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int)]
     lib.lf_lum_posterior_info.restype = ctypes.c_int
     lib.lf_lum_posterior_info.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.lf_veff_true.restype = ctypes.c_int
+    lib.lf_veff_true.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                 ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int)]
+    lib.lf_veff_true_info.restype = ctypes.c_int
+    lib.lf_veff_true_info.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.lf_veff_true_ms.restype = ctypes.c_int
+    lib.lf_veff_true_ms.argtypes = [_c_double_p]
     lib.lf_deconv_wide_info.restype = ctypes.c_int
     lib.lf_deconv_wide_info.argtypes = [_c_double_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                         _c_double_p, ctypes.POINTER(ctypes.c_int), _c_double_p, ctypes.c_int, _c_double_p, _c_double_p]
@@ -536,6 +544,22 @@ def lum_posterior_info():
     return {"row_tile": rt.value, "max_rows": mr.value}
 
 
+def veff_true_info():
+    """lf_veff_true_info: dict max_rows, max_bins, row_group (the rows of one launch group: the workspace's height).  Touches no
+    GPU."""
+    mr, mb = ctypes.c_int(0), ctypes.c_int(0)
+    rg = load().lf_veff_true_info(ctypes.byref(mr), ctypes.byref(mb))
+    return {"max_rows": mr.value, "max_bins": mb.value, "row_group": rg}
+
+
+def veff_true_ms():
+    """lf_veff_true_ms: the device milliseconds (node kernel, chunk sums, quantiles) of the last lf_veff_true call"""
+    ms = np.zeros(3)
+    if load().lf_veff_true_ms(_ptr(ms)) != LF_OK:
+        raise RuntimeError("lf_veff_true_ms: no successful lf_veff_true call yet")
+    return ms
+
+
 def _ptr(a):
     return a.ctypes.data_as(_c_double_p) if a is not None else None
 
@@ -746,6 +770,24 @@ class LFContext(object):
         used = ctypes.c_int(0)
         self._check(self._lib.lf_lum_posterior(self._h, _ptr(th), th.shape[0], _ptr(m1), _ptr(m2), ctypes.byref(used)))
         return m1, m2, used.value
+
+    def veff_true(self, theta, edges, pref0, vol, q=(16.0, 50.0, 84.0), method=LF_Q_LINEAR):
+        """theta (R, ndim) or (ndim,) host array, 1 <= R <= 4096; edges (nbin + 1,) ascending -> (out (nq, nbin), values
+        (R, nbin), n_used): lf_veff_true, the deconvolved 1/Veff points - every source's posterior of the true luminosity
+        binned with the completeness at the node's true flux, per row (NaN for a row whose plain lnprob is not finite), and
+        NumPy's percentiles q of every bin over the used rows.  method LF_Q_MEDIAN: one row of out, q
+        ignored.  Needs set_lum_err."""
+        th = self._theta(theta)
+        ed = _f64(edges).ravel()
+        nbin = ed.size - 1
+        qa = _f64(np.atleast_1d(q)).ravel() if method == LF_Q_LINEAR else np.zeros(1)
+        nq = qa.size if method == LF_Q_LINEAR else 1
+        out = np.empty((nq, max(nbin, 0)), dtype=np.float64)
+        values = np.empty((th.shape[0], max(nbin, 0)), dtype=np.float64)
+        used = ctypes.c_int(0)
+        self._check(self._lib.lf_veff_true(self._h, _ptr(th), th.shape[0], _ptr(ed), nbin, float(pref0), float(vol), nq, _ptr(qa),
+                                           int(method), _ptr(out), _ptr(values), ctypes.byref(used)))
+        return out, values, used.value
 
     def lnprob_err_torch(self, theta):
         """theta: float64 device tensor (B, ndim) on this context's device; enqueues lf_lnprob_err_batch_device on torch's

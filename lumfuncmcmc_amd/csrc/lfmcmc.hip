@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <string>
 #include <type_traits>
@@ -37,6 +38,7 @@
 #include "lf_pers.h"
 #include "lf_pt.h"
 #include "lf_veffdraws.h"
+#include "lf_vefftrue.h"
 
 namespace {
 
@@ -187,6 +189,9 @@ struct lf_ctx {
     Buf<int> d_lp_caller;
     int lp_nslots = 0;
     Buf<double> d_lumpost;
+    Buf<int> d_vt_inwide;               // lf_vefftrue.h: 1 for the sources of the wide list, in the device's order
+    Buf<double> d_vt_work;              // lf_veff_true's workspace: edges, quantile table, partial sums, values, used rows, out
+    Buf<int> d_vt_slot;                 // ... and the rows' places among the used rows
     hipStream_t stream = nullptr;
     hipStream_t last_stream = nullptr;   // stream of the previous enqueue (workspace is shared)
     bool any_enqueued = false;
@@ -1576,6 +1581,9 @@ int lf_set_lum_err(lf_ctx* c, const double* sigma, int K, const double* logf, co
     for (int64_t i = 0; i < N; ++i) caller[(size_t)i] = (int)c->perm[(size_t)i];
     for (size_t j = 0; j < wl.src.size(); ++j) caller[(size_t)N + j] = (int)c->perm[(size_t)wl.src[j]];
     if ((rc = upload(c, c->d_lp_caller, caller)) != LF_OK) return rc;
+    std::vector<int> in_wide((size_t)N, 0);
+    for (int64_t i : wl.src) in_wide[(size_t)i] = 1;
+    if ((rc = upload(c, c->d_vt_inwide, in_wide)) != LF_OK) return rc;
     c->lp_nslots = (int)caller.size();
     c->deconvc = dc;
     c->deconv_set = true;
@@ -1673,6 +1681,135 @@ int lf_lum_posterior(lf_ctx* c, const double* theta, int R, double* m1, double* 
     LF_HIP(c, hipMemcpyAsync(m1, x.m1, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     LF_HIP(c, hipMemcpyAsync(m2, x.m2, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     LF_HIP(c, hipStreamSynchronize(c->stream));
+    return LF_OK;
+}
+
+static double g_vefft_ms[3] = {-1.0, -1.0, -1.0};      // device times of the last lf_veff_true call's three stages under lf_set_profiling (any context's)
+
+int lf_veff_true_info(int* max_rows, int* max_bins) {
+    if (max_rows) *max_rows = lf::VEFFT_MAX_ROWS;
+    if (max_bins) *max_bins = lf::VEFFT_MAXBIN;
+    return lf::VEFFT_ROWS;
+}
+
+int lf_veff_true_ms(double ms[3]) {
+    if (!ms) return LF_ERR_ARG;
+    for (int s = 0; s < 3; ++s) ms[s] = g_vefft_ms[s];
+    return g_vefft_ms[0] < 0.0 ? LF_ERR_ARG : LF_OK;
+}
+
+namespace {
+// the events around every launch of lf_veff_true: made as they are recorded, destroyed with the call
+struct Stamps {
+    std::vector<hipEvent_t> ev;
+    ~Stamps() {
+        for (hipEvent_t e : ev) hipEventDestroy(e);
+    }
+    hipError_t mark(hipStream_t s) {
+        hipEvent_t e;
+        hipError_t rc = hipEventCreate(&e);
+        if (rc != hipSuccess) return rc;
+        ev.push_back(e);
+        return hipEventRecord(e, s);
+    }
+};
+}  // namespace
+
+int lf_veff_true(lf_ctx* c, const double* theta, int R, const double* edges, int nbin, double pref0, double vol, int nq, const double* q,
+                 int method, double* out, double* values, int* n_used) {
+    using namespace lf;
+    // every argument is checked before the device is touched
+    int rc = family_check(c, "lf_veff_true", true, theta, R, out);
+    if (rc != LF_OK) return rc;
+    auto bad = [&](const std::string& m) {
+        c->err = "lf_veff_true: " + m;
+        return (int)LF_ERR_ARG;
+    };
+    if (!edges || !n_used) return bad("NULL pointer");
+    if (R > VEFFT_MAX_ROWS) return bad("R outside 1.." + std::to_string(VEFFT_MAX_ROWS));
+    if (nbin < 1 || nbin > VEFFT_MAXBIN) return bad("nbin outside 1.." + std::to_string(VEFFT_MAXBIN));
+    for (int b = 0; b <= nbin; ++b)
+        if (!std::isfinite(edges[b]) || (b > 0 && !(edges[b] > edges[b - 1]))) return bad("edges must be finite and strictly ascending");
+    if (!(pref0 > 0.0) || !(vol > 0.0) || !std::isfinite(pref0) || !std::isfinite(vol)) return bad("pref0 and vol must be finite and > 0");
+    if (!lfh::quantiles(R, nq, q, method, BANDS_MAXQ).ok) return bad("bad nq, q or method");
+    if ((rc = stage_theta(c, theta, R)) != LF_OK) return rc;
+    if ((rc = src_chunk_table(c)) != LF_OK) return rc;
+    // the rows' plain lnprob decides which are used: R' is counted here, the kernels read the same array
+    double* d_lnp = c->d_outB;
+    if ((rc = enqueue(c, c->d_theta, R, d_lnp, nullptr, nullptr, c->stream)) != LF_OK) return rc;
+    if ((rc = fetch(c, c->h_out, d_lnp, (size_t)R)) != LF_OK) return rc;
+    std::vector<int> slot((size_t)R, 0);
+    int used = 0;
+    for (int r = 0; r < R; ++r) {
+        slot[(size_t)r] = used;
+        used += std::isfinite(c->h_out[r]) ? 1 : 0;
+    }
+    *n_used = used;
+    for (double& t : g_vefft_ms) t = -1.0;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const size_t nb = (size_t)nbin;
+    if (used == 0) {
+        std::fill(out, out + (size_t)nq * nb, nan);
+        if (values) std::fill(values, values + (size_t)R * nb, nan);
+        return LF_OK;
+    }
+    const lfh::Quantiles qt = lfh::quantiles(used, nq, q, method, BANDS_MAXQ);
+    VeffTrueArgs x{};
+    x.d = deconv_args(c, c->d_theta, d_lnp, nullptr);
+    if (c->wide.n) x.w = deconv_wide_args(c, x.d);
+    x.n0 = c->N > 0 ? c->src_chunks.n : 0, x.nw = c->wide.n;
+    x.in_wide = c->d_vt_inwide;
+    x.nbin = nbin;
+    x.pv = pref0 * vol;
+    const size_t nch = (size_t)(x.n0 + x.nw);
+    // one workspace on the context, grown when a call needs more: edges | quantile table | partial | values | used | out
+    const size_t o_q = nb + 1, o_part = o_q + qt.tab.size(), o_val = o_part + nch * VEFFT_ROWS * nb, o_used = o_val + (size_t)R * nb,
+                 o_out = o_used + (size_t)used * nb, need = o_out + (size_t)nq * nb;
+    if (need > c->d_vt_work.size() && (rc = grow(c, c->d_vt_work, need)) != LF_OK) return rc;
+    if ((size_t)R > c->d_vt_slot.size() && (rc = grow(c, c->d_vt_slot, (size_t)R)) != LF_OK) return rc;
+    double* wk = c->d_vt_work;
+    LF_HIP(c, hipMemcpyAsync(wk, edges, (nb + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    LF_HIP(c, hipMemcpyAsync(wk + o_q, qt.tab.data(), qt.tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    LF_HIP(c, hipMemcpyAsync(c->d_vt_slot, slot.data(), (size_t)R * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    LF_HIP(c, hipStreamSynchronize(c->stream));            // (the sources of the copies are this call's own)
+    x.edges = wk, x.partial = wk + o_part, x.values = wk + o_val, x.used = wk + o_used, x.slot = c->d_vt_slot;
+    double *d_q = wk + o_q, *d_used = wk + o_used, *d_out = wk + o_out, *d_val = wk + o_val;
+    // the stages' times are taken only under lf_set_profiling: an event pair around every launch keeps it from overlapping the
+    // one before
+    const bool timed = c->profiling > 0;
+    Stamps st;
+    const unsigned bblocks = (unsigned)((nbin + BLOCK - 1) / BLOCK);
+    const unsigned lds = (unsigned)vefft_dyn_lds_bytes(nbin);
+    hipError_t he = hipSuccess;
+    launch_rows(c->kc.variant, 1, [&](auto v, int, int) {
+        for (int row0 = 0; row0 < R && he == hipSuccess; row0 += VEFFT_ROWS) {
+            const unsigned nr = (unsigned)std::min(VEFFT_ROWS, R - row0);
+            if (timed && (he = st.mark(c->stream)) != hipSuccess) break;
+            if (nch > 0) hipLaunchKernelGGL(lf_vefftrue_part<v()>, dim3((unsigned)nch, nr), dim3(BLOCK), lds, c->stream, x, row0);
+            if (timed && (he = st.mark(c->stream)) != hipSuccess) break;
+            hipLaunchKernelGGL(lf_vefftrue_reduce, dim3(bblocks, nr), dim3(BLOCK), 0, c->stream, x, row0);
+        }
+    });
+    LF_HIP(c, he);
+    LF_HIP(c, hipGetLastError());
+    if (timed) LF_HIP(c, st.mark(c->stream));
+    const int G = BANDS_SLOTS >> qt.lg;
+    hipLaunchKernelGGL(veffd_quant, dim3((unsigned)((nbin + G - 1) / G)), dim3(BANDS_THREADS), 0, c->stream, d_used, used, qt.lg, nbin, d_q,
+                       nq, method == LF_Q_MEDIAN ? 1 : 0, d_out);
+    LF_HIP(c, hipGetLastError());
+    if (timed) LF_HIP(c, st.mark(c->stream));
+    LF_HIP(c, hipMemcpyAsync(out, d_out, (size_t)nq * nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (values) LF_HIP(c, hipMemcpyAsync(values, d_val, (size_t)R * nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    LF_HIP(c, hipStreamSynchronize(c->stream));
+    // part: the even intervals, reduce: the odd ones (the last ends at the quantile stage's first stamp), then the quantiles
+    double ms[3] = {0.0, 0.0, 0.0};
+    const size_t ne = st.ev.size();
+    for (size_t i = 0; i + 1 < ne; ++i) {
+        float t = 0.0f;
+        LF_HIP(c, hipEventElapsedTime(&t, st.ev[i], st.ev[i + 1]));
+        ms[i + 2 == ne ? 2 : (i & 1)] += t;
+    }
+    for (int s = 0; s < 3 && timed; ++s) g_vefft_ms[s] = ms[s];
     return LF_OK;
 }
 

@@ -212,10 +212,14 @@ def check_sigma(sigma, n, K=None, unchecked=False):
     return s
 
 
-def _row_terms(inp, sigma, th, x, lnw, moments=False):
+def _row_terms(inp, sigma, th, x, lnw, moments=False, nodes=False):
     """Delta_i [N] of one theta row (catalogue order); no prior test: what the formulas give.  moments=True: instead the
     posterior moments of delta over the nodes (csrc/lf_lumpost.h), (e1 [N], e2 [N], e1_abs [N]) = sum_k p_k delta_k, sum_k p_k
-    delta_k^2 and sum_k p_k |delta_k|, their numerators carried by the same running maximum; 0 where sigma = 0."""
+    delta_k^2 and sum_k p_k |delta_k|, their numerators carried by the same running maximum; 0 where sigma = 0.  nodes=True:
+    instead the nodes themselves (csrc/lf_vefftrue.h), (p [K, N], L [K, N], l [K, N]): the weight p_k = exp(a_k - m) / sum_j
+    exp(a_j - m) with the loop's maximum and sum (0 for a node whose exponent is -inf, or when the sum is not > 0), the node's
+    true luminosity lum + dl - one rounded product, one rounded add - and l at its true flux; a source with sigma = 0 is one
+    node: p = (1, 0, ..), every L = lum."""
     v = inp["variant"]
     p = G._split(inp, th)
     fi = np.asarray(inp["field_ind"])
@@ -241,11 +245,16 @@ def _row_terms(inp, sigma, th, x, lnw, moments=False):
     m = np.full(N, -np.inf)
     acc = np.zeros(N)
     num = np.zeros((3, N))             # moments: the weighted numerators of delta, delta^2, |delta|
+    if nodes:
+        ak, Lk, lk = (np.empty((len(x), N)) for _ in range(3))
     for k in range(len(x)):
         dl = s2 * x[k]
         em = np.expm1(LN10 * dl)
-        a = lnw[k] + ((c1l * dl - t * em) + (_lcomp(y0 + dl, v0 * (em + 1.0), aC) - l0))
+        lc = _lcomp(y0 + dl, v0 * (em + 1.0), aC)
+        a = lnw[k] + ((c1l * dl - t * em) + (lc - l0))
         skip = a == -np.inf
+        if nodes:
+            ak[k], Lk[k], lk[k] = a, lum + dl, lc
         d = a - m
         e = np.exp(-np.abs(d))
         up = d > 0.0
@@ -256,6 +265,12 @@ def _row_terms(inp, sigma, th, x, lnw, moments=False):
                 num[j] = np.where(skip, num[j], np.where(up, num[j] * e + q, num[j] + e * q))
         acc = np.where(skip, acc, acc_n)
         m = np.where(skip, m, m_n)
+    if nodes:
+        on = sigma > 0.0
+        pk = np.where((ak == -np.inf) | ~(acc > 0.0), 0.0, np.exp(ak - m) / acc)
+        pk = np.where(on, pk, 0.0)
+        pk[0] = np.where(on, pk[0], 1.0)
+        return pk, Lk, lk
     if moments:
         on = sigma > 0.0
         return tuple(np.where(on, num[j] / acc, 0.0) for j in range(3))
@@ -329,6 +344,61 @@ def lum_posterior(inp, sigma, theta, K=None, wide=False, terms=False):
                 tot[:, idx] += _row_terms(sub, sigma[idx], row, x, lnw, moments=True)
         out = np.where(sigma > 0.0, tot / len(used) if len(used) else np.full_like(tot, np.nan), 0.0)
     return (out[0], out[1], len(used)) + ((out[2],) if terms else ())
+
+
+def veff_true(inp, sigma, theta, edges, pref0, vol, K=None, wide=False):
+    """The deconvolved 1/Veff points (csrc/lf_vefftrue.h): theta (R, ndim) or (ndim,), edges (nbin + 1,)
+    ascending -> (values (R, nbin), n_used).  Per row, every source's posterior of its true luminosity - the weights p_k on
+    the nodes L_k = lum + dl_k of the source's rule (_rules; a source with sigma = 0: one node at lum with p = 1) - is binned
+    with the completeness at the node's TRUE flux:
+        values[r][b] = sum_i sum_k [edges[b] <= L_ik < edges[b + 1]] p_irk exp(-l_irk) / (pref0 vol),
+    exp(-l) being 1 / fc of the modified Fleming curve.  The bin of a node is searchsorted(edges, L, side="right") - 1; nodes
+    outside [edges[0], edges[nbin]) are dropped.  A row is used when its plain lnprob (grad.py's twin) is finite; an unused row
+    is NaN.  The posterior is binned as the rule's discrete measure: one source's bin masses are granular at the node spacing,
+    the sum over sources spread against the edges is not (the section has the measured figures)."""
+    K = DEFAULT_ORDER if K is None else int(K)
+    if K not in ORDERS:
+        raise ValueError("deconvolve_order must be one of %s" % (ORDERS,))
+    th = np.atleast_2d(np.asarray(theta, dtype=np.float64))
+    if th.shape[1] != G.ndim_of(inp):
+        raise ValueError("theta must be (R, %d), got %s" % (G.ndim_of(inp), th.shape))
+    ed = np.ascontiguousarray(edges, dtype=np.float64).ravel()
+    nbin = ed.size - 1
+    if nbin < 1 or not np.all(np.isfinite(ed)) or np.any(np.diff(ed) <= 0.0):
+        raise ValueError("edges must be finite and strictly ascending, two at least")
+    if not (pref0 > 0.0 and vol > 0.0):
+        raise ValueError("pref0 and vol must be > 0")
+    sigma = check_sigma(sigma, len(inp["lum"]), K, True)
+    use = np.isfinite(np.atleast_1d(G.lnprob_grad(inp, th)[0]))
+    values = np.full((len(th), nbin), np.nan)
+    rules = _rules(inp, sigma, K, wide)
+    pv = pref0 * vol
+    with np.errstate(all="ignore"):
+        for r in np.flatnonzero(use):
+            acc = np.zeros(nbin)
+            for sub, idx, x, lnw in rules:
+                sg = sigma if idx is None else sigma[idx]
+                p, L, l = _row_terms(sub, sg, th[r], x, lnw, nodes=True)
+                b = np.searchsorted(ed, L, side="right") - 1
+                ok = (b >= 0) & (b < nbin) & (p > 0.0)
+                acc += np.bincount(b[ok], weights=p[ok] * (np.exp(-l[ok]) / pv), minlength=nbin)
+            values[r] = acc
+    return values, int(use.sum())
+
+
+def veff_true_quantiles(inp, sigma, theta, edges, pref0, vol, q=(16.0, 50.0, 84.0), method="linear", K=None, wide=False):
+    """veff_true and over its used rows np.percentile(q) per bin (method "linear") or np.median (method "median": one row):
+    (out (nq, nbin), values (R, nbin), n_used); no used row: NaN everywhere."""
+    if method not in ("linear", "median"):
+        raise ValueError("method must be 'linear' or 'median'")
+    values, used = veff_true(inp, sigma, theta, edges, pref0, vol, K=K, wide=wide)
+    qa = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    nq = qa.size if method == "linear" else 1
+    if used == 0:
+        return np.full((nq, values.shape[1]), np.nan), values, 0
+    rows = values[~np.all(np.isnan(values), axis=1)]              # (an unused row is NaN throughout)
+    out = np.percentile(rows, qa, axis=0) if method == "linear" else np.median(rows, axis=0)[None]
+    return out, values, used
 
 
 def _lcomp_grad(y, v, aC, kappa):

@@ -606,6 +606,34 @@ class _Base(object):
             spread = np.sqrt(np.maximum(m2 - m1 * m1, 0.0))
         return {"lum_true": np.asarray(self.lum, dtype=np.float64) + m1, "lum_true_e": spread, "shift": m1, "n_used": int(used)}
 
+    def veff_deconvolved(self, percentiles=(16, 50, 84), ndraws=200, lnprobcut=7.5, method="linear", device=None):
+        """The deconvolved 1/Veff points: per posterior draw, every source's posterior of its TRUE
+        luminosity under the flux-error-convolved model, binned on VeffLF's bins with the completeness at the true flux, and
+        the percentiles of every bin over the draws whose plain lnprob is finite (ndraws random draws, taken as lf_percentiles
+        takes them; at most 4096).  Returns a dict: Lavg (nbins,), percentiles (nq, nbins) and values (ndraws, nbins; NaN for an
+        unused draw) in dn/dlogL like lfbinorig, n_used, and var_post = np.var(values of the used draws, axis=0, ddof=1) - the
+        posterior part of the points' variance; NaN when fewer than two draws are used (no variance can be formed).  Needs deconvolve=True (whose min_comp_frac <= 0.001 makes the volume one
+        scalar).  device=True: the GPU (lf_veff_true), False: NumPy (deconv.veff_true_quantiles); None = the GPU when this
+        object already holds a device context.  self.lum, var and lfbinorig are not touched."""
+        if not self.deconvolve:
+            raise ValueError("veff_deconvolved needs an object made with deconvolve=True")
+        from . import deconv
+        lfbands._method(method)
+        rows = self._posterior_rows(ndraws, lnprobcut)[:, :-1]
+        edges, Lavg, dL, _ = veff.luminosity_bins(self.lum, self.nbins)
+        vol = float(veff.comoving_volume(self.dVdzf, self.zmin, self.zmax))
+        pref0 = sum(self.Omega_0) / hs.SQARCSEC
+        if self._band_device(device):
+            out, values, used = self.context().veff_true(rows, edges, pref0, vol, q=percentiles, method=lfbands.METHODS[method])
+        else:
+            out, values, used = deconv.veff_true_quantiles(self.kernel_inputs(), np.asarray(self.lum_e, dtype=np.float64), rows, edges,
+                                                           pref0, vol, q=percentiles, method=method, K=self.deconvolve_order,
+                                                           wide=self.deconvolve_wide)
+        values = values / dL
+        ok = ~np.all(np.isnan(values), axis=1)
+        return {"Lavg": Lavg, "percentiles": out / dL, "values": values, "n_used": int(used),
+                "var_post": np.var(values[ok], axis=0, ddof=1) if ok.sum() > 1 else np.full(self.nbins, np.nan)}
+
     def _mock_generator(self, device):
         """MockGenerator (GPU) or MockTwin (NumPy) over this object's unsharded kernel_inputs(); device=None = the GPU when
         this object already holds a context.  The device generator is kept for the object's configuration."""
