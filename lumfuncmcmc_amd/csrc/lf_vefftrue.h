@@ -7,6 +7,9 @@
 //     values[r][b] = sum_i sum_k [edges[b] <= L_ik < edges[b + 1]] p_irk exp(-l_irk) / (pref0 vol)
 // l_irk = ln fc^(1/d) at the node's TRUE flux, the value comp_form<false> gives inside the node loop: exp(-l) is 1 / fc of the
 // modified Fleming curve.  A source with sigma_i = 0 is one node at dl = 0 with p = 1.  A node whose exponent is -inf has p = 0.
+// The product p exp(-l) is formed in ONE exponent, exp(bv_k - m) / sum with bv_k = av_k without its + l_k: for a node far below
+// Flim (l of -1e3 .. -1e5) exp(av_k - m) is 0 or subnormal and exp(-l) is +inf while their product is an ordinary number
+// (DESIGN.md section 3.27).
 //
 // lf_vefftrue_part    grid (narrow chunks + wide chunks, rows of the launch's group), 256 threads: block (c, j) takes chunk c
 //                     of lf_lumpost_part's tables and row row0 + j.  The node table, the edges and one histogram per wave go
@@ -165,12 +168,13 @@ __global__ __launch_bounds__(BLOCK) void lf_vefftrue_part(VeffTrueArgs x, int ro
                     const double L = vefft_node(s.lum, s.s2, nd[k], dl);
                     const double em = expm1(LF_LN10 * dl);
                     const double l = comp_form<false>(w.aC, w.aC_ln, w.kc2, s.y0 + dl, s.v0 * (em + 1.0)).l;
-                    av[p] = nd[K + k] + ((w.c1l * dl - s.t * em) + (l - s.l0));
-                    val[p] = exp(-l) / x.pv;
+                    const double sch = w.c1l * dl - s.t * em;
+                    av[p] = nd[K + k] + (sch + (l - s.l0));
+                    val[p] = nd[K + k] + (sch - s.l0);                 // av - l, formed without l
                     bin[p] = vefft_bin(ed, nbin, L);
                 } else if (s.kind == 1 && k == 0) {
                     av[p] = 0.0;
-                    val[p] = exp(-s.l0) / x.pv;
+                    val[p] = -s.l0;
                     bin[p] = vefft_bin(ed, nbin, s.lum);
                 }
                 m = fmax(m, av[p]);
@@ -187,7 +191,8 @@ __global__ __launch_bounds__(BLOCK) void lf_vefftrue_part(VeffTrueArgs x, int ro
 #pragma unroll
             for (int p = 0; p < VEFFT_PASSES; ++p) {
                 if (p >= npass) continue;
-                double v = e[p] > 0.0 ? (e[p] / tot) * val[p] : 0.0;      // (p = 0 adds exactly 0, whatever 1 / fc is)
+                // p exp(-l) / pv in one exponent; a node whose exponent is -inf adds exactly 0
+                double v = av[p] == -HUGE_VAL ? 0.0 : (exp(val[p] - m) / tot) / x.pv;
                 const int b = bin[p];
                 // the segment's sum to its last lane (a source's lanes: k0 >= off keeps a half-wave to itself)
 #pragma unroll

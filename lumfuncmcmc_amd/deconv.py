@@ -219,7 +219,10 @@ def _row_terms(inp, sigma, th, x, lnw, moments=False, nodes=False):
     instead the nodes themselves (csrc/lf_vefftrue.h), (p [K, N], L [K, N], l [K, N]): the weight p_k = exp(a_k - m) / sum_j
     exp(a_j - m) with the loop's maximum and sum (0 for a node whose exponent is -inf, or when the sum is not > 0), the node's
     true luminosity lum + dl - one rounded product, one rounded add - and l at its true flux; a source with sigma = 0 is one
-    node: p = (1, 0, ..), every L = lum."""
+    node: p = (1, 0, ..), every L = lum.  nodes="product": one more, r [K, N] = p_k exp(-l_k) formed in ONE exponent,
+    exp(b_k - m) / sum with b_k = a_k without its + l_k (far below Flim exp(a_k - m) is 0 or subnormal and exp(-l_k) is +inf
+    while the product is an ordinary number); exactly 0 where p is 0 by rule (an exponent of -inf, the other nodes of a source
+    with sigma = 0)."""
     v = inp["variant"]
     p = G._split(inp, th)
     fi = np.asarray(inp["field_ind"])
@@ -246,15 +249,16 @@ def _row_terms(inp, sigma, th, x, lnw, moments=False, nodes=False):
     acc = np.zeros(N)
     num = np.zeros((3, N))             # moments: the weighted numerators of delta, delta^2, |delta|
     if nodes:
-        ak, Lk, lk = (np.empty((len(x), N)) for _ in range(3))
+        ak, Lk, lk, bk = (np.empty((len(x), N)) for _ in range(4))
     for k in range(len(x)):
         dl = s2 * x[k]
         em = np.expm1(LN10 * dl)
         lc = _lcomp(y0 + dl, v0 * (em + 1.0), aC)
-        a = lnw[k] + ((c1l * dl - t * em) + (lc - l0))
+        sch = c1l * dl - t * em
+        a = lnw[k] + (sch + (lc - l0))
         skip = a == -np.inf
         if nodes:
-            ak[k], Lk[k], lk[k] = a, lum + dl, lc
+            ak[k], Lk[k], lk[k], bk[k] = a, lum + dl, lc, lnw[k] + (sch - l0)
         d = a - m
         e = np.exp(-np.abs(d))
         up = d > 0.0
@@ -270,6 +274,11 @@ def _row_terms(inp, sigma, th, x, lnw, moments=False, nodes=False):
         pk = np.where((ak == -np.inf) | ~(acc > 0.0), 0.0, np.exp(ak - m) / acc)
         pk = np.where(on, pk, 0.0)
         pk[0] = np.where(on, pk[0], 1.0)
+        if nodes == "product":
+            rk = np.where((ak == -np.inf) | ~(acc > 0.0), 0.0, np.exp(bk - m) / acc)
+            rk = np.where(on, rk, 0.0)
+            rk[0] = np.where(on, rk[0], np.exp(-l0))
+            return pk, Lk, lk, rk
         return pk, Lk, lk
     if moments:
         on = sigma > 0.0
@@ -378,10 +387,10 @@ def veff_true(inp, sigma, theta, edges, pref0, vol, K=None, wide=False):
             acc = np.zeros(nbin)
             for sub, idx, x, lnw in rules:
                 sg = sigma if idx is None else sigma[idx]
-                p, L, l = _row_terms(sub, sg, th[r], x, lnw, nodes=True)
+                p, L, l, pf = _row_terms(sub, sg, th[r], x, lnw, nodes="product")
                 b = np.searchsorted(ed, L, side="right") - 1
-                ok = (b >= 0) & (b < nbin) & (p > 0.0)
-                acc += np.bincount(b[ok], weights=p[ok] * (np.exp(-l[ok]) / pv), minlength=nbin)
+                ok = (b >= 0) & (b < nbin) & (pf > 0.0)
+                acc += np.bincount(b[ok], weights=pf[ok] / pv, minlength=nbin)
             values[r] = acc
     return values, int(use.sum())
 

@@ -418,8 +418,10 @@ def deconv_slots_from_twin(variant, th, g):
     return out
 
 
-def deconv_item_mp(variant, th, s, i, x, lnw):
-    """(Delta_i, its yardstick, slots[4], yards[4], p_k, a_k) of source i under row th at 40 digits"""
+def deconv_item_mp(variant, th, s, i, x, lnw, full=False):
+    """(Delta_i, its yardstick, slots[4], yards[4], p_k, a_k) of source i under row th at 40 digits; full=True: one more, a
+    dict of what tests/lf_convproblib.py judges the other copies of the node loop by - "A" (the yardsticks' largest exponent
+    addend), "adds" (each node's own largest), "dl" (delta_k), "l" (l at the node's true flux), "l0" (at the catalogued flux)"""
     Ls, _, al, flim, aC = _row_parts(variant, False, th)
     if variant != FREE:
         flim, aC = FLIM0, ALPHA0
@@ -439,11 +441,12 @@ def deconv_item_mp(variant, th, s, i, x, lnw):
     v0 = mpf(s["U"][i]) * mp.exp(MLN10 * kap / aC) / flim
     r0 = comp_mp(aC, y0, v0, kap)
     s2 = mp.sqrt(2) * mpf(s["sigma"][i])
-    a, q, qa, adds = [], [], [], []
+    a, q, qa, adds, lk = [], [], [], [], []
     for k in range(len(x)):
         dl = s2 * mpf(x[k])
         em = mp.expm1(MLN10 * dl)
         rk = comp_mp(aC, y0 + dl, v0 * (1 + em), kap)
+        lk.append(rk[0])
         a.append(mpf(lnw[k]) + c1l * dl - t * em + rk[0] - r0[0])
         adds.append(max(abs(c1l * dl), abs(tc * em), abs(rk[0]), abs(r0[0]), abs(mpf(lnw[k]))))
         q.append((dl, em, rk[1], rk[2]))
@@ -468,7 +471,8 @@ def deconv_item_mp(variant, th, s, i, x, lnw):
         else:
             slots += [mp.mpf(0)] * 2
             mags += [mp.mpf(0)] * 2
-    return Dl, float(u * (abs(Dl) + 1 + A)), slots, [float(u * m * (1 + A)) for m in mags], p, a
+    out = (Dl, float(u * (abs(Dl) + 1 + A)), slots, [float(u * m * (1 + A)) for m in mags], p, a)
+    return out + ({"A": A, "dl": [qk[0] for qk in q], "l": lk, "l0": r0[0], "adds": adds},) if full else out
 
 
 @functools.lru_cache(None)

@@ -15,7 +15,7 @@ MAXBIN, KMAX, ROW_BYTES = 1024, 144, 176
 LDS = 2 * KMAX * 8 + ROW_BYTES                                        # static
 DYN = lambda nbin: (((nbin + 2) & ~1) + 4 * nbin) * 8                # noqa: E731  (dynamic: edges, padded to an even count, four histograms)
 # variant (LF_FREE 0, LF_FIXCOMP 1, LF_ZEVOL 2): VGPRs, SGPRs, occupancy (waves per SIMD)
-PINNED = {0: (82, 100, 5), 1: (82, 100, 5), 2: (82, 100, 5)}
+PINNED = {0: (84, 100, 5), 1: (84, 100, 5), 2: (82, 100, 5)}
 
 
 @pytest.fixture(scope="module")
