@@ -50,11 +50,11 @@ def write_integrals(LFmod, path):
     tableio.write_fixed_width_two_line(path, cols, labels, formats={l: ("%0.4f" if l == "z" else "%0.6e") for l in labels})
 
 
-def write_veff_band(LFmod, path):
+def write_veff_band(LFmod, path, volumes="fixed"):
     """The 1/Veff points with the band the completeness posterior gives them (veff_percentiles) next
-    to the bootstrap error of the catalogue alone."""
+    to the bootstrap error of the catalogue alone.  volumes "per_draw": z_max per source and draw (section 3.29)."""
     np.random.seed(4)
-    band = LFmod.veff_percentiles(percentiles=(16, 50, 84))
+    band = LFmod.veff_percentiles(percentiles=(16, 50, 84), volumes=volumes)
     labels = ["Luminosity", "BinLF", "BinLFErr", "BinLF_16", "BinLF_50", "BinLF_84", "BinLFErrComp"]
     tableio.write_fixed_width_two_line(path, [band["Lavg"], LFmod.lfbinorig, np.sqrt(LFmod.var)] + list(band["percentiles"]) +
                                        [np.sqrt(band["var_comp"])], labels)
@@ -102,6 +102,9 @@ def main():
     ap.add_argument("--veff-band", action="store_true",
                     help="also write the 1/Veff points with their 16 / 50 / 84 %% band over the completeness posterior and "
                          "sqrt(var_comp) (veff_percentiles; DESIGN.md section 3.17; not with --fix-comp)")
+    ap.add_argument("--veff-volumes", choices=("fixed", "per_draw"), default="fixed",
+                    help="with --veff-band: the sources' volumes at the current Flim and alpha for every draw (fixed), or out to "
+                         "the z_max of each draw's own flux cut (per_draw; DESIGN.md section 3.29)")
     ap.add_argument("--deconvolve", action="store_true",
                     help="fit the likelihood convolved with the catalogue's flux errors (Eddington-bias correction, deconvolve=True; "
                          "DESIGN.md section 3.18; errors above 0.09 dex are refused; --until-converged and --pt run the device "
@@ -217,7 +220,7 @@ def main():
             print("  field %d: %6d %8.1f %.3f   bright: %6d %8.1f %.3f" % (f, pp["observed_total"][f], np.median(pp["replicated_total"][:, f]),
                                                                          pp["p_upper_total"][f], ob, np.median(rb), np.mean(rb >= ob)))
     if args.veff_band:
-        write_veff_band(LFmod, os.path.join(args.out, "veffband_%s.dat" % tag))
+        write_veff_band(LFmod, os.path.join(args.out, "veffband_%s.dat" % tag), volumes=args.veff_volumes)
     print("wrote", sorted(os.listdir(args.out)))
     LFmod.close()
 

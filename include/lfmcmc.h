@@ -562,11 +562,33 @@ int lf_veff_draws(int device, int64_t n, const double *flux, const int32_t *fiel
                   int32_t nq, const double *q, int32_t method, double *out, double *values);
 
 /* ms[3]: device times in ms of the three stages (per-chunk sums, per-bin sums, quantiles) of the most recent successful
- * lf_veff_draws call in this process (hipEvents; measurement only).  LF_ERR_ARG when there is none. */
+ * lf_veff_draws or lf_veff_draws_zmax call in this process (hipEvents; measurement only).  LF_ERR_ARG when there is none. */
 int lf_veff_draws_ms(double *ms);
 
 /* Sources per chunk of lf_veff_draws's fixed summation order (VEFFD_CHUNK of csrc/lf_veffdraws.h). */
 int lf_veff_draws_chunk(void);
+
+/* lf_veff_draws with every source's volume ending at the z_max of the DRAW's own flux cut (csrc/lf_veffdraws.h; DESIGN.md
+ * section 3.29): for source i and draw r the luminosity distance at which the source would be seen at the cut is
+ *   D_ir = dist[i] * fmin[r][field_i]^(-1/2)  [Mpc],   dist[i] = sqrt(L_i / 4 pi) / Mpc_cm,   fmin[R][nf] in erg cm^-2 s^-1,
+ * one rounded product, and vol_i of lf_veff_draws' weight becomes V(D_ir), the comoving volume between zmin and
+ * min(zmax, DL^-1(D_ir)), evaluated on the device from the table (vt_head, vt_zc, vt_rec) that lumfuncmcmc_amd/voltable.py
+ * builds and validates against the host's integral:
+ *   vt_head[8]   D_0 = DL(zmin), D_K = DL(zmax), V_total, 32 / (D_K - D_0), the first node of dV/dz above zmin, 1 / the nodes'
+ *                spacing, 0, 0
+ *   vt_zc[32][8] z = DL^-1(D) on 32 equal pieces of [D_0, D_K]: coefficients in t = (D - D_0) vt_head[3] - piece, constant first
+ *   vt_rec[vt_nrec][8]  one record per interval between the knots zmin < nodes < zmax: D_k, D_k+1, t_k, V(t_k), V(t_k+1),
+ *                dV/dz(t_k), half its slope, 0
+ * D >= D_K (fmin = 0 is legal and means D = +inf) gives exactly V_total - with every fmin 0 the values are lf_veff_draws'
+ * with vol = NULL and vol_all = V_total, bit for bit; D <= D_0 gives 0 and the source drops out of that draw.  Everything
+ * else - the sums' fixed order, the quantiles, out and values, the argument checks - is lf_veff_draws'.  In addition
+ * LF_ERR_ARG, before the device is touched, for a NULL dist, fmin or table pointer, a dist or fmin that is not finite or is
+ * negative, and a malformed table (a non-finite entry, edges that do not increase strictly from D_0 to D_K, volumes that
+ * decrease or do not run from 0 to V_total > 0).  lf_veff_draws_ms reports the stages of whichever of the two ran last. */
+int lf_veff_draws_zmax(int device, int64_t n, const double *flux, const int32_t *field, const double *dist, double pref0,
+                       double fcmin, const int32_t *bin_of, int32_t nbin, int32_t nf, int32_t R, const double *draws,
+                       const double *fmin, const double *vt_head, const double *vt_zc, const double *vt_rec, int64_t vt_nrec,
+                       int32_t nq, const double *q, int32_t method, double *out, double *values);
 
 /* Mock catalogues drawn from the model on the device (csrc/lf_mock.h).  The intensity is the
  * likelihood's own interpolant: the trapezoid sum of piece B over the integration grid is exactly the integral of

@@ -53,7 +53,7 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_mock_destroy", "lf_mock_counts", "lf_mock_draw", "lf_mock_hist", "lf_mock_last_error", "lf_chain_diag",
            "lf_sampler_diag", "lf_ptsampler_diag", "lf_chain_window", "lf_diag_last", "lf_lnprob_grad_batch",
            "lf_lnprob_grad_batch_device", "lf_lumfunc_integral_quantiles", "lf_lumfunc_integral_quantiles_ms", "lf_veff_draws", "lf_veff_draws_ms",
-           "lf_veff_draws_chunk", "lf_set_lum_err", "lf_lnprob_err_batch", "lf_lnprob_err_batch_device", "lf_gauss_hermite",
+           "lf_veff_draws_chunk", "lf_veff_draws_zmax", "lf_set_lum_err", "lf_lnprob_err_batch", "lf_lnprob_err_batch_device", "lf_gauss_hermite",
            "lf_deconv_info", "lf_deconv_wide_info", "lf_lnprob_err_grad_batch", "lf_lnprob_err_grad_batch_device", "lf_sampler_set_likelihood",
            "lf_ptsampler_set_likelihood", "lf_lum_posterior", "lf_lum_posterior_info",
            "lf_veff_true", "lf_veff_true_info", "lf_veff_true_ms",
@@ -173,6 +173,11 @@ def load():
     lib.lf_veff_draws.argtypes = [ctypes.c_int, ctypes.c_int64, _c_double_p, ctypes.POINTER(ctypes.c_int32), _c_double_p, ctypes.c_double,
                                   ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
                                   ctypes.c_int32, _c_double_p, ctypes.c_int32, _c_double_p, ctypes.c_int32, _c_double_p, _c_double_p]
+    lib.lf_veff_draws_zmax.restype = ctypes.c_int
+    lib.lf_veff_draws_zmax.argtypes = [ctypes.c_int, ctypes.c_int64, _c_double_p, ctypes.POINTER(ctypes.c_int32), _c_double_p, ctypes.c_double,
+                                       ctypes.c_double, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                       _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int32,
+                                       _c_double_p, ctypes.c_int32, _c_double_p, _c_double_p]
     lib.lf_veff_draws_ms.restype = ctypes.c_int
     lib.lf_veff_draws_ms.argtypes = [_c_double_p]
     lib.lf_veff_draws_chunk.restype = ctypes.c_int
@@ -478,9 +483,43 @@ def veff_draws_device(flux, field, vol, pref0, fcmin, bin_of, nbin, draws, q=(16
     return out, val
 
 
+def veff_draws_zmax_device(flux, field, dist, pref0, fcmin, bin_of, nbin, draws, fmin, table, q=(16.0, 50.0, 84.0), method=LF_Q_LINEAR,
+                           device=0):
+    """lf_veff_draws_zmax (include/lfmcmc.h): veff_draws_device with the volume of every (source, draw) evaluated on the
+    device.  dist: sqrt(L_i / 4 pi) / Mpc_cm per source (veff.source_distance_scale); fmin (R, nf): the flux cut of each draw
+    and field in erg cm^-2 s^-1, 0 for none; table: a voltable.VolumeTable.  Returns (out (nq, nbin), values (R, nbin))."""
+    lib = load()
+    flux = _f64(flux).ravel()
+    n = flux.size
+    dist = _f64(dist).ravel()
+    f32 = np.ascontiguousarray(field, dtype=np.int32).ravel()
+    b32 = np.ascontiguousarray(bin_of, dtype=np.int32).ravel()
+    draws = np.ascontiguousarray(np.atleast_2d(np.asarray(draws, dtype=np.float64)))
+    R, nf = draws.shape[0], draws.shape[1] - 1
+    fmin = _f64(fmin).ravel()
+    if f32.size != n or b32.size != n or dist.size != n:
+        raise ValueError("field, bin_of and dist must have the length of flux")
+    if fmin.size != R * nf:
+        raise ValueError("fmin must have one value per draw and field")
+    head, zc, rec = _f64(table.head).ravel(), _f64(table.zc), _f64(table.rec)
+    if head.size != 8 or zc.ndim != 2 or zc.shape[1] != 8 or zc.shape[0] != 32 or rec.ndim != 2 or rec.shape[1] != 8:
+        raise ValueError("not a volume table: head (8,), zc (32, 8), rec (K, 8)")
+    qa = _f64(np.atleast_1d(q)).ravel() if method == LF_Q_LINEAR else np.zeros(1)
+    nq = qa.size
+    out = np.empty((nq, nbin))
+    val = np.empty((R, nbin))
+    ip = ctypes.POINTER(ctypes.c_int32)
+    rc = lib.lf_veff_draws_zmax(int(device), n, _ptr(flux), f32.ctypes.data_as(ip), _ptr(dist), float(pref0), float(fcmin) if fcmin else 0.0,
+                                b32.ctypes.data_as(ip), int(nbin), int(nf), int(R), _ptr(draws), _ptr(fmin), _ptr(head), _ptr(zc),
+                                _ptr(rec), int(rec.shape[0]), nq, _ptr(qa), int(method), _ptr(out), _ptr(val))
+    if rc != LF_OK:
+        raise LFError("lf_veff_draws_zmax failed (%d)" % rc)
+    return out, val
+
+
 def veff_draws_ms():
-    """Device times (ms) of the three stages of the last lf_veff_draws call in this process: per-chunk sums, per-bin
-    sums, quantiles."""
+    """Device times (ms) of the three stages of the last lf_veff_draws or lf_veff_draws_zmax call in this process:
+    per-chunk sums, per-bin sums, quantiles."""
     ms = np.zeros(3)
     if load().lf_veff_draws_ms(_ptr(ms)) != LF_OK:
         raise LFError("no lf_veff_draws call has completed")

@@ -2021,11 +2021,41 @@ int lf_lumfunc_quantiles_ms(double* ms) {
     return g_bands_ms < 0.0 ? LF_ERR_ARG : LF_OK;
 }
 
-static double g_veffd_ms[3] = {-1.0, -1.0, -1.0};      // device times of the last lf_veff_draws call's three stages
+static double g_veffd_ms[3] = {-1.0, -1.0, -1.0};      // device times of the last lf_veff_draws / lf_veff_draws_zmax call's three stages
 
-int lf_veff_draws(int device, int64_t n, const double* flux, const int32_t* field, const double* vol, double vol_all, double pref0,
-                  double fcmin, const int32_t* bin_of, int32_t nbin, int32_t nf, int32_t R, const double* draws, int32_t nq,
-                  const double* q, int32_t method, double* out, double* values) {
+// The volume table of lf_veff_draws_zmax as the caller passes it (lumfuncmcmc_amd/voltable.py)
+struct VeffzTable {
+    const double *fmin, *head, *zc, *rec;
+    int64_t nrec;
+};
+
+// every field of the table the kernel's search and clamps rely on: finite, edges strictly increasing and chained from D_0 to
+// D_K, volumes non-decreasing from 0 to V_total > 0
+static bool veffz_table_ok(const VeffzTable& t) {
+    if (!t.head || !t.zc || !t.rec || t.nrec < 1 || t.nrec > (int64_t)INT32_MAX) return false;
+    for (int j = 0; j < 6; ++j)
+        if (!std::isfinite(t.head[j])) return false;
+    const double d_lo = t.head[0], d_hi = t.head[1], v_total = t.head[2], invw = t.head[3];
+    if (!(d_lo > 0.0) || !(d_hi > d_lo) || !(v_total > 0.0) || !(invw > 0.0) || !(t.head[5] >= 0.0)) return false;
+    if (!((d_hi - d_lo) * invw <= lf::VEFFZ_NPIECE + 0.5)) return false;
+    for (int j = 0; j < lf::VEFFZ_NPIECE * (lf::VEFFZ_DEG + 1); ++j)
+        if (!std::isfinite(t.zc[j])) return false;
+    for (int64_t k = 0; k < t.nrec; ++k) {
+        const double* r = t.rec + (size_t)k * lf::VEFFZ_REC;
+        for (int j = 0; j < 7; ++j)
+            if (!std::isfinite(r[j])) return false;
+        if (!(r[1] > r[0]) || !(r[4] >= r[3])) return false;
+        if (k + 1 < t.nrec && (r[1] != r[lf::VEFFZ_REC] || r[4] != r[lf::VEFFZ_REC + 3])) return false;
+    }
+    const double* last = t.rec + (size_t)(t.nrec - 1) * lf::VEFFZ_REC;
+    return t.rec[0] == d_lo && t.rec[3] == 0.0 && last[1] == d_hi && last[4] == v_total;
+}
+
+// lf_veff_draws (zt == NULL: second = vol or NULL for vol_all) and lf_veff_draws_zmax (second = dist): the argument checks,
+// the sort by bin, the chunks and stages 2 and 3 are shared; stage 1 is veffd_partial or veffd_partial_zmax
+static int veffd_run(int device, int64_t n, const double* flux, const int32_t* field, const double* second, double vol_all, double pref0,
+                     double fcmin, const int32_t* bin_of, int32_t nbin, int32_t nf, int32_t R, const double* draws, const VeffzTable* zt,
+                     int32_t nq, const double* q, int32_t method, double* out, double* values) {
 #pragma clang fp contract(off)
     // every argument is checked before the device is touched
     if (!flux || !field || !bin_of || !draws || !out || n <= 0 || n > (int64_t)INT32_MAX || nbin < 1 || nbin > lf::VEFF_MAXBIN || nf < 1 ||
@@ -2043,22 +2073,37 @@ int lf_veff_draws(int device, int64_t n, const double* flux, const int32_t* fiel
             if (!std::isfinite(d[f]) || d[f] <= 0.0) return LF_ERR_ARG;
         if (!std::isfinite(d[nf]) || d[nf] == 0.0) return LF_ERR_ARG;
     }
+    std::vector<double> cfac;                                // fmin^(-1/2) per draw and field; +inf for no cut
+    if (zt) {
+        if (!second || !zt->fmin || !veffz_table_ok(*zt)) return LF_ERR_ARG;
+        for (int64_t i = 0; i < n; ++i)
+            if (!std::isfinite(second[i]) || second[i] < 0.0) return LF_ERR_ARG;
+        cfac.resize((size_t)R * nf);
+        for (size_t j = 0; j < cfac.size(); ++j) {
+            if (!std::isfinite(zt->fmin[j]) || zt->fmin[j] < 0.0) return LF_ERR_ARG;
+            cfac[j] = 1.0 / std::sqrt(zt->fmin[j]);
+        }
+    }
     // stable counting sort of the sources by bin; the sources outside [0, nbin) are dropped
     std::vector<int64_t> first((size_t)nbin + 1, 0);
     for (int64_t i = 0; i < n; ++i)
         if (bin_of[i] >= 0 && bin_of[i] < nbin) ++first[(size_t)bin_of[i] + 1];
     for (int b = 0; b < nbin; ++b) first[b + 1] += first[b];
     const int64_t m = first[nbin];
-    std::vector<double> sflux((size_t)m), sipv((size_t)m);
+    std::vector<double> sflux((size_t)m), sipv((size_t)m);   // sipv: 1 / (pref0 vol), or the source's s_i under zt
     std::vector<int> sfield((size_t)m);
     {
         std::vector<int64_t> at(first.begin(), first.end() - 1);
         for (int64_t i = 0; i < n; ++i) {
             if (bin_of[i] < 0 || bin_of[i] >= nbin) continue;
             const int64_t k = at[bin_of[i]]++;
-            const double v = vol ? vol[i] : vol_all;
             sflux[k] = flux[i];
-            sipv[k] = v > 0.0 ? 1.0 / (pref0 * v) : 0.0;
+            if (zt) {
+                sipv[k] = second[i];
+            } else {
+                const double v = second ? second[i] : vol_all;
+                sipv[k] = v > 0.0 ? 1.0 / (pref0 * v) : 0.0;
+            }
             sfield[k] = field[i];
         }
     }
@@ -2076,18 +2121,29 @@ int lf_veff_draws(int device, int64_t n, const double* flux, const int32_t* fiel
     bin_c0[nbin] = (int)nch;
     const double ratio = fcmin > 0.0 ? lfh::fc_ratio(fcmin) : 0.0;
     if (hipSetDevice(device) != hipSuccess) return LF_ERR_NODEV;
-    Buf<double> d_flux, d_ipv, d_draws, d_part, d_val, d_q, d_out;
+    Buf<double> d_flux, d_ipv, d_draws, d_part, d_val, d_q, d_out, d_cfac, d_zc, d_rec;
     Buf<int> d_field, d_clen, d_c0;
     Buf<long long> d_cstart;
     HostCall hc;
     for (double& t : g_veffd_ms) t = -1.0;
+    if (zt && !(hc.ok(d_cfac.upload(cfac.data(), cfac.size())) && hc.ok(d_zc.upload(zt->zc, (size_t)lf::VEFFZ_NPIECE * (lf::VEFFZ_DEG + 1))) &&
+                hc.ok(d_rec.upload(zt->rec, (size_t)zt->nrec * lf::VEFFZ_REC))))
+        return hc.rc;
     if (hc.ok(d_flux.upload(sflux.data(), (size_t)m)) && hc.ok(d_ipv.upload(sipv.data(), (size_t)m)) && hc.ok(d_field.upload(sfield.data(), (size_t)m)) &&
         hc.ok(d_cstart.upload(cstart.data(), nch)) && hc.ok(d_clen.upload(clen.data(), nch)) && hc.ok(d_c0.upload(bin_c0.data(), bin_c0.size())) &&
         hc.ok(d_draws.upload(draws, (size_t)R * (nf + 1))) && hc.ok(d_q.upload(qtab.data(), qtab.size())) &&
         hc.ok(alloc_all(d_part, nch * (size_t)R, d_val, (size_t)R * nbin, d_out, (size_t)nq * nbin))) {
         const unsigned tiles = (unsigned)((R + lf::VEFFD_THREADS - 1) / lf::VEFFD_THREADS);
         hc.stamp(0, 0);
-        if (nch > 0) {
+        if (nch > 0 && zt) {
+            const lf::VeffzHead head = {zt->head[0], zt->head[1], zt->head[3], zt->head[4], zt->head[5], 1.0 / (pref0 * zt->head[2]),
+                                        (int)zt->nrec};
+            auto kernel = nf <= lf::VEFFZ_FEW ? (fcmin > 0.0 ? lf::veffd_partial_zmax<true, lf::VEFFZ_FEW> : lf::veffd_partial_zmax<false, lf::VEFFZ_FEW>)
+                                              : (fcmin > 0.0 ? lf::veffd_partial_zmax<true, lf::VEFFD_MAXF> : lf::veffd_partial_zmax<false, lf::VEFFD_MAXF>);
+            hipLaunchKernelGGL(kernel, dim3((unsigned)nch, tiles), dim3(lf::VEFFD_THREADS), 0, 0, d_flux, d_ipv, d_field, d_cstart, d_clen,
+                               d_draws, d_cfac, (int)nf, (int)R, ratio, pref0, head, d_zc, d_rec, d_part);
+            hc.ok(hipGetLastError());
+        } else if (nch > 0) {
             auto kernel = fcmin > 0.0 ? lf::veffd_partial<true> : lf::veffd_partial<false>;
             hipLaunchKernelGGL(kernel, dim3((unsigned)nch, tiles), dim3(lf::VEFFD_THREADS), 0, 0, d_flux, d_ipv, d_field, d_cstart, d_clen,
                                d_draws, (int)nf, (int)R, ratio, d_part);
@@ -2109,6 +2165,21 @@ int lf_veff_draws(int device, int64_t n, const double* flux, const int32_t* fiel
             for (double& t : g_veffd_ms) t = -1.0;
     }
     return hc.rc;
+}
+
+int lf_veff_draws(int device, int64_t n, const double* flux, const int32_t* field, const double* vol, double vol_all, double pref0,
+                  double fcmin, const int32_t* bin_of, int32_t nbin, int32_t nf, int32_t R, const double* draws, int32_t nq,
+                  const double* q, int32_t method, double* out, double* values) {
+    return veffd_run(device, n, flux, field, vol, vol_all, pref0, fcmin, bin_of, nbin, nf, R, draws, nullptr, nq, q, method, out, values);
+}
+
+int lf_veff_draws_zmax(int device, int64_t n, const double* flux, const int32_t* field, const double* dist, double pref0, double fcmin,
+                       const int32_t* bin_of, int32_t nbin, int32_t nf, int32_t R, const double* draws, const double* fmin,
+                       const double* vt_head, const double* vt_zc, const double* vt_rec, int64_t vt_nrec, int32_t nq, const double* q,
+                       int32_t method, double* out, double* values) {
+    if (!dist || !fmin) return LF_ERR_ARG;
+    const VeffzTable zt = {fmin, vt_head, vt_zc, vt_rec, vt_nrec};
+    return veffd_run(device, n, flux, field, dist, 0.0, pref0, fcmin, bin_of, nbin, nf, R, draws, &zt, nq, q, method, out, values);
 }
 
 int lf_veff_draws_ms(double* ms) {

@@ -914,36 +914,57 @@ class LumFuncMCMC(_Base):
         return lfintegrals.quantiles(self._variant(), kind, recs, logLmin, q=percentiles, method=method,
                                      device=self._band_device(device), device_index=self.device)
 
-    def veff_percentiles(self, percentiles=(16, 50, 84), ndraws=200, lnprobcut=7.5, method="linear", device=None):
+    def veff_percentiles(self, percentiles=(16, 50, 84), ndraws=200, lnprobcut=7.5, method="linear", device=None, volumes="fixed"):
         """The 1/Veff points marginalised over the completeness posterior: the binned 1/Veff LF of
         the catalogue under the Flim and alpha of each of ndraws random posterior draws (taken as lf_percentiles takes
         them), on the bins of VeffLF.  Returns a dict: Lavg (nbins,), percentiles (nq, nbins) and values (ndraws, nbins) in
         dn/dlogL like lfbinorig, and var_comp = np.var(values, axis=0, ddof=1) - the completeness part of the points'
         variance, to be added to the bootstrap self.var by whoever wants a total (self.var, Flim and alpha are not
-        touched).  The volumes are VeffLF's: shared by all sources for min_comp_frac <= 0.001 (exact); otherwise each
-        source's volume out to the z_max of the object's CURRENT Flim and alpha, held fixed over the draws (z_max per source
-        and draw is not computed: only sources at the flux cut see the difference).  method and device as lf_percentiles."""
+        touched).  The volumes are VeffLF's: shared by all sources for min_comp_frac <= 0.001 (exact); otherwise
+        volumes="fixed" takes each source's volume out to the z_max of the object's CURRENT Flim and alpha and holds it
+        over the draws, volumes="per_draw" ends it at the z_max of each draw's own flux cut, the root of
+        fleming = min_comp_frac at the draw's Flim and alpha (on the device from a validated table
+        of the volume, on the host by one inversion per source and draw).  method and device as lf_percentiles."""
         if self.fix_comp:
             raise ValueError("this object was built with fix_comp=True: there is no completeness posterior to marginalise over")
+        if volumes not in ("fixed", "per_draw"):
+            raise ValueError("volumes must be 'fixed' or 'per_draw', not %r" % (volumes,))
         lfbands._method(method)
         rows = self._posterior_rows(ndraws, lnprobcut)
         k = 2 if self.fix_sch_al else 3                        # theta's layout: set_parameters_from_list
         draws = np.column_stack([1.0e-17 * rows[:, k:k + self.nfields], rows[:, k + self.nfields]])
         self.getFlim()
-        if self.min_comp_frac <= 0.001:
-            zmaxval = self.zmax
-        else:
-            root = self.rootsf.ev(self.Flims_arr, self.alpha)
-            zmaxval = np.minimum(self.zmax, veff.max_redshift(10 ** self.lum, root, _cosmo))
-        vol = veff.comoving_volume(self.dVdzf, self.zmin, zmaxval)
         field = np.repeat(np.arange(self.nfields), np.diff(self.field_ind))
         _, Lavg, dL, idx = veff.luminosity_bins(self.lum, self.nbins)
-        out, values = veff.veff_draws_quantiles(self.flux, field, vol, sum(self.Omega_0) / hs.SQARCSEC, self.fcmin, idx, self.nbins,
-                                                draws, q=percentiles, method=method, device=self._band_device(device),
-                                                device_index=self.device)
+        pref0 = sum(self.Omega_0) / hs.SQARCSEC
+        dev = self._band_device(device)
+        if volumes == "per_draw" and self.min_comp_frac > 0.001:
+            fmin = self.rootsf.ev(rows[:, k:k + self.nfields], rows[:, k + self.nfields][:, None])
+            table = self._volume_table() if dev else None
+            out, values = veff.veff_draws_zmax_quantiles(self.lum, self.flux, field, fmin, self.zmin, self.zmax, self.dVdzf, _cosmo,
+                                                         pref0, self.fcmin, idx, self.nbins, draws, q=percentiles, method=method,
+                                                         device=dev, device_index=self.device, table=table)
+        else:                                                  # without a flux cut the roots are 0: the shared volume is exact
+            if self.min_comp_frac <= 0.001:
+                zmaxval = self.zmax
+            else:
+                root = self.rootsf.ev(self.Flims_arr, self.alpha)
+                zmaxval = np.minimum(self.zmax, veff.max_redshift(10 ** self.lum, root, _cosmo))
+            vol = veff.comoving_volume(self.dVdzf, self.zmin, zmaxval)
+            out, values = veff.veff_draws_quantiles(self.flux, field, vol, pref0, self.fcmin, idx, self.nbins,
+                                                    draws, q=percentiles, method=method, device=dev, device_index=self.device)
         values = values / dL
         return {"Lavg": Lavg, "percentiles": out / dL, "values": values,
                 "var_comp": np.var(values, axis=0, ddof=1) if len(values) > 1 else np.zeros(self.nbins)}
+
+    def _volume_table(self):
+        """The device's table of the volume out to a luminosity distance (voltable), built and validated once per
+        (zmin, zmax); refused when it misses the 1e-13 of V_total it is documented to hold."""
+        from . import voltable
+        key = (float(self.zmin), float(self.zmax))
+        if getattr(self, "_voltable", None) is None or self._voltable[0] != key:
+            self._voltable = (key, voltable.require(voltable.build(_cosmo, self.dVdzf, self.zmin, self.zmax)))
+        return self._voltable[1]
 
     def VeffLF(self, device=None):
         """1/Veff weights per source and the binned LF with bootstrap errors (lumfuncmcmc.py:515-525).  device=True

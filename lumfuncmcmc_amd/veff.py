@@ -47,14 +47,10 @@ def max_redshift_fsolve(lum_lin, fmin, cosmo, z0=1.5):
     return out
 
 
-def max_redshift(lum_lin, fmin, cosmo, z0=1.5):
-    """Redshift at which luminosity lum_lin (erg/s) is seen at flux fmin: the root of
-    4 pi (DL(z) Mpc)^2 fmin = L that V.getMaxz finds with fsolve, for all sources at once.  DL is monotonic, so
-    the root is DL^-1 of a target distance: a table gives the first guess, Newton steps on the exact DL (secant
-    slope from the table) polish it to 1e-13 - the reference's fsolve stops at 1.5e-8."""
-    lum_lin = np.asarray(lum_lin, dtype=np.float64)
-    fmin = np.asarray(fmin, dtype=np.float64)
-    target = np.sqrt(lum_lin / (4.0 * np.pi * fmin)) / MPC_CM_EXACT            # Mpc
+def redshift_at_distance(target, cosmo, tol=1e-13, maxit=6):
+    """DL^-1 of luminosity distances in Mpc (NaN where the distance is not finite and positive): a table gives the first
+    guess, Newton steps on the exact DL (secant slope from the table) polish it until the largest step is below tol."""
+    target = np.asarray(target, dtype=np.float64)
     out = np.full(target.shape, np.nan)
     good = np.isfinite(target) & (target > 0)
     if not good.any():
@@ -66,13 +62,23 @@ def max_redshift(lum_lin, fmin, cosmo, z0=1.5):
     dtab = np.asarray(cosmo.luminosity_distance(ztab))
     slope = np.gradient(dtab, ztab)
     z = np.interp(target[good], dtab, ztab)
-    for _ in range(6):
+    for _ in range(maxit):
         step = (np.asarray(cosmo.luminosity_distance(z)) - target[good]) / np.interp(z, ztab, slope)
         z = np.clip(z - step, 0.0, zhi)
-        if np.max(np.abs(step)) < 1e-13 * max(1.0, zhi):
+        if np.max(np.abs(step)) < tol * max(1.0, zhi):
             break
     out[good] = z
     return out
+
+
+def max_redshift(lum_lin, fmin, cosmo, z0=1.5):
+    """Redshift at which luminosity lum_lin (erg/s) is seen at flux fmin: the root of
+    4 pi (DL(z) Mpc)^2 fmin = L that V.getMaxz finds with fsolve, for all sources at once.  DL is monotonic, so
+    the root is DL^-1 of a target distance (redshift_at_distance), polished to 1e-13 - the reference's fsolve stops at
+    1.5e-8."""
+    lum_lin = np.asarray(lum_lin, dtype=np.float64)
+    fmin = np.asarray(fmin, dtype=np.float64)
+    return redshift_at_distance(np.sqrt(lum_lin / (4.0 * np.pi * fmin)) / MPC_CM_EXACT, cosmo)
 
 
 def comoving_volume(dVdzf, zmin, zmaxval):
@@ -175,6 +181,54 @@ def veff_draws_quantiles(flux, field, vol, pref0, fcmin, bin_of, nbin, draws, q=
         return capi.veff_draws_device(flux, field, vol, pref0, fcmin, bin_of, nbin, draws, q=q, method=lfbands.METHODS[method],
                                       device=device_index)
     values = veff_draws(flux, field, vol, pref0, fcmin, bin_of, nbin, draws)
+    if method == "linear":
+        out = np.percentile(values, np.atleast_1d(np.asarray(q, dtype=np.float64)), axis=0)
+    else:
+        out = np.median(values, axis=0)[None]
+    return out, values
+
+
+def veff_draws_zmax(lum, flux, field, fmin, zmin, zmax, dVdzf, cosmo, pref0, fcmin, bin_of, nbin, draws):
+    """veff_draws with every source's volume ending at the z_max of the draw's own flux cut (NumPy twin of
+    lf_veff_draws_zmax).  lum: log10 L per source; fmin (R, nf): the flux cut of each draw and
+    field in erg cm^-2 s^-1 (0: no cut, z_max = zmax).  Row r is, by definition,
+        zmax_i = min(zmax, max_redshift(10^lum, fmin[r][field]));  vol = comoving_volume(dVdzf, zmin, zmax_i)
+        veff_draws(..., vol, ..., draws[r:r + 1])
+    - a loop over the existing functions, N inversions of the luminosity distance per draw."""
+    lum_lin = 10 ** np.asarray(lum, dtype=np.float64)
+    field = np.asarray(field, dtype=np.int64)
+    draws = np.atleast_2d(np.asarray(draws, dtype=np.float64))
+    fmin = np.asarray(fmin, dtype=np.float64).reshape(draws.shape[0], draws.shape[1] - 1)
+    values = np.zeros((draws.shape[0], nbin))
+    for r in range(draws.shape[0]):
+        fm = fmin[r][field]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            # the whole array, as the definition has it: max_redshift itself leaves the fmin = 0 entries (an infinite distance)
+            # out of the batch it inverts, so the Newton stop sees the same sources either way
+            zi = np.where(fm > 0, max_redshift(lum_lin, fm, cosmo), np.inf)
+        vol = comoving_volume(dVdzf, zmin, np.minimum(zmax, zi))
+        values[r] = veff_draws(flux, field, vol, pref0, fcmin, bin_of, nbin, draws[r:r + 1])[0]
+    return values
+
+
+def source_distance_scale(lum):
+    """s_i = sqrt(L_i / 4 pi) / Mpc_cm: a source's luminosity distance at the flux cut fmin is s_i fmin^(-1/2) Mpc."""
+    return np.sqrt(10 ** np.asarray(lum, dtype=np.float64) / (4.0 * np.pi)) / MPC_CM_EXACT
+
+
+def veff_draws_zmax_quantiles(lum, flux, field, fmin, zmin, zmax, dVdzf, cosmo, pref0, fcmin, bin_of, nbin, draws,
+                              q=(16.0, 50.0, 84.0), method="linear", device=False, device_index=0, table=None):
+    """Percentiles over the draws of veff_draws_zmax's values, as veff_draws_quantiles.  device=True: one device job
+    (lf_veff_draws_zmax) that evaluates the volume per (source, draw) from `table` (voltable.build; built when None); a table
+    that was not validated or misses 1e-13 of the total volume is refused (voltable.require)."""
+    from . import lfbands
+    lfbands._method(method)
+    if device:
+        from . import capi, voltable
+        table = voltable.require(voltable.build(cosmo, dVdzf, zmin, zmax) if table is None else table)
+        return capi.veff_draws_zmax_device(flux, field, source_distance_scale(lum), pref0, fcmin, bin_of, nbin, draws, fmin, table,
+                                           q=q, method=lfbands.METHODS[method], device=device_index)
+    values = veff_draws_zmax(lum, flux, field, fmin, zmin, zmax, dVdzf, cosmo, pref0, fcmin, bin_of, nbin, draws)
     if method == "linear":
         out = np.percentile(values, np.atleast_1d(np.asarray(q, dtype=np.float64)), axis=0)
     else:
