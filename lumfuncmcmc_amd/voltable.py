@@ -16,7 +16,8 @@ z = DL^-1(D).  The table is V(D) as piecewise polynomials in D, kept in factored
     (Chebyshev interpolation of the inverse, iterated to 1e-15, then the power basis).
 
 `VolumeTable.eval` is the device's evaluation operation by operation (IEEE products and sums, no contraction), so it
-returns the device's bits; `VolumeTable.validate` measures eps_T = max |V_table - V_twin| / V_total.
+returns the device's bits (held per element on the device by tests/test_gpu_volterms.py, and against a 40-digit reference by
+tests/test_volterms_cpu.py); `VolumeTable.validate` measures eps_T = max |V_table - V_twin| / V_total.
 """
 import numpy as np
 
