@@ -6,7 +6,7 @@
     -> set_median_fit (median LF + 1/Veff estimate) -> the reference's output tables.
 
     python examples/fit_synthetic.py [--nsrc 20000] [--nwalkers 64] [--nsteps 300] [--fix-comp] [--until-converged] [--map]
-                                     [--integrals] [--pt] [--deconvolve [--deconvolve-tile] [--deconvolve-wide] [--deconvolved-lums FILE]]
+                                     [--integrals] [--pt] [--deconvolve [--deconvolve-tile] [--deconvolve-wide] [--deconvolve-cut] [--deconvolved-lums FILE]]
 """
 import argparse
 import os
@@ -117,6 +117,9 @@ def main():
     ap.add_argument("--deconvolve-wide", action="store_true",
                     help="with --deconvolve: errors above 0.09 dex, up to 0.30 dex, are integrated by the wide rule instead of "
                          "being refused (deconvolve_wide=True; DESIGN.md section 3.21)")
+    ap.add_argument("--deconvolve-cut", action="store_true",
+                    help="with --deconvolve: fit at min_comp_frac = 0.5, the classes' default, with the cut on the observed flux "
+                         "modelled (deconvolve_cut=True; DESIGN.md section 3.31); not with --map or --veff-deconvolved")
     ap.add_argument("--deconvolved-lums", metavar="FILE", default="",
                     help="with --deconvolve: every source's posterior mean and spread of its TRUE luminosity over 200 posterior "
                          "draws (deconvolved_luminosities; DESIGN.md section 3.22) written to FILE: ID, lum, lum_e, lum_true, "
@@ -142,6 +145,8 @@ def main():
         ap.error("--deconvolved-lums needs --deconvolve")
     if args.veff_deconvolved and not args.deconvolve:
         ap.error("--veff-deconvolved needs --deconvolve")
+    if args.deconvolve_cut and (not args.deconvolve or args.map or args.veff_deconvolved):
+        ap.error("--deconvolve-cut needs --deconvolve, and neither --map nor --veff-deconvolved (DESIGN.md section 3.31)")
     if args.pt and args.until_converged:
         ap.error("--pt and --until-converged are two fits: choose one")
     os.makedirs(args.out, exist_ok=True)
@@ -155,9 +160,10 @@ def main():
                         sch_al_lims=synth.SCH_AL_LIMS, Lstar=synth.LSTAR, Lstar_lims=synth.LSTAR_LIMS,
                         phistar=synth.PHISTAR, phistar_lims=synth.PHISTAR_LIMS, Lc=synth.LC, Lh=synth.LH,
                         nwalkers=args.nwalkers, nsteps=args.nsteps, fix_sch_al=False, fix_comp=args.fix_comp,
-                        min_comp_frac=0.0, Flim_lims=synth.FLIM_LIMS, alpha_lims=synth.ALPHA_LIMS,
+                        min_comp_frac=0.5 if args.deconvolve_cut else 0.0, Flim_lims=synth.FLIM_LIMS, alpha_lims=synth.ALPHA_LIMS,
                         field_names=field_names, field_ind=field_ind, compress=args.compress, deconvolve=args.deconvolve,
-                        deconvolve_tile=args.deconvolve_tile, deconvolve_wide=args.deconvolve_wide)
+                        deconvolve_tile=args.deconvolve_tile, deconvolve_wide=args.deconvolve_wide,
+                        deconvolve_cut=args.deconvolve_cut)
     print("setup %.2f s for %d sources" % (time.time() - t0, len(LFmod.lum)))
     np.random.seed(3)
     plain_map = None

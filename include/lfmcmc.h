@@ -264,6 +264,38 @@ int lf_veff_true(lf_ctx *ctx, const double *theta, int R, const double *edges, i
 int lf_veff_true_info(int *max_rows, int *max_bins);
 int lf_veff_true_ms(double ms[3]);
 
+/* The convolved likelihood under a cut on the OBSERVED flux (csrc/lf_deconv_cut.h): contexts whose grid
+ * has its own luminosity nodes per redshift column (min_comp_frac > 0.001).  A source is catalogued when its observed
+ * luminosity L_o = L_t + eps, eps ~ N(0, s^2), lies at or above the grid's lower edge Lam(z) = logL[0][.]; s = sigma_f(log10 of
+ * the TRUE flux) is field f's error model: linear between nodes[M] (log10 flux, increasing), constant outside, sigma[nf][M] in
+ * dex (the mocks' model, lf_mock_set_error_model).  The expected counts become B + Delta B,
+ *     Delta B = sum_f sum_j wz_j V_j [ int_{Lam-H}^{Lam} phi Omega Q(-u) dL - int_{Lam}^{min(Lam+H, Lh)} phi Omega Q(u) dL ],
+ *     u = (L - Lam_j) / s_f(L - ld2_j),  Q(x) = erfc(x / sqrt 2) / 2,  H = 7.5 max_m sigma[f][m],
+ * and every value entry of the convolved likelihood (lf_lnprob_err_batch, _device, both device samplers' convolved likelihood,
+ * with "deconv_tile" and "deconv_wide") returns lnprob + Delta - Delta B; the per-source term keeps the catalogued sigma_i.
+ * The nodes and whole weights (u does not depend on theta) are host tables in extended precision: panels of 8 Gauss-Legendre
+ * nodes laid from the edge outwards, no wider than 2.5 x the smallest sigma on them, 0.25 dex, and the distance to the next
+ * node of the error model; per (field, column) the error against the integral is below 1e-7 of the column's plain integral
+ * for sigma up to 0.30 dex.  Without this call nothing changes.
+ * lf_set_cut_error_model: BEFORE lf_set_lum_err, which then accepts such a context (FIXCOMP, ZEVOL: and makes the tables, with
+ * the completeness flim0, alpha0 it is given folded in; the descriptor of such a context must also hold volume_part and
+ * dl_zarr).  LF_ERR_ARG with a message for: NULL pointers, M outside 1..64, nodes not finite or not increasing, sigma not
+ * finite, < 0 or above 0.30 dex (the limit is stated), a field whose sigma is 0 at some nodes only, a model that needs more
+ * than 64 panels on one side of the edge, a context without the cut (separable grid), a source-sharded context, and a call
+ * after lf_set_lum_err.  Still refused on such a context, with what is missing in the message: lf_lnprob_err_grad_batch(_device)
+ * (the gradient of Delta B) and lf_veff_true (per-source volumes); lf_lum_posterior is served (a source's posterior given that
+ * it is catalogued does not involve B).
+ * lf_cut_term_batch: Delta B alone for B rows (host pointers, synchronous; after lf_set_lum_err); NaN for a row whose plain
+ * lnprob is not finite.  Summed in one fixed order without atomics: a row's bits do not depend on B or on its place.
+ * lf_cut_info: the nodes per field and H per field (up to cap entries; either may be NULL), the nodes per block and the number
+ * of blocks per row (-1 before the tables are made); returns nf.  FIXCOMP, ZEVOL: until lf_set_lum_err has made the tables the
+ * node counts are those of the placement alone; a node whose weight underflows with the completeness folded in is dropped
+ * then, so they may shrink.  Option "deconv_cut_limit" = n > 0, set before the tables are
+ * made (tests): only the first n nodes of every field are kept. */
+int lf_set_cut_error_model(lf_ctx *ctx, const double *nodes, int M, const double *sigma);
+int lf_cut_term_batch(lf_ctx *ctx, const double *theta, int B, double *out);
+int lf_cut_info(lf_ctx *ctx, int32_t *nnodes, double *H, int cap, int *chunk, int *chunks);
+
 /* Kernel timing for bench.py: level 1 brackets lf_main, level 2 every launch, with hipEvents on
  * the stream the launch runs on (0 = off; each event pair costs a few microseconds of stream time: the events are
  * barrier packets, and the next launch no longer overlaps the previous one's tail - measured 7.6 us per evaluation

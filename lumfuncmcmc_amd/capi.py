@@ -57,7 +57,8 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_deconv_info", "lf_deconv_wide_info", "lf_lnprob_err_grad_batch", "lf_lnprob_err_grad_batch_device", "lf_sampler_set_likelihood",
            "lf_ptsampler_set_likelihood", "lf_lum_posterior", "lf_lum_posterior_info",
            "lf_veff_true", "lf_veff_true_info", "lf_veff_true_ms",
-           "lf_mock_set_error_model", "lf_mock_draw_err", "lf_mock_hist_err")
+           "lf_mock_set_error_model", "lf_mock_draw_err", "lf_mock_hist_err",
+           "lf_set_cut_error_model", "lf_cut_term_batch", "lf_cut_info")
 
 _lib = None
 
@@ -116,6 +117,13 @@ def load():
     lib.lf_lnprob_err_batch.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int, _c_double_p]
     lib.lf_lnprob_err_batch_device.restype = ctypes.c_int
     lib.lf_lnprob_err_batch_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    lib.lf_set_cut_error_model.restype = ctypes.c_int
+    lib.lf_set_cut_error_model.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int, _c_double_p]
+    lib.lf_cut_term_batch.restype = ctypes.c_int
+    lib.lf_cut_term_batch.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int, _c_double_p]
+    lib.lf_cut_info.restype = ctypes.c_int
+    lib.lf_cut_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), _c_double_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                ctypes.POINTER(ctypes.c_int)]
     lib.lf_gauss_hermite.restype = ctypes.c_int
     lib.lf_gauss_hermite.argtypes = [ctypes.c_int, _c_double_p, _c_double_p]
     lib.lf_lnprob_err_grad_batch.restype = ctypes.c_int
@@ -664,6 +672,10 @@ class LFContext(object):
             else:
                 keep["flim0"] = _f64(inp["Flim0"])
                 d.alpha0 = float(inp["alpha0"])
+            # (read by lf_set_cut_error_model alone: the columns' volume element and distance)
+            if inp.get("volume_part") is not None and inp.get("DL_zarr") is not None:
+                keep["volume_part"] = _f64(inp["volume_part"])
+                keep["dl_zarr"] = _f64(inp["DL_zarr"])
         for k in ("logf", "z", "om_arr", "volume_part", "dl_zarr", "integ_part", "flim0"):
             setattr(d, k, _ptr(keep.get(k)))
         d.field_ind = fi.ctypes.data_as(_c_int64_p)
@@ -791,6 +803,37 @@ class LFContext(object):
         self._check(self._lib.lf_set_lum_err(self._h, _ptr(sg), int(K), None if self.variant == "free" else _ptr(self._logf),
                                              _ptr(self._flim0), float(self._alpha0)))
         self.deconv_order = int(K)
+
+    def set_cut_error_model(self, nodes, sigma):
+        """lf_set_cut_error_model: the error model sigma (nf, M) in dex at the log10 flux nodes (M,) of the cut on the observed
+        flux, on a context whose grid has its own luminosity nodes per column (min_comp_frac > 0.001).
+        Before set_lum_err, which then accepts such a context; lnprob_err_batch and the device samplers' convolved likelihood
+        then hold lnprob + Delta - Delta B."""
+        nd = _f64(nodes).ravel()
+        sg = np.ascontiguousarray(np.atleast_2d(np.asarray(sigma, dtype=np.float64)))
+        if sg.shape != (self.nf, nd.size):
+            raise ValueError("sigma must be (nf, M) = (%d, %d), got %s" % (self.nf, nd.size, sg.shape))
+        self._check(self._lib.lf_set_cut_error_model(self._h, _ptr(nd), int(nd.size), _ptr(sg)))
+
+    def cut_term_batch(self, theta):
+        """theta (B, ndim) or (ndim,) host array -> Delta B (B,), the cut's change of the expected counts: lf_cut_term_batch
+        (NaN for a row whose plain lnprob is not finite).  Needs set_cut_error_model and set_lum_err."""
+        th = self._theta(theta)
+        out = np.empty(th.shape[0], dtype=np.float64)
+        if th.shape[0]:
+            self._check(self._lib.lf_cut_term_batch(self._h, _ptr(th), th.shape[0], _ptr(out)))
+        return out
+
+    def cut_info(self):
+        """lf_cut_info: dict nnodes (nf,), H (nf,), chunk (nodes per block), chunks (blocks per row; -1 before the tables are made)."""
+        n = np.zeros(self.nf, dtype=np.int32)
+        H = np.zeros(self.nf)
+        chunk, chunks = ctypes.c_int(0), ctypes.c_int(0)
+        rc = self._lib.lf_cut_info(self._h, n.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(H), self.nf, ctypes.byref(chunk),
+                                   ctypes.byref(chunks))
+        if rc < 0:
+            self._check(rc)
+        return {"nnodes": n, "H": H, "chunk": chunk.value, "chunks": chunks.value}
 
     def lnprob_err_batch(self, theta):
         """theta (B, ndim) or (ndim,) host array -> the flux-error-convolved lnprob (B,): lf_lnprob_err_batch."""

@@ -9,7 +9,9 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../include/lfmcmc.h"
@@ -797,6 +799,162 @@ inline WideList wide_list(const std::vector<double>& sigma, const std::vector<in
             }
         }
     return wl;
+}
+
+// ---- the change of the expected counts under a cut on the observed flux (lf_deconv_cut.h) ----
+// One field's sigma at log10 flux t: linear between the nodes, constant outside (mock.py: sigma_lookup; lf_mock_noise.h:
+// mock_sigma).  T = double: the statements the panels are placed with (deconv.py: _cut_sigma has the same ones); long double:
+// the weights'.
+template <typename T>
+inline T cut_sigma(const double* nodes, const double* sig, int M, T t) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    if (M == 1 || !(t > (T)nodes[0])) return (T)sig[0];
+    if (t >= (T)nodes[M - 1]) return (T)sig[M - 1];
+    int i = (int)(std::upper_bound(nodes, nodes + M, (double)t) - nodes) - 1;
+    i = std::min(std::max(i, 0), M - 2);
+    return (T)sig[i] + (t - (T)nodes[i]) * (((T)sig[i + 1] - (T)sig[i]) / ((T)nodes[i + 1] - (T)nodes[i]));
+}
+
+// What is wrong with an error model (nodes[M] ascending, sigma[nf][M]), or "" - lf_set_cut_error_model's refusals
+inline std::string cut_model_check(const double* nodes, int M, const double* sigma, int nf) {
+    if (!nodes || !sigma) return "NULL nodes or sigma";
+    if (M < 1 || M > DECONV_CUT_MAX_NODES) return "M must be in 1.." + std::to_string(DECONV_CUT_MAX_NODES);
+    for (int m = 0; m < M; ++m) {
+        if (!std::isfinite(nodes[m])) return "nodes must be finite";
+        if (m > 0 && !(nodes[m] > nodes[m - 1])) return "nodes must increase";
+    }
+    for (int f = 0; f < nf; ++f) {
+        int zeros = 0;
+        for (int m = 0; m < M; ++m) {
+            const double s = sigma[(size_t)f * M + m];
+            if (!std::isfinite(s) || s < 0.0) return "sigma must be finite and >= 0";
+            if (s > DECONV_CUT_SIGMA_MAX) {
+                char msg[200];
+                std::snprintf(msg, sizeof(msg), "sigma = %.4g dex of field %d is above %.2f dex, the largest value the cut model is "
+                              "validated for (per-column error below 1e-7)", s, f, DECONV_CUT_SIGMA_MAX);
+                return msg;
+            }
+            zeros += s == 0.0 ? 1 : 0;
+        }
+        if (zeros != 0 && zeros != M)
+            return "the sigma of field " + std::to_string(f) + " is 0 at some nodes and not at others: all 0 (no errors) or all > 0";
+    }
+    return "";
+}
+
+// The node tables: per field f with errors and redshift column j the composite Gauss-Legendre rule on [Lam - H, Lam] and
+// [Lam, min(Lam + H, top)], Lam = lam[j] the grid's lower edge, H = DECONV_CUT_T x the field's largest sigma.  Panels of
+// DECONV_CUT_NPAN nodes are laid from Lam outwards, each no wider than DECONV_CUT_PANEL_SIGMA x the smallest sigma on it,
+// than DECONV_CUT_H dex, and than the distance to the next node of the error model (where s has a kink); a panel wholly
+// beyond |u| = DECONV_CUT_UMAX is not made.  Placement in double with the statements of deconv.py: _cut_panels (the same
+// panels on both sides); the weights in long double:
+//     c = -/+ wz_j vol_j (GL weight) Q(|u|) om0_f [fc^(1/d) at the node: fixed completeness],  u = (L - Lam) / s_f(L - ld2_j),
+// the weights of MINUS Delta B (- below the cut, + above).  Nodes whose weight is exactly 0 are dropped.  limit > 0 (tests):
+// only the first `limit` nodes of every field are kept.  A field's nodes are contiguous, columns ascending; chunks of
+// DECONV_CUT_CH nodes of one field.  err: "" or what is refused.
+struct CutTables {
+    std::string err;
+    std::vector<double> L, P, c, a3, a4;          // a3: FREE log flux, ZEVOL redshift; a4: FREE 10^(a3 + 17)
+    std::vector<int> start, len, field;
+    int nnodes[MAXF] = {};
+    double H[MAXF] = {};
+};
+inline CutTables cut_tables(int variant, int nf, int S, const double* lam, const double* top, const double* zarr, const double* vol,
+                            const double* ld2, const double* om0, const double* flim0, double alpha0, double kappa, const double* nodes,
+                            int M, const double* sigma, int64_t limit) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    CutTables t;
+    long double gxl[64], gwl[64];
+    gauss_legendre(DECONV_CUT_NPAN, gxl, gwl);
+    double gx[DECONV_CUT_NPAN];
+    for (int k = 0; k < DECONV_CUT_NPAN; ++k) gx[k] = (double)gxl[k];
+    const long double SQRT2 = std::sqrt(2.0L), LN10 = std::log(10.0L);
+    for (int f = 0; f < nf; ++f) {
+        const double* sg = sigma + (size_t)f * M;
+        const double smax = *std::max_element(sg, sg + M);
+        const double H = DECONV_CUT_T * smax;
+        t.H[f] = H;
+        const size_t first = t.L.size();
+        for (int j = 0; j < S && H > 0.0; ++j) {
+            const double dl = j > 0 ? zarr[j] - zarr[j - 1] : 0.0, dr = j < S - 1 ? zarr[j + 1] - zarr[j] : 0.0;
+            const long double wv = (long double)(0.5 * (dl + dr)) * (long double)vol[j] * (long double)om0[f];
+            for (int side = 0; side < 2; ++side) {
+                const double dir = side == 0 ? -1.0 : 1.0;
+                const double total = side == 0 ? H : std::fmin(lam[j] + H, top[j]) - lam[j];
+                std::vector<double> brk;
+                for (int m = 0; m < M; ++m) {
+                    const double x = nodes[m] + ld2[j];
+                    const double dk = side == 0 ? lam[j] - x : x - lam[j];
+                    if (dk > 0.0 && dk < total) brk.push_back(dk);
+                }
+                std::sort(brk.begin(), brk.end());
+                double d = 0.0;
+                size_t kb = 0;
+                int made = 0;
+                while (d < total) {
+                    while (kb < brk.size() && brk[kb] <= d) ++kb;
+                    const double seg_end = kb < brk.size() ? brk[kb] : total;
+                    const double s0 = cut_sigma<double>(nodes, sg, M, lam[j] + dir * d - ld2[j]);
+                    double h = std::fmin(std::fmin(DECONV_CUT_PANEL_SIGMA * s0, DECONV_CUT_H), seg_end - d);
+                    double s1 = cut_sigma<double>(nodes, sg, M, lam[j] + dir * (d + h) - ld2[j]);
+                    if (s1 < s0) {
+                        h = std::fmin(h, DECONV_CUT_PANEL_SIGMA * s1);
+                        s1 = cut_sigma<double>(nodes, sg, M, lam[j] + dir * (d + h) - ld2[j]);
+                    }
+                    double dn = d + h;
+                    if (seg_end - dn < 1.0e-9) dn = seg_end, h = dn - d;
+                    if (!(h > 0.0)) break;
+                    if (!(d > DECONV_CUT_UMAX * std::fmax(s0, s1))) {
+                        if (++made > DECONV_CUT_MAX_PANELS) {
+                            t.err = "the error model of field " + std::to_string(f) + " needs more than " +
+                                    std::to_string(DECONV_CUT_MAX_PANELS) + " panels on one side of the cut in redshift column " +
+                                    std::to_string(j) + ": its sigma varies too strongly across the band of 7.5 sigma_max";
+                            return t;
+                        }
+                        const double half = 0.5 * h, mid = (lam[j] + dir * d) + dir * half;
+                        for (int k = 0; k < DECONV_CUT_NPAN; ++k) {
+                            const double Ln = mid + half * gx[k];
+                            const long double Lq = (long double)Ln, tf = Lq - (long double)ld2[j];
+                            const long double s = cut_sigma<long double>(nodes, sg, M, tf);
+                            const long double u = (Lq - (long double)lam[j]) / s;
+                            long double w = wv * ((long double)half * gwl[k]) * (0.5L * erfcl(std::fabs(u) / SQRT2));
+                            if (variant != LF_FREE) {
+                                // fc^(1/d) at the node's flux, the fixed curve (lf_grad.h: comp_form's statements)
+                                const long double y = (tf + 17.0L) - std::log10((long double)flim0[f]);
+                                const long double num = (long double)alpha0 * y, den = std::sqrt(num * num + 1.0L);
+                                const long double v = std::exp(LN10 * (y + (long double)kappa / (long double)alpha0));
+                                const long double dd = -std::expm1(-v);
+                                const long double lnfc = num < 0.0L ? -std::log(2.0L * den * (den - num)) : std::log1p(-0.5L / (den * (den + num)));
+                                w *= std::exp(lnfc / dd);
+                            }
+                            const double c = (double)(side == 0 ? -w : w);
+                            if (c == 0.0 || c != c) continue;
+                            const double a3 = variant == LF_FREE ? Ln - ld2[j] : (variant == LF_ZEVOL ? zarr[j] : 0.0);
+                            t.L.push_back(Ln);
+                            t.P.push_back(std::pow(10.0, Ln - LF_LREF));
+                            t.c.push_back(c);
+                            t.a3.push_back(a3);
+                            t.a4.push_back(variant == LF_FREE ? std::pow(10.0, a3 - LF_FREF) : 0.0);
+                        }
+                    }
+                    d = dn;
+                }
+            }
+        }
+        if (limit > 0 && t.L.size() - first > (size_t)limit)
+            for (std::vector<double>* a : {&t.L, &t.P, &t.c, &t.a3, &t.a4}) a->resize(first + (size_t)limit);
+        t.nnodes[f] = (int)(t.L.size() - first);
+        for (size_t s = first; s < t.L.size(); s += DECONV_CUT_CH) {
+            t.start.push_back((int)s);
+            t.len.push_back((int)std::min<size_t>(DECONV_CUT_CH, t.L.size() - s));
+            t.field.push_back(f);
+        }
+    }
+    return t;
 }
 
 // ---- lf_free's static deal (lf_layout.h: DEAL_*): flux bins, then cell chunks, each to the virtual workgroup that would be done

@@ -120,6 +120,19 @@ struct DeconvConst {
     double alpha0;               // FIXCOMP, ZEVOL: the fixed completeness the model was built with
     double flim0[MAXF];          // ... in theta's units (1e-17)
 };
+// The change of the expected counts under a cut on the OBSERVED flux (lf_deconv_cut.h): nodes per block;
+// the half-width of the band around the cut in units of a field's largest sigma; the nodes of a panel of the composite
+// Gauss-Legendre rule, a panel's largest width in units of the smallest sigma on it and in dex; |u| beyond which a panel is
+// not made (Q(9) = 1.1e-19); the most panels on one side of one (field, column); the largest sigma the rule is validated for.
+constexpr int DECONV_CUT_CH = 1024;
+constexpr double DECONV_CUT_T = 7.5;
+constexpr int DECONV_CUT_NPAN = 8;
+constexpr double DECONV_CUT_PANEL_SIGMA = 2.5;
+constexpr double DECONV_CUT_H = 0.25;
+constexpr double DECONV_CUT_UMAX = 9.0;
+constexpr int DECONV_CUT_MAX_PANELS = 64;
+constexpr double DECONV_CUT_SIGMA_MAX = 0.30;
+constexpr int DECONV_CUT_MAX_NODES = 64;     // nodes of an error model (lf_mock_noise.h: MOCK_MAX_NODES)
 // The per-source posterior of the true luminosity (lf_lumpost.h).  LUMPOST_RT: rows of a tile, summed in
 // row order; the tiles' sums are added in tile order.  A tile's rows share nothing but the node table and one 16-byte store
 // per source, against K exponents each, so the height buys no arithmetic; 2 keeps the sum of LUMPOST_RT + 1 equal addends to

@@ -23,6 +23,7 @@
 #include "lf_devmem.h"
 #include "lf_diag.h"
 #include "lf_deconv.h"
+#include "lf_deconv_cut.h"
 #include "lf_deconv_grad.h"
 #include "lf_deconv_tile.h"
 #include "lf_deconv_wide.h"
@@ -184,6 +185,22 @@ struct lf_ctx {
         Buf<int> d_start, d_len, d_class, d_field_all;
         int K[lf::DECONV_WIDE_NCLASS] = {}, off[lf::DECONV_WIDE_NCLASS] = {};
     } wide;
+    // the cut on the observed flux (lf_deconv_cut.h; lf_set_cut_error_model): what the tables are made from - the grid's lower
+    // and upper edges per redshift column, the redshifts, and where the descriptor gave them dVc/dz/dOmega and log10(4 pi DL^2)
+    // (empty: not given) - the error model, and the node tables with their chunks (n: chunks; 0 without the model, or with
+    // sigma = 0 throughout)
+    std::vector<double> h_edge_lo, h_edge_hi, h_zarr, h_vol, h_ld2, h_om0;
+    int64_t opt_cut_limit = 0;          // > 0: only the first so many nodes of every field (tests)
+    struct {
+        bool model = false, built = false;       // an error model is set; the tables are made (fixed completeness: by lf_set_lum_err)
+        int M = 0;
+        std::vector<double> nodes, sigma;
+        int n = 0;
+        int nnodes[lf::MAXF] = {};
+        double H[lf::MAXF] = {};
+        Buf<double> d_L, d_P, d_c, d_a3, d_a4;
+        Buf<int> d_start, d_len, d_field;
+    } cut;
     // the per-source posterior of the true luminosity (lf_lumpost.h): every slot's source in the caller's order - the context's
     // sources, then those of the wide list (lf_set_lum_err) - and the workspace: the slabs, the running sums, m1 and m2
     Buf<int> d_lp_caller;
@@ -943,12 +960,19 @@ int family_check(lf_ctx* c, const char* fn, bool err, const void* theta, int B, 
     return LF_OK;
 }
 
+// what stays refused on a context with the cut model (lf_set_cut_error_model), with what is missing
+int cut_refuse(lf_ctx* c, const char* fn, const char* missing) {
+    if (!c->cut.model) return LF_OK;
+    c->err = std::string(fn) + ": not under a cut on the observed flux (lf_set_cut_error_model): " + missing;
+    return LF_ERR_ARG;
+}
+
 // What the correction's kernels need before anything is enqueued: the chunk table and the blocks' partial sums [rows][chunks]
 // (grad: and [rows][chunks][DGRAD_SLOTS]); chunks: the narrow ones and behind them those of the wide list.
 int deconv_prepare(lf_ctx* c, int B, bool grad) {
     int rc;
     if ((rc = src_chunk_table(c)) != LF_OK) return rc;
-    const size_t need = (size_t)B * std::max(c->src_chunks.n + c->wide.n, 1);
+    const size_t need = (size_t)B * std::max(c->src_chunks.n + c->wide.n + c->cut.n, 1);
     if (need > c->d_dpart.size() && (rc = grow(c, c->d_dpart, need)) != LF_OK) return rc;
     if (grad && need * lf::DGRAD_SLOTS > c->d_dgpart.size() && (rc = grow(c, c->d_dgpart, need * lf::DGRAD_SLOTS)) != LF_OK) return rc;
     return LF_OK;
@@ -959,7 +983,37 @@ lf::DeconvArgs deconv_args(lf_ctx* c, const double* d_theta, double* d_lnp, doub
     const ChunkTable& t = c->src_chunks;
     return lf::DeconvArgs{c->gradc, c->deconvc, d_theta, d_lnp, c->d_dpart, d_out, c->d_lum, c->d_a1, c->d_P,
                           fr ? c->d_a1.get() : c->d_elogf.get(), fr ? c->d_U.get() : c->d_eU.get(), c->d_sigma, c->d_ghnodes,
-                          t.d_start, t.d_len, c->wide.n ? c->wide.d_field_all.get() : t.d_field.get(), t.n + c->wide.n};
+                          t.d_start, t.d_len, c->wide.n ? c->wide.d_field_all.get() : t.d_field.get(), t.n + c->wide.n + c->cut.n};
+}
+
+// The cut model's node tables (lf_hostprep.h: cut_tables) from the context's error model, to the device.  flim0, alpha0: the
+// fixed completeness (FIXCOMP, ZEVOL; FREE: not read).
+int cut_build(lf_ctx* c, const double* flim0, double alpha0) {
+    auto& t = c->cut;
+    t.built = false, t.n = 0;
+    const lfh::CutTables h = lfh::cut_tables(c->kc.variant, c->kc.nf, c->kc.S, c->h_edge_lo.data(), c->h_edge_hi.data(), c->h_zarr.data(),
+                                             c->h_vol.data(), c->h_ld2.data(), c->h_om0.data(), flim0, alpha0, c->gradc.kappa,
+                                             t.nodes.data(), t.M, t.sigma.data(), c->opt_cut_limit);
+    if (!h.err.empty()) {
+        c->err = "lf_set_cut_error_model: " + h.err;
+        return LF_ERR_ARG;
+    }
+    for (int f = 0; f < c->kc.nf; ++f) t.nnodes[f] = h.nnodes[f], t.H[f] = h.H[f];
+    if (!h.start.empty()) {
+        int rc = upload(c, t.d_L, h.L, t.d_P, h.P, t.d_c, h.c, t.d_a3, h.a3, t.d_a4, h.a4);
+        if (rc != LF_OK) return rc;
+        if ((rc = upload(c, t.d_start, h.start, t.d_len, h.len, t.d_field, h.field)) != LF_OK) return rc;
+    }
+    t.n = (int)h.start.size();
+    t.built = true;
+    return LF_OK;
+}
+
+// lf_deconv_cut.h's arguments for rows whose slots start at `part` ([rows][stride]; the cut blocks' behind the first `before`)
+lf::DeconvCutArgs deconv_cut_args(lf_ctx* c, const double* d_theta, const double* d_lnp, double* part, int stride, int before, double* d_out) {
+    const auto& t = c->cut;
+    return lf::DeconvCutArgs{c->gradc, d_theta, d_lnp, part + before, d_out, t.d_L, t.d_P, t.d_c, t.d_a3, t.d_a4,
+                             t.d_start, t.d_len, t.d_field, stride, t.n};
 }
 
 // lf_deconv_wide.h's arguments from the narrow kernels' (da: the rows of one launch): the wide list's arrays and chunks, the
@@ -989,7 +1043,7 @@ void launch_deconv(lf_ctx* c, const lf::DeconvArgs& da, int B, hipStream_t s, bo
         g.lnprob += b0;
         g.part += (size_t)b0 * g.nch;
         g.out += b0;
-        const int n0 = c->src_chunks.n, nw = c->wide.n;     // the narrow blocks of a row and the wide ones (g.nch = n0 + nw)
+        const int n0 = c->src_chunks.n, nw = c->wide.n;     // the narrow blocks of a row and the wide ones (g.nch = n0 + nw + the cut's)
         bool tiled = false;
         if constexpr (v() != LF_FREE) {
             tiled = tile && n0 > 0;
@@ -999,6 +1053,9 @@ void launch_deconv(lf_ctx* c, const lf::DeconvArgs& da, int B, hipStream_t s, bo
         }
         if (n0 > 0 && !tiled) hipLaunchKernelGGL(lf_deconv_part<v()>, dim3((unsigned)n0, (unsigned)nb), dim3(BLOCK), 0, s, g);
         if (nw > 0) hipLaunchKernelGGL(lf_deconv_wide_part<v()>, dim3((unsigned)nw, (unsigned)nb), dim3(BLOCK), 0, s, deconv_wide_args(c, g));
+        if (c->cut.n > 0)
+            hipLaunchKernelGGL(lf_deconv_cut_part<v()>, dim3((unsigned)c->cut.n, (unsigned)nb), dim3(BLOCK), 0, s,
+                               deconv_cut_args(c, g.theta, g.lnprob, g.part, g.nch, n0 + nw, nullptr));
         hipLaunchKernelGGL(lf_deconv_final, dim3((unsigned)nb), dim3(64), 0, s, g);
     });
 }
@@ -1202,6 +1259,22 @@ int build(lf_ctx* c, const lf_desc* d) {
     c->gradc = lfh::grad_const(kc, d->N, d->variant == LF_ZEVOL ? cat.a1.data() : nullptr);
     c->perm = cat.perm;
     c->grid_separable = lfh::same_columns(d->logL, d->S);
+    {
+        const size_t S = (size_t)d->S;
+        c->h_edge_lo.assign(d->logL, d->logL + S);
+        c->h_edge_hi.assign(d->logL + (S - 1) * S, d->logL + S * S);
+        c->h_zarr.assign(d->zarr, d->zarr + S);
+        if (d->volume_part) c->h_vol.assign(d->volume_part, d->volume_part + S);
+        if (d->dl_zarr) {
+            c->h_ld2.resize(S);
+            for (size_t k = 0; k < S; ++k) {
+                const double dlcm = LF_MPC_CM * d->dl_zarr[k];
+                c->h_ld2[k] = std::log10(4.0 * M_PI * dlcm * dlcm);
+            }
+        }
+        c->h_om0.resize((size_t)nf);
+        for (int f = 0; f < nf; ++f) c->h_om0[(size_t)f] = d->omega0[f] / LF_SQARCSEC;
+    }
     int rc;
     kc.cells = 0;
     kc.zcell_rho = 0.0;
@@ -1490,9 +1563,10 @@ int lf_set_lum_err(lf_ctx* c, const double* sigma, int K, const double* logf, co
     if (N > 0 && !sigma) return bad("NULL sigma");
     const double smax = lfh::deconv_sigma_max(K);
     if (smax < 0.0) return bad("order K = " + std::to_string(K) + " is not supported (4, 6, 8, 10, 12, 16, 20, 24, 32)");
-    if (!c->grid_separable)
+    if (!c->grid_separable && !c->cut.model)
         return bad("the grid's redshift columns have their own luminosity nodes (min_comp_frac > 0.001): a cut on the observed "
-                   "flux would change the expected counts, which this model leaves as they are");
+                   "flux would change the expected counts, which this model leaves as they are (lf_set_cut_error_model, called "
+                   "first, adds that change)");
     const bool fr = c->kc.variant == LF_FREE;
     if (!fr) {
         if (!flim0 || (N > 0 && !logf)) return bad("fixed completeness (FIXCOMP, ZEVOL) needs logf and flim0");
@@ -1586,7 +1660,93 @@ int lf_set_lum_err(lf_ctx* c, const double* sigma, int K, const double* logf, co
     if ((rc = upload(c, c->d_vt_inwide, in_wide)) != LF_OK) return rc;
     c->lp_nslots = (int)caller.size();
     c->deconvc = dc;
+    // the cut model's tables at a fixed completeness: the curve arrived with this call
+    if (c->cut.model && !fr && (rc = cut_build(c, flim0, alpha0)) != LF_OK) {
+        if (rc == LF_ERR_ARG) c->err = "lf_set_lum_err: the cut model's tables: " + c->err;
+        return rc;
+    }
     c->deconv_set = true;
+    return LF_OK;
+}
+
+int lf_set_cut_error_model(lf_ctx* c, const double* nodes, int M, const double* sigma) {
+    if (!c) return LF_ERR_ARG;
+    auto bad = [&](const std::string& m) {
+        c->err = "lf_set_cut_error_model: " + m;
+        return (int)LF_ERR_ARG;
+    };
+    if (c->opt_skip_grid || c->kc.grid_parts > 1) return bad("no convolved likelihood of a source-sharded context (options skip_grid, grid_share)");
+    if (c->grid_separable)
+        return bad("every redshift column of the grid has the same luminosity nodes (min_comp_frac <= 0.001): there is no cut on "
+                   "the observed flux, and the expected counts stay as they are");
+    if (c->deconv_set) return bad("luminosity errors are set already: call this before lf_set_lum_err");
+    if (c->h_vol.empty() || c->h_ld2.empty()) return bad("the descriptor must hold volume_part and dl_zarr (FIXCOMP, ZEVOL too) for the cut model");
+    const std::string why = lfh::cut_model_check(nodes, M, sigma, c->kc.nf);
+    if (!why.empty()) return bad(why);
+    LF_HIP(c, hipSetDevice(c->device));
+    LF_HIP(c, hipDeviceSynchronize());               // (a call in flight may read the buffers replaced below)
+    auto& t = c->cut;
+    t.model = false, t.built = false, t.n = 0;
+    t.M = M;
+    t.nodes.assign(nodes, nodes + M);
+    t.sigma.assign(sigma, sigma + (size_t)c->kc.nf * M);
+    if (c->kc.variant == LF_FREE) {
+        t.model = true;
+        const int rc = cut_build(c, nullptr, 0.0);
+        if (rc != LF_OK) t.model = false;
+        return rc;
+    }
+    // fixed completeness: the tables hold the curve, which lf_set_lum_err brings; a dry run refuses now what would be refused then
+    const lfh::CutTables dry = lfh::cut_tables(LF_FREE, c->kc.nf, c->kc.S, c->h_edge_lo.data(), c->h_edge_hi.data(), c->h_zarr.data(),
+                                               c->h_vol.data(), c->h_ld2.data(), c->h_om0.data(), nullptr, 0.0, 0.0, t.nodes.data(), M,
+                                               t.sigma.data(), c->opt_cut_limit);
+    if (!dry.err.empty()) return bad(dry.err);
+    for (int f = 0; f < c->kc.nf; ++f) t.nnodes[f] = dry.nnodes[f], t.H[f] = dry.H[f];
+    t.model = true;
+    return LF_OK;
+}
+
+int lf_cut_info(lf_ctx* c, int32_t* nnodes, double* H, int cap, int* chunk, int* chunks) {
+    if (!c) return LF_ERR_ARG;
+    if (chunk) *chunk = lf::DECONV_CUT_CH;
+    if (!c->cut.model) {
+        c->err = "lf_cut_info: no cut model set (call lf_set_cut_error_model first)";
+        return LF_ERR_ARG;
+    }
+    if (chunks) *chunks = c->cut.built ? c->cut.n : -1;
+    for (int f = 0; f < c->kc.nf && f < cap; ++f) {
+        if (nnodes) nnodes[f] = c->cut.nnodes[f];
+        if (H) H[f] = c->cut.H[f];
+    }
+    return c->kc.nf;
+}
+
+int lf_cut_term_batch(lf_ctx* c, const double* theta, int B, double* out) {
+    using namespace lf;
+    int rc = family_check(c, "lf_cut_term_batch", true, theta, B, out);
+    if (rc != LF_OK) return rc;
+    if (!c->cut.model || !c->cut.built) {
+        c->err = "lf_cut_term_batch: no cut model set (call lf_set_cut_error_model, then lf_set_lum_err)";
+        return LF_ERR_ARG;
+    }
+    if ((rc = stage_theta(c, theta, B)) != LF_OK) return rc;
+    const int n = c->cut.n;
+    const size_t need = (size_t)B * std::max(n, 1);
+    if (need > c->d_dpart.size() && (rc = grow(c, c->d_dpart, need)) != LF_OK) return rc;
+    if ((rc = enqueue(c, c->d_theta, B, c->d_outB, nullptr, nullptr, c->stream)) != LF_OK) return rc;
+    const DeconvCutArgs ca = deconv_cut_args(c, c->d_theta, c->d_outB, c->d_dpart, n, 0, c->d_outA);
+    launch_rows(c->kc.variant, B, [&](auto v, int b0, int nb) {
+        DeconvCutArgs g = ca;
+        g.theta += (size_t)b0 * g.gc.ndim;
+        g.lnprob += b0;
+        g.part += (size_t)b0 * g.stride;
+        g.out += b0;
+        if (n > 0) hipLaunchKernelGGL(lf_deconv_cut_part<v()>, dim3((unsigned)n, (unsigned)nb), dim3(BLOCK), 0, c->stream, g);
+        hipLaunchKernelGGL(lf_deconv_cut_final, dim3((unsigned)nb), dim3(64), 0, c->stream, g);
+    });
+    LF_HIP(c, hipGetLastError());
+    if ((rc = fetch(c, c->h_out, c->d_outA, (size_t)B)) != LF_OK) return rc;
+    std::memcpy(out, c->h_out, (size_t)B * sizeof(double));
     return LF_OK;
 }
 
@@ -1612,6 +1772,7 @@ int lf_lnprob_err_batch(lf_ctx* c, const double* theta, int B, double* out) {
 int lf_lnprob_err_grad_batch_device(lf_ctx* c, const double* d_theta, int B, double* d_lnprob_err, double* d_grad, void* hip_stream) {
     int rc = family_check(c, "lf_lnprob_err_grad_batch_device", true, d_theta, B, d_grad);
     if (rc != LF_OK) return rc;
+    if ((rc = cut_refuse(c, "lf_lnprob_err_grad_batch_device", "the gradient of Delta B, the cut's change of the expected counts, is not provided")) != LF_OK) return rc;
     LF_HIP(c, hipSetDevice(c->device));
     // (the rows' plain lnprob, and the value when it is not asked for: into the context's own buffers, sized before the
     // lnprob path may replace them)
@@ -1620,8 +1781,9 @@ int lf_lnprob_err_grad_batch_device(lf_ctx* c, const double* d_theta, int B, dou
 }
 
 int lf_lnprob_err_grad_batch(lf_ctx* c, const double* theta, int B, double* lnprob_err, double* grad) {
-    const int rc = family_check(c, "lf_lnprob_err_grad_batch", true, theta, B, grad);
+    int rc = family_check(c, "lf_lnprob_err_grad_batch", true, theta, B, grad);
     if (rc != LF_OK) return rc;
+    if ((rc = cut_refuse(c, "lf_lnprob_err_grad_batch", "the gradient of Delta B, the cut's change of the expected counts, is not provided")) != LF_OK) return rc;
     return host_value_grad(c, theta, B, lnprob_err, grad, [&](double* d_val, double* d_grad) {
         return enqueue_deconv_grad(c, c->d_theta, B, c->d_outB, d_val, d_grad, c->stream);
     });
@@ -1721,6 +1883,7 @@ int lf_veff_true(lf_ctx* c, const double* theta, int R, const double* edges, int
     // every argument is checked before the device is touched
     int rc = family_check(c, "lf_veff_true", true, theta, R, out);
     if (rc != LF_OK) return rc;
+    if ((rc = cut_refuse(c, "lf_veff_true", "per-source volumes (a z_max per source under the cut) are not provided: the points take one volume")) != LF_OK) return rc;
     auto bad = [&](const std::string& m) {
         c->err = "lf_veff_true: " + m;
         return (int)LF_ERR_ARG;
@@ -2235,6 +2398,7 @@ int lf_set_option(lf_ctx* c, const char* key, int64_t value) {
         {"deconv_unchecked", [](lf_ctx* c, int64_t v) { c->opt_deconv_unchecked = v != 0; }},
         {"deconv_tile", [](lf_ctx* c, int64_t v) { c->opt_deconv_tile = v != 0; }},
         {"deconv_wide", [](lf_ctx* c, int64_t v) { c->opt_deconv_wide = v != 0; }},
+        {"deconv_cut_limit", [](lf_ctx* c, int64_t v) { c->opt_cut_limit = v < 0 ? 0 : v; }},
         {"persistent", [](lf_ctx* c, int64_t v) { c->opt_persistent = v < 0 ? 0 : (v > 2 ? 2 : v); }},
         {"profile_every", [](lf_ctx* c, int64_t v) { c->opt_profile_every = v < 1 ? 1 : v; c->prof_tick = 0; }},
         {"profile_span", [](lf_ctx* c, int64_t v) { c->opt_profile_span = v < 1 ? 1 : v; c->prof_tick = 0; }},

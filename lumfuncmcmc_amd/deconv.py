@@ -313,9 +313,12 @@ def delta(inp, sigma, theta, K=None, terms=False, unchecked=True, wide=False):
     return (tot, D, sabs) if terms else tot
 
 
-def lnprob_err(inp, sigma, theta, K=None, terms=False, wide=False):
+def lnprob_err(inp, sigma, theta, K=None, terms=False, wide=False, cut=None):
     """lnprob + Delta per row, with lnprob from grad.py's twin; a row whose lnprob is -inf stays -inf, NaN becomes -inf.
-    terms=True: (value, lnprob, S_abs)."""
+    terms=True: (value, lnprob, S_abs).  cut=(nodes, sigma (nf, M)): the value under a cut on the observed flux, lnprob +
+    Delta - Delta B (lnprob_err_cut)."""
+    if cut is not None:
+        return lnprob_err_cut(inp, sigma, theta, cut, K=K, terms=terms, wide=wide)
     th = np.asarray(theta, dtype=np.float64)
     single = th.ndim == 1
     th2 = np.atleast_2d(th)
@@ -557,3 +560,211 @@ def lnprob_err_grad(inp, sigma, theta, K=None, terms=False, wide=False):
     if single:
         return (val[0], g[0], s[0]) if terms else (val[0], g[0])
     return (val, g, s) if terms else (val, g)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The cut on the OBSERVED flux (csrc/lf_deconv_cut.h): contexts with min_comp_frac > 0.001, whose grid
+# has its own luminosity nodes per redshift column.  A source is catalogued when L_o = L_t + eps >= Lam(z), the grid's lower
+# edge (row 0 of logL), eps ~ N(0, s^2) with s = sigma_f(log10 of the TRUE flux) the field's error model (mock.sigma_lookup's
+# arithmetic).  The expected counts become B + Delta B,
+#     Delta B = sum_f sum_j wz_j V_j [ int_{Lam-H}^{Lam} phi Omega Q(-u) dL - int_{Lam}^{min(Lam+H, Lh)} phi Omega Q(u) dL ],
+#     u = (L - Lam_j) / s_f(L - ld2_j),   Q(x) = erfc(x / sqrt 2) / 2,   H = CUT_T max sigma_f,
+# and lnprob_cut = lnprob + Delta - Delta B.  cut_nodes places the same panels as lf_hostprep.h: cut_tables (statements in
+# double, written the same way); cut_term evaluates Delta B directly, erfc per node, in double.
+CUT_T = 7.5                     # lf_layout.h: DECONV_CUT_*
+CUT_NPANEL = 8
+CUT_PANEL_SIGMA = 2.5
+CUT_H = 0.25
+CUT_UMAX = 9.0
+CUT_MAX_PANELS = 64
+CUT_SIGMA_MAX = 0.30
+CUT_MAX_NODES = 64
+CUT_CHUNK = 1024
+
+
+def check_cut_error_model(nodes, sigma, nf):
+    """(nodes (M,), sigma (nf, M)) as float64, refused as lf_set_cut_error_model refuses them"""
+    nd = np.ascontiguousarray(nodes, dtype=np.float64).ravel()
+    sg = np.ascontiguousarray(np.atleast_2d(np.asarray(sigma, dtype=np.float64)))
+    M = nd.size
+    if M < 1 or M > CUT_MAX_NODES:
+        raise ValueError("M must be in 1..%d" % CUT_MAX_NODES)
+    if sg.shape != (nf, M):
+        raise ValueError("sigma must be (nf, M) = (%d, %d), got %s" % (nf, M, sg.shape))
+    if not np.all(np.isfinite(nd)) or np.any(np.diff(nd) <= 0.0):
+        raise ValueError("nodes must be finite and increase")
+    if not np.all(np.isfinite(sg)) or np.any(sg < 0.0):
+        raise ValueError("sigma must be finite and >= 0")
+    if np.any(sg > CUT_SIGMA_MAX):
+        raise ValueError("sigma = %.4g dex is above %.2f dex, the largest value the cut model is validated for (per-column error "
+                         "below 1e-7)" % (sg.max(), CUT_SIGMA_MAX))
+    for f in range(nf):
+        z = int(np.sum(sg[f] == 0.0))
+        if z not in (0, M):
+            raise ValueError("the sigma of field %d is 0 at some nodes and not at others: all 0 (no errors) or all > 0" % f)
+    return nd, sg
+
+
+def _cut_sigma(nodes, sig, t):
+    """one field's sigma at log10 flux t, a scalar: lf_hostprep.h: cut_sigma's statements"""
+    M = len(nodes)
+    if M == 1 or not (t > nodes[0]):
+        return float(sig[0])
+    if t >= nodes[M - 1]:
+        return float(sig[M - 1])
+    i = min(max(int(np.searchsorted(nodes, t, side="right")) - 1, 0), M - 2)
+    return float(sig[i] + (t - nodes[i]) * ((sig[i + 1] - sig[i]) / (nodes[i + 1] - nodes[i])))
+
+
+def _cut_panels(lam, total, dirn, ld2, nodes, sig):
+    """[(d, h)]: the panels of one side of one (field, column), from the edge outwards (lf_hostprep.h: cut_tables' loop)"""
+    brk = []
+    for m in range(len(nodes)):
+        x = float(nodes[m]) + ld2
+        dk = lam - x if dirn < 0 else x - lam
+        if 0.0 < dk < total:
+            brk.append(dk)
+    brk.sort()
+    out, d, kb = [], 0.0, 0
+    while d < total:
+        while kb < len(brk) and brk[kb] <= d:
+            kb += 1
+        seg_end = brk[kb] if kb < len(brk) else total
+        s0 = _cut_sigma(nodes, sig, lam + dirn * d - ld2)
+        h = min(min(CUT_PANEL_SIGMA * s0, CUT_H), seg_end - d)
+        s1 = _cut_sigma(nodes, sig, lam + dirn * (d + h) - ld2)
+        if s1 < s0:
+            h = min(h, CUT_PANEL_SIGMA * s1)
+            s1 = _cut_sigma(nodes, sig, lam + dirn * (d + h) - ld2)
+        dn = d + h
+        if seg_end - dn < 1.0e-9:
+            dn = seg_end
+            h = dn - d
+        if not h > 0.0:
+            break
+        if not d > CUT_UMAX * max(s0, s1):
+            out.append((d, h))
+            if len(out) > CUT_MAX_PANELS:
+                raise ValueError("the error model needs more than %d panels on one side of the cut: its sigma varies too strongly "
+                                 "across the band of 7.5 sigma_max" % CUT_MAX_PANELS)
+        d = dn
+    return out
+
+
+def _cut_grid(inp):
+    logL = np.asarray(inp["logL"], dtype=np.float64)
+    zarr = np.asarray(inp["zarr"], dtype=np.float64)
+    wz = np.zeros_like(zarr)
+    dz = np.diff(zarr)
+    wz[1:] += dz
+    wz[:-1] += dz
+    wz *= 0.5                                            # (0.5 (dl + dr): lf_hostprep.h's statement)
+    ld2 = np.log10(4.0 * np.pi * (G.MPC_CM * np.asarray(inp["DL_zarr"], dtype=np.float64)) ** 2)
+    return logL[0], logL[-1], zarr, wz, np.asarray(inp["volume_part"], dtype=np.float64), ld2
+
+
+def cut_nodes(inp, nodes, sigma, limit=0, fields=None):
+    """The node list of Delta B: per field a dict L, col, w (the signed weight of Delta B without Omega: +/- wz_j V_j (GL
+    weight) Q(|u|); + below the edge, - above), logf (L - ld2_j); nodes whose w is exactly 0 dropped; limit > 0: the first
+    `limit` nodes only (option "deconv_cut_limit").  Also H (nf,)."""
+    nf = len(inp["field_ind"]) - 1
+    nd, sg = check_cut_error_model(nodes, sigma, nf)
+    from scipy.special import erfc
+    lam, top, zarr, wz, vol, ld2 = _cut_grid(inp)
+    gxl, gwl = gauss_legendre(CUT_NPANEL)
+    gx, gw = gxl.astype(np.float64), gwl.astype(np.float64)
+    out, H = [], np.zeros(nf)
+    for f in range(nf):
+        H[f] = CUT_T * sg[f].max()
+        Ls, cols, ws = [], [], []
+        for j in range(len(zarr) if H[f] > 0.0 and (fields is None or f in fields) else 0):
+            for dirn in (-1.0, 1.0):
+                total = H[f] if dirn < 0 else min(lam[j] + H[f], top[j]) - lam[j]
+                for d, h in _cut_panels(float(lam[j]), float(total), dirn, float(ld2[j]), nd, sg[f]):
+                    half = 0.5 * h
+                    mid = (lam[j] + dirn * d) + dirn * half
+                    Ln = mid + half * gx
+                    s = np.array([_cut_sigma(nd, sg[f], t) for t in Ln - ld2[j]])
+                    u = (Ln - lam[j]) / s
+                    w = -dirn * (wz[j] * vol[j]) * (half * gw) * (0.5 * erfc(np.abs(u) / np.sqrt(2.0)))
+                    Ls.append(Ln), cols.append(np.full(CUT_NPANEL, j)), ws.append(w)
+        L = np.concatenate(Ls) if Ls else np.zeros(0)
+        col = np.concatenate(cols).astype(np.int64) if Ls else np.zeros(0, dtype=np.int64)
+        w = np.concatenate(ws) if Ls else np.zeros(0)
+        keep = w != 0.0
+        L, col, w = L[keep], col[keep], w[keep]
+        if limit > 0:
+            L, col, w = L[:limit], col[:limit], w[:limit]
+        out.append({"L": L, "col": col, "w": w, "logf": L - ld2[col]})
+    return out, H
+
+
+def _cut_phi_omega(inp, th, f, L, col, logf):
+    """phi_theta(L[, z_col]) Omega_theta(L, z_col) of field f's nodes at one theta row: piece B's node form, float Omega_0"""
+    v = inp["variant"]
+    p = G._split(inp, th)
+    c1 = p["al"] + 1.0
+    kappa = G._kappa(inp["fcmin"])
+    om0 = float(np.asarray(inp["Omega_0"], dtype=np.float64)[f]) / G.SQARCSEC
+    if v == "zevol":
+        lg = G._basis(np.asarray(inp["zarr"], dtype=np.float64)[col], inp["pivots"])
+        x = L - np.tensordot(np.asarray(p["L"], dtype=float), lg, axes=1)
+        ph = np.tensordot(np.asarray(p["phi"], dtype=float), lg, axes=1)
+    else:
+        x, ph = L - p["L"], p["phi"]
+    tlf = LN10 * np.exp(LN10 * (ph + x * c1) - 10.0 ** x)
+    if v == "free":
+        Flim, aC = float(p["Flim"][f]), float(p["aC"])
+    else:
+        Flim, aC = float(np.asarray(inp["Flim0"], dtype=float)[f]), float(inp["alpha0"])
+    y = (logf + 17.0) - np.log10(Flim)
+    vv = 10.0 ** (logf + 17.0) * (np.exp(LN10 * kappa / aC) / Flim)
+    return tlf * om0 * np.exp(_lcomp(y, vv, aC))
+
+
+def cut_term(inp, nodes, sigma, theta, terms=False, limit=0, fields=None, per_column=False):
+    """theta (B, ndim) or (ndim,) -> Delta B [B]; terms=True: also S_abs [B] = sum_n |c_n phi Omega|, the scale rounding is
+    judged by.  No prior test: what the formulas give (the device gives NaN for a row whose plain lnprob is not finite).  A
+    node whose term is 0 or NaN adds exactly 0.  Summed field by field in node order.  fields: only these fields' nodes.
+    per_column=True: instead Delta B per (row, field, column) [B, nf, S]."""
+    th = np.asarray(theta, dtype=np.float64)
+    single = th.ndim == 1
+    th = np.atleast_2d(th)
+    if th.shape[1] != G.ndim_of(inp):
+        raise ValueError("theta must be (B, %d), got %s" % (G.ndim_of(inp), th.shape))
+    nl, _ = cut_nodes(inp, nodes, sigma, limit=limit, fields=fields)
+    S = len(inp["zarr"])
+    tot, sabs = np.zeros(len(th)), np.zeros(len(th))
+    pc = np.zeros((len(th), len(nl), S))
+    with np.errstate(all="ignore"):
+        for b, row in enumerate(th):
+            for f, n in enumerate(nl):
+                if n["L"].size == 0:
+                    continue
+                I = n["w"] * _cut_phi_omega(inp, row, f, n["L"], n["col"], n["logf"])
+                I = np.where(np.abs(I) > 0.0, I, 0.0)
+                tot[b] += I.sum()
+                sabs[b] += np.abs(I).sum()
+                if per_column:
+                    pc[b, f] = np.bincount(n["col"], weights=I, minlength=S)
+    if per_column:
+        return pc[0] if single else pc
+    if single:
+        return (tot[0], sabs[0]) if terms else tot[0]
+    return (tot, sabs) if terms else tot
+
+
+def lnprob_err_cut(inp, sigma, theta, cut, K=None, terms=False, wide=False, limit=0):
+    """lnprob + Delta - Delta B per row: lnprob_err's value and cut_term's, cut = (nodes, sigma (nf, M)); a row whose lnprob is
+    not finite stays -inf.  terms=True: (value, lnprob, S_abs of Delta + S_abs of Delta B)."""
+    th = np.asarray(theta, dtype=np.float64)
+    single = th.ndim == 1
+    th2 = np.atleast_2d(th)
+    val, lp, sabs = lnprob_err(inp, sigma, th2, K=K, terms=True, wide=wide)
+    dB, sB = cut_term(inp, cut[0], cut[1], th2, terms=True, limit=limit)
+    with np.errstate(all="ignore"):
+        out = np.where(np.isfinite(lp), val - dB, -np.inf)
+    out = np.where(np.isnan(out), -np.inf, out)
+    if single:
+        return (out[0], lp[0], sabs[0] + sB[0]) if terms else out[0]
+    return (out, lp, sabs + sB) if terms else out

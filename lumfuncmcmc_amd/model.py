@@ -186,6 +186,8 @@ class _Base(object):
             if self.compress:
                 self._ctx.set_option("compress", 1)
             if self.deconvolve:
+                if self.deconvolve_cut:
+                    self._ctx.set_cut_error_model(*self.deconvolve_cut_errors)
                 self._ctx.set_lum_err(self.lum_e, self.deconvolve_order, unchecked=self.deconvolve_unchecked,
                                        wide=self.deconvolve_wide)
             if self.deconvolve_tile:
@@ -200,17 +202,35 @@ class _Base(object):
     deconvolve_tile = False        # True: the context option "deconv_tile" (csrc/lf_deconv_tile.h; no effect with free completeness)
     deconvolve_wide = False        # True: lum_e above the order's range, up to 0.30 dex, by the wide rule (csrc/lf_deconv_wide.h)
 
-    def _init_deconvolve(self, deconvolve, deconvolve_order, deconvolve_tile=False, deconvolve_wide=False):
+    deconvolve_cut = False         # True: the cut on the observed flux of min_comp_frac > 0.001 is modelled (csrc/lf_deconv_cut.h)
+    deconvolve_cut_errors = None   # its error model (nodes (M,), sigma (nf, M)); None: the one this catalogue shows (error_model())
+
+    def _init_deconvolve(self, deconvolve, deconvolve_order, deconvolve_tile=False, deconvolve_wide=False, deconvolve_cut=False,
+                         deconvolve_cut_errors=None):
         from . import deconv
         self.deconvolve, self.deconvolve_order = bool(deconvolve), deconvolve_order
         self.deconvolve_tile, self.deconvolve_wide = bool(deconvolve_tile), bool(deconvolve_wide)
+        self.deconvolve_cut = bool(deconvolve_cut)
+        if self.deconvolve_cut and not self.min_comp_frac > 0.001:
+            raise ValueError("deconvolve_cut=True needs min_comp_frac > 0.001: with min_comp_frac <= 0.001 there is no cut on the "
+                             "observed flux, and deconvolve=True alone is the model")
+        if deconvolve_cut and not self.deconvolve:
+            raise ValueError("deconvolve_cut=True needs deconvolve=True: it is the convolved likelihood's expected counts that the "
+                             "cut on the observed flux changes")
         if not self.deconvolve:
             return
         if self.lum_e is None:
             raise ValueError("deconvolve=True needs lum_e (or flux_e): the sources' errors are what the likelihood is convolved with")
-        if self.min_comp_frac > 0.001:
+        if self.min_comp_frac > 0.001 and not self.deconvolve_cut:
             raise ValueError("deconvolve=True needs min_comp_frac <= 0.001: a cut on the observed flux would change the "
-                             "expected counts, which the convolved likelihood leaves as they are")
+                             "expected counts, which the convolved likelihood leaves as they are (deconvolve_cut=True adds "
+                             "that change)")
+        if self.deconvolve_cut:
+            # The error model at the TRUE flux.  The default is read off the catalogue, which has no sources below the cut:
+            # there it continues as a constant (the faintest node's value).  A caller who knows the errors below the cut
+            # passes (nodes, sigma) with nodes there.
+            nodes, sig = self.error_model() if deconvolve_cut_errors is None else deconvolve_cut_errors
+            self.deconvolve_cut_errors = deconv.check_cut_error_model(nodes, sig, self.nfields)
         if self.shard != "walkers":
             raise NotImplementedError("deconvolve=True is not implemented for shard='sources'")
         K = deconv.DEFAULT_ORDER if deconvolve_order is None else int(deconvolve_order)
@@ -418,6 +438,10 @@ class _Base(object):
             raise NotImplementedError("the gradient runs on one GPU: source- or walker-sharded gradients are not implemented")
         if self.lnprob_fn is not None:
             raise NotImplementedError("the gradient comes from the device context: it cannot use lnprob_fn")
+        if likelihood == "convolved" and self.deconvolve_cut:
+            raise NotImplementedError("the convolved likelihood's gradient is not implemented under deconvolve_cut=True: the "
+                                      "gradient of Delta B, the cut's change of the expected counts, is missing (fit_model, "
+                                      "fit_model_converged and fit_model_pt sample it without a gradient)")
         return self.context().lnprob_err_grad if likelihood == "convolved" else self.context().lnprob_grad
 
     def fit_model_map(self, nstarts=16, seed=None, tol=1e-6, likelihood=None):
@@ -617,6 +641,9 @@ class _Base(object):
         object already holds a device context.  self.lum, var and lfbinorig are not touched."""
         if not self.deconvolve:
             raise ValueError("veff_deconvolved needs an object made with deconvolve=True")
+        if self.deconvolve_cut:
+            raise NotImplementedError("veff_deconvolved is not implemented under deconvolve_cut=True: with min_comp_frac > 0.001 "
+                                      "every source has its own volume (a z_max per source), and the deconvolved points take one")
         from . import deconv
         lfbands._method(method)
         rows = self._posterior_rows(ndraws, lnprobcut)[:, :-1]
@@ -772,7 +799,8 @@ class LumFuncMCMC(_Base):
                  phistar=-3.0, phistar_lims=[-8.0, 5.0], Lc=40.0, Lh=46.0, nwalkers=100, nsteps=1000,
                  fix_sch_al=False, fcmin=0.1, fix_comp=False, min_comp_frac=0.5,
                  field_names=None, field_ind=None, diff_rand=True, device=0, compress=False, shard="walkers",
-                 deconvolve=False, deconvolve_order=None, deconvolve_tile=False, deconvolve_wide=False):
+                 deconvolve=False, deconvolve_order=None, deconvolve_tile=False, deconvolve_wide=False,
+                 deconvolve_cut=False, deconvolve_cut_errors=None):
         self._common_init(z, flux, flux_e, lum, lum_e)
         self.device = device
         self.compress = bool(compress)
@@ -804,7 +832,7 @@ class LumFuncMCMC(_Base):
         self.size_ln = 201 if self.fix_comp else 101
         self.setlnsimple(need_integ=bool(self.fix_comp))
         self.setup_logging()
-        self._init_deconvolve(deconvolve, deconvolve_order, deconvolve_tile, deconvolve_wide)
+        self._init_deconvolve(deconvolve, deconvolve_order, deconvolve_tile, deconvolve_wide, deconvolve_cut, deconvolve_cut_errors)
 
     def getRoot(self, size=201):
         self.rootsf = hs.completeness_roots(self.Flim_lims, self.alpha_lims, self.fcmin, self.min_comp_frac, size)
@@ -1005,7 +1033,8 @@ class LumFuncMCMCz(_Base):
                  phistar=-3.0, phistar_lims=[-8.0, 5.0], Lc=40.0, Lh=46.0, nwalkers=100, nsteps=1000,
                  fcmin=0.1, min_comp_frac=0.5, field_names=None,
                  field_ind=None, z1=1.20, z2=1.53, z3=1.86, fix_sch_al=False, device=0, compress=False, shard="walkers",
-                 deconvolve=False, deconvolve_order=None, deconvolve_tile=False, deconvolve_wide=False):
+                 deconvolve=False, deconvolve_order=None, deconvolve_tile=False, deconvolve_wide=False,
+                 deconvolve_cut=False, deconvolve_cut_errors=None):
         self._common_init(z, flux, flux_e, lum, lum_e)
         self.device = device
         self.compress = bool(compress)
@@ -1038,7 +1067,7 @@ class LumFuncMCMCz(_Base):
         self.size_ln = 201
         self.setlnsimple(need_integ=True)
         self.setup_logging()
-        self._init_deconvolve(deconvolve, deconvolve_order, deconvolve_tile, deconvolve_wide)
+        self._init_deconvolve(deconvolve, deconvolve_order, deconvolve_tile, deconvolve_wide, deconvolve_cut, deconvolve_cut_errors)
 
     def getRoot(self):
         """Per-field flux at which the completeness equals min_comp_frac (lumfuncmcmc_z.py:292-297);
