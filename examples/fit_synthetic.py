@@ -133,6 +133,10 @@ def main():
                          "DESIGN.md sections 3.11, 3.23), p-values per field printed: `none` bins the replicates' true "
                          "luminosities (the comparison for a plain fit), `catalogue` their observed ones under the catalogue's own "
                          "error model (the comparison for --deconvolve)")
+    ap.add_argument("--predictive-cut", action="store_true",
+                    help="with --deconvolve-cut: the posterior predictive check against replicates of the cut process the fit "
+                         "models - sources scattered in and out across the grid's lower edge included - under the fit's own error "
+                         "model (posterior_predictive(cut=True); DESIGN.md section 3.32); the faintest bins are printed as well")
     ap.add_argument("--pt", action="store_true",
                     help="parallel-tempered fit and the evidence by thermodynamic integration (fit_model_pt; DESIGN.md section "
                          "3.10) instead of fit_model")
@@ -225,6 +229,15 @@ def main():
             ob, rb = pp["observed"][f, bright:].sum(), pp["replicated"][:, f, bright:].sum(axis=1)
             print("  field %d: %6d %8.1f %.3f   bright: %6d %8.1f %.3f" % (f, pp["observed_total"][f], np.median(pp["replicated_total"][:, f]),
                                                                          pp["p_upper_total"][f], ob, np.median(rb), np.mean(rb >= ob)))
+    if args.predictive_cut:
+        pp = LFmod.posterior_predictive(seed=11, cut=True)
+        print("posterior predictive check against the cut process, per field: observed total, median replicated total, "
+              "P(rep >= obs), and the same for the two faintest bins")
+        for f in range(pp["nf"]):
+            ob, rb = pp["observed"][f, 1:3].sum(), pp["replicated"][:, f, 1:3].sum(axis=1)
+            print("  field %d: %6d %8.1f %.3f   at the cut: %6d %8.1f %.3f" % (f, pp["observed_total"][f],
+                                                                              np.median(pp["replicated_total"][:, f]),
+                                                                              pp["p_upper_total"][f], ob, np.median(rb), np.mean(rb >= ob)))
     if args.veff_band:
         write_veff_band(LFmod, os.path.join(args.out, "veffband_%s.dat" % tag), volumes=args.veff_volumes)
     print("wrote", sorted(os.listdir(args.out)))

@@ -668,6 +668,29 @@ int lf_mock_draw_err(lf_mock *m, const double *theta, int32_t R, const int64_t *
  * an all-zero sigma the histogram is lf_mock_hist's. */
 int lf_mock_hist_err(lf_mock *m, const double *theta, int32_t R, const int64_t *row_ids, uint64_t seed, int32_t nbins,
                      const double *edges, int64_t *hist);
+/* Mock catalogues of the cut process (csrc/lf_mock_cut.h): what the convolved likelihood under a cut
+ * on the observed flux models (lf_set_cut_error_model).  A source is catalogued when L_obs = L_true + sigma n >= Lam_k =
+ * logL[0][k], k the redshift column of the node it picked and sigma = sigma(field, L_true - ld2n[k]).  The candidates are two
+ * independent Poisson processes: piece "above", lf_mock_draw_err's sources (the same counts, true draws and deviates n), and
+ * piece "below" on a band grid below the edge, on Philox purposes 4-7; both are observed and cut in the same way.
+ * lf_mock_set_cut_band: AFTER lf_mock_set_error_model (a new error model clears the band).  logLb [S][S]: column k holds S
+ * ascending nodes from Lam_k - H to Lam_k (H: the caller's, 7.5 max sigma covers the error model); integ_part_b [nf][S][S]:
+ * FIXCOMP, ZEVOL - volume_part[k] Omega_0[f] / sqarcsec times the fixed completeness curve at the band's nodes; FREE: not read
+ * (NULL).  A field whose sigma is 0 at every node gets no band mass.  LF_ERR_ARG with the reason for: no error model, a NULL
+ * logLb, a band node that is not finite or a column that does not ascend strictly, row S - 1 of logLb different from row 0 of
+ * logL, a missing integ_part_b, an entry of it that is not finite or < 0.
+ * lf_mock_draw_cut: n_cand and mean [R][nf][2] (piece "above", piece "below") are always written.  When their total is
+ * above cap, or cap is 0, nothing else is (LF_OK: the caller sizes the arrays and calls again).  Otherwise every candidate's z,
+ * logL_true, logL_obs, sigma, field and keep flag (1: catalogued): per (row, field) piece "above" in index order, then piece
+ * "below"; kept [R][nf] counts the flags set.  lf_mock_hist_cut: lf_mock_hist_err of the kept candidates, and their number per
+ * (row, field) in kept [R][nf].  Refusals of lf_mock_draw_err and lf_mock_hist_err; an expected count above 2^31 names its
+ * piece; LF_ERR_ARG without a band. */
+int lf_mock_set_cut_band(lf_mock *m, const double *logLb, const double *integ_part_b);
+int lf_mock_draw_cut(lf_mock *m, const double *theta, int32_t R, const int64_t *row_ids, uint64_t seed, int64_t cap, double *z,
+                     double *logL_true, double *logL_obs, double *sigma, int32_t *field, int32_t *keep, int64_t *n_cand,
+                     double *mean, int64_t *kept);
+int lf_mock_hist_cut(lf_mock *m, const double *theta, int32_t R, const int64_t *row_ids, uint64_t seed, int32_t nbins,
+                     const double *edges, int64_t *hist, int64_t *kept);
 /* Last error of this handle; m == NULL: of the last failed lf_mock_create.  Never NULL. */
 const char *lf_mock_last_error(const lf_mock *m);
 

@@ -58,7 +58,8 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_ptsampler_set_likelihood", "lf_lum_posterior", "lf_lum_posterior_info",
            "lf_veff_true", "lf_veff_true_info", "lf_veff_true_ms",
            "lf_mock_set_error_model", "lf_mock_draw_err", "lf_mock_hist_err",
-           "lf_set_cut_error_model", "lf_cut_term_batch", "lf_cut_info")
+           "lf_set_cut_error_model", "lf_cut_term_batch", "lf_cut_info",
+           "lf_mock_set_cut_band", "lf_mock_draw_cut", "lf_mock_hist_cut")
 
 _lib = None
 
@@ -245,6 +246,14 @@ def load():
                                      _c_double_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int32)]
     lib.lf_mock_hist_err.restype = ctypes.c_int
     lib.lf_mock_hist_err.argtypes = lib.lf_mock_hist.argtypes
+    lib.lf_mock_set_cut_band.restype = ctypes.c_int
+    lib.lf_mock_set_cut_band.argtypes = [ctypes.c_void_p, _c_double_p, _c_double_p]
+    lib.lf_mock_draw_cut.restype = ctypes.c_int
+    lib.lf_mock_draw_cut.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int32, _c_int64_p, ctypes.c_uint64, ctypes.c_int64, _c_double_p,
+                                     _c_double_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                     _c_int64_p, _c_double_p, _c_int64_p]
+    lib.lf_mock_hist_cut.restype = ctypes.c_int
+    lib.lf_mock_hist_cut.argtypes = lib.lf_mock_hist.argtypes + [_c_int64_p]
     lib.lf_mock_last_error.restype = ctypes.c_char_p
     lib.lf_mock_last_error.argtypes = [ctypes.c_void_p]
     lib.lf_compress_keys.restype = ctypes.c_int64

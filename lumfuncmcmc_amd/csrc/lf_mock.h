@@ -359,6 +359,27 @@ __device__ __forceinline__ void mock_source(const MockConst& mc, int rf, int f, 
     L = mock_hat(x0, j > 0 ? x0 - lc[(size_t)(j - 1) * S] : 0.0, j < S - 1 ? lc[(size_t)(j + 1) * S] - x0 : 0.0, u53(q[0], q[1]));
 }
 
+// the same source (the same statements and streams), and the column k of the node it picked (lf_mock_cut.h)
+__device__ __forceinline__ void mock_source(const MockConst& mc, int rf, int f, unsigned long long row_id, unsigned int i,
+                                            unsigned long long seed, const double* __restrict__ cdfL,
+                                            const double* __restrict__ cdfZ, double& z, double& L, int& k) {
+#pragma clang fp contract(off)
+    const int S = mc.S;
+    unsigned int r[4], q[4];
+    mock_philox(row_id, i, 1u, f, seed, r);
+    mock_philox(row_id, i, 2u, f, seed, q);
+    const double* cz = cdfZ + (size_t)rf * S;
+    const double t = u53(r[0], r[1]) * cz[S - 1];
+    k = mock_search(cz, S, t);
+    const double tl = t - (k > 0 ? cz[k - 1] : 0.0);
+    const int j = mock_search(cdfL + ((size_t)rf * S + k) * S, S, tl);
+    const double* zr = mc.zarr;
+    z = mock_hat(zr[k], k > 0 ? zr[k] - zr[k - 1] : 0.0, k < S - 1 ? zr[k + 1] - zr[k] : 0.0, u53(r[2], r[3]));
+    const double* lc = mc.logL + k;
+    const double x0 = lc[(size_t)j * S];
+    L = mock_hat(x0, j > 0 ? x0 - lc[(size_t)(j - 1) * S] : 0.0, j < S - 1 ? lc[(size_t)(j + 1) * S] - x0 : 0.0, u53(q[0], q[1]));
+}
+
 // offsets [nrf + 1]: sources of rf are [off[rf], off[rf + 1]); rf = first index with off[rf + 1] > g
 __device__ __forceinline__ int mock_owner(const long long* __restrict__ off, int nrf, long long g) {
     int lo = 0, hi = nrf - 1;

@@ -36,6 +36,7 @@
 #include "lf_free.h"
 #include "lf_mock.h"
 #include "lf_mock_noise.h"
+#include "lf_mock_cut.h"
 #include "lf_pers.h"
 #include "lf_pt.h"
 #include "lf_veffdraws.h"
@@ -3126,6 +3127,13 @@ struct lf_mock {
     lf::MockNoise mn{};                   // the error model (section 3.23); mn.M == 0: none set
     Buf<double> d_nodes, d_sigma, d_ld2n; // its tables
     Buf<double> d_Lobs, d_sg;             // as d_z: the observed luminosities and sigmas of the largest chunk drawn so far
+    bool band = false;                    // the cut process (section 3.32): lf_mock_set_cut_band has made piece "below"
+    lf::MockConst mcb{};                  // mc with the band's logL and integ_part; a field without errors has no mass in it
+    Buf<double> d_logLb, d_ipb;
+    Buf<double> d_cdfLb, d_colmb, d_cdfZb, d_meanb;       // the band's cumulative sums of a chunk, as d_cdfL ..
+    Buf<long long> d_countb, d_offb, d_dst;               // d_dst: [2][rch nf] the pieces' first slots in the outputs
+    Buf<int> d_keep;
+    Buf<unsigned long long> d_kept;
     std::string err;
 };
 
@@ -3367,6 +3375,7 @@ int lf_mock_set_error_model(lf_mock* m, int32_t M, const double* logf_nodes, con
     m->err.clear();
     if (M == 0) {
         m->mn.M = 0;
+        m->band = false;
         return LF_OK;
     }
     if (M < 0 || M > lf::MOCK_MAX_NODES) return mock_fail(m, fn, "M must be in 0.." + std::to_string(lf::MOCK_MAX_NODES));
@@ -3388,6 +3397,7 @@ int lf_mock_set_error_model(lf_mock* m, int32_t M, const double* logf_nodes, con
     }
     LF_HIP(m, hipSetDevice(m->device));
     m->mn.M = 0;                          // (a failed upload leaves no model)
+    m->band = false;                      // (a band belongs to the model it was made under: lf_mock_set_cut_band comes after)
     LF_HIP(m, m->d_nodes.upload(logf_nodes, (size_t)M));
     LF_HIP(m, m->d_sigma.upload(sigma, (size_t)nf * M));
     LF_HIP(m, m->d_ld2n.upload(ld2n.data(), (size_t)S));
@@ -3480,6 +3490,231 @@ int lf_mock_hist_err(lf_mock* m, const double* theta, int32_t R, const int64_t* 
             LF_HIP(m, hipGetLastError());
         }
         LF_HIP(m, hipMemcpy(hist + (size_t)r0 * nf * ns, m->d_hist, (size_t)nrf * ns * sizeof(int64_t), hipMemcpyDeviceToHost));
+    }
+    return LF_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Mock catalogues of the cut process (csrc/lf_mock_cut.h)
+// ------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// both pieces' masses, cumulative sums, means and counts of rows r0 .. r0 + n - 1: mock_masses for piece "above", the same
+// two kernels on the band grid plus the band's own Poisson stream for piece "below"; a refused mean names its piece
+int mock_masses_cut(lf_mock* m, const char* fn, const double* theta, int32_t r0, int n, const int64_t* row_ids, uint64_t seed,
+                    std::vector<double>& muA, std::vector<long long>& nA, std::vector<double>& muB, std::vector<long long>& nB) {
+    const int nf = m->mc.nf, S = m->mc.S, nrf = n * nf;
+    const int rc = mock_masses(m, fn, theta, r0, n, row_ids, seed, muA, nA);
+    if (rc == LF_ERR_ARG) m->err += " (piece \"above\")";
+    if (rc != LF_OK) return rc;
+    hipLaunchKernelGGL(lf::lf_mock_mass, dim3((unsigned)S, (unsigned)nrf), dim3(lf::MOCK_THREADS), 0, 0, m->mcb, m->d_theta, m->d_cdfLb,
+                       m->d_colmb);
+    LF_HIP(m, hipGetLastError());
+    hipLaunchKernelGGL(lf::lf_mock_total, dim3((unsigned)nrf), dim3(lf::MOCK_THREADS), 0, 0, S, nf, m->d_colmb, m->d_rid,
+                       (unsigned long long)seed, m->d_cdfZb, m->d_meanb, m->d_countb);
+    LF_HIP(m, hipGetLastError());
+    hipLaunchKernelGGL(lf::lf_mock_count_cut, dim3((unsigned)((nrf + lf::MOCK_THREADS - 1) / lf::MOCK_THREADS)), dim3(lf::MOCK_THREADS), 0,
+                       0, nrf, nf, m->d_meanb, m->d_rid, (unsigned long long)seed, m->d_countb);
+    LF_HIP(m, hipGetLastError());
+    muB.resize((size_t)nrf);
+    nB.resize((size_t)nrf);
+    LF_HIP(m, hipMemcpy(muB.data(), m->d_meanb, (size_t)nrf * sizeof(double), hipMemcpyDeviceToHost));
+    LF_HIP(m, hipMemcpy(nB.data(), m->d_countb, (size_t)nrf * sizeof(long long), hipMemcpyDeviceToHost));
+    for (int i = 0; i < nrf; ++i)
+        if (nB[(size_t)i] < 0) {
+            char b[200];
+            std::snprintf(b, sizeof b, "row %d field %d: expected count %.17g is not finite, negative or above 2^31 (piece \"below\")",
+                          r0 + i / nf, i % nf, muB[(size_t)i]);
+            return mock_fail(m, fn, b);
+        }
+    return LF_OK;
+}
+
+int mock_cut_ready(lf_mock* m, const char* fn) {
+    if (m->mn.M == 0) return mock_fail(m, fn, "no error model is set (lf_mock_set_error_model)");
+    if (!m->band) return mock_fail(m, fn, "no cut band is set (lf_mock_set_cut_band, after lf_mock_set_error_model)");
+    return LF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lf_mock_set_cut_band(lf_mock* m, const double* logLb, const double* integ_part_b) {
+    static const char* fn = "lf_mock_set_cut_band";
+    if (!m) return LF_ERR_ARG;
+    m->err.clear();
+    if (m->mn.M == 0) return mock_fail(m, fn, "no error model is set: lf_mock_set_error_model comes first");
+    if (!logLb) return mock_fail(m, fn, "logLb is NULL");
+    const int nf = m->mc.nf, S = m->mc.S, M = m->mn.M;
+    const size_t SS = (size_t)S * S;
+    const bool table = m->mc.variant != LF_FREE;
+    if (table && !integ_part_b) return mock_fail(m, fn, "FIXCOMP/ZEVOL need integ_part_b (the fixed completeness curve at the band's nodes)");
+    LF_HIP(m, hipSetDevice(m->device));
+    std::vector<double> edge((size_t)S), sig((size_t)nf * M);
+    LF_HIP(m, hipMemcpy(edge.data(), m->d_grid[0], (size_t)S * sizeof(double), hipMemcpyDeviceToHost));
+    LF_HIP(m, hipMemcpy(sig.data(), m->d_sigma, sig.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int k = 0; k < S; ++k) {
+        for (int j = 0; j < S; ++j)
+            if (!std::isfinite(logLb[(size_t)j * S + k]) || (j > 0 && !(logLb[(size_t)j * S + k] > logLb[(size_t)(j - 1) * S + k])))
+                return mock_fail(m, fn, "column " + std::to_string(k) + " node " + std::to_string(j) +
+                                            ": the band's luminosity nodes must be finite and strictly ascending");
+        if (logLb[(size_t)(S - 1) * S + k] != edge[(size_t)k])
+            return mock_fail(m, fn, "column " + std::to_string(k) + ": row S - 1 of logLb must equal row 0 of logL (the edge of the cut)");
+    }
+    std::vector<double> ipb;
+    if (table) {
+        ipb.assign(integ_part_b, integ_part_b + (size_t)nf * SS);
+        for (size_t i = 0; i < ipb.size(); ++i)
+            if (!std::isfinite(ipb[i]) || ipb[i] < 0.0)
+                return mock_fail(m, fn, "field " + std::to_string(i / SS) + ": integ_part_b must be finite and >= 0");
+    }
+    m->band = false;
+    m->mcb = m->mc;
+    // a field whose sigma is 0 everywhere keeps no band source: it gets no mass (and so no candidates)
+    for (int f = 0; f < nf; ++f) {
+        bool none = true;
+        for (int i = 0; i < M; ++i) none = none && sig[(size_t)f * M + i] == 0.0;
+        if (!none) continue;
+        if (table) std::fill(ipb.begin() + (size_t)f * SS, ipb.begin() + (size_t)(f + 1) * SS, 0.0);
+        else m->mcb.om0s[f] = 0.0;
+    }
+    LF_HIP(m, m->d_logLb.upload(logLb, SS));
+    if (table) LF_HIP(m, m->d_ipb.upload(ipb.data(), ipb.size()));
+    const size_t nrf = (size_t)m->rch * nf;
+    if (m->d_cdfLb.size() < nrf * SS)
+        LF_HIP(m, alloc_all(m->d_cdfLb, nrf * SS, m->d_colmb, nrf * S, m->d_cdfZb, nrf * S, m->d_meanb, nrf, m->d_countb, nrf, m->d_offb,
+                            nrf + 1, m->d_dst, 2 * nrf, m->d_kept, nrf));
+    m->mcb.logL = m->d_logLb;
+    m->mcb.integ_part = table ? m->d_ipb.get() : nullptr;
+    m->band = true;
+    return LF_OK;
+}
+
+int lf_mock_draw_cut(lf_mock* m, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed, int64_t cap, double* z,
+                     double* logL_true, double* logL_obs, double* sigma, int32_t* field, int32_t* keep, int64_t* n_cand, double* mean,
+                     int64_t* kept) {
+    static const char* fn = "lf_mock_draw_cut";
+    if (!m) return LF_ERR_ARG;
+    int rc = mock_check(m, fn, theta, R);
+    if (rc != LF_OK) return rc;
+    if ((rc = mock_cut_ready(m, fn)) != LF_OK) return rc;
+    if (!n_cand || !mean) return mock_fail(m, fn, "n_cand or mean is NULL");
+    if (cap < 0) return mock_fail(m, fn, "cap must be >= 0");
+    if (cap > 0 && (!z || !logL_true || !logL_obs || !sigma || !field || !keep || !kept))
+        return mock_fail(m, fn, "z, logL_true, logL_obs, sigma, field, keep or kept is NULL");
+    LF_HIP(m, hipSetDevice(m->device));
+    const int nf = m->mc.nf;
+    std::vector<double> muA, muB;
+    std::vector<long long> nA, nB, off, dst;
+    int64_t total = 0;
+    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
+        const int rows = std::min<int32_t>(m->rch, R - r0);
+        if ((rc = mock_masses_cut(m, fn, theta, r0, rows, row_ids, seed, muA, nA, muB, nB)) != LF_OK) return rc;
+        for (int i = 0; i < rows * nf; ++i) {
+            const size_t o = 2 * ((size_t)r0 * nf + i);
+            n_cand[o] = nA[(size_t)i], n_cand[o + 1] = nB[(size_t)i];
+            mean[o] = muA[(size_t)i], mean[o + 1] = muB[(size_t)i];
+            total += nA[(size_t)i] + nB[(size_t)i];
+        }
+    }
+    if (total > cap || cap == 0) return LF_OK;          // the counts alone: the caller sizes the arrays and calls again
+    for (int64_t i = 0; i < (int64_t)R * nf; ++i) kept[i] = 0;
+    int64_t done = 0;
+    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
+        const int rows = std::min<int32_t>(m->rch, R - r0);
+        const int nrf = rows * nf;
+        // (one chunk: its cumulative sums are still on the device)
+        if (R > m->rch && (rc = mock_masses_cut(m, fn, theta, r0, rows, row_ids, seed, muA, nA, muB, nB)) != LF_OK) return rc;
+        const int64_t* nc = n_cand + 2 * (size_t)r0 * nf;
+        dst.assign(2 * (size_t)nrf, 0);
+        long long tot = 0;
+        for (int i = 0; i < nrf; ++i) {
+            dst[(size_t)i] = tot;
+            dst[(size_t)nrf + i] = tot + nc[2 * i];
+            tot += nc[2 * i] + nc[2 * i + 1];
+        }
+        if (tot == 0) continue;
+        if ((size_t)tot > m->d_z.size() && (rc = grow(m, m->d_z, (size_t)tot, false)) != LF_OK) return rc;
+        if ((size_t)tot > m->d_L.size() && (rc = grow(m, m->d_L, (size_t)tot, false)) != LF_OK) return rc;
+        if ((size_t)tot > m->d_Lobs.size() && (rc = grow(m, m->d_Lobs, (size_t)tot, false)) != LF_OK) return rc;
+        if ((size_t)tot > m->d_sg.size() && (rc = grow(m, m->d_sg, (size_t)tot, false)) != LF_OK) return rc;
+        if ((size_t)tot > m->d_fld.size() && (rc = grow(m, m->d_fld, (size_t)tot, false)) != LF_OK) return rc;
+        if ((size_t)tot > m->d_keep.size() && (rc = grow(m, m->d_keep, (size_t)tot, false)) != LF_OK) return rc;
+        LF_HIP(m, hipMemcpy(m->d_dst, dst.data(), dst.size() * sizeof(long long), hipMemcpyHostToDevice));
+        for (int piece = 0; piece < 2; ++piece) {
+            off.assign((size_t)nrf + 1, 0);
+            for (int i = 0; i < nrf; ++i) off[(size_t)i + 1] = off[(size_t)i] + nc[2 * i + piece];
+            const long long n = off[(size_t)nrf];
+            if (n == 0) continue;
+            long long* d_off = piece ? m->d_offb : m->d_off;
+            LF_HIP(m, hipMemcpy(d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice));
+            const lf::MockCut ct{m->d_grid[0], piece ? lf::MOCK_CUT_BAND : 0u};
+            hipLaunchKernelGGL(lf::lf_mock_draw_cut, dim3((unsigned)((n + lf::MOCK_THREADS - 1) / lf::MOCK_THREADS)), dim3(lf::MOCK_THREADS), 0,
+                               0, piece ? m->mcb : m->mc, m->mn, ct, nrf, d_off, m->d_dst + (size_t)piece * nrf, m->d_rid,
+                               (unsigned long long)seed, piece ? m->d_cdfLb : m->d_cdfL, piece ? m->d_cdfZb : m->d_cdfZ, m->d_z, m->d_L,
+                               m->d_Lobs, m->d_sg, m->d_fld, m->d_keep);
+            LF_HIP(m, hipGetLastError());
+        }
+        LF_HIP(m, hipMemcpy(z + done, m->d_z, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
+        LF_HIP(m, hipMemcpy(logL_true + done, m->d_L, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
+        LF_HIP(m, hipMemcpy(logL_obs + done, m->d_Lobs, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
+        LF_HIP(m, hipMemcpy(sigma + done, m->d_sg, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
+        LF_HIP(m, hipMemcpy(field + done, m->d_fld, (size_t)tot * sizeof(int), hipMemcpyDeviceToHost));
+        LF_HIP(m, hipMemcpy(keep + done, m->d_keep, (size_t)tot * sizeof(int), hipMemcpyDeviceToHost));
+        for (int i = 0; i < nrf; ++i) {
+            const int64_t a = done + dst[(size_t)i], b = a + nc[2 * i] + nc[2 * i + 1];
+            int64_t k = 0;
+            for (int64_t s = a; s < b; ++s) k += keep[s] != 0;
+            kept[(size_t)r0 * nf + i] = k;
+        }
+        done += tot;
+    }
+    return LF_OK;
+}
+
+int lf_mock_hist_cut(lf_mock* m, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed, int32_t nbins,
+                     const double* edges, int64_t* hist, int64_t* kept) {
+    static const char* fn = "lf_mock_hist_cut";
+    if (!m) return LF_ERR_ARG;
+    int rc = mock_check(m, fn, theta, R);
+    if (rc != LF_OK) return rc;
+    if ((rc = mock_cut_ready(m, fn)) != LF_OK) return rc;
+    if (nbins < 1 || nbins > lf::MOCK_MAX_BINS)
+        return mock_fail(m, fn, "nbins must be in 1.." + std::to_string(lf::MOCK_MAX_BINS));
+    if (!edges || !hist || !kept) return mock_fail(m, fn, "edges, hist or kept is NULL");
+    for (int i = 0; i <= nbins; ++i)
+        if (!std::isfinite(edges[i]) || (i > 0 && !(edges[i] >= edges[i - 1])))
+            return mock_fail(m, fn, "edges must be finite and non-decreasing");
+    LF_HIP(m, hipSetDevice(m->device));
+    LF_HIP(m, hipMemcpy(m->d_edges, edges, (size_t)(nbins + 1) * sizeof(double), hipMemcpyHostToDevice));
+    const int nf = m->mc.nf, ns = nbins + 2;
+    std::vector<double> muA, muB;
+    std::vector<long long> nA, nB, blk;
+    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
+        const int rows = std::min<int32_t>(m->rch, R - r0);
+        const int nrf = rows * nf;
+        if ((rc = mock_masses_cut(m, fn, theta, r0, rows, row_ids, seed, muA, nA, muB, nB)) != LF_OK) return rc;
+        if ((size_t)nrf * ns > m->d_hist.size() && (rc = grow(m, m->d_hist, (size_t)nrf * ns, false)) != LF_OK) return rc;
+        LF_HIP(m, hipMemset(m->d_hist, 0, (size_t)nrf * ns * sizeof(unsigned long long)));
+        LF_HIP(m, hipMemset(m->d_kept, 0, (size_t)nrf * sizeof(unsigned long long)));
+        for (int piece = 0; piece < 2; ++piece) {
+            const std::vector<long long>& n = piece ? nB : nA;
+            blk.assign((size_t)nrf + 1, 0);
+            for (int i = 0; i < nrf; ++i) blk[(size_t)i + 1] = blk[(size_t)i] + (n[(size_t)i] + lf::MOCK_HIST_CHUNK - 1) / lf::MOCK_HIST_CHUNK;
+            if (blk[(size_t)nrf] == 0) continue;
+            long long* d_blk = piece ? m->d_offb : m->d_off;
+            LF_HIP(m, hipMemcpy(d_blk, blk.data(), blk.size() * sizeof(long long), hipMemcpyHostToDevice));
+            const lf::MockCut ct{m->d_grid[0], piece ? lf::MOCK_CUT_BAND : 0u};
+            hipLaunchKernelGGL(lf::lf_mock_hist_cut, dim3((unsigned)blk[(size_t)nrf]), dim3(lf::MOCK_THREADS), 0, 0, piece ? m->mcb : m->mc,
+                               m->mn, ct, nrf, d_blk, piece ? m->d_countb : m->d_count, m->d_rid, (unsigned long long)seed,
+                               piece ? m->d_cdfLb : m->d_cdfL, piece ? m->d_cdfZb : m->d_cdfZ, nbins, m->d_edges, m->d_hist, m->d_kept);
+            LF_HIP(m, hipGetLastError());
+        }
+        LF_HIP(m, hipMemcpy(hist + (size_t)r0 * nf * ns, m->d_hist, (size_t)nrf * ns * sizeof(int64_t), hipMemcpyDeviceToHost));
+        LF_HIP(m, hipMemcpy(kept + (size_t)r0 * nf, m->d_kept, (size_t)nrf * sizeof(int64_t), hipMemcpyDeviceToHost));
     }
     return LF_OK;
 }

@@ -237,6 +237,7 @@ class MockTwin(object):
         self.wL = trapz_weights(self.logL, axis=0)
         self.dl_zarr = inp.get("DL_zarr")     # every variant's kernel_inputs() has it; only the error model needs it
         self.noise = None
+        self._band = None                     # piece "below" of the cut process (set_cut_band)
 
     # ---------------------------------------------------------------- the density
     def lam(self, theta):
@@ -295,10 +296,15 @@ class MockTwin(object):
 
     def sources(self, theta, row_id, f, seed, index, cdfs=None):
         """(z, logL) of sources `index` of field f of one row."""
+        return self._sources(theta, row_id, f, f, seed, index, cdfs)[:2]
+
+    def _sources(self, theta, row_id, f, fs, seed, index, cdfs=None):
+        """(z, logL, k) of sources `index` of field f: k the redshift column of the node each picked; fs the field word of
+        the Philox streams (f; the band of the cut process: f | CUT_BAND)."""
         cdfL, cdfZ = (self._cdfs(theta) if cdfs is None else cdfs)[:2]
         idx = np.asarray(index, dtype=np.uint64)
-        r = _words(row_id, idx, 1, f, seed)
-        q = _words(row_id, idx, 2, f, seed)
+        r = _words(row_id, idx, 1, fs, seed)
+        q = _words(row_id, idx, 2, fs, seed)
         cz = cdfZ[f]
         t = philox.u53(r[0], r[1]) * cz[-1]
         k = _first_above(np.broadcast_to(cz, (t.size, self.S)), t)
@@ -315,7 +321,7 @@ class MockTwin(object):
         x0 = L[j, k]
         a = np.where(j > 0, x0 - L[np.maximum(j - 1, 0), k], 0.0)
         b = np.where(j < S - 1, L[np.minimum(j + 1, S - 1), k] - x0, 0.0)
-        return z, hat_inverse(x0, a, b, philox.u53(q[0], q[1]))
+        return z, hat_inverse(x0, a, b, philox.u53(q[0], q[1])), k
 
     def draw(self, thetas, seed, row_ids=None, count=None):
         """(z, logL, field, offsets): the sources of every (row, field) in that order; offsets [R nf + 1]."""
@@ -349,7 +355,7 @@ class MockTwin(object):
     def set_error_model(self, nodes, sigma):
         """sigma(field, log10 flux) of L_obs = L_true + sigma n: `nodes` (M,) log10 flux, `sigma` (nf, M); None clears it."""
         if nodes is None:
-            self.noise = None
+            self.noise = self._band = None
             return
         nodes, sigma = check_error_model(nodes, sigma, self.nf)
         if self.dl_zarr is None:
@@ -358,6 +364,7 @@ class MockTwin(object):
         if dl.shape != (self.S,) or not np.isfinite(dl).all() or (dl <= 0.0).any():
             raise MockError("DL_zarr must hold S finite values > 0")
         self.noise = (nodes, sigma, ld2_nodes(dl))
+        self._band = None                     # (a band belongs to the model it was made under)
 
     def _observe(self, z, L, fld, off, rid, seed):
         if self.noise is None:
@@ -385,6 +392,180 @@ class MockTwin(object):
         z, L, Lobs, sg, fld, off = self.draw_noisy(thetas, seed, row_ids)
         R = np.atleast_2d(thetas).shape[0]
         return bin_sources(Lobs, off, edges).reshape(R, self.nf, edges.size + 1)
+
+    # ---------------------------------------------------------------- the cut process (lf_mock_cut.h)
+    def set_cut_band(self, logLb, integ_part_b=None):
+        """Piece "below" of the cut process: `logLb` (S, S) from band_grid, `integ_part_b` (nf, S, S) from band_integ_part
+        (FIXCOMP, ZEVOL; FREE: None).  After set_error_model (a new error model clears the band); None clears it."""
+        import copy
+        self._band = None
+        if logLb is None:
+            return
+        if self.noise is None:
+            raise MockError("no error model is set: set_error_model comes first")
+        logLb, ipb = check_cut_band(logLb, integ_part_b, self.logL, self.nf, self.variant != "free")
+        b = copy.copy(self)
+        b.logL, b.wL, b.noise = logLb, trapz_weights(logLb, axis=0), None
+        quiet = ~self.noise[1].any(axis=1)          # a field without errors keeps no band source: no mass
+        if self.variant == "free":
+            b.om0s = np.where(quiet, 0.0, self.om0s)
+        else:
+            b.ip = np.where(quiet[:, None, None], 0.0, ipb)
+        self._band = b
+
+    def candidates_cut(self, thetas, seed, row_ids=None):
+        """Every candidate of the cut process: (z, L_true, L_obs, sigma, field, keep, n_cand (R, nf, 2), mean (R, nf, 2)).
+        Per (row, field) piece "above" in index order, then piece "below"; keep: L_obs >= the edge of the column picked."""
+        th = _rows(thetas, self.ndim)
+        R, nf = th.shape[0], self.nf
+        rid = _row_ids(row_ids, R)
+        if self.noise is None:
+            raise MockError("no error model is set (set_error_model)")
+        if self._band is None:
+            raise MockError("no cut band is set (set_cut_band, after set_error_model)")
+        if not np.isfinite(th).all():
+            raise MockError("row %d: theta is not finite" % int(np.flatnonzero(~np.isfinite(th).all(axis=1))[0]))
+        nodes, sigma, ld2n = self.noise
+        edge = self.logL[0]
+        pieces = (self, self._band)
+        cache = {}
+
+        def cdfs(r):
+            key = th[r].tobytes()
+            if key not in cache:
+                if len(cache) >= 4:
+                    cache.clear()
+                cache[key] = [p._cdfs(th[r]) for p in pieces]
+            return cache[key]
+
+        n_cand = np.zeros((R, nf, 2), dtype=np.int64)
+        mean = np.zeros((R, nf, 2))
+        for r in range(R):
+            cd = cdfs(r)
+            for p in range(2):
+                mean[r, :, p] = cd[p][2]
+                n_cand[r, :, p] = poisson(cd[p][2], rid[r], np.arange(nf) | (p * CUT_BAND), seed)
+        if (n_cand < 0).any():
+            r, f, p = np.argwhere(n_cand < 0)[0]
+            raise MockError("row %d field %d: expected count %.17g is not finite, negative or above 2^31 (piece \"%s\")"
+                            % (r, f, mean[r, f, p], PIECES[p]))
+        cols = [[] for _ in range(6)]
+        for r in range(R):
+            if not n_cand[r].any():
+                continue
+            cd = cdfs(r)
+            for f in range(nf):
+                for p in range(2):
+                    n = int(n_cand[r, f, p])
+                    if not n:
+                        continue
+                    idx, fs = np.arange(n, dtype=np.uint64), f | (p * CUT_BAND)
+                    z, L, k = pieces[p]._sources(th[r], rid[r], f, fs, seed, idx, cd[p])
+                    sg = sigma_lookup(nodes, sigma[f], L - ld2n[k])
+                    Lo = L + sg * _noise(rid[r], idx, fs, seed)
+                    for c, v in zip(cols, (z, L, Lo, sg, np.full(n, f, dtype=np.int32), (Lo >= edge[k]).astype(np.int32))):
+                        c.append(v)
+        cat = lambda v, dt: np.concatenate(v).astype(dt) if v else np.zeros(0, dtype=dt)   # noqa: E731
+        dts = (np.float64,) * 4 + (np.int32,) * 2
+        return tuple(cat(c, dt) for c, dt in zip(cols, dts)) + (n_cand, mean)
+
+    def draw_cut(self, thetas, seed, row_ids=None):
+        """The catalogued sources of the cut process: (z, L_true, L_obs, sigma, field, offsets, info) - see compact_cut."""
+        return compact_cut(*self.candidates_cut(thetas, seed, row_ids))
+
+    def hist_cut(self, thetas, edges, seed, row_ids=None):
+        """(hist (R, nf, nbins + 2) of the catalogued sources' L_obs, kept (R, nf))."""
+        edges = _edges(edges)
+        z, L, Lobs, sg, fld, off, info = self.draw_cut(thetas, seed, row_ids)
+        R = np.atleast_2d(thetas).shape[0]
+        return bin_sources(Lobs, off, edges).reshape(R, self.nf, edges.size + 1), info["kept"]
+
+
+CUT_BAND = 0x400              # piece "below": ORed into the field word of the streams, purposes 4 + (0 .. 3) (lf_mock_cut.h)
+PIECES = ("above", "below")
+
+
+def check_cut_band(logLb, integ_part_b, logL, nf, table):
+    """(logLb (S, S), integ_part_b (nf, S, S) or None) as float64, or MockError naming what lf_mock_set_cut_band refuses."""
+    S = logL.shape[0]
+    lb = np.ascontiguousarray(np.asarray(logLb, dtype=np.float64))
+    if lb.shape != (S, S):
+        raise MockError("logLb must be (S, S) = (%d, %d), got %s" % (S, S, lb.shape))
+    bad = ~np.isfinite(lb)
+    bad[1:] |= ~(np.diff(lb, axis=0) > 0)
+    if bad.any():
+        k, j = np.argwhere(bad.T)[0]
+        raise MockError("column %d node %d: the band's luminosity nodes must be finite and strictly ascending" % (k, j))
+    if (lb[-1] != logL[0]).any():
+        raise MockError("column %d: row S - 1 of logLb must equal row 0 of logL (the edge of the cut)"
+                        % int(np.flatnonzero(lb[-1] != logL[0])[0]))
+    if not table:
+        return lb, None
+    if integ_part_b is None:
+        raise MockError("FIXCOMP/ZEVOL need integ_part_b (the fixed completeness curve at the band's nodes)")
+    ipb = np.ascontiguousarray(np.asarray(integ_part_b, dtype=np.float64))
+    if ipb.shape != (nf, S, S):
+        raise MockError("integ_part_b must be (nf, S, S) = (%d, %d, %d), got %s" % (nf, S, S, ipb.shape))
+    bad = ~np.isfinite(ipb) | (ipb < 0.0)
+    if bad.any():
+        raise MockError("field %d: integ_part_b must be finite and >= 0" % int(np.argwhere(bad)[0][0]))
+    return lb, ipb
+
+
+def cut_depth(sigma, T=7.5):
+    """H of the band: T (deconv.CUT_T) times the largest sigma over all fields and nodes."""
+    return float(T) * float(np.max(sigma))
+
+
+def band_grid(inp, H):
+    """The band grid of the cut process for the inputs `inp`: (S, S), column k's S nodes equally spaced over
+    [Lam_k - H, Lam_k], Lam_k = logL[0, k] (the last row is the edge, bit for bit)."""
+    logL = np.asarray(inp["logL"], dtype=np.float64)
+    if not (np.isfinite(H) and H > 0.0):
+        raise MockError("the band's depth H must be finite and > 0 (an error model that is 0 everywhere needs no band)")
+    S = logL.shape[0]
+    out = np.empty((S, S))
+    for k in range(S):
+        out[:, k] = np.linspace(logL[0, k] - H, logL[0, k], S)
+    out[-1] = logL[0]
+    return out
+
+
+def band_integ_part(inp, logLb):
+    """integ_part of the band for FIXCOMP and ZEVOL inputs: (nf, S, S), volume_part[k] Omega_0[f] / sqarcsec times the modified
+    Fleming curve at the fixed Flim0[f], alpha0 at the node's log10 flux logLb[j, k] - ld2n[k], in the form without
+    cancellation that Delta B uses (deconv._cut_phi_omega), not the reference's spline."""
+    from . import deconv
+    from . import grad as G
+    lb = np.asarray(logLb, dtype=np.float64)
+    nf = len(inp["field_ind"]) - 1
+    vp = np.asarray(inp["volume_part"], dtype=np.float64)
+    logf = lb - ld2_nodes(inp["DL_zarr"])[None]
+    kappa, aC = G._kappa(inp["fcmin"]), float(inp["alpha0"])
+    out = np.empty((nf,) + lb.shape)
+    with np.errstate(all="ignore"):
+        for f in range(nf):
+            Flim = float(np.asarray(inp["Flim0"], dtype=np.float64)[f])
+            om0 = float(np.asarray(inp["Omega_0"], dtype=np.float64)[f]) / G.SQARCSEC
+            y = (logf + 17.0) - np.log10(Flim)
+            vv = 10.0 ** (logf + 17.0) * (np.exp(G.LN10 * kappa / aC) / Flim)
+            out[f] = vp[None] * (om0 * np.exp(deconv._lcomp(y, vv, aC)))
+    return np.where(np.isfinite(out), out, 0.0)
+
+
+def compact_cut(z, L_true, L_obs, sigma, field, keep, n_cand, mean):
+    """The catalogued sources of candidates_cut: (z, L_true, L_obs, sigma, field, offsets [R nf + 1], info), per (row, field)
+    piece "above" in index order, then piece "below".  info: n_cand, mean (R, nf, 2), kept (R, nf), n_candidates (R, nf) and
+    n_scattered_in (R, nf): the kept sources of piece "below", whose L_true lies below their edge (at it only when a hat's
+    root rounds to 1, a chance of about 2^-53 per source)."""
+    R, nf = n_cand.shape[:2]
+    k = keep != 0
+    seg = np.repeat(np.arange(R * nf * 2), n_cand.ravel())
+    per = np.bincount(seg[k], minlength=R * nf * 2).reshape(R, nf, 2).astype(np.int64)
+    kept = per.sum(axis=2)
+    off = np.concatenate([[0], np.cumsum(kept.ravel())]).astype(np.int64)
+    info = {"n_cand": n_cand, "mean": mean, "kept": kept, "n_candidates": n_cand.sum(axis=2), "n_scattered_in": per[:, :, 1]}
+    return z[k], L_true[k], L_obs[k], sigma[k], field[k], off, info
 
 
 MAX_NODES = 64                # lf_mock_noise.h: MOCK_MAX_NODES
@@ -651,6 +832,75 @@ class MockGenerator(object):
                                                nb, capi._ptr(e), out.ctypes.data_as(capi._c_int64_p)))
         return out
 
+    # ---------------------------------------------------------------- the cut process (lf_mock_cut.h)
+    def set_cut_band(self, logLb, integ_part_b=None):
+        """As MockTwin.set_cut_band, uploaded through lf_mock_set_cut_band (which validates again).  None: a band stays on
+        the device until the next set_error_model; the calls below then refuse through this flag."""
+        from . import capi
+        self._band_set = False
+        if logLb is None:
+            return
+        lb = capi._f64(logLb)
+        if lb.shape != (self.S, self.S):
+            raise MockError("logLb must be (S, S) = (%d, %d), got %s" % (self.S, self.S, lb.shape))
+        ipb = None
+        if integ_part_b is not None and self.variant != "free":
+            ipb = capi._f64(integ_part_b)
+            if ipb.shape != (self.nf, self.S, self.S):
+                raise MockError("integ_part_b must be (nf, S, S) = (%d, %d, %d), got %s" % (self.nf, self.S, self.S, ipb.shape))
+        self._check(self._lib.lf_mock_set_cut_band(self._h, capi._ptr(lb), capi._ptr(ipb)))
+        self._band_set = True
+
+    def candidates_cut(self, thetas, seed, row_ids=None):
+        """As MockTwin.candidates_cut, drawn, observed and cut on the device (lf_mock_draw_cut)."""
+        from . import capi
+        th = _rows(thetas, self.ndim)
+        R = th.shape[0]
+        rid = _row_ids(row_ids, R)
+        if not getattr(self, "_band_set", True):
+            raise MockError("no cut band is set (set_cut_band, after set_error_model)")
+        n_cand = np.zeros((R, self.nf, 2), dtype=np.int64)
+        mean = np.zeros((R, self.nf, 2))
+        kept = np.zeros((R, self.nf), dtype=np.int64)
+        i32 = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))   # noqa: E731
+
+        def call(cap, z, L, Lobs, sg, fld, keep):
+            self._check(self._lib.lf_mock_draw_cut(self._h, capi._ptr(th), R, rid.ctypes.data_as(capi._c_int64_p), ctypes.c_uint64(int(seed)),
+                                                   cap, capi._ptr(z), capi._ptr(L), capi._ptr(Lobs), capi._ptr(sg),
+                                                   i32(fld) if fld is not None else None, i32(keep) if keep is not None else None,
+                                                   n_cand.ctypes.data_as(capi._c_int64_p), capi._ptr(mean),
+                                                   kept.ctypes.data_as(capi._c_int64_p)))
+
+        call(0, None, None, None, None, None, None)
+        total = int(n_cand.sum())
+        z, L, Lobs, sg = np.empty(total), np.empty(total), np.empty(total), np.empty(total)
+        fld, keep = np.empty(total, dtype=np.int32), np.empty(total, dtype=np.int32)
+        if total:
+            call(total, z, L, Lobs, sg, fld, keep)
+        return z, L, Lobs, sg, fld, keep, n_cand, mean
+
+    def draw_cut(self, thetas, seed, row_ids=None):
+        """The catalogued sources of the cut process: (z, L_true, L_obs, sigma, field, offsets, info) - see compact_cut (the
+        compaction runs on the host: the arrays are copied there anyway)."""
+        return compact_cut(*self.candidates_cut(thetas, seed, row_ids))
+
+    def hist_cut(self, thetas, edges, seed, row_ids=None):
+        """(hist (R, nf, nbins + 2) of the catalogued sources' L_obs, kept (R, nf)) without writing sources (lf_mock_hist_cut)."""
+        from . import capi
+        th = _rows(thetas, self.ndim)
+        R = th.shape[0]
+        rid = _row_ids(row_ids, R)
+        if not getattr(self, "_band_set", True):
+            raise MockError("no cut band is set (set_cut_band, after set_error_model)")
+        e = _edges(edges)
+        nb = e.size - 1
+        out = np.empty((R, self.nf, nb + 2), dtype=np.int64)
+        kept = np.empty((R, self.nf), dtype=np.int64)
+        self._check(self._lib.lf_mock_hist_cut(self._h, capi._ptr(th), R, rid.ctypes.data_as(capi._c_int64_p), ctypes.c_uint64(int(seed)),
+                                               nb, capi._ptr(e), out.ctypes.data_as(capi._c_int64_p),
+                                               kept.ctypes.data_as(capi._c_int64_p)))
+        return out, kept
+
     def close(self):
         if self._h is not None:
             self._lib.lf_mock_destroy(self._h)
@@ -675,12 +925,15 @@ def lum_noise(n_per_field, row_id, seed):
     """Standard normal deviates of the sources 0 .. n_f - 1 of every field f of one row (concatenated field by field):
     Box-Muller on the two 53-bit uniforms of the Philox block (row_id, index, NOISE_PURPOSE, f) - a stream of its own, so the
     noiseless draws keep their bits.  Host arithmetic for both generators."""
-    out = []
-    for f, n in enumerate(n_per_field):
-        w = _words(row_id, np.arange(int(n), dtype=np.uint64), NOISE_PURPOSE, f, seed)
-        u1, u2 = philox.u53(w[0], w[1]), philox.u53(w[2], w[3])
-        out.append(np.sqrt(-2.0 * np.log1p(-u1)) * np.cos(2.0 * np.pi * u2))         # (1 - u1 in (0, 1]: no log of 0)
+    out = [_noise(row_id, np.arange(int(n), dtype=np.uint64), f, seed) for f, n in enumerate(n_per_field)]
     return np.concatenate(out) if out else np.zeros(0)
+
+
+def _noise(row_id, index, fs, seed):
+    """lum_noise's deviates of the sources `index` of one field word fs (f; the band of the cut process: f | CUT_BAND)"""
+    w = _words(row_id, index, NOISE_PURPOSE, fs, seed)
+    u1, u2 = philox.u53(w[0], w[1]), philox.u53(w[2], w[3])
+    return np.sqrt(-2.0 * np.log1p(-u1)) * np.cos(2.0 * np.pi * u2)                  # (1 - u1 in (0, 1]: no log of 0)
 
 
 def catalogue_lists(z, logL, field, nf, lum_err=None, seed=0, row_id=0):
@@ -712,17 +965,25 @@ def observed_lists(z, logL_true, logL_obs, sigma, field, nf):
     return {"z": split(z), "lum": split(logL_obs), "lum_e": split(sigma), "field_ind": fi, "lum_true": split(logL_true)}
 
 
-def predictive(gen, rows, edges, observed_lum, observed_fi, seed, noisy=False):
+def predictive(gen, rows, edges, observed_lum, observed_fi, seed, noisy=False, cut=False):
     """Posterior predictive check of the logL histogram per field: `rows` (R, ndim) posterior draws, `edges` (B + 1),
     the observed catalogue's lum and field_ind.  noisy: the replicates are binned by their observed luminosities under
-    the generator's error model (hist_noisy).  Returns the dict of _Base.posterior_predictive."""
+    the generator's error model (hist_noisy).  cut: the replicates are catalogues of the cut process (hist_cut; the generator
+    holds an error model and a band) - `replicated` then bins the catalogued sources only, and the dict also holds
+    `replicated_kept` (R, nf), their number.  `expected` stays the count above the edge before the observation, B.  Returns the
+    dict of _Base.posterior_predictive."""
     edges = _edges(edges)
     nf = len(observed_fi) - 1
     obs = bin_sources(np.asarray(observed_lum, dtype=np.float64), np.asarray(observed_fi, dtype=np.int64), edges)
-    rep = gen.hist_noisy(rows, edges, seed) if noisy else gen.hist(rows, edges, seed)
+    kept = None
+    if cut:
+        rep, kept = gen.hist_cut(rows, edges, seed)
+    else:
+        rep = gen.hist_noisy(rows, edges, seed) if noisy else gen.hist(rows, edges, seed)
     expected = gen.counts(rows, seed)[0]
     obs_tot, rep_tot = obs.sum(axis=1), rep.sum(axis=2)
-    return {"edges": edges, "observed": obs, "replicated": rep, "expected": expected,
+    extra = {"replicated_kept": kept} if cut else {}
+    return {**extra, "edges": edges, "observed": obs, "replicated": rep, "expected": expected,
             "percentiles": np.percentile(rep, (16.0, 50.0, 84.0), axis=0),
             "p_upper": np.mean(rep >= obs[None], axis=0), "p_lower": np.mean(rep <= obs[None], axis=0),
             "observed_total": obs_tot, "replicated_total": rep_tot,

@@ -688,7 +688,32 @@ class _Base(object):
         nodes, sigma = spec
         return mock.check_error_model(nodes, sigma, self.nfields)
 
-    def mock_catalogue(self, theta, seed=None, device=None, lum_err=None):
+    def _cut_model(self, spec, keyword):
+        """(nodes, sigma) of the error model of a cut mock: `spec` as _noise_model takes it; None on a deconvolve_cut=True
+        object: its deconvolve_cut_errors, so that the mock and the likelihood use one model."""
+        if not self.min_comp_frac > 0.001:
+            raise ValueError("cut=True needs min_comp_frac > 0.001: with min_comp_frac <= 0.001 the grid has one lower edge for "
+                             "all redshifts, at min(lum), and there is no cut on the observed flux to draw")
+        if spec is None and self.deconvolve_cut:
+            return self.deconvolve_cut_errors
+        pair = isinstance(spec, (tuple, list)) and len(spec) == 2 and np.ndim(spec[1]) == 2
+        if not (isinstance(spec, str) or pair):
+            raise ValueError("cut=True needs a flux-dependent error model: %s=\"catalogue\" or a (nodes, sigma) pair (a "
+                             "deconvolve_cut=True object supplies its deconvolve_cut_errors by default), got %r" % (keyword, spec))
+        return self._noise_model(spec)
+
+    def _set_cut_process(self, gen, model):
+        """the error model and the band of the cut process on a generator"""
+        from . import deconv
+        inp = self.kernel_inputs()
+        gen.set_error_model(*model)
+        H = mock.cut_depth(model[1], deconv.CUT_T)
+        if not H > 0.0:
+            raise ValueError("cut=True needs an error model with sigma > 0 somewhere: without errors no source crosses the cut")
+        logLb = mock.band_grid(inp, H)
+        gen.set_cut_band(logLb, None if inp["variant"] == "free" else mock.band_integ_part(inp, logLb))
+
+    def mock_catalogue(self, theta, seed=None, device=None, lum_err=None, cut=False):
         """One catalogue drawn from the model at `theta`: the Poisson process whose likelihood
         lnprob evaluates, on this object's integration grid.  Returns the per-field lists both constructors take - z, lum,
         lum_e (zeros), field_ind - plus theta and seed.  seed=None draws one from numpy's global state (as fit_model does);
@@ -699,10 +724,26 @@ class _Base(object):
         noiseless values.  None: the output is what it was without the keyword, bit for bit.  lum_err="catalogue" (this
         catalogue's self.error_model()) or a (nodes, sigma) pair: the width is a function of the field and of the source's
         true log10 flux (section 3.23), lum_e holds every source's own sigma, and on the device path the noise is added on
-        the GPU (the same stream and expression: the NumPy path agrees to the rounding of the device's cos and log1p)."""
+        the GPU (the same stream and expression: the NumPy path agrees to the rounding of the device's cos and log1p).
+
+        cut=True (needs min_comp_frac > 0.001 and a flux-dependent error model, by default the
+        deconvolve_cut_errors of a deconvolve_cut=True object): a catalogue of the process deconvolve_cut=True models.  Sources
+        are also drawn below the grid's lower edge, every source is observed with sigma at its true flux, and only those
+        whose observed luminosity reaches the edge of their redshift column are returned (per field: those from above the
+        edge, then those scattered in).  The lists also hold lum_true, n_candidates and n_scattered_in (per field: the
+        sources drawn, and the returned ones whose lum_true lies below their edge).  cut=False: nothing changes."""
         if seed is None:
             seed = int(np.random.randint(0, 2 ** 31 - 1))
         theta = np.asarray(theta, dtype=np.float64).ravel()
+        if cut:
+            model = self._cut_model(lum_err, "lum_err")
+            gen = self._mock_generator(device)
+            self._set_cut_process(gen, model)
+            z, lum, lobs, sg, fld, _, info = gen.draw_cut(theta[None], seed)
+            out = mock.observed_lists(z, lum, lobs, sg, fld, self.nfields)
+            out["n_candidates"], out["n_scattered_in"] = info["n_candidates"][0].copy(), info["n_scattered_in"][0].copy()
+            out["theta"], out["seed"] = theta.copy(), int(seed)
+            return out
         gen = self._mock_generator(device)
         # (a pair's sigma is two-dimensional, (nf, M): a sequence of two numbers stays one value per field)
         if isinstance(lum_err, str) or (isinstance(lum_err, (tuple, list)) and len(lum_err) == 2 and np.ndim(lum_err[1]) == 2):
@@ -715,7 +756,7 @@ class _Base(object):
         out["theta"], out["seed"] = theta.copy(), int(seed)
         return out
 
-    def posterior_predictive(self, edges=None, ndraws=200, lnprobcut=7.5, seed=None, device=None, noise=None):
+    def posterior_predictive(self, edges=None, ndraws=200, lnprobcut=7.5, seed=None, device=None, noise=None, cut=False):
         """Posterior predictive check of the observed luminosities per field: ndraws posterior rows (drawn as
         set_median_fit draws them), one mock catalogue each, binned in logL with `edges` (default: 20 equal bins over
         [min(lum), max(lum)]) by searchsorted(edges, x, side="right") - slot 0 below edges[0], slot B + 1 at or above
@@ -731,20 +772,30 @@ class _Base(object):
         deconvolve_wide=True) posterior describes the true luminosities; the catalogue holds the observed ones, so its
         replicates are to be compared with the catalogue under noise="catalogue" - without it the check reports a
         bright-end excess that is only the Eddington bias the fit removed.  The dict also holds `noise` (None, "catalogue"
-        or "model") and `sigma_model` (None or the (nodes, sigma) used)."""
+        or "model") and `sigma_model` (None or the (nodes, sigma) used).
+
+        cut=True (as in mock_catalogue): the replicates are catalogues of the cut process - what a
+        deconvolve_cut=True fit models, sources scattered in and out across the grid's lower edge included.  The dict then
+        also holds `replicated_kept` [R, nf] and cut = True; `expected` stays the count above the edge before the observation
+        (B; the cut process expects B + Delta B).  noise=None then means the object's deconvolve_cut_errors."""
+        model = self._cut_model(noise, "noise") if cut else None
         rows = self._posterior_rows(ndraws, lnprobcut)[:, :-1]
         if edges is None:
             edges = np.linspace(np.min(self.lum), np.max(self.lum), 21)
         if seed is None:
             seed = int(np.random.randint(0, 2 ** 31 - 1))
         gen = self._mock_generator(device)
-        model = None
-        if noise is not None:
+        if cut:
+            self._set_cut_process(gen, model)
+        elif noise is not None:
             model = self._noise_model(noise)
             gen.set_error_model(*model)
-        out = mock.predictive(gen, rows, edges, self.lum, np.asarray(self.field_ind, dtype=np.int64), seed, noisy=noise is not None)
-        out["noise"] = None if noise is None else ("catalogue" if isinstance(noise, str) else "model")
+        out = mock.predictive(gen, rows, edges, self.lum, np.asarray(self.field_ind, dtype=np.int64), seed, noisy=noise is not None,
+                              cut=cut)
+        out["noise"] = ("model" if cut else None) if noise is None else ("catalogue" if isinstance(noise, str) else "model")
         out["sigma_model"] = model
+        if cut:
+            out["cut"] = True
         return out
 
     def add_fitinfo_to_table(self, percentiles, start_value=1, lnprobcut=7.5):
