@@ -119,7 +119,9 @@ def main():
                          "being refused (deconvolve_wide=True; DESIGN.md section 3.21)")
     ap.add_argument("--deconvolve-cut", action="store_true",
                     help="with --deconvolve: fit at min_comp_frac = 0.5, the classes' default, with the cut on the observed flux "
-                         "modelled (deconvolve_cut=True; DESIGN.md section 3.31); not with --map or --veff-deconvolved")
+                         "modelled (deconvolve_cut=True; DESIGN.md section 3.31); with --map the gradient of the cut's term is "
+                         "served too (deconvolve_cut_grad=True; DESIGN.md section 3.33) and the convolved and the plain maximum "
+                         "are printed side by side, as without the cut; not with --veff-deconvolved")
     ap.add_argument("--deconvolved-lums", metavar="FILE", default="",
                     help="with --deconvolve: every source's posterior mean and spread of its TRUE luminosity over 200 posterior "
                          "draws (deconvolved_luminosities; DESIGN.md section 3.22) written to FILE: ID, lum, lum_e, lum_true, "
@@ -149,8 +151,8 @@ def main():
         ap.error("--deconvolved-lums needs --deconvolve")
     if args.veff_deconvolved and not args.deconvolve:
         ap.error("--veff-deconvolved needs --deconvolve")
-    if args.deconvolve_cut and (not args.deconvolve or args.map or args.veff_deconvolved):
-        ap.error("--deconvolve-cut needs --deconvolve, and neither --map nor --veff-deconvolved (DESIGN.md section 3.31)")
+    if args.deconvolve_cut and (not args.deconvolve or args.veff_deconvolved):
+        ap.error("--deconvolve-cut needs --deconvolve, and not --veff-deconvolved (DESIGN.md section 3.31)")
     if args.pt and args.until_converged:
         ap.error("--pt and --until-converged are two fits: choose one")
     os.makedirs(args.out, exist_ok=True)
@@ -167,7 +169,7 @@ def main():
                         min_comp_frac=0.5 if args.deconvolve_cut else 0.0, Flim_lims=synth.FLIM_LIMS, alpha_lims=synth.ALPHA_LIMS,
                         field_names=field_names, field_ind=field_ind, compress=args.compress, deconvolve=args.deconvolve,
                         deconvolve_tile=args.deconvolve_tile, deconvolve_wide=args.deconvolve_wide,
-                        deconvolve_cut=args.deconvolve_cut)
+                        deconvolve_cut=args.deconvolve_cut, deconvolve_cut_grad=args.deconvolve_cut and args.map)
     print("setup %.2f s for %d sources" % (time.time() - t0, len(LFmod.lum)))
     np.random.seed(3)
     plain_map = None

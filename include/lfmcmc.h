@@ -283,8 +283,8 @@ int lf_veff_true_ms(double ms[3]);
  * finite, < 0 or above 0.30 dex (the limit is stated), a field whose sigma is 0 at some nodes only, a model that needs more
  * than 64 panels on one side of the edge, a context without the cut (separable grid), a source-sharded context, and a call
  * after lf_set_lum_err.  Still refused on such a context, with what is missing in the message: lf_lnprob_err_grad_batch(_device)
- * (the gradient of Delta B) and lf_veff_true (per-source volumes); lf_lum_posterior is served (a source's posterior given that
- * it is catalogued does not involve B).
+ * (the gradient of Delta B; served with the option "deconv_cut_grad", below) and lf_veff_true (per-source volumes);
+ * lf_lum_posterior is served (a source's posterior given that it is catalogued does not involve B).
  * lf_cut_term_batch: Delta B alone for B rows (host pointers, synchronous; after lf_set_lum_err); NaN for a row whose plain
  * lnprob is not finite.  Summed in one fixed order without atomics: a row's bits do not depend on B or on its place.
  * lf_cut_info: the nodes per field and H per field (up to cap entries; either may be NULL), the nodes per block and the number
@@ -295,6 +295,23 @@ int lf_veff_true_ms(double ms[3]);
 int lf_set_cut_error_model(lf_ctx *ctx, const double *nodes, int M, const double *sigma);
 int lf_cut_term_batch(lf_ctx *ctx, const double *theta, int B, double *out);
 int lf_cut_info(lf_ctx *ctx, int32_t *nnodes, double *H, int cap, int *chunk, int *chunks);
+
+/* The gradient of Delta B (csrc/lf_deconv_cut_grad.h).  u does not depend on theta, so -Delta B =
+ * sum_n c_n phi_theta(L_n[, z_j]) [fc^(1/d)_theta: FREE] over the tables above, and its derivatives are those of the expected
+ * counts' lattice nodes with c_n as the weight: per node I_n times ln10 (10^x - alpha - 1), ln10, ln10 x (x = L_n - L*) for L*,
+ * phi*, alpha (z-evolving: times the Lagrange basis for L_m, phi_m), and for FREE I_n dF_n / Flim_f (the field's nodes only) and
+ * I_n dC_n.  First stage: lf_cut_term_batch's grid, chunks and node order, one running sum per element kind, the block's tail
+ * as there; second stage: one wave per row, lane l adds chunks l, l + 64, ..., then the shuffle tree.  No atomics: a row's bits
+ * do not depend on B or on its place.
+ * Option "deconv_cut_grad" (lf_set_option; default 0): with 1, lf_lnprob_err_grad_batch and _device serve a context with the
+ * cut model - the value is lf_lnprob_err_batch's, bit for bit (lnprob + Delta - Delta B), and every gradient element is the
+ * plain one, plus Delta's, plus that of -Delta B, added in that order; rows whose plain lnprob is not finite: NaN.  With 0 the
+ * two entries refuse such a context as before.  Without a cut model the option does nothing; with a cut model of sigma = 0
+ * (no nodes) nothing more is launched.  It may be switched between calls.
+ * lf_cut_term_grad_batch: Delta B [B] and d Delta B / d theta [B][ndim] for B rows (host pointers, synchronous; after
+ * lf_set_lum_err; whatever the option says).  out is lf_cut_term_batch's, bit for bit; a row whose plain lnprob is not finite
+ * has NaN in out and in every element. */
+int lf_cut_term_grad_batch(lf_ctx *ctx, const double *theta, int B, double *out, double *grad);
 
 /* Kernel timing for bench.py: level 1 brackets lf_main, level 2 every launch, with hipEvents on
  * the stream the launch runs on (0 = off; each event pair costs a few microseconds of stream time: the events are

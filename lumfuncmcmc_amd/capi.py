@@ -58,7 +58,7 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_ptsampler_set_likelihood", "lf_lum_posterior", "lf_lum_posterior_info",
            "lf_veff_true", "lf_veff_true_info", "lf_veff_true_ms",
            "lf_mock_set_error_model", "lf_mock_draw_err", "lf_mock_hist_err",
-           "lf_set_cut_error_model", "lf_cut_term_batch", "lf_cut_info",
+           "lf_set_cut_error_model", "lf_cut_term_batch", "lf_cut_info", "lf_cut_term_grad_batch",
            "lf_mock_set_cut_band", "lf_mock_draw_cut", "lf_mock_hist_cut")
 
 _lib = None
@@ -122,6 +122,8 @@ def load():
     lib.lf_set_cut_error_model.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int, _c_double_p]
     lib.lf_cut_term_batch.restype = ctypes.c_int
     lib.lf_cut_term_batch.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int, _c_double_p]
+    lib.lf_cut_term_grad_batch.restype = ctypes.c_int
+    lib.lf_cut_term_grad_batch.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p]
     lib.lf_cut_info.restype = ctypes.c_int
     lib.lf_cut_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), _c_double_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                 ctypes.POINTER(ctypes.c_int)]
@@ -832,6 +834,12 @@ class LFContext(object):
         if th.shape[0]:
             self._check(self._lib.lf_cut_term_batch(self._h, _ptr(th), th.shape[0], _ptr(out)))
         return out
+
+    def cut_term_grad(self, theta):
+        """theta (B, ndim) or (ndim,) host array -> (Delta B (B,), d Delta B / d theta (B, ndim)): lf_cut_term_grad_batch.  Delta
+        B is cut_term_batch's, bit for bit; a row whose plain lnprob is not finite has NaN throughout.
+        Served whatever the option "deconv_cut_grad" says."""
+        return self._value_grad(self._lib.lf_cut_term_grad_batch, theta)
 
     def cut_info(self):
         """lf_cut_info: dict nnodes (nf,), H (nf,), chunk (nodes per block), chunks (blocks per row; -1 before the tables are made)."""

@@ -24,6 +24,7 @@
 #include "lf_diag.h"
 #include "lf_deconv.h"
 #include "lf_deconv_cut.h"
+#include "lf_deconv_cut_grad.h"
 #include "lf_deconv_grad.h"
 #include "lf_deconv_tile.h"
 #include "lf_deconv_wide.h"
@@ -192,6 +193,8 @@ struct lf_ctx {
     // sigma = 0 throughout)
     std::vector<double> h_edge_lo, h_edge_hi, h_zarr, h_vol, h_ld2, h_om0;
     int64_t opt_cut_limit = 0;          // > 0: only the first so many nodes of every field (tests)
+    int64_t opt_cut_grad = 0;           // 1: the gradient entries of the convolved likelihood serve the cut model (lf_deconv_cut_grad.h)
+    Buf<double> d_cgpart;               // the cut gradient's partial sums [rows][cut chunks][GRAD_SLOTS]
     struct {
         bool model = false, built = false;       // an error model is set; the tables are made (fixed completeness: by lf_set_lum_err)
         int M = 0;
@@ -968,6 +971,12 @@ int cut_refuse(lf_ctx* c, const char* fn, const char* missing) {
     return LF_ERR_ARG;
 }
 
+// the cut gradient's partial sums for B rows (lf_deconv_cut_grad.h)
+int cut_grad_workspace(lf_ctx* c, int B) {
+    const size_t need = (size_t)B * std::max(c->cut.n, 1) * lf::GRAD_SLOTS;
+    return need > c->d_cgpart.size() ? grow(c, c->d_cgpart, need) : LF_OK;
+}
+
 // What the correction's kernels need before anything is enqueued: the chunk table and the blocks' partial sums [rows][chunks]
 // (grad: and [rows][chunks][DGRAD_SLOTS]); chunks: the narrow ones and behind them those of the wide list.
 int deconv_prepare(lf_ctx* c, int B, bool grad) {
@@ -976,6 +985,7 @@ int deconv_prepare(lf_ctx* c, int B, bool grad) {
     const size_t need = (size_t)B * std::max(c->src_chunks.n + c->wide.n + c->cut.n, 1);
     if (need > c->d_dpart.size() && (rc = grow(c, c->d_dpart, need)) != LF_OK) return rc;
     if (grad && need * lf::DGRAD_SLOTS > c->d_dgpart.size() && (rc = grow(c, c->d_dgpart, need * lf::DGRAD_SLOTS)) != LF_OK) return rc;
+    if (grad && c->opt_cut_grad && c->cut.n > 0) return cut_grad_workspace(c, B);
     return LF_OK;
 }
 
@@ -1015,6 +1025,16 @@ lf::DeconvCutArgs deconv_cut_args(lf_ctx* c, const double* d_theta, const double
     const auto& t = c->cut;
     return lf::DeconvCutArgs{c->gradc, d_theta, d_lnp, part + before, d_out, t.d_L, t.d_P, t.d_c, t.d_a3, t.d_a4,
                              t.d_start, t.d_len, t.d_field, stride, t.n};
+}
+
+// lf_deconv_cut_grad.h's arguments for rows [b0, ...) of a call whose arguments are ca (cgpart: [rows][cut chunks][GRAD_SLOTS])
+lf::DeconvCutGradArgs deconv_cut_grad_args(const lf::DeconvCutArgs& ca, int b0, double* cgpart, double* grad, bool alone) {
+    lf::DeconvCutGradArgs g{ca, cgpart + (size_t)b0 * ca.nch * lf::GRAD_SLOTS, grad + (size_t)b0 * ca.gc.ndim, alone ? 1 : 0};
+    g.d.theta += (size_t)b0 * ca.gc.ndim;
+    g.d.lnprob += b0;
+    if (g.d.part) g.d.part += (size_t)b0 * ca.stride;
+    if (g.d.out) g.d.out += b0;
+    return g;
 }
 
 // lf_deconv_wide.h's arguments from the narrow kernels' (da: the rows of one launch): the wide list's arrays and chunks, the
@@ -1074,7 +1094,8 @@ int enqueue_deconv(lf_ctx* c, const double* d_theta, int B, double* d_lnp, doubl
 
 // The flux-error-convolved lnprob of B rows and its gradient (lf_deconv_grad.h), all on `s`: the plain lnprob and the plain
 // gradient (enqueue_grad: d_lnp, d_grad), the value's kernels as enqueue_deconv launches them on that lnprob (d_out: what
-// lf_lnprob_err_batch_device gives, bit for bit), then the correction's gradient, added to d_grad in place.
+// lf_lnprob_err_batch_device gives, bit for bit), then the correction's gradient, added to d_grad in place,
+// and with the option "deconv_cut_grad" under a cut model the gradient of -Delta B (lf_deconv_cut_grad.h), added behind it.
 int enqueue_deconv_grad(lf_ctx* c, const double* d_theta, int B, double* d_lnp, double* d_out, double* d_grad, hipStream_t s) {
     using namespace lf;
     int rc;
@@ -1082,18 +1103,27 @@ int enqueue_deconv_grad(lf_ctx* c, const double* d_theta, int B, double* d_lnp, 
     if ((rc = enqueue_grad(c, d_theta, B, d_lnp, d_grad, s)) != LF_OK) return rc;
     const DeconvGradArgs da{deconv_args(c, d_theta, d_lnp, d_out), c->d_dgpart, d_grad};
     launch_deconv(c, da.d, B, s, false);          // (the gradient's value: the per-row kernels whatever "deconv_tile" says)
+    // the cut's gradient (option "deconv_cut_grad"; no nodes - an error model of sigma = 0 -: nothing is launched)
+    const bool cut_grad = c->opt_cut_grad && c->cut.n > 0;
+    const DeconvCutArgs ca = deconv_cut_args(c, d_theta, d_lnp, nullptr, 0, 0, nullptr);
     launch_rows(c->kc.variant, B, [&](auto v, int b0, int nb) {
         DeconvGradArgs g = da;
+        const int n0 = c->src_chunks.n, nw = c->wide.n;
         g.d.theta += (size_t)b0 * g.d.gc.ndim;
         g.d.lnprob += b0;
+        g.d.nch = n0 + nw;                        // (Delta's blocks: the cut's have no slots in gpart, and no field in chunk_field)
         g.gpart += (size_t)b0 * g.d.nch * DGRAD_SLOTS;
         g.grad += (size_t)b0 * g.d.gc.ndim;
-        const int n0 = c->src_chunks.n, nw = c->wide.n;
         if (n0 > 0) hipLaunchKernelGGL(lf_deconv_grad_part<v()>, dim3((unsigned)n0, (unsigned)nb), dim3(BLOCK), 0, s, g);
         if (nw > 0)
             hipLaunchKernelGGL(lf_deconv_wide_grad_part<v()>, dim3((unsigned)nw, (unsigned)nb), dim3(BLOCK), 0, s,
                                DeconvWideGradArgs{deconv_wide_args(c, g.d), g.gpart + (size_t)n0 * DGRAD_SLOTS});
         hipLaunchKernelGGL(lf_deconv_grad_final<v()>, dim3((unsigned)nb), dim3(64), 0, s, g);
+        if (cut_grad) {                           // (per element: plain, then Delta, then the cut)
+            const DeconvCutGradArgs cg = deconv_cut_grad_args(ca, b0, c->d_cgpart, d_grad, false);
+            hipLaunchKernelGGL(lf_deconv_cut_grad_part<v()>, dim3((unsigned)c->cut.n, (unsigned)nb), dim3(BLOCK), 0, s, cg);
+            hipLaunchKernelGGL(lf_deconv_cut_grad_final<v()>, dim3((unsigned)nb), dim3(64), 0, s, cg);
+        }
     });
     LF_HIP(c, hipGetLastError());
     return LF_OK;
@@ -1751,6 +1781,35 @@ int lf_cut_term_batch(lf_ctx* c, const double* theta, int B, double* out) {
     return LF_OK;
 }
 
+int lf_cut_term_grad_batch(lf_ctx* c, const double* theta, int B, double* out, double* grad) {
+    using namespace lf;
+    int rc = family_check(c, "lf_cut_term_grad_batch", true, theta, B, out && grad ? out : nullptr);
+    if (rc != LF_OK) return rc;
+    if (!c->cut.model || !c->cut.built) {
+        c->err = "lf_cut_term_grad_batch: no cut model set (call lf_set_cut_error_model, then lf_set_lum_err)";
+        return LF_ERR_ARG;
+    }
+    return host_value_grad(c, theta, B, out, grad, [&](double* d_val, double* d_grad) -> int {
+        int rc;
+        const int n = c->cut.n;
+        const size_t need = (size_t)B * std::max(n, 1);
+        if (need > c->d_dpart.size() && (rc = grow(c, c->d_dpart, need)) != LF_OK) return rc;
+        if ((rc = cut_grad_workspace(c, B)) != LF_OK) return rc;
+        if ((rc = enqueue(c, c->d_theta, B, c->d_outB, nullptr, nullptr, c->stream)) != LF_OK) return rc;
+        const DeconvCutArgs ca = deconv_cut_args(c, c->d_theta, c->d_outB, c->d_dpart, n, 0, d_val);
+        launch_rows(c->kc.variant, B, [&](auto v, int b0, int nb) {
+            const DeconvCutGradArgs cg = deconv_cut_grad_args(ca, b0, c->d_cgpart, d_grad, true);
+            if (n > 0) {
+                hipLaunchKernelGGL(lf_deconv_cut_part<v()>, dim3((unsigned)n, (unsigned)nb), dim3(BLOCK), 0, c->stream, cg.d);
+                hipLaunchKernelGGL(lf_deconv_cut_grad_part<v()>, dim3((unsigned)n, (unsigned)nb), dim3(BLOCK), 0, c->stream, cg);
+            }
+            hipLaunchKernelGGL(lf_deconv_cut_grad_final<v()>, dim3((unsigned)nb), dim3(64), 0, c->stream, cg);
+        });
+        LF_HIP(c, hipGetLastError());
+        return LF_OK;
+    });
+}
+
 int lf_lnprob_err_batch_device(lf_ctx* c, const double* d_theta, int B, double* d_out, void* hip_stream) {
     int rc = family_check(c, "lf_lnprob_err_batch_device", true, d_theta, B, d_out);
     if (rc != LF_OK) return rc;
@@ -1773,7 +1832,7 @@ int lf_lnprob_err_batch(lf_ctx* c, const double* theta, int B, double* out) {
 int lf_lnprob_err_grad_batch_device(lf_ctx* c, const double* d_theta, int B, double* d_lnprob_err, double* d_grad, void* hip_stream) {
     int rc = family_check(c, "lf_lnprob_err_grad_batch_device", true, d_theta, B, d_grad);
     if (rc != LF_OK) return rc;
-    if ((rc = cut_refuse(c, "lf_lnprob_err_grad_batch_device", "the gradient of Delta B, the cut's change of the expected counts, is not provided")) != LF_OK) return rc;
+    if (!c->opt_cut_grad && (rc = cut_refuse(c, "lf_lnprob_err_grad_batch_device", "the gradient of Delta B, the cut's change of the expected counts, is not provided")) != LF_OK) return rc;
     LF_HIP(c, hipSetDevice(c->device));
     // (the rows' plain lnprob, and the value when it is not asked for: into the context's own buffers, sized before the
     // lnprob path may replace them)
@@ -1784,7 +1843,7 @@ int lf_lnprob_err_grad_batch_device(lf_ctx* c, const double* d_theta, int B, dou
 int lf_lnprob_err_grad_batch(lf_ctx* c, const double* theta, int B, double* lnprob_err, double* grad) {
     int rc = family_check(c, "lf_lnprob_err_grad_batch", true, theta, B, grad);
     if (rc != LF_OK) return rc;
-    if ((rc = cut_refuse(c, "lf_lnprob_err_grad_batch", "the gradient of Delta B, the cut's change of the expected counts, is not provided")) != LF_OK) return rc;
+    if (!c->opt_cut_grad && (rc = cut_refuse(c, "lf_lnprob_err_grad_batch", "the gradient of Delta B, the cut's change of the expected counts, is not provided")) != LF_OK) return rc;
     return host_value_grad(c, theta, B, lnprob_err, grad, [&](double* d_val, double* d_grad) {
         return enqueue_deconv_grad(c, c->d_theta, B, c->d_outB, d_val, d_grad, c->stream);
     });
@@ -2400,6 +2459,7 @@ int lf_set_option(lf_ctx* c, const char* key, int64_t value) {
         {"deconv_tile", [](lf_ctx* c, int64_t v) { c->opt_deconv_tile = v != 0; }},
         {"deconv_wide", [](lf_ctx* c, int64_t v) { c->opt_deconv_wide = v != 0; }},
         {"deconv_cut_limit", [](lf_ctx* c, int64_t v) { c->opt_cut_limit = v < 0 ? 0 : v; }},
+        {"deconv_cut_grad", [](lf_ctx* c, int64_t v) { c->opt_cut_grad = v != 0; }},
         {"persistent", [](lf_ctx* c, int64_t v) { c->opt_persistent = v < 0 ? 0 : (v > 2 ? 2 : v); }},
         {"profile_every", [](lf_ctx* c, int64_t v) { c->opt_profile_every = v < 1 ? 1 : v; c->prof_tick = 0; }},
         {"profile_span", [](lf_ctx* c, int64_t v) { c->opt_profile_span = v < 1 ? 1 : v; c->prof_tick = 0; }},

@@ -544,10 +544,12 @@ def delta_grad(inp, sigma, theta, K=None, terms=False, per_source=False, wide=Fa
     return out if terms else out[:2]
 
 
-def lnprob_err_grad(inp, sigma, theta, K=None, terms=False, wide=False):
+def lnprob_err_grad(inp, sigma, theta, K=None, terms=False, wide=False, cut=None, limit=0):
     """(value[B], grad[B, ndim]) of the convolved lnprob: lnprob_err's value, grad.lnprob_grad's gradient plus dDelta; a row
     whose lnprob is not finite gets NaN in every element (the plain gradient's convention).  terms=True: also S_abs[B, ndim],
-    the sum of both parts' scales."""
+    the sum of both parts' scales.  cut=(nodes, sigma (nf, M)): under a cut on the observed flux (DESIGN.md sections 3.31,
+    3.33) - the value is lnprob_err_cut's, the gradient that minus cut_term_grad's, S_abs with the cut's scale added (limit:
+    cut_nodes')."""
     th = np.asarray(theta, dtype=np.float64)
     single = th.ndim == 1
     th2 = np.atleast_2d(th)
@@ -557,6 +559,10 @@ def lnprob_err_grad(inp, sigma, theta, K=None, terms=False, wide=False):
         val = np.where(np.isfinite(lp), lp + tot, -np.inf)
         val = np.where(np.isnan(val), -np.inf, val)
         g, s = g0 + dD, s0 + s1                     # (g0, s0 are NaN where lnprob is not finite)
+        if cut is not None:
+            val = lnprob_err_cut(inp, sigma, th2, cut, K=K, wide=wide, limit=limit)
+            _, gB, sB = cut_term_grad(inp, cut[0], cut[1], th2, terms=True, limit=limit)
+            g, s = g - gB, s + sB
     if single:
         return (val[0], g[0], s[0]) if terms else (val[0], g[0])
     return (val, g, s) if terms else (val, g)
@@ -768,3 +774,90 @@ def lnprob_err_cut(inp, sigma, theta, cut, K=None, terms=False, wide=False, limi
     if single:
         return (out[0], lp[0], sabs[0] + sB[0]) if terms else out[0]
     return (out, lp, sabs + sB) if terms else out
+
+
+def _cut_grad_terms(inp, th, f, L, col, logf, w):
+    """Field f's nodes at one theta row -> (I [n], d [n, ndim]): the terms I_n = w_n phi Omega of Delta B (cut_term's, the same
+    statements but for the z-evolving L*(z) and phi*(z), below) and every term's share of d Delta B / d theta_e - I_n times piece B's node derivatives (csrc/lf_grad.h: ln10
+    (10^x - alpha - 1), ln10, ln10 x for L*, phi*, alpha; z-evolving: times the Lagrange basis; FREE: dF / Flim_f in field f's
+    element, dC).  A node whose I is 0 or NaN is exactly 0 throughout."""
+    v, fsa = inp["variant"], bool(inp["fix_sch_al"])
+    p = G._split(inp, th)
+    nd = G.ndim_of(inp)
+    nf = len(inp["field_ind"]) - 1
+    c1 = p["al"] + 1.0
+    kappa = G._kappa(inp["fcmin"])
+    om0 = float(np.asarray(inp["Omega_0"], dtype=np.float64)[f]) / G.SQARCSEC
+    lg = None
+    if v == "zevol":
+        # L*(z) = sum_m l_m(z) L_m at |L_m| of 43 carries 43 eps sum_m |l_m| in double, which 10^x turns into a relative 1e-14 of
+        # every term (the kernel's and cut_term's x; nothing cancels it).  Here the basis and both sums are taken in extended
+        # precision and rounded once, so that the formula test against 30 digits sees the formulas, not that rounding.
+        ld = np.longdouble
+        z = np.asarray(inp["zarr"], dtype=np.float64)[col].astype(ld)
+        z1, z2, z3 = (ld(float(q)) for q in inp["pivots"])
+        le = [(z - z2) * (z - z3) / ((z1 - z2) * (z1 - z3)), (z - z1) * (z - z3) / ((z2 - z1) * (z2 - z3)),
+              (z - z1) * (z - z2) / ((z3 - z1) * (z3 - z2))]
+        x = (L.astype(ld) - sum(le[m] * ld(float(p["L"][m])) for m in range(3))).astype(np.float64)
+        ph = sum(le[m] * ld(float(p["phi"][m])) for m in range(3)).astype(np.float64)
+        lg = [q.astype(np.float64) for q in le]
+    else:
+        x, ph = L - p["L"], p["phi"]
+    t = 10.0 ** x
+    tlf = LN10 * np.exp(LN10 * (ph + x * c1) - t)
+    if v == "free":
+        Flim, aC = float(p["Flim"][f]), float(p["aC"])
+    else:
+        Flim, aC = float(np.asarray(inp["Flim0"], dtype=float)[f]), float(inp["alpha0"])
+    y = (logf + 17.0) - np.log10(Flim)
+    vv = 10.0 ** (logf + 17.0) * (np.exp(LN10 * kappa / aC) / Flim)
+    lc, dF, dC = _lcomp_grad(y, vv, aC, kappa)
+    I = w * (tlf * om0 * np.exp(lc))
+    ok = np.abs(I) > 0.0
+    I = np.where(ok, I, 0.0)
+    d = np.zeros((L.size, nd))
+    wl = LN10 * (I * (t - c1))
+    if v == "zevol":
+        for m in range(3):
+            d[:, m] = lg[m] * wl
+            d[:, 3 + m] = LN10 * (lg[m] * I)
+        if not fsa:
+            d[:, 6] = LN10 * (I * x)
+    else:
+        d[:, 0] = wl
+        d[:, 1] = LN10 * I
+        if not fsa:
+            d[:, 2] = LN10 * (I * x)
+        if v == "free":
+            kF = 2 if fsa else 3
+            d[:, kF + f] = (I * dF) / Flim
+            d[:, kF + nf] = I * dC
+    return I, np.where(ok[:, None], d, 0.0)
+
+
+def cut_term_grad(inp, nodes, sigma, theta, terms=False, limit=0, fields=None):
+    """theta (B, ndim) or (ndim,) -> (Delta B [B], d Delta B / d theta [B, ndim]): cut_term's sum over cut_nodes' tables (FREE,
+    FIXCOMP: its bits; z-evolving: within 1e-13 of its scale, _cut_grad_terms says why) and its exact derivative with respect to the row's own elements, field by field in node order (csrc/lf_deconv_cut_grad.h; DESIGN.md
+    section 3.33).  terms=True: also S_abs [B, ndim], per element the sum of the absolute values of its terms, the scale
+    rounding is judged by.  No prior test: what the formulas give.  A node whose term is 0 or NaN adds exactly 0 to every
+    element; the Flim_g element holds field g's nodes only.  fields: only these fields' nodes."""
+    th = np.asarray(theta, dtype=np.float64)
+    single = th.ndim == 1
+    th = np.atleast_2d(th)
+    nd = G.ndim_of(inp)
+    if th.shape[1] != nd:
+        raise ValueError("theta must be (B, %d), got %s" % (nd, th.shape))
+    nl, _ = cut_nodes(inp, nodes, sigma, limit=limit, fields=fields)
+    tot, g, sabs = np.zeros(len(th)), np.zeros((len(th), nd)), np.zeros((len(th), nd))
+    with np.errstate(all="ignore"):
+        for b, row in enumerate(th):
+            for f, n in enumerate(nl):
+                if n["L"].size == 0:
+                    continue
+                I, d = _cut_grad_terms(inp, row, f, n["L"], n["col"], n["logf"], n["w"])
+                tot[b] += I.sum()
+                g[b] += d.sum(axis=0)
+                sabs[b] += np.abs(d).sum(axis=0)
+    if single:
+        return (tot[0], g[0], sabs[0]) if terms else (tot[0], g[0])
+    return (tot, g, sabs) if terms else (tot, g)

@@ -188,6 +188,8 @@ class _Base(object):
             if self.deconvolve:
                 if self.deconvolve_cut:
                     self._ctx.set_cut_error_model(*self.deconvolve_cut_errors)
+                    if self.deconvolve_cut_grad:
+                        self._ctx.set_option("deconv_cut_grad", 1)
                 self._ctx.set_lum_err(self.lum_e, self.deconvolve_order, unchecked=self.deconvolve_unchecked,
                                        wide=self.deconvolve_wide)
             if self.deconvolve_tile:
@@ -204,13 +206,18 @@ class _Base(object):
 
     deconvolve_cut = False         # True: the cut on the observed flux of min_comp_frac > 0.001 is modelled (csrc/lf_deconv_cut.h)
     deconvolve_cut_errors = None   # its error model (nodes (M,), sigma (nf, M)); None: the one this catalogue shows (error_model())
+    deconvolve_cut_grad = False    # True: the gradient of the cut's term is served too (csrc/lf_deconv_cut_grad.h): MAP fits under the cut
 
     def _init_deconvolve(self, deconvolve, deconvolve_order, deconvolve_tile=False, deconvolve_wide=False, deconvolve_cut=False,
-                         deconvolve_cut_errors=None):
+                         deconvolve_cut_errors=None, deconvolve_cut_grad=False):
         from . import deconv
         self.deconvolve, self.deconvolve_order = bool(deconvolve), deconvolve_order
         self.deconvolve_tile, self.deconvolve_wide = bool(deconvolve_tile), bool(deconvolve_wide)
         self.deconvolve_cut = bool(deconvolve_cut)
+        self.deconvolve_cut_grad = bool(deconvolve_cut_grad)
+        if self.deconvolve_cut_grad and not self.deconvolve_cut:
+            raise ValueError("deconvolve_cut_grad=True needs deconvolve_cut=True: it is the gradient of Delta B, the cut's change "
+                             "of the expected counts, that it adds")
         if self.deconvolve_cut and not self.min_comp_frac > 0.001:
             raise ValueError("deconvolve_cut=True needs min_comp_frac > 0.001: with min_comp_frac <= 0.001 there is no cut on the "
                              "observed flux, and deconvolve=True alone is the model")
@@ -438,7 +445,7 @@ class _Base(object):
             raise NotImplementedError("the gradient runs on one GPU: source- or walker-sharded gradients are not implemented")
         if self.lnprob_fn is not None:
             raise NotImplementedError("the gradient comes from the device context: it cannot use lnprob_fn")
-        if likelihood == "convolved" and self.deconvolve_cut:
+        if likelihood == "convolved" and self.deconvolve_cut and not self.deconvolve_cut_grad:
             raise NotImplementedError("the convolved likelihood's gradient is not implemented under deconvolve_cut=True: the "
                                       "gradient of Delta B, the cut's change of the expected counts, is missing (fit_model, "
                                       "fit_model_converged and fit_model_pt sample it without a gradient)")
@@ -454,7 +461,9 @@ class _Base(object):
         dict with converged, on_bound, niter and decrement.  likelihood: None (the plain likelihood; an object made with
         deconvolve=True refuses and asks for the choice), "convolved" (deconvolve=True only: the flux-error-convolved
         likelihood, LFContext.lnprob_err_grad) or "plain" (also under deconvolve=True: the two maxima side by side give the
-        catalogue's Eddington shift); map_info["likelihood"] records which one ran."""
+        catalogue's Eddington shift); map_info["likelihood"] records which one ran.  Under deconvolve_cut=True (min_comp_frac >
+        0.001) the convolved likelihood's gradient needs deconvolve_cut_grad=True, which adds the gradient of Delta B (DESIGN.md
+        section 3.33); without it the call refuses."""
         from . import mapfit
         likelihood = self._map_likelihood(likelihood)
         f = self._grad_fn(likelihood)
@@ -490,7 +499,7 @@ class _Base(object):
         instead of the prior box; a row outside the box or with a lnprob that is not finite is drawn again, so every walker
         starts with a finite lnprob.  A coordinate held at a bound has no variance in map_cov: it is scattered into the box
         by |N(0, (1e-3 width)^2)| so that the ensemble is not degenerate there.  likelihood: whose lnprob has to be finite
-        (as in fit_model_map)."""
+        (as in fit_model_map; "convolved" under deconvolve_cut=True needs deconvolve_cut_grad=True, as there)."""
         if getattr(self, "map_theta", None) is None:
             raise RuntimeError("map_init_walkers: call fit_model_map first")
         if not np.all(np.isfinite(self.map_cov)):
@@ -851,7 +860,7 @@ class LumFuncMCMC(_Base):
                  fix_sch_al=False, fcmin=0.1, fix_comp=False, min_comp_frac=0.5,
                  field_names=None, field_ind=None, diff_rand=True, device=0, compress=False, shard="walkers",
                  deconvolve=False, deconvolve_order=None, deconvolve_tile=False, deconvolve_wide=False,
-                 deconvolve_cut=False, deconvolve_cut_errors=None):
+                 deconvolve_cut=False, deconvolve_cut_errors=None, deconvolve_cut_grad=False):
         self._common_init(z, flux, flux_e, lum, lum_e)
         self.device = device
         self.compress = bool(compress)
@@ -883,7 +892,8 @@ class LumFuncMCMC(_Base):
         self.size_ln = 201 if self.fix_comp else 101
         self.setlnsimple(need_integ=bool(self.fix_comp))
         self.setup_logging()
-        self._init_deconvolve(deconvolve, deconvolve_order, deconvolve_tile, deconvolve_wide, deconvolve_cut, deconvolve_cut_errors)
+        self._init_deconvolve(deconvolve, deconvolve_order, deconvolve_tile, deconvolve_wide, deconvolve_cut, deconvolve_cut_errors,
+                              deconvolve_cut_grad)
 
     def getRoot(self, size=201):
         self.rootsf = hs.completeness_roots(self.Flim_lims, self.alpha_lims, self.fcmin, self.min_comp_frac, size)
@@ -1085,7 +1095,7 @@ class LumFuncMCMCz(_Base):
                  fcmin=0.1, min_comp_frac=0.5, field_names=None,
                  field_ind=None, z1=1.20, z2=1.53, z3=1.86, fix_sch_al=False, device=0, compress=False, shard="walkers",
                  deconvolve=False, deconvolve_order=None, deconvolve_tile=False, deconvolve_wide=False,
-                 deconvolve_cut=False, deconvolve_cut_errors=None):
+                 deconvolve_cut=False, deconvolve_cut_errors=None, deconvolve_cut_grad=False):
         self._common_init(z, flux, flux_e, lum, lum_e)
         self.device = device
         self.compress = bool(compress)
@@ -1118,7 +1128,8 @@ class LumFuncMCMCz(_Base):
         self.size_ln = 201
         self.setlnsimple(need_integ=True)
         self.setup_logging()
-        self._init_deconvolve(deconvolve, deconvolve_order, deconvolve_tile, deconvolve_wide, deconvolve_cut, deconvolve_cut_errors)
+        self._init_deconvolve(deconvolve, deconvolve_order, deconvolve_tile, deconvolve_wide, deconvolve_cut, deconvolve_cut_errors,
+                              deconvolve_cut_grad)
 
     def getRoot(self):
         """Per-field flux at which the completeness equals min_comp_frac (lumfuncmcmc_z.py:292-297);
