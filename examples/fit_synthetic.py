@@ -121,7 +121,8 @@ def main():
                     help="with --deconvolve: fit at min_comp_frac = 0.5, the classes' default, with the cut on the observed flux "
                          "modelled (deconvolve_cut=True; DESIGN.md section 3.31); with --map the gradient of the cut's term is "
                          "served too (deconvolve_cut_grad=True; DESIGN.md section 3.33) and the convolved and the plain maximum "
-                         "are printed side by side, as without the cut; not with --veff-deconvolved")
+                         "are printed side by side, as without the cut; with --veff-deconvolved the points take the catalogued volume per "
+                         "node (deconvolve_cut_veff=True; DESIGN.md section 3.34)")
     ap.add_argument("--deconvolved-lums", metavar="FILE", default="",
                     help="with --deconvolve: every source's posterior mean and spread of its TRUE luminosity over 200 posterior "
                          "draws (deconvolved_luminosities; DESIGN.md section 3.22) written to FILE: ID, lum, lum_e, lum_true, "
@@ -151,8 +152,8 @@ def main():
         ap.error("--deconvolved-lums needs --deconvolve")
     if args.veff_deconvolved and not args.deconvolve:
         ap.error("--veff-deconvolved needs --deconvolve")
-    if args.deconvolve_cut and (not args.deconvolve or args.veff_deconvolved):
-        ap.error("--deconvolve-cut needs --deconvolve, and not --veff-deconvolved (DESIGN.md section 3.31)")
+    if args.deconvolve_cut and not args.deconvolve:
+        ap.error("--deconvolve-cut needs --deconvolve (DESIGN.md section 3.31)")
     if args.pt and args.until_converged:
         ap.error("--pt and --until-converged are two fits: choose one")
     os.makedirs(args.out, exist_ok=True)
@@ -169,7 +170,8 @@ def main():
                         min_comp_frac=0.5 if args.deconvolve_cut else 0.0, Flim_lims=synth.FLIM_LIMS, alpha_lims=synth.ALPHA_LIMS,
                         field_names=field_names, field_ind=field_ind, compress=args.compress, deconvolve=args.deconvolve,
                         deconvolve_tile=args.deconvolve_tile, deconvolve_wide=args.deconvolve_wide,
-                        deconvolve_cut=args.deconvolve_cut, deconvolve_cut_grad=args.deconvolve_cut and args.map)
+                        deconvolve_cut=args.deconvolve_cut, deconvolve_cut_grad=args.deconvolve_cut and args.map,
+                        deconvolve_cut_veff=args.deconvolve_cut and args.veff_deconvolved)
     print("setup %.2f s for %d sources" % (time.time() - t0, len(LFmod.lum)))
     np.random.seed(3)
     plain_map = None

@@ -283,7 +283,8 @@ int lf_veff_true_ms(double ms[3]);
  * finite, < 0 or above 0.30 dex (the limit is stated), a field whose sigma is 0 at some nodes only, a model that needs more
  * than 64 panels on one side of the edge, a context without the cut (separable grid), a source-sharded context, and a call
  * after lf_set_lum_err.  Still refused on such a context, with what is missing in the message: lf_lnprob_err_grad_batch(_device)
- * (the gradient of Delta B; served with the option "deconv_cut_grad", below) and lf_veff_true (per-source volumes);
+ * (the gradient of Delta B; served with the option "deconv_cut_grad", below) and lf_veff_true (per-source volumes; served
+ * with the option "deconv_cut_veff", below, by the catalogued volume per node);
  * lf_lum_posterior is served (a source's posterior given that it is catalogued does not involve B).
  * lf_cut_term_batch: Delta B alone for B rows (host pointers, synchronous; after lf_set_lum_err); NaN for a row whose plain
  * lnprob is not finite.  Summed in one fixed order without atomics: a row's bits do not depend on B or on its place.
@@ -312,6 +313,30 @@ int lf_cut_info(lf_ctx *ctx, int32_t *nnodes, double *H, int cap, int *chunk, in
  * lf_set_lum_err; whatever the option says).  out is lf_cut_term_batch's, bit for bit; a row whose plain lnprob is not finite
  * has NaN in out and in every element. */
 int lf_cut_term_grad_batch(lf_ctx *ctx, const double *theta, int B, double *out, double *grad);
+
+/* The deconvolved 1/Veff points under the cut: the catalogued volume per node (csrc/lf_vefftrue_cut.h).
+ * Under the cut a true luminosity L of field f is catalogued in the part
+ *     g_f(L) = (sum_j wv_j Q(-u_fj(L))) / (sum_j wv_j),  wv_j = wz_j V_j,  u_fj = (L - Lam_j) / s_f(L - ld2_j)
+ * of the survey volume (all S columns, the grid and the error model of lf_set_cut_error_model), and node k of source i gets the
+ * weight p_irk / (pref0 fc vol g_f(i)(L_ik)).  The sum: columns left to right, no fma contraction; u > 9: a term of exactly
+ * wv_j; u < -9: exactly 0; else wv_j 0.5 erfc(-u / sqrt 2); a field whose sigma is 0 at every node: wv_j when L >= Lam_j.  g does
+ * not depend on theta: 1 / g is tabulated once per (source, node) at the first call after lf_set_lum_err - 8 bytes per slot, N K
+ * for the sources of the Gauss-Hermite order and 144 per source of the wide list (256 MB at 1e6 sources and K = 32) - and kept
+ * until lf_set_lum_err, lf_set_cut_error_model or another min_vol_frac; LF_ERR_NOMEM with the size in the message when the
+ * table cannot be allocated.  A node with g = 0 or g < min_vol_frac adds exactly 0 to every bin.
+ * Option "deconv_cut_veff" (lf_set_option; default 0): with 1, lf_veff_true serves a context with the cut model (min_vol_frac
+ * = 0); with 0 it refuses such a context as before.  Without a cut model the option does nothing: lf_veff_true's bits.
+ * lf_veff_true_cut: lf_veff_true with min_vol_frac in 0..1 (> 0 only with a cut model); the same host function, the same
+ * refusals under the entry's own name.
+ * lf_veff_true_cut_info: the table's (source, node) slots, its bytes, and how many nodes were dropped (any may be NULL);
+ * LF_ERR_ARG before a table is made.  lf_veff_true_cut_ms: the device time of the kernel that last made the table (hipEvents).
+ * lf_cut_volume: g for n caller points (field[n] in 0..nf-1, L[n] finite; host pointers, synchronous; 1 <= n <= 2^24), by the
+ * device function the table is made with; needs lf_set_cut_error_model only. */
+int lf_veff_true_cut(lf_ctx *ctx, const double *theta, int R, const double *edges, int nbin, double pref0, double vol,
+                     double min_vol_frac, int nq, const double *q, int method, double *out, double *values, int *n_used);
+int lf_veff_true_cut_info(lf_ctx *ctx, int64_t *slots, int64_t *bytes, int64_t *dropped);
+int lf_veff_true_cut_ms(lf_ctx *ctx, double *ms);
+int lf_cut_volume(lf_ctx *ctx, const int32_t *field, const double *L, int64_t n, double *g_out);
 
 /* Kernel timing for bench.py: level 1 brackets lf_main, level 2 every launch, with hipEvents on
  * the stream the launch runs on (0 = off; each event pair costs a few microseconds of stream time: the events are

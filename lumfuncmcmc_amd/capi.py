@@ -59,7 +59,8 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_veff_true", "lf_veff_true_info", "lf_veff_true_ms",
            "lf_mock_set_error_model", "lf_mock_draw_err", "lf_mock_hist_err",
            "lf_set_cut_error_model", "lf_cut_term_batch", "lf_cut_info", "lf_cut_term_grad_batch",
-           "lf_mock_set_cut_band", "lf_mock_draw_cut", "lf_mock_hist_cut")
+           "lf_mock_set_cut_band", "lf_mock_draw_cut", "lf_mock_hist_cut",
+           "lf_veff_true_cut", "lf_veff_true_cut_info", "lf_veff_true_cut_ms", "lf_cut_volume")
 
 _lib = None
 
@@ -141,6 +142,14 @@ def load():
     lib.lf_veff_true.restype = ctypes.c_int
     lib.lf_veff_true.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                  ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int)]
+    lib.lf_veff_true_cut.restype = ctypes.c_int
+    lib.lf_veff_true_cut.argtypes = (lib.lf_veff_true.argtypes[:7] + [ctypes.c_double] + lib.lf_veff_true.argtypes[7:])
+    lib.lf_veff_true_cut_info.restype = ctypes.c_int
+    lib.lf_veff_true_cut_info.argtypes = [ctypes.c_void_p, _c_int64_p, _c_int64_p, _c_int64_p]
+    lib.lf_veff_true_cut_ms.restype = ctypes.c_int
+    lib.lf_veff_true_cut_ms.argtypes = [ctypes.c_void_p, _c_double_p]
+    lib.lf_cut_volume.restype = ctypes.c_int
+    lib.lf_cut_volume.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), _c_double_p, ctypes.c_int64, _c_double_p]
     lib.lf_veff_true_info.restype = ctypes.c_int
     lib.lf_veff_true_info.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.lf_veff_true_ms.restype = ctypes.c_int
@@ -870,12 +879,14 @@ class LFContext(object):
         self._check(self._lib.lf_lum_posterior(self._h, _ptr(th), th.shape[0], _ptr(m1), _ptr(m2), ctypes.byref(used)))
         return m1, m2, used.value
 
-    def veff_true(self, theta, edges, pref0, vol, q=(16.0, 50.0, 84.0), method=LF_Q_LINEAR):
+    def veff_true(self, theta, edges, pref0, vol, q=(16.0, 50.0, 84.0), method=LF_Q_LINEAR, min_vol_frac=0.0):
         """theta (R, ndim) or (ndim,) host array, 1 <= R <= 4096; edges (nbin + 1,) ascending -> (out (nq, nbin), values
         (R, nbin), n_used): lf_veff_true, the deconvolved 1/Veff points - every source's posterior of the true luminosity
         binned with the completeness at the node's true flux, per row (NaN for a row whose plain lnprob is not finite), and
         NumPy's percentiles q of every bin over the used rows.  method LF_Q_MEDIAN: one row of out, q
-        ignored.  Needs set_lum_err."""
+        ignored.  Needs set_lum_err.  On a context with the cut model and the option "deconv_cut_veff" every node's weight is
+        divided by its catalogued volume fraction g, and a node with g = 0 or g < min_vol_frac is dropped (lf_veff_true_cut;
+        DESIGN.md section 3.34)."""
         th = self._theta(theta)
         ed = _f64(edges).ravel()
         nbin = ed.size - 1
@@ -884,9 +895,34 @@ class LFContext(object):
         out = np.empty((nq, max(nbin, 0)), dtype=np.float64)
         values = np.empty((th.shape[0], max(nbin, 0)), dtype=np.float64)
         used = ctypes.c_int(0)
-        self._check(self._lib.lf_veff_true(self._h, _ptr(th), th.shape[0], _ptr(ed), nbin, float(pref0), float(vol), nq, _ptr(qa),
-                                           int(method), _ptr(out), _ptr(values), ctypes.byref(used)))
+        if min_vol_frac == 0.0:
+            self._check(self._lib.lf_veff_true(self._h, _ptr(th), th.shape[0], _ptr(ed), nbin, float(pref0), float(vol), nq, _ptr(qa),
+                                               int(method), _ptr(out), _ptr(values), ctypes.byref(used)))
+        else:
+            self._check(self._lib.lf_veff_true_cut(self._h, _ptr(th), th.shape[0], _ptr(ed), nbin, float(pref0), float(vol),
+                                                   float(min_vol_frac), nq, _ptr(qa), int(method), _ptr(out), _ptr(values),
+                                                   ctypes.byref(used)))
         return out, values, used.value
+
+    def veff_true_cut_info(self):
+        """lf_veff_true_cut_info: dict slots, bytes, dropped of the table of catalogued volumes the last veff_true call under
+        the cut made or reused, and ms, the device time of the kernel that made it."""
+        sl, by, dr = (np.zeros(1, dtype=np.int64) for _ in range(3))
+        ms = np.zeros(1)
+        self._check(self._lib.lf_veff_true_cut_info(self._h, sl.ctypes.data_as(_c_int64_p), by.ctypes.data_as(_c_int64_p),
+                                                    dr.ctypes.data_as(_c_int64_p)))
+        self._check(self._lib.lf_veff_true_cut_ms(self._h, _ptr(ms)))
+        return {"slots": int(sl[0]), "bytes": int(by[0]), "dropped": int(dr[0]), "ms": float(ms[0])}
+
+    def cut_volume(self, field, L):
+        """field (n,) or a scalar, L (n,) -> g (n,): lf_cut_volume, the part of the survey volume in which a true luminosity L of
+        the field is catalogued under the cut (deconv.cut_volume_fraction's statements on the device).  Needs
+        set_cut_error_model."""
+        Lq = _f64(np.atleast_1d(L)).ravel()
+        fq = np.ascontiguousarray(np.broadcast_to(np.asarray(field, dtype=np.int32), Lq.shape))
+        g = np.empty(Lq.size, dtype=np.float64)
+        self._check(self._lib.lf_cut_volume(self._h, fq.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(Lq), Lq.size, _ptr(g)))
+        return g
 
     def lnprob_err_torch(self, theta):
         """theta: float64 device tensor (B, ndim) on this context's device; enqueues lf_lnprob_err_batch_device on torch's

@@ -42,6 +42,7 @@
 #include "lf_pt.h"
 #include "lf_veffdraws.h"
 #include "lf_vefftrue.h"
+#include "lf_vefftrue_cut.h"
 
 namespace {
 
@@ -213,6 +214,20 @@ struct lf_ctx {
     Buf<int> d_vt_inwide;               // lf_vefftrue.h: 1 for the sources of the wide list, in the device's order
     Buf<double> d_vt_work;              // lf_veff_true's workspace: edges, quantile table, partial sums, values, used rows, out
     Buf<int> d_vt_slot;                 // ... and the rows' places among the used rows
+    // the catalogued volume per node under the cut (lf_vefftrue_cut.h; option "deconv_cut_veff"): the model's image, the table
+    // of 1 / g per (source, node) slot - made at the first lf_veff_true call after lf_set_lum_err, for one min_vol_frac, and
+    // kept until the luminosity errors, the error model or min_vol_frac change - and the chunks' dropped counts
+    int64_t opt_cut_veff = 0;           // 1: lf_veff_true serves a context with the cut model
+    struct {
+        bool img = false, built = false;      // the image is made (per error model); the table is made
+        double min_vol_frac = 0.0;
+        size_t slots = 0;
+        long long wide_off = 0, dropped = 0;
+        double ms = -1.0;               // the table kernel's device time when it was last made under lf_set_profiling
+        lf::VeffCutTab tab{};
+        Buf<double> d_img, d_invg;
+        Buf<int> d_drop;
+    } cutv;
     hipStream_t stream = nullptr;
     hipStream_t last_stream = nullptr;   // stream of the previous enqueue (workspace is shared)
     bool any_enqueued = false;
@@ -1626,6 +1641,7 @@ int lf_set_lum_err(lf_ctx* c, const double* sigma, int K, const double* logf, co
     LF_HIP(c, hipSetDevice(c->device));
     LF_HIP(c, hipDeviceSynchronize());               // (a call in flight may read the buffers replaced below)
     c->deconv_set = false;
+    c->cutv.built = false;
     std::vector<double> sg((size_t)N), lf_, u_, nodes((size_t)2 * K);
     for (int64_t i = 0; i < N; ++i) sg[(size_t)i] = sigma[c->perm[(size_t)i]];
     lfh::gauss_hermite(K, nodes.data(), nodes.data() + K);
@@ -1718,6 +1734,7 @@ int lf_set_cut_error_model(lf_ctx* c, const double* nodes, int M, const double* 
     LF_HIP(c, hipDeviceSynchronize());               // (a call in flight may read the buffers replaced below)
     auto& t = c->cut;
     t.model = false, t.built = false, t.n = 0;
+    c->cutv.built = false, c->cutv.img = false;
     t.M = M;
     t.nodes.assign(nodes, nodes + M);
     t.sigma.assign(sigma, sigma + (size_t)c->kc.nf * M);
@@ -1937,17 +1954,176 @@ struct Stamps {
 };
 }  // namespace
 
+namespace {
+// The cut model's image for lf_vefftrue_cut.h - lam, ld2, wv = wz V, the error model - to the device, once per error model.
+// wv and its sum are formed here with the statements of deconv.py: cut_volume_fraction (no contraction, left to right).
+int cut_volume_image(lf_ctx* c, const char* fn) {
+#pragma clang fp contract(off)
+    auto& v = c->cutv;
+    if (v.img) return LF_OK;
+    const int S = c->kc.S, M = c->cut.M, nf = c->kc.nf;
+    if (lf::vefft_cut_lds_bytes(S, M, nf) > 60 * 1024) {
+        c->err = std::string(fn) + ": the grid's " + std::to_string(S) + " redshift columns and the error model's " + std::to_string(M) +
+                 " nodes need " + std::to_string(lf::vefft_cut_lds_bytes(S, M, nf)) + " bytes of LDS, above the 61440 the kernel stages";
+        return LF_ERR_ARG;
+    }
+    std::vector<double> img((size_t)lf::vefft_cut_slots(S, M, nf));
+    double den = 0.0;
+    for (int j = 0; j < S; ++j) {
+        const double dl = j > 0 ? c->h_zarr[j] - c->h_zarr[j - 1] : 0.0, dr = j < S - 1 ? c->h_zarr[j + 1] - c->h_zarr[j] : 0.0;
+        const double wz = 0.5 * (dl + dr);
+        const double wv = wz * c->h_vol[j];
+        img[(size_t)j] = c->h_edge_lo[j], img[(size_t)S + j] = c->h_ld2[j], img[(size_t)2 * S + j] = wv;
+        den += wv;
+    }
+    unsigned step = 0;
+    for (int m = 0; m < M; ++m) img[(size_t)3 * S + m] = c->cut.nodes[m];
+    for (int f = 0; f < nf; ++f) {
+        bool zero = true;
+        for (int m = 0; m < M; ++m) {
+            const double sg = c->cut.sigma[(size_t)f * M + m];
+            img[(size_t)3 * S + M + (size_t)f * M + m] = sg;
+            zero = zero && sg == 0.0;
+        }
+        step |= zero ? 1u << f : 0u;
+    }
+    if (!(den > 0.0) || !std::isfinite(den)) {
+        c->err = std::string(fn) + ": the grid's volume, the sum of wz V over the redshift columns, is not finite and > 0";
+        return LF_ERR_ARG;
+    }
+    const int rc = upload(c, v.d_img, img);
+    if (rc != LF_OK) return rc;
+    v.tab = lf::VeffCutTab{v.d_img, S, M, nf, step, den, 0.0};
+    v.img = true;
+    return LF_OK;
+}
+
+// The table of 1 / g per (source, node) slot (lf_vefftrue_cutvol), made when it is missing or was made for another
+// min_vol_frac.  x: the call's arguments (the chunk tables and the sources' arrays).
+int cut_volume_table(lf_ctx* c, const char* fn, const lf::VeffTrueArgs& x, double min_vol_frac) {
+    using namespace lf;
+    auto& v = c->cutv;
+    if (v.built && v.min_vol_frac == min_vol_frac) return LF_OK;
+    int rc = cut_volume_image(c, fn);
+    if (rc != LF_OK) return rc;
+    v.built = false;
+    const size_t N = (size_t)c->N, nwide = (size_t)c->lp_nslots - N;
+    const size_t slots = N * (size_t)x.d.dc.K + nwide * (size_t)DECONV_WIDE_KMAX;
+    const size_t nch = (size_t)(x.n0 + x.nw);
+    if (slots > v.d_invg.size()) {
+        LF_HIP(c, hipDeviceSynchronize());
+        if (v.d_invg.alloc(slots) != hipSuccess) {
+            (void)hipGetLastError();
+            c->err = std::string(fn) + ": no device memory for the table of catalogued volumes: " + std::to_string(slots) +
+                     " (source, node) slots of 8 bytes, " + std::to_string(slots * 8) + " bytes (option deconv_cut_veff)";
+            return LF_ERR_NOMEM;
+        }
+    }
+    if (nch > v.d_drop.size() && (rc = grow(c, v.d_drop, nch)) != LF_OK) return rc;
+    v.slots = slots, v.wide_off = (long long)(N * (size_t)x.d.dc.K);
+    VeffCutTab t = v.tab;
+    t.min_vol_frac = min_vol_frac;
+    Stamps st;
+    LF_HIP(c, hipMemsetAsync(v.d_invg, 0, slots * sizeof(double), c->stream));
+    LF_HIP(c, st.mark(c->stream));
+    if (nch > 0)
+        hipLaunchKernelGGL(lf_vefftrue_cutvol, dim3((unsigned)nch), dim3(BLOCK), (unsigned)vefft_cut_lds_bytes(t.S, t.M, t.nf), c->stream, x, t,
+                           v.d_invg.get(), v.wide_off, v.d_drop.get());
+    LF_HIP(c, hipGetLastError());
+    LF_HIP(c, st.mark(c->stream));
+    std::vector<int> drop(nch, 0);
+    if (nch > 0) LF_HIP(c, hipMemcpyAsync(drop.data(), v.d_drop, nch * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    LF_HIP(c, hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    LF_HIP(c, hipEventElapsedTime(&ms, st.ev[0], st.ev[1]));
+    v.ms = ms;
+    v.dropped = 0;
+    for (int d : drop) v.dropped += d;
+    v.min_vol_frac = min_vol_frac;
+    v.built = true;
+    return LF_OK;
+}
+
+int veff_true_host(lf_ctx* c, const char* fn, const double* theta, int R, const double* edges, int nbin, double pref0, double vol,
+                   double min_vol_frac, int nq, const double* q, int method, double* out, double* values, int* n_used);
+}  // namespace
+
 int lf_veff_true(lf_ctx* c, const double* theta, int R, const double* edges, int nbin, double pref0, double vol, int nq, const double* q,
                  int method, double* out, double* values, int* n_used) {
+    return veff_true_host(c, "lf_veff_true", theta, R, edges, nbin, pref0, vol, 0.0, nq, q, method, out, values, n_used);
+}
+
+int lf_veff_true_cut(lf_ctx* c, const double* theta, int R, const double* edges, int nbin, double pref0, double vol, double min_vol_frac,
+                     int nq, const double* q, int method, double* out, double* values, int* n_used) {
+    return veff_true_host(c, "lf_veff_true_cut", theta, R, edges, nbin, pref0, vol, min_vol_frac, nq, q, method, out, values, n_used);
+}
+
+int lf_veff_true_cut_info(lf_ctx* c, int64_t* slots, int64_t* bytes, int64_t* dropped) {
+    if (!c) return LF_ERR_ARG;
+    if (!c->cutv.built) {
+        c->err = "lf_veff_true_cut_info: no table of catalogued volumes yet (option deconv_cut_veff, a cut model, then lf_veff_true)";
+        return LF_ERR_ARG;
+    }
+    if (slots) *slots = (int64_t)c->cutv.slots;
+    if (bytes) *bytes = (int64_t)(c->cutv.slots * sizeof(double));
+    if (dropped) *dropped = (int64_t)c->cutv.dropped;
+    return LF_OK;
+}
+
+int lf_veff_true_cut_ms(lf_ctx* c, double* ms) {
+    if (!c || !ms) return LF_ERR_ARG;
+    *ms = c->cutv.ms;
+    return c->cutv.ms < 0.0 ? LF_ERR_ARG : LF_OK;
+}
+
+int lf_cut_volume(lf_ctx* c, const int32_t* field, const double* L, int64_t n, double* g_out) {
     using namespace lf;
-    // every argument is checked before the device is touched
-    int rc = family_check(c, "lf_veff_true", true, theta, R, out);
-    if (rc != LF_OK) return rc;
-    if ((rc = cut_refuse(c, "lf_veff_true", "per-source volumes (a z_max per source under the cut) are not provided: the points take one volume")) != LF_OK) return rc;
+    if (!c) return LF_ERR_ARG;
     auto bad = [&](const std::string& m) {
-        c->err = "lf_veff_true: " + m;
+        c->err = "lf_cut_volume: " + m;
         return (int)LF_ERR_ARG;
     };
+    if (!c->cut.model) return bad("no cut model set (call lf_set_cut_error_model first)");
+    if (n < 1 || n > (int64_t)1 << 24) return bad("n outside 1..16777216");
+    if (!field || !L || !g_out) return bad("NULL pointer");
+    for (int64_t i = 0; i < n; ++i) {
+        if (field[i] < 0 || field[i] >= c->kc.nf) return bad("field outside 0.." + std::to_string(c->kc.nf - 1) + " (point " + std::to_string(i) + ")");
+        if (!std::isfinite(L[i])) return bad("L must be finite (point " + std::to_string(i) + ")");
+    }
+    LF_HIP(c, hipSetDevice(c->device));
+    int rc = cut_volume_image(c, "lf_cut_volume");
+    if (rc != LF_OK) return rc;
+    Buf<double> d_L, d_g;
+    Buf<int> d_f;
+    LF_HIP(c, d_L.upload(L, (size_t)n));
+    LF_HIP(c, d_f.upload(field, (size_t)n));
+    LF_HIP(c, d_g.alloc((size_t)n));
+    const VeffCutTab t = c->cutv.tab;
+    hipLaunchKernelGGL(lf_cut_volume_points, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), (unsigned)vefft_cut_lds_bytes(t.S, t.M, t.nf),
+                       c->stream, t, d_f.get(), d_L.get(), (int)n, d_g.get());
+    LF_HIP(c, hipGetLastError());
+    LF_HIP(c, hipMemcpyAsync(g_out, d_g, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    LF_HIP(c, hipStreamSynchronize(c->stream));
+    return LF_OK;
+}
+
+namespace {
+int veff_true_host(lf_ctx* c, const char* fn, const double* theta, int R, const double* edges, int nbin, double pref0, double vol,
+                   double min_vol_frac, int nq, const double* q, int method, double* out, double* values, int* n_used) {
+    using namespace lf;
+    // every argument is checked before the device is touched
+    int rc = family_check(c, fn, true, theta, R, out);
+    if (rc != LF_OK) return rc;
+    if (!c->opt_cut_veff &&
+        (rc = cut_refuse(c, fn, "per-source volumes (a z_max per source under the cut) are not provided: the points take one volume")) != LF_OK)
+        return rc;
+    const bool cut = c->cut.model;
+    auto bad = [&](const std::string& m) {
+        c->err = std::string(fn) + ": " + m;
+        return (int)LF_ERR_ARG;
+    };
+    if (!(min_vol_frac >= 0.0) || !(min_vol_frac <= 1.0)) return bad("min_vol_frac outside 0..1");
+    if (min_vol_frac > 0.0 && !cut) return bad("min_vol_frac > 0 needs a cut model (lf_set_cut_error_model): without one every node has the whole volume");
     if (!edges || !n_used) return bad("NULL pointer");
     if (R > VEFFT_MAX_ROWS) return bad("R outside 1.." + std::to_string(VEFFT_MAX_ROWS));
     if (nbin < 1 || nbin > VEFFT_MAXBIN) return bad("nbin outside 1.." + std::to_string(VEFFT_MAXBIN));
@@ -1996,6 +2172,9 @@ int lf_veff_true(lf_ctx* c, const double* theta, int R, const double* edges, int
     LF_HIP(c, hipMemcpyAsync(c->d_vt_slot, slot.data(), (size_t)R * sizeof(int), hipMemcpyHostToDevice, c->stream));
     LF_HIP(c, hipStreamSynchronize(c->stream));            // (the sources of the copies are this call's own)
     x.edges = wk, x.partial = wk + o_part, x.values = wk + o_val, x.used = wk + o_used, x.slot = c->d_vt_slot;
+    if (cut && (rc = cut_volume_table(c, fn, x, min_vol_frac)) != LF_OK) return rc;
+    const double* d_invg = c->cutv.d_invg;
+    const long long wide_off = c->cutv.wide_off;
     double *d_q = wk + o_q, *d_used = wk + o_used, *d_out = wk + o_out, *d_val = wk + o_val;
     // the stages' times are taken only under lf_set_profiling: an event pair around every launch keeps it from overlapping the
     // one before
@@ -2008,7 +2187,10 @@ int lf_veff_true(lf_ctx* c, const double* theta, int R, const double* edges, int
         for (int row0 = 0; row0 < R && he == hipSuccess; row0 += VEFFT_ROWS) {
             const unsigned nr = (unsigned)std::min(VEFFT_ROWS, R - row0);
             if (timed && (he = st.mark(c->stream)) != hipSuccess) break;
-            if (nch > 0) hipLaunchKernelGGL(lf_vefftrue_part<v()>, dim3((unsigned)nch, nr), dim3(BLOCK), lds, c->stream, x, row0);
+            if (nch > 0 && cut)
+                hipLaunchKernelGGL(lf_vefftrue_part_cut<v()>, dim3((unsigned)nch, nr), dim3(BLOCK), lds, c->stream, x, row0, d_invg, wide_off);
+            else if (nch > 0)
+                hipLaunchKernelGGL(lf_vefftrue_part<v()>, dim3((unsigned)nch, nr), dim3(BLOCK), lds, c->stream, x, row0);
             if (timed && (he = st.mark(c->stream)) != hipSuccess) break;
             hipLaunchKernelGGL(lf_vefftrue_reduce, dim3(bblocks, nr), dim3(BLOCK), 0, c->stream, x, row0);
         }
@@ -2035,6 +2217,7 @@ int lf_veff_true(lf_ctx* c, const double* theta, int R, const double* edges, int
     for (int s = 0; s < 3 && timed; ++s) g_vefft_ms[s] = ms[s];
     return LF_OK;
 }
+}  // namespace
 
 int lf_set_profiling(lf_ctx* c, int enabled) {
     if (!c) return LF_ERR_ARG;
@@ -2460,6 +2643,7 @@ int lf_set_option(lf_ctx* c, const char* key, int64_t value) {
         {"deconv_wide", [](lf_ctx* c, int64_t v) { c->opt_deconv_wide = v != 0; }},
         {"deconv_cut_limit", [](lf_ctx* c, int64_t v) { c->opt_cut_limit = v < 0 ? 0 : v; }},
         {"deconv_cut_grad", [](lf_ctx* c, int64_t v) { c->opt_cut_grad = v != 0; }},
+        {"deconv_cut_veff", [](lf_ctx* c, int64_t v) { c->opt_cut_veff = v != 0; }},
         {"persistent", [](lf_ctx* c, int64_t v) { c->opt_persistent = v < 0 ? 0 : (v > 2 ? 2 : v); }},
         {"profile_every", [](lf_ctx* c, int64_t v) { c->opt_profile_every = v < 1 ? 1 : v; c->prof_tick = 0; }},
         {"profile_span", [](lf_ctx* c, int64_t v) { c->opt_profile_span = v < 1 ? 1 : v; c->prof_tick = 0; }},

@@ -358,7 +358,7 @@ def lum_posterior(inp, sigma, theta, K=None, wide=False, terms=False):
     return (out[0], out[1], len(used)) + ((out[2],) if terms else ())
 
 
-def veff_true(inp, sigma, theta, edges, pref0, vol, K=None, wide=False):
+def veff_true(inp, sigma, theta, edges, pref0, vol, K=None, wide=False, cut=None, min_vol_frac=0.0):
     """The deconvolved 1/Veff points (csrc/lf_vefftrue.h): theta (R, ndim) or (ndim,), edges (nbin + 1,)
     ascending -> (values (R, nbin), n_used).  Per row, every source's posterior of its true luminosity - the weights p_k on
     the nodes L_k = lum + dl_k of the source's rule (_rules; a source with sigma = 0: one node at lum with p = 1) - is binned
@@ -367,7 +367,10 @@ def veff_true(inp, sigma, theta, edges, pref0, vol, K=None, wide=False):
     exp(-l) being 1 / fc of the modified Fleming curve.  The bin of a node is searchsorted(edges, L, side="right") - 1; nodes
     outside [edges[0], edges[nbin]) are dropped.  A row is used when its plain lnprob (grad.py's twin) is finite; an unused row
     is NaN.  The posterior is binned as the rule's discrete measure: one source's bin masses are granular at the node spacing,
-    the sum over sources spread against the edges is not (the section has the measured figures)."""
+    the sum over sources spread against the edges is not (the section has the measured figures).
+    cut=(nodes, sigma (nf, M)): under a cut on the observed flux every node's pf / (pref0 vol) is
+    divided by g_f(L_ik), the part of the survey volume in which its true luminosity is catalogued (cut_volume_fraction); a
+    node with g = 0 or g < min_vol_frac adds exactly 0.  cut=None: the bits of before."""
     K = DEFAULT_ORDER if K is None else int(K)
     if K not in ORDERS:
         raise ValueError("deconvolve_order must be one of %s" % (ORDERS,))
@@ -385,25 +388,32 @@ def veff_true(inp, sigma, theta, edges, pref0, vol, K=None, wide=False):
     values = np.full((len(th), nbin), np.nan)
     rules = _rules(inp, sigma, K, wide)
     pv = pref0 * vol
+    gtab = None if cut is None else cut_volume_table(inp, sigma, cut, K=K, wide=wide, min_vol_frac=min_vol_frac)[0]
     with np.errstate(all="ignore"):
         for r in np.flatnonzero(use):
             acc = np.zeros(nbin)
-            for sub, idx, x, lnw in rules:
+            for ir, (sub, idx, x, lnw) in enumerate(rules):
                 sg = sigma if idx is None else sigma[idx]
                 p, L, l, pf = _row_terms(sub, sg, th[r], x, lnw, nodes="product")
                 b = np.searchsorted(ed, L, side="right") - 1
                 ok = (b >= 0) & (b < nbin) & (pf > 0.0)
-                acc += np.bincount(b[ok], weights=pf[ok] / pv, minlength=nbin)
+                if gtab is None:
+                    acc += np.bincount(b[ok], weights=pf[ok] / pv, minlength=nbin)
+                else:
+                    g, keep = gtab[ir]
+                    ok &= keep
+                    acc += np.bincount(b[ok], weights=(pf[ok] / pv) / g[ok], minlength=nbin)
             values[r] = acc
     return values, int(use.sum())
 
 
-def veff_true_quantiles(inp, sigma, theta, edges, pref0, vol, q=(16.0, 50.0, 84.0), method="linear", K=None, wide=False):
+def veff_true_quantiles(inp, sigma, theta, edges, pref0, vol, q=(16.0, 50.0, 84.0), method="linear", K=None, wide=False, cut=None,
+                        min_vol_frac=0.0):
     """veff_true and over its used rows np.percentile(q) per bin (method "linear") or np.median (method "median": one row):
-    (out (nq, nbin), values (R, nbin), n_used); no used row: NaN everywhere."""
+    (out (nq, nbin), values (R, nbin), n_used); no used row: NaN everywhere.  cut, min_vol_frac: veff_true's."""
     if method not in ("linear", "median"):
         raise ValueError("method must be 'linear' or 'median'")
-    values, used = veff_true(inp, sigma, theta, edges, pref0, vol, K=K, wide=wide)
+    values, used = veff_true(inp, sigma, theta, edges, pref0, vol, K=K, wide=wide, cut=cut, min_vol_frac=min_vol_frac)
     qa = np.atleast_1d(np.asarray(q, dtype=np.float64))
     nq = qa.size if method == "linear" else 1
     if used == 0:
@@ -667,6 +677,76 @@ def _cut_grid(inp):
     wz *= 0.5                                            # (0.5 (dl + dr): lf_hostprep.h's statement)
     ld2 = np.log10(4.0 * np.pi * (G.MPC_CM * np.asarray(inp["DL_zarr"], dtype=np.float64)) ** 2)
     return logL[0], logL[-1], zarr, wz, np.asarray(inp["volume_part"], dtype=np.float64), ld2
+
+
+def _cut_sigma_vec(nodes, sig, t):
+    """_cut_sigma for an array t: the same statements, element by element"""
+    M = len(nodes)
+    if M == 1:
+        return np.full(np.shape(t), float(sig[0]))
+    i = np.clip(np.searchsorted(nodes, t, side="right") - 1, 0, M - 2)
+    s = sig[i] + (t - nodes[i]) * ((sig[i + 1] - sig[i]) / (nodes[i + 1] - nodes[i]))
+    s = np.where(t >= nodes[M - 1], sig[M - 1], s)
+    return np.where(t > nodes[0], s, sig[0])
+
+
+def cut_volume_fraction(inp, nodes, sigma, field, L):
+    """g_f(L), the part of the survey volume in which a true luminosity L of field f is catalogued under the cut on the observed
+    flux (csrc/lf_vefftrue_cut.h), on the likelihood's own grid and with its own error model:
+        g_f(L) = (sum_j wv_j Q(-u_fj)) / (sum_j wv_j),  wv_j = wz_j V_j,  u_fj = (L - lam_j) / s_f(L - ld2_j),
+    Q(x) = erfc(x / sqrt 2) / 2.  field (n,) or a scalar, L (n,) -> g (n,).  The kernel's statements: the columns added left to
+    right into one accumulator, the denominator the same way; u > CUT_UMAX: a term of exactly wv_j, u < -CUT_UMAX: exactly 0,
+    else wv_j 0.5 erfc(-u / sqrt 2); a field whose sigma is 0 at every node: the step, wv_j when L >= lam_j."""
+    from scipy.special import erfc
+    nf = len(inp["field_ind"]) - 1
+    nd, sg = check_cut_error_model(nodes, sigma, nf)
+    Lq = np.atleast_1d(np.asarray(L, dtype=np.float64))
+    fq = np.broadcast_to(np.asarray(field, dtype=np.int64), Lq.shape)
+    if np.any(fq < 0) or np.any(fq >= nf):
+        raise ValueError("field must be in 0..%d" % (nf - 1))
+    lam, _, _, wz, vol, ld2 = _cut_grid(inp)
+    wv = wz * vol
+    den = 0.0
+    for j in range(len(wv)):
+        den = den + float(wv[j])
+    g = np.zeros(Lq.shape)
+    with np.errstate(all="ignore"):
+        for f in np.unique(fq):
+            at = fq == f
+            Lf = Lq[at]
+            acc = np.zeros(Lf.shape)
+            step = bool(np.all(sg[f] == 0.0))
+            for j in range(len(wv)):
+                if step:
+                    term = np.where(Lf >= lam[j], wv[j], 0.0)
+                else:
+                    u = (Lf - lam[j]) / _cut_sigma_vec(nd, sg[f], Lf - ld2[j])
+                    term = np.where(u > CUT_UMAX, wv[j], np.where(u < -CUT_UMAX, 0.0, wv[j] * (0.5 * erfc(-u / np.sqrt(2.0)))))
+                acc = acc + term
+            g[at] = acc / den
+    return g
+
+
+def cut_volume_table(inp, sigma, cut, K=None, wide=False, min_vol_frac=0.0):
+    """([(g [K_rule, N_rule], keep [K_rule, N_rule])] per rule of _rules, n_dropped): cut_volume_fraction at every node L_ik =
+    lum_i + sqrt(2) sigma_i x_k of every source's rule (one rounded product, one rounded add: the bits that choose the bin),
+    which nodes are kept (g > 0 and g >= min_vol_frac), and how many (source, node) slots are dropped - a source with sigma
+    = 0 has one slot, its node at lum_i.  None of it depends on theta."""
+    K = DEFAULT_ORDER if K is None else int(K)
+    sigma = check_sigma(sigma, len(inp["lum"]), K, True)
+    out, dropped = [], 0
+    for sub, idx, x, lnw in _rules(inp, sigma, K, wide):
+        sg = sigma if idx is None else sigma[idx]
+        lum = np.asarray(sub["lum"], dtype=np.float64)
+        fld = np.repeat(np.arange(len(sub["field_ind"]) - 1), np.diff(np.asarray(sub["field_ind"])))
+        L = lum[None, :] + (np.sqrt(2.0) * sg)[None, :] * np.asarray(x)[:, None]
+        g = cut_volume_fraction(inp, cut[0], cut[1], np.broadcast_to(fld, L.shape).ravel(), L.ravel()).reshape(L.shape)
+        keep = (g > 0.0) & (g >= min_vol_frac)
+        slot = np.ones(L.shape, dtype=bool)
+        slot[1:, sg == 0.0] = False
+        dropped += int(np.sum(slot & ~keep))
+        out.append((g, keep))
+    return out, dropped
 
 
 def cut_nodes(inp, nodes, sigma, limit=0, fields=None):

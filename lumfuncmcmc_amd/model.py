@@ -190,6 +190,8 @@ class _Base(object):
                     self._ctx.set_cut_error_model(*self.deconvolve_cut_errors)
                     if self.deconvolve_cut_grad:
                         self._ctx.set_option("deconv_cut_grad", 1)
+                    if self.deconvolve_cut_veff:
+                        self._ctx.set_option("deconv_cut_veff", 1)
                 self._ctx.set_lum_err(self.lum_e, self.deconvolve_order, unchecked=self.deconvolve_unchecked,
                                        wide=self.deconvolve_wide)
             if self.deconvolve_tile:
@@ -207,14 +209,19 @@ class _Base(object):
     deconvolve_cut = False         # True: the cut on the observed flux of min_comp_frac > 0.001 is modelled (csrc/lf_deconv_cut.h)
     deconvolve_cut_errors = None   # its error model (nodes (M,), sigma (nf, M)); None: the one this catalogue shows (error_model())
     deconvolve_cut_grad = False    # True: the gradient of the cut's term is served too (csrc/lf_deconv_cut_grad.h): MAP fits under the cut
+    deconvolve_cut_veff = False    # True: veff_deconvolved is served under the cut, by the catalogued volume per node (csrc/lf_vefftrue_cut.h)
 
     def _init_deconvolve(self, deconvolve, deconvolve_order, deconvolve_tile=False, deconvolve_wide=False, deconvolve_cut=False,
-                         deconvolve_cut_errors=None, deconvolve_cut_grad=False):
+                         deconvolve_cut_errors=None, deconvolve_cut_grad=False, deconvolve_cut_veff=False):
         from . import deconv
         self.deconvolve, self.deconvolve_order = bool(deconvolve), deconvolve_order
         self.deconvolve_tile, self.deconvolve_wide = bool(deconvolve_tile), bool(deconvolve_wide)
         self.deconvolve_cut = bool(deconvolve_cut)
         self.deconvolve_cut_grad = bool(deconvolve_cut_grad)
+        self.deconvolve_cut_veff = bool(deconvolve_cut_veff)
+        if self.deconvolve_cut_veff and not self.deconvolve_cut:
+            raise ValueError("deconvolve_cut_veff=True needs deconvolve_cut=True: it is the cut's catalogued volume per node that "
+                             "it divides the deconvolved 1/Veff points by")
         if self.deconvolve_cut_grad and not self.deconvolve_cut:
             raise ValueError("deconvolve_cut_grad=True needs deconvolve_cut=True: it is the gradient of Delta B, the cut's change "
                              "of the expected counts, that it adds")
@@ -639,7 +646,7 @@ class _Base(object):
             spread = np.sqrt(np.maximum(m2 - m1 * m1, 0.0))
         return {"lum_true": np.asarray(self.lum, dtype=np.float64) + m1, "lum_true_e": spread, "shift": m1, "n_used": int(used)}
 
-    def veff_deconvolved(self, percentiles=(16, 50, 84), ndraws=200, lnprobcut=7.5, method="linear", device=None):
+    def veff_deconvolved(self, percentiles=(16, 50, 84), ndraws=200, lnprobcut=7.5, method="linear", device=None, min_vol_frac=0.0):
         """The deconvolved 1/Veff points: per posterior draw, every source's posterior of its TRUE
         luminosity under the flux-error-convolved model, binned on VeffLF's bins with the completeness at the true flux, and
         the percentiles of every bin over the draws whose plain lnprob is finite (ndraws random draws, taken as lf_percentiles
@@ -647,10 +654,14 @@ class _Base(object):
         unused draw) in dn/dlogL like lfbinorig, n_used, and var_post = np.var(values of the used draws, axis=0, ddof=1) - the
         posterior part of the points' variance; NaN when fewer than two draws are used (no variance can be formed).  Needs deconvolve=True (whose min_comp_frac <= 0.001 makes the volume one
         scalar).  device=True: the GPU (lf_veff_true), False: NumPy (deconv.veff_true_quantiles); None = the GPU when this
-        object already holds a device context.  self.lum, var and lfbinorig are not touched."""
+        object already holds a device context.  self.lum, var and lfbinorig are not touched.
+        Under deconvolve_cut=True (min_comp_frac > 0.001) it needs deconvolve_cut_veff=True: every node's weight is then divided
+        by g, the part of the survey volume in which its true luminosity is catalogued under the cut (deconvolve_cut_errors'
+        model), nodes with g = 0 or g < min_vol_frac are dropped, and the dict gains n_dropped, the
+        number of dropped (source, node) pairs."""
         if not self.deconvolve:
             raise ValueError("veff_deconvolved needs an object made with deconvolve=True")
-        if self.deconvolve_cut:
+        if self.deconvolve_cut and not self.deconvolve_cut_veff:
             raise NotImplementedError("veff_deconvolved is not implemented under deconvolve_cut=True: with min_comp_frac > 0.001 "
                                       "every source has its own volume (a z_max per source), and the deconvolved points take one")
         from . import deconv
@@ -659,16 +670,31 @@ class _Base(object):
         edges, Lavg, dL, _ = veff.luminosity_bins(self.lum, self.nbins)
         vol = float(veff.comoving_volume(self.dVdzf, self.zmin, self.zmax))
         pref0 = sum(self.Omega_0) / hs.SQARCSEC
+        cut = self.deconvolve_cut_errors if self.deconvolve_cut else None
+        if cut is None and min_vol_frac != 0.0:
+            raise ValueError("min_vol_frac needs an object made with deconvolve_cut=True, deconvolve_cut_veff=True")
+        dropped = None
         if self._band_device(device):
-            out, values, used = self.context().veff_true(rows, edges, pref0, vol, q=percentiles, method=lfbands.METHODS[method])
+            ctx = self.context()
+            out, values, used = ctx.veff_true(rows, edges, pref0, vol, q=percentiles, method=lfbands.METHODS[method],
+                                              min_vol_frac=min_vol_frac)
+            if cut is not None:
+                dropped = ctx.veff_true_cut_info()["dropped"]
         else:
-            out, values, used = deconv.veff_true_quantiles(self.kernel_inputs(), np.asarray(self.lum_e, dtype=np.float64), rows, edges,
-                                                           pref0, vol, q=percentiles, method=method, K=self.deconvolve_order,
-                                                           wide=self.deconvolve_wide)
+            sg = np.asarray(self.lum_e, dtype=np.float64)
+            out, values, used = deconv.veff_true_quantiles(self.kernel_inputs(), sg, rows, edges, pref0, vol, q=percentiles, method=method,
+                                                           K=self.deconvolve_order, wide=self.deconvolve_wide, cut=cut,
+                                                           min_vol_frac=min_vol_frac)
+            if cut is not None:
+                dropped = deconv.cut_volume_table(self.kernel_inputs(), sg, cut, K=self.deconvolve_order, wide=self.deconvolve_wide,
+                                                  min_vol_frac=min_vol_frac)[1]
         values = values / dL
         ok = ~np.all(np.isnan(values), axis=1)
-        return {"Lavg": Lavg, "percentiles": out / dL, "values": values, "n_used": int(used),
-                "var_post": np.var(values[ok], axis=0, ddof=1) if ok.sum() > 1 else np.full(self.nbins, np.nan)}
+        res = {"Lavg": Lavg, "percentiles": out / dL, "values": values, "n_used": int(used),
+               "var_post": np.var(values[ok], axis=0, ddof=1) if ok.sum() > 1 else np.full(self.nbins, np.nan)}
+        if dropped is not None:
+            res["n_dropped"] = int(dropped)
+        return res
 
     def _mock_generator(self, device):
         """MockGenerator (GPU) or MockTwin (NumPy) over this object's unsharded kernel_inputs(); device=None = the GPU when
@@ -860,7 +886,7 @@ class LumFuncMCMC(_Base):
                  fix_sch_al=False, fcmin=0.1, fix_comp=False, min_comp_frac=0.5,
                  field_names=None, field_ind=None, diff_rand=True, device=0, compress=False, shard="walkers",
                  deconvolve=False, deconvolve_order=None, deconvolve_tile=False, deconvolve_wide=False,
-                 deconvolve_cut=False, deconvolve_cut_errors=None, deconvolve_cut_grad=False):
+                 deconvolve_cut=False, deconvolve_cut_errors=None, deconvolve_cut_grad=False, deconvolve_cut_veff=False):
         self._common_init(z, flux, flux_e, lum, lum_e)
         self.device = device
         self.compress = bool(compress)
@@ -893,7 +919,7 @@ class LumFuncMCMC(_Base):
         self.setlnsimple(need_integ=bool(self.fix_comp))
         self.setup_logging()
         self._init_deconvolve(deconvolve, deconvolve_order, deconvolve_tile, deconvolve_wide, deconvolve_cut, deconvolve_cut_errors,
-                              deconvolve_cut_grad)
+                              deconvolve_cut_grad, deconvolve_cut_veff)
 
     def getRoot(self, size=201):
         self.rootsf = hs.completeness_roots(self.Flim_lims, self.alpha_lims, self.fcmin, self.min_comp_frac, size)
@@ -1095,7 +1121,7 @@ class LumFuncMCMCz(_Base):
                  fcmin=0.1, min_comp_frac=0.5, field_names=None,
                  field_ind=None, z1=1.20, z2=1.53, z3=1.86, fix_sch_al=False, device=0, compress=False, shard="walkers",
                  deconvolve=False, deconvolve_order=None, deconvolve_tile=False, deconvolve_wide=False,
-                 deconvolve_cut=False, deconvolve_cut_errors=None, deconvolve_cut_grad=False):
+                 deconvolve_cut=False, deconvolve_cut_errors=None, deconvolve_cut_grad=False, deconvolve_cut_veff=False):
         self._common_init(z, flux, flux_e, lum, lum_e)
         self.device = device
         self.compress = bool(compress)
@@ -1129,7 +1155,7 @@ class LumFuncMCMCz(_Base):
         self.setlnsimple(need_integ=True)
         self.setup_logging()
         self._init_deconvolve(deconvolve, deconvolve_order, deconvolve_tile, deconvolve_wide, deconvolve_cut, deconvolve_cut_errors,
-                              deconvolve_cut_grad)
+                              deconvolve_cut_grad, deconvolve_cut_veff)
 
     def getRoot(self):
         """Per-field flux at which the completeness equals min_comp_frac (lumfuncmcmc_z.py:292-297);
