@@ -136,6 +136,11 @@ def main():
                          "DESIGN.md sections 3.11, 3.23), p-values per field printed: `none` bins the replicates' true "
                          "luminosities (the comparison for a plain fit), `catalogue` their observed ones under the catalogue's own "
                          "error model (the comparison for --deconvolve)")
+    ap.add_argument("--predictive-z", nargs="?", type=int, const=10, default=None, metavar="NZ",
+                    help="the posterior predictive check in redshift as well (posterior_predictive(z_edges=...); DESIGN.md section "
+                         "3.35): NZ equal redshift bins over [zmin, zmax] (default 10).  Prints N(z) observed beside the replicates' "
+                         "16/50/84 %% band and the deviance p-value per field; with --predictive-cut the replicates are those of the "
+                         "cut process, with --predictive-noise their luminosities carry the noise asked for there")
     ap.add_argument("--predictive-cut", action="store_true",
                     help="with --deconvolve-cut: the posterior predictive check against replicates of the cut process the fit "
                          "models - sources scattered in and out across the grid's lower edge included - under the fit's own error "
@@ -242,6 +247,20 @@ def main():
             print("  field %d: %6d %8.1f %.3f   at the cut: %6d %8.1f %.3f" % (f, pp["observed_total"][f],
                                                                               np.median(pp["replicated_total"][:, f]),
                                                                               pp["p_upper_total"][f], ob, np.median(rb), np.mean(rb >= ob)))
+    if args.predictive_z:
+        noise = "catalogue" if args.predictive_noise == "catalogue" else None
+        pp = LFmod.posterior_predictive(seed=11, cut=args.predictive_cut, noise=noise,
+                                        z_edges=np.linspace(LFmod.zmin, LFmod.zmax, args.predictive_z + 1))
+        print("posterior predictive check in (z, logL) (noise: %s%s), per field: N(z) observed | 16 / 50 / 84 %% of the replicates, "
+              "bin by bin, then the deviance, P(D_rep >= D_obs) and the observed sources in cells no replicate fills"
+              % (pp["noise"], ", cut process" if args.predictive_cut else ""))
+        for f in range(pp["nf"]):
+            for b in range(1, args.predictive_z + 1):
+                lo, mid, hi = pp["percentiles_z"][:, f, b]
+                print("  field %d  z %.3f-%.3f: %6d | %8.1f %8.1f %8.1f" % (f, pp["z_edges"][b - 1], pp["z_edges"][b], pp["observed_z"][f, b],
+                                                                       lo, mid, hi))
+            print("  field %d  deviance %.1f  p_deviance %.3f  in empty cells %d (of %d empty)"
+                  % (f, pp["deviance"][f], pp["p_deviance"][f], pp["observed_in_empty"][f], pp["n_empty_cells"][f]))
     if args.veff_band:
         write_veff_band(LFmod, os.path.join(args.out, "veffband_%s.dat" % tag), volumes=args.veff_volumes)
     print("wrote", sorted(os.listdir(args.out)))

@@ -733,6 +733,24 @@ int lf_mock_draw_cut(lf_mock *m, const double *theta, int32_t R, const int64_t *
                      double *mean, int64_t *kept);
 int lf_mock_hist_cut(lf_mock *m, const double *theta, int32_t R, const int64_t *row_ids, uint64_t seed, int32_t nbins,
                      const double *edges, int64_t *hist, int64_t *kept);
+/* The mocks binned in redshift and luminosity (csrc/lf_mock_hist2.h): the histogram of the pair
+ * (z, L) per (row, field) of the catalogue lf_mock_draw, lf_mock_draw_err or lf_mock_draw_cut would write, without writing
+ * sources.  L is logL (lf_mock_hist2), logL_obs (lf_mock_hist2_err) or logL_obs of the catalogued candidates
+ * (lf_mock_hist2_cut); redshift carries no noise.  Slots as lf_mock_hist on both axes: sz = searchsorted(z_edges, z,
+ * side="right") in 0 .. nz + 1, sl = searchsorted(edges, L, side="right") in 0 .. nl + 1; z_edges [nz + 1], edges [nl + 1],
+ * hist [R][nf][nz + 2][nl + 2].  Summed over sz the histogram is lf_mock_hist's (lf_mock_hist_err's, lf_mock_hist_cut's) for the
+ * same rows and seed, integer for integer; two calls give the same bits (integer atomics).  count: NULL = the Poisson counts
+ * lf_mock_counts returns; else [R][nf] as lf_mock_draw takes it.  lf_mock_hist2_cut draws its own counts and returns
+ * kept [R][nf] as lf_mock_hist_cut does.  LF_ERR_ARG, with lf_mock_last_error saying why, before the device is touched:
+ * everything lf_mock_hist (lf_mock_hist_err, lf_mock_hist_cut) refuses, a count < 0 or >= 2^32, nz or nl outside 1..1022,
+ * (nz + 2)(nl + 2) above 8192 slots (the message names the limit), edges on either axis that are not finite and non-decreasing.
+ * The handle stays usable after an error. */
+int lf_mock_hist2(lf_mock *m, const double *theta, int32_t R, const int64_t *row_ids, uint64_t seed, const int64_t *count,
+                  int32_t nz, const double *z_edges, int32_t nl, const double *edges, int64_t *hist);
+int lf_mock_hist2_err(lf_mock *m, const double *theta, int32_t R, const int64_t *row_ids, uint64_t seed, const int64_t *count,
+                      int32_t nz, const double *z_edges, int32_t nl, const double *edges, int64_t *hist);
+int lf_mock_hist2_cut(lf_mock *m, const double *theta, int32_t R, const int64_t *row_ids, uint64_t seed, int32_t nz,
+                      const double *z_edges, int32_t nl, const double *edges, int64_t *hist, int64_t *kept);
 /* Last error of this handle; m == NULL: of the last failed lf_mock_create.  Never NULL. */
 const char *lf_mock_last_error(const lf_mock *m);
 

