@@ -60,6 +60,17 @@ def write_veff_band(LFmod, path, volumes="fixed"):
                                        [np.sqrt(band["var_comp"])], labels)
 
 
+def write_veff_slices(LFmod, out, tag, S):
+    """The 1/Veff points of S equal-count redshift slices, one table per slice in VeffLF's format, with the model averaged over
+    the slice (veff_slices)"""
+    np.random.seed(5)
+    res = LFmod.veff_slices(z_edges=S, percentiles=(16, 50, 84))
+    labels = ["Luminosity", "BinLF", "BinLFErr", "Model_16", "Model_50", "Model_84"]
+    for s in range(S):
+        path = os.path.join(out, "VeffLF_%s_z%.3f-%.3f.dat" % (tag, res["z_edges"][s], res["z_edges"][s + 1]))
+        tableio.write_fixed_width_two_line(path, [res["Lavg"][s], res["lf"][s], np.sqrt(res["var"][s])] + list(res["model"][:, s]), labels)
+
+
 def write_deconvolved_lums(LFmod, path):
     """the per-source posterior of the true luminosity (deconvolved_luminosities) as a table, and the mean shift of the faintest
     and the brightest tenth of the catalogue"""
@@ -105,6 +116,9 @@ def main():
     ap.add_argument("--veff-volumes", choices=("fixed", "per_draw"), default="fixed",
                     help="with --veff-band: the sources' volumes at the current Flim and alpha for every draw (fixed), or out to "
                          "the z_max of each draw's own flux cut (per_draw; DESIGN.md section 3.29)")
+    ap.add_argument("--veff-slices", type=int, default=0, metavar="S",
+                    help="also write the 1/Veff points of S equal-count redshift slices, one VeffLF table per slice, with the model "
+                         "averaged over the slice (veff_slices; DESIGN.md section 3.36)")
     ap.add_argument("--deconvolve", action="store_true",
                     help="fit the likelihood convolved with the catalogue's flux errors (Eddington-bias correction, deconvolve=True; "
                          "DESIGN.md section 3.18; errors above 0.09 dex are refused; --until-converged and --pt run the device "
@@ -263,6 +277,8 @@ def main():
                   % (f, pp["deviance"][f], pp["p_deviance"][f], pp["observed_in_empty"][f], pp["n_empty_cells"][f]))
     if args.veff_band:
         write_veff_band(LFmod, os.path.join(args.out, "veffband_%s.dat" % tag), volumes=args.veff_volumes)
+    if args.veff_slices:
+        write_veff_slices(LFmod, args.out, tag, args.veff_slices)
     print("wrote", sorted(os.listdir(args.out)))
     LFmod.close()
 

@@ -583,6 +583,27 @@ int lf_veff(int device, int64_t n, const double *flux, const double *flim, const
             double alpha, double fcmin, const int32_t *bin_of, int32_t nbin, int32_t nboot, const int64_t *boot_idx, uint64_t seed,
             double *phi, double *sums);
 
+/* The 1/Veff points in redshift slices with a bootstrap per slice (post-fit, no context needed; csrc/lf_veffslices.h, DESIGN.md
+ * section 3.36) - the device form of VmaxLumFunc.zEvolSteps (VmaxLumFunc.py:611-660).  All arrays host, length n unless noted.
+ *   phi[i] = 1 / (pref0 * fleming(flux[i], flim[i], alpha, fcmin) * vol[i]), 0 where vol[i] <= 0: lf_veff's weights with the
+ *   volume of the source's own slice (every source gets one, with or without a slice);
+ *   slice_of[i] in [0, nslice): the source's slice, anything else = no slice (it enters no sum); bin_of[i] as in lf_veff;
+ *   sums[(nboot + 1) * nslice * nbin]: [0][s][b] = the sum of phi over the sources of slice s and bin b; [k][s][b], k = 1..nboot,
+ *   the same over resample k of slice s: n_s draws j = 0 .. n_s - 1 among the slice's n_s sources, source number
+ *   min(floor(u n_s), n_s - 1) of the slice in the caller's order, u the 53-bit uniform of the first two words of
+ *   Philox4x32-10(counter (j, s, k, 0x736c6963), key seed) - or boot_idx[(k - 1) * m + p] when given: m = the number of sources
+ *   with a slice, p = the source's position when these are sorted by slice (stable), the value its draw, a source number
+ *   within the slice, in [0, n_s): LF_ERR_ARG otherwise;
+ *   counts[nslice * nbin]: the catalogue's sources per slice and bin.
+ * Every argument is checked before the device is touched: a NULL pointer (boot_idx may be NULL), n <= 0 or above 2^31 - 1,
+ * nslice or nbin outside 1..64, nboot outside 0..10000, pref0 <= 0 give LF_ERR_ARG.  The sums are added in one fixed order,
+ * without floating-point atomics: the same inputs give the same bits on every call.  Synchronous. */
+int lf_veff_slices(int device, int64_t n, const double *flux, const double *flim, const double *vol, double pref0, double alpha,
+                   double fcmin, const int32_t *slice_of, int32_t nslice, const int32_t *bin_of, int32_t nbin, int32_t nboot,
+                   const int64_t *boot_idx, uint64_t seed, double *phi, double *sums, int64_t *counts);
+/* device time in ms of the last lf_veff_slices call's two kernels (veffs_partial, veffs_reduce); -1 before the first */
+double lf_veff_slices_ms(void);
+
 /* Percentiles over R posterior draws of the model LF at P points (post-fit; no context needed, synchronous, like lf_veff).
  * Replaces the draw loop + np.median of LumFuncMCMC.set_median_fit (lumfuncmcmc.py:527-567) and gives the bands around it.
  * draws: R x 3 (LF_FREE / LF_FIXCOMP: logLstar, logphistar, alpha) or R x 7 (LF_ZEVOL: aL, bL, cL, aphi, bphi, cphi, alpha -

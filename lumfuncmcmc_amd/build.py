@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liblfmcmc.so")
 SOURCES = [os.path.join(CSRC, "lfmcmc.hip")]
-HEADERS = [os.path.join(CSRC, h) for h in ("lf_kernels.h", "lf_bands.h", "lf_veffdraws.h", "lf_vefftrue.h", "lf_vefftrue_part_body.h", "lf_vefftrue_cut.h", "lf_gammainc.h", "lf_gammainc_coef.h", "lf_diag.h", "lf_grad.h", "lf_deconv.h", "lf_deconv_grad.h", "lf_deconv_tile.h", "lf_deconv_wide.h", "lf_deconv_cut.h", "lf_deconv_cut_grad.h", "lf_lumpost.h", "lf_mock.h", "lf_mock_noise.h", "lf_mock_cut.h", "lf_mock_hist2.h", "lf_tile.h", "lf_pt.h", "lf_free.h", "lf_pers.h", "lf_math.h", "lf_tables.h", "lf_compress.h", "lf_gridbound.h", "lf_devmem.h", "lf_hostcall.h", "lf_layout.h", "lf_hostprep.h")] + \
+HEADERS = [os.path.join(CSRC, h) for h in ("lf_kernels.h", "lf_bands.h", "lf_veffdraws.h", "lf_veffslices.h", "lf_vefftrue.h", "lf_vefftrue_part_body.h", "lf_vefftrue_cut.h", "lf_gammainc.h", "lf_gammainc_coef.h", "lf_diag.h", "lf_grad.h", "lf_deconv.h", "lf_deconv_grad.h", "lf_deconv_tile.h", "lf_deconv_wide.h", "lf_deconv_cut.h", "lf_deconv_cut_grad.h", "lf_lumpost.h", "lf_mock.h", "lf_mock_noise.h", "lf_mock_cut.h", "lf_mock_hist2.h", "lf_tile.h", "lf_pt.h", "lf_free.h", "lf_pers.h", "lf_math.h", "lf_tables.h", "lf_compress.h", "lf_gridbound.h", "lf_devmem.h", "lf_hostcall.h", "lf_layout.h", "lf_hostprep.h")] + \
           [os.path.join(os.path.dirname(HERE), "include", "lfmcmc.h")]
 
 

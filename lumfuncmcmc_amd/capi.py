@@ -60,7 +60,8 @@ EXPORTS = ("lf_abi_version", "lf_create", "lf_destroy", "lf_ndim", "lf_lnprob_ba
            "lf_mock_set_error_model", "lf_mock_draw_err", "lf_mock_hist_err",
            "lf_set_cut_error_model", "lf_cut_term_batch", "lf_cut_info", "lf_cut_term_grad_batch",
            "lf_mock_set_cut_band", "lf_mock_draw_cut", "lf_mock_hist_cut",
-           "lf_veff_true_cut", "lf_veff_true_cut_info", "lf_veff_true_cut_ms", "lf_cut_volume")
+           "lf_veff_true_cut", "lf_veff_true_cut_info", "lf_veff_true_cut_ms", "lf_cut_volume",
+           "lf_veff_slices", "lf_veff_slices_ms")
 # the mocks binned in (z, logL).  Kept apart from EXPORTS: tests/test_capi_cpu.py compares that tuple
 # with a scan of the header that reads names made of letters and underscores only.
 EXPORTS_HIST2 = ("lf_mock_hist2", "lf_mock_hist2_err", "lf_mock_hist2_cut")
@@ -181,6 +182,12 @@ def load():
     lib.lf_veff.argtypes = [ctypes.c_int, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p, ctypes.c_double, ctypes.c_double,
                             ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
                             _c_int64_p, ctypes.c_uint64, _c_double_p, _c_double_p]
+    lib.lf_veff_slices.restype = ctypes.c_int
+    lib.lf_veff_slices.argtypes = [ctypes.c_int, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p, ctypes.c_double, ctypes.c_double,
+                                   ctypes.c_double, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                   ctypes.c_int32, ctypes.c_int32, _c_int64_p, ctypes.c_uint64, _c_double_p, _c_double_p, _c_int64_p]
+    lib.lf_veff_slices_ms.restype = ctypes.c_double
+    lib.lf_veff_slices_ms.argtypes = []
     lib.lf_lumfunc_quantiles.restype = ctypes.c_int
     lib.lf_lumfunc_quantiles.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int32, _c_double_p, ctypes.c_int64, _c_double_p,
                                          _c_double_p, ctypes.c_int32, _c_double_p, ctypes.c_int32, _c_double_p, _c_double_p]
@@ -427,6 +434,41 @@ def veff_device(flux, flim, vol, pref0, alpha, fcmin, bin_of=None, nbin=0, nboot
     if rc != LF_OK:
         raise LFError("lf_veff failed (%d)" % rc)
     return phi, sums
+
+
+def veff_slices(flux, flim, vol, pref0, alpha, fcmin, slice_of, nslice, bin_of, nbin, nboot=0, boot_idx=None, seed=0, device=0):
+    """lf_veff_slices (include/lfmcmc.h): the 1/Veff weights with a volume per source, their binned sums per redshift slice
+    over the catalogue and over nboot bootstrap resamples of each slice, and the catalogue's counts.  slice_of outside
+    [0, nslice): no slice; bin_of outside [0, nbin): no bin; boot_idx (nboot, m): the draws as source numbers within the slice,
+    for the m sources with a slice in slice-sorted order.  Returns (phi[n], sums[nboot + 1, nslice, nbin], counts[nslice, nbin]).
+    The arguments are checked by the library before the device is touched: LFError."""
+    lib = load()
+    flux, flim, vol = _f64(flux), _f64(flim), _f64(vol)
+    n = flux.size
+    ip = ctypes.POINTER(ctypes.c_int32)
+    s32 = np.ascontiguousarray(slice_of, dtype=np.int32)
+    b32 = np.ascontiguousarray(bin_of, dtype=np.int32)
+    if not (flim.size == vol.size == s32.size == b32.size == n):
+        raise ValueError("flux, flim, vol, slice_of and bin_of must have one length")
+    bidx = None if boot_idx is None else np.ascontiguousarray(boot_idx, dtype=np.int64)
+    m = int(((s32 >= 0) & (s32 < nslice)).sum())
+    if bidx is not None and bidx.shape != (nboot, m):
+        raise ValueError("boot_idx must be (nboot, sources with a slice)")
+    phi = np.empty(n)
+    sums = np.zeros((max(int(nboot), 0) + 1, max(int(nslice), 0), max(int(nbin), 0)))
+    counts = np.zeros((max(int(nslice), 0), max(int(nbin), 0)), dtype=np.int64)
+    rc = lib.lf_veff_slices(int(device), n, _ptr(flux), _ptr(flim), _ptr(vol), float(pref0), float(alpha), float(fcmin) if fcmin else 0.0,
+                            s32.ctypes.data_as(ip), int(nslice), b32.ctypes.data_as(ip), int(nbin), int(nboot),
+                            None if bidx is None else bidx.ctypes.data_as(_c_int64_p), ctypes.c_uint64(int(seed)), _ptr(phi),
+                            _ptr(sums), counts.ctypes.data_as(_c_int64_p))
+    if rc != LF_OK:
+        raise LFError("lf_veff_slices failed (%d)" % rc)
+    return phi, sums, counts
+
+
+def veff_slices_ms():
+    """Device time (ms) of the two kernels of the last lf_veff_slices call in this process (-1 before the first)."""
+    return float(load().lf_veff_slices_ms())
 
 
 def lumfunc_quantiles(variant, draws, logL, z=None, q=(16.0, 50.0, 84.0), method=LF_Q_LINEAR, values=False, device=0):

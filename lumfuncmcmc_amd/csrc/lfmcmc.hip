@@ -44,6 +44,7 @@
 #include "lf_veffdraws.h"
 #include "lf_vefftrue.h"
 #include "lf_vefftrue_cut.h"
+#include "lf_veffslices.h"
 
 namespace {
 
@@ -2324,6 +2325,98 @@ int lf_veff(int device, int64_t n, const double* flux, const double* flim, const
     }
     return hc.rc;
 }
+
+static double g_veffs_ms = -1.0;      // device time of the last lf_veff_slices call's two kernels (veffs_partial, veffs_reduce)
+
+int lf_veff_slices(int device, int64_t n, const double* flux, const double* flim, const double* vol, double pref0, double alpha, double fcmin,
+                   const int32_t* slice_of, int32_t nslice, const int32_t* bin_of, int32_t nbin, int32_t nboot, const int64_t* boot_idx,
+                   uint64_t seed, double* phi, double* sums, int64_t* counts) {
+    // every argument is checked before the device is touched
+    if (!flux || !flim || !vol || !slice_of || !bin_of || !phi || !sums || !counts || n <= 0 || n > (int64_t)INT32_MAX || nslice < 1 ||
+        nslice > lf::VEFFS_MAXSLICE || nbin < 1 || nbin > lf::VEFFS_MAXBIN || nboot < 0 || nboot > lf::VEFFS_MAXBOOT || !(pref0 > 0.0))
+        return LF_ERR_ARG;
+    // stable counting sort of the sources by slice; a source outside [0, nslice) has no slice and enters no sum
+    std::vector<int> off((size_t)nslice + 1, 0);
+    for (int64_t i = 0; i < n; ++i)
+        if (slice_of[i] >= 0 && slice_of[i] < nslice) ++off[(size_t)slice_of[i] + 1];
+    for (int s = 0; s < nslice; ++s) off[s + 1] += off[s];
+    const int m = off[nslice];
+    std::vector<int> order((size_t)m);
+    {
+        std::vector<int> at(off.begin(), off.end() - 1);
+        for (int64_t i = 0; i < n; ++i)
+            if (slice_of[i] >= 0 && slice_of[i] < nslice) order[(size_t)at[slice_of[i]]++] = (int)i;
+    }
+    // the caller's resampling indices address the slice's records on the device: outside [0, n_s) they are refused here
+    if (boot_idx)
+        for (int k = 0; k < nboot; ++k)
+            for (int s = 0; s < nslice; ++s) {
+                const int64_t ns = off[s + 1] - off[s];
+                const int64_t* row = boot_idx + (size_t)k * (size_t)m;
+                for (int p = off[s]; p < off[s + 1]; ++p)
+                    if (row[p] < 0 || row[p] >= ns) return LF_ERR_ARG;
+            }
+    // chunks of at most VEFFS_CHUNK draws within a slice; c0[s] = the first chunk of slice s
+    std::vector<lf::VeffsChunk> chunks;
+    std::vector<int> c0((size_t)nslice + 1, 0);
+    for (int s = 0; s < nslice; ++s) {
+        c0[s] = (int)chunks.size();
+        const int ns = off[s + 1] - off[s];
+        for (int f = 0; f < ns; f += lf::VEFFS_CHUNK) chunks.push_back({s, f, std::min(lf::VEFFS_CHUNK, ns - f), off[s], ns, 0});
+    }
+    const size_t nch = chunks.size();
+    c0[nslice] = (int)nch;
+    const int nres = nboot + 1;
+    const size_t cells = (size_t)nslice * nbin;
+    if (hipSetDevice(device) != hipSuccess) return LF_ERR_NODEV;
+    Buf<double> d_flux, d_flim, d_vol, d_phi, d_part, d_sums;
+    Buf<int> d_slice, d_bin, d_order, d_c0;
+    Buf<long long> d_idx;
+    Buf<unsigned long long> d_counts;
+    Buf<lf::VeffsRec> d_rec;
+    Buf<lf::VeffsChunk> d_chunk;
+    HostCall hc;
+    g_veffs_ms = -1.0;
+    static_assert(sizeof(int) == sizeof(int32_t) && sizeof(long long) == sizeof(int64_t), "the caller's arrays are uploaded as they are");
+    if (hc.ok(d_flux.upload(flux, (size_t)n)) && hc.ok(d_flim.upload(flim, (size_t)n)) && hc.ok(d_vol.upload(vol, (size_t)n)) &&
+        hc.ok(d_slice.upload(slice_of, (size_t)n)) && hc.ok(d_bin.upload(bin_of, (size_t)n)) && hc.ok(d_order.upload(order.data(), (size_t)m)) &&
+        hc.ok(d_chunk.upload(chunks.data(), nch)) && hc.ok(d_c0.upload(c0.data(), c0.size())) &&
+        (!boot_idx || hc.ok(d_idx.upload((const long long*)boot_idx, (size_t)nboot * (size_t)m))) &&
+        hc.ok(alloc_all(d_phi, (size_t)n, d_rec, (size_t)m, d_part, (size_t)nres * nch * nbin, d_sums, (size_t)nres * cells, d_counts, cells)) &&
+        hc.ok(hipMemset(d_counts, 0, cells * sizeof(unsigned long long)))) {
+        hipLaunchKernelGGL(lf::veff_weights, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_flux, d_flim, d_vol, 0.0, pref0, alpha,
+                           fcmin > 0.0 ? lfh::fc_ratio(fcmin) : 0.0, fcmin > 0.0 ? 1 : 0, (long long)n, d_phi);
+        hc.ok(hipGetLastError());
+        if (m > 0) {
+            hipLaunchKernelGGL(lf::veffs_pack, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, d_phi, d_slice, d_bin, d_order, m, (int)nbin, d_rec);
+            hc.ok(hipGetLastError());
+        }
+        hc.stamp(0, 0);
+        if (nch > 0) {
+            // the smallest instantiation that holds the call's bins: the most lanes
+            auto kernel = nbin <= 16 ? lf::veffs_partial<16> : (nbin <= 32 ? lf::veffs_partial<32> : lf::veffs_partial<64>);
+            const unsigned lanes = (unsigned)(lf::VEFFS_LDS_DOUBLES / (nbin <= 16 ? 16 : (nbin <= 32 ? 32 : 64)));
+            hipLaunchKernelGGL(kernel, dim3((unsigned)nch, (unsigned)nres), dim3(lanes), 0, 0, d_rec, d_chunk, (int)nch, (int)nbin, d_idx,
+                               (long long)m, (unsigned long long)seed, d_part);
+            hc.ok(hipGetLastError());
+        }
+        // enough workgroups for the (k, s, b) sums, and for the last row's pass over the records
+        const unsigned gx = (unsigned)std::max<size_t>((cells + lf::VEFFS_REDUCE_THREADS - 1) / lf::VEFFS_REDUCE_THREADS,
+                                                       std::min<size_t>(((size_t)m + 4095) / 4096, 256));
+        hipLaunchKernelGGL(lf::veffs_reduce, dim3(gx, (unsigned)nres + 1), dim3(lf::VEFFS_REDUCE_THREADS), 0, 0, d_part, d_c0, (int)nch, (int)nslice,
+                           (int)nbin, nres, d_rec, m, d_sums, d_counts);
+        hc.ok(hipGetLastError());
+        hc.stamp(1, 0);
+        hc.ok(hipMemcpy(sums, d_sums, (size_t)nres * cells * sizeof(double), hipMemcpyDeviceToHost));
+        hc.ok(hipMemcpy(counts, d_counts, cells * sizeof(int64_t), hipMemcpyDeviceToHost));
+        hc.ok(hipMemcpy(phi, d_phi, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+        hc.elapsed(0, 1, &g_veffs_ms);
+        if (hc.rc != LF_OK) g_veffs_ms = -1.0;
+    }
+    return hc.rc;
+}
+
+double lf_veff_slices_ms(void) { return g_veffs_ms; }
 
 static double g_bands_ms = -1.0;      // device time of the last lf_lumfunc_quantiles kernel (lf_lumfunc_quantiles_ms)
 static double g_integ_ms = -1.0;      // the same of lf_lumfunc_integral_quantiles

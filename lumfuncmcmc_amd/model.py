@@ -881,6 +881,49 @@ class _Base(object):
             self.log.warning("skipping the 1/Veff estimate: %s" % e)
             self.Lavg = self.lfbinorig = self.var = None
 
+    SLICE_NODES = 8                # Gauss-Legendre nodes per redshift slice of veff_slices' model band
+
+    def veff_slices(self, z_edges="auto", bins="common", device=None, model=True, percentiles=(16, 50, 84), ndraws=200, lnprobcut=7.5):
+        """The 1/Veff points in redshift slices, next to the model averaged over the same slices (DESIGN.md section 3.36;
+        VmaxLumFunc.zEvolSteps).  z_edges: S + 1 increasing redshifts inside [zmin, zmax], an integer S for S equal-count
+        slices (veff.slice_edges), or "auto" = 5.  A source's volume runs from its slice's lower edge to the upper edge or to
+        its own z_max (VeffLF's), whichever is lower; every slice is resampled on its own, nboot times.  bins="common": the
+        luminosity bins of the whole catalogue for every slice; "slice": each slice's own, as the reference has them.
+        Returns a dict: z_edges (S + 1,), Lavg (S, nbins), lf, var (S, nbins) in dn/dlogL like lfbinorig and var, counts
+        (S, nbins), n_slice (S,), seed (the bootstrap's, drawn from numpy's global state), and with model=True also model
+        (len(percentiles), S, nbins): the percentiles over ndraws posterior draws (taken as lf_percentiles takes them) of the
+        model LF at Lavg, averaged over the slice with the weight dV/dz - for LumFuncMCMC, which has no z dependence,
+        lf_percentiles at Lavg.  device=True: the GPU (lf_veff_slices, a fixed order of summation), False: NumPy; None = the
+        GPU when this object already holds a device context.  self.Lavg, self.lfbinorig and self.var are not touched."""
+        if isinstance(z_edges, str):
+            if z_edges != "auto":
+                raise ValueError("z_edges must be 'auto', a number of slices or the edges themselves, not %r" % (z_edges,))
+            z_edges = 5
+        edges = veff.slice_edges(self.z, z_edges) if np.ndim(z_edges) == 0 else np.asarray(z_edges, dtype=np.float64)
+        if edges[0] < self.zmin or edges[-1] > self.zmax:
+            raise ValueError("z_edges must lie inside [zmin, zmax] = [%r, %r]" % (self.zmin, self.zmax))
+        slice_of = veff.slice_index(self.z, edges)
+        S = edges.size - 1
+        vol = veff.slice_volumes(self.dVdzf, edges, slice_of, self._veff_zmaxval())
+        dev = self._band_device(device)
+        seed = int(np.random.randint(0, 2 ** 31 - 1))
+        run = veff.veff_slices_device if dev else veff.veff_slices_host
+        _, Lavg, lf, var, counts, n_slice = run(self.lum, self.flux, 1.0e-17 * self.Flims_arr, vol, slice_of, S, sum(self.Omega_0),
+                                                self.alpha, self.fcmin, nboot=self.nboot, nbin=self.nbins, bins=bins, seed=seed,
+                                                **({"device": self.device} if dev else {}))
+        out = {"z_edges": edges, "Lavg": Lavg, "lf": lf, "var": var, "counts": counts, "n_slice": n_slice, "seed": seed}
+        if model:
+            nobin = np.isnan(Lavg)                                  # (bins="slice": a slice without bins)
+            band = self._slice_band(edges, np.where(nobin, 0.0, Lavg), percentiles, ndraws, lnprobcut, dev)
+            band[:, nobin] = np.nan
+            out["model"] = band
+        return out
+
+    def _slice_band(self, edges, Lavg, percentiles, ndraws, lnprobcut, dev):
+        """(nq, S, nbins): without a z dependence the slice average is the model itself"""
+        band = self.lf_percentiles(percentiles=percentiles, logL=Lavg.ravel(), ndraws=ndraws, lnprobcut=lnprobcut, device=dev)
+        return band.reshape((band.shape[0],) + Lavg.shape)
+
     def close(self):
         # (a device sampler holds its context's handle: it goes first; what it read back stays on it)
         for s in (getattr(self, "sampler", None), getattr(self, "pt_sampler", None)):
@@ -1105,14 +1148,15 @@ class LumFuncMCMC(_Base):
         """1/Veff weights per source and the binned LF with bootstrap errors (lumfuncmcmc.py:515-525).  device=True
         runs weights, binning and bootstrap on the GPU (lf_veff; resamples drawn with Philox instead of numpy's global
         state), False on the host; None = the GPU when this object already holds a device context."""
+        self._veff(sum(self.Omega_0), self._veff_zmaxval(), device)
+
+    def _veff_zmaxval(self):
+        """Where a source's volume ends: zmax, or its own z_max under the flux cut of min_comp_frac, clipped to zmax"""
         self.getFlim()
-        sum_Omega = sum(self.Omega_0)
         if self.min_comp_frac <= 0.001:
-            zmaxval = self.zmax
-        else:
-            root = self.rootsf.ev(self.Flims_arr, self.alpha)
-            zmaxval = np.minimum(self.zmax, veff.max_redshift(10 ** self.lum, root, _cosmo))
-        self._veff(sum_Omega, zmaxval, device)
+            return self.zmax
+        root = self.rootsf.ev(self.Flims_arr, self.alpha)
+        return np.minimum(self.zmax, veff.max_redshift(10 ** self.lum, root, _cosmo))
 
     def triangle_plot(self, outname, lnprobcut=7.5, imgtype='png'):
         """lumfuncmcmc.py:604-651.  The figure itself (corner + matplotlib) is outside the scope of this build; what the
@@ -1286,12 +1330,28 @@ class LumFuncMCMCz(_Base):
 
     def VeffLF(self, device=None):
         """lumfuncmcmc_z.py:470-478 (device: see LumFuncMCMC.VeffLF)."""
-        sum_Omega = sum(self.Omega_0)
+        self._veff(sum(self.Omega_0), self._veff_zmaxval(), device)
+
+    def _veff_zmaxval(self):
         if self.min_comp_frac <= 0.001:
-            zmaxval = self.zmax
+            return self.zmax
+        return np.minimum(self.zmax, veff.max_redshift(10 ** self.lum, self.roots_arr, _cosmo))
+
+    def _slice_band(self, edges, Lavg, percentiles, ndraws, lnprobcut, dev):
+        """(nq, S, nbins): per posterior draw the model LF at SLICE_NODES Gauss-Legendre redshifts of every slice, averaged
+        with the weights w_g dV/dz(z_g) (veff.slice_model_average); np.percentile over the draws."""
+        rows = self._posterior_rows(ndraws, lnprobcut)
+        recs = lfbands.pack_draws("zevol", rows, fix_sch_al=self.fix_sch_al, sch_al=self.sch_al, pivots=(self.z1, self.z2, self.z3))
+        zg, wg = veff.slice_nodes(edges, self.SLICE_NODES)
+        S, G, nb = zg.shape[0], zg.shape[1], Lavg.shape[1]
+        Lp = np.ascontiguousarray(np.broadcast_to(Lavg[:, None, :], (S, G, nb))).ravel()
+        zp = np.ascontiguousarray(np.broadcast_to(zg[:, :, None], (S, G, nb))).ravel()
+        if dev:
+            values = lfbands.quantiles_device("zevol", recs, Lp, z=zp, q=percentiles, values=True, device=self.device)[1]
         else:
-            zmaxval = np.minimum(self.zmax, veff.max_redshift(10 ** self.lum, self.roots_arr, _cosmo))
-        self._veff(sum_Omega, zmaxval, device)
+            values = lfbands.lf_values("zevol", recs, Lp, z=zp)
+        avg = veff.slice_model_average(values.reshape(-1, S, G, nb), wg * self.dVdzf(zg))
+        return np.percentile(avg, np.atleast_1d(np.asarray(percentiles, dtype=np.float64)), axis=0)
 
     def triangle_plot(self, outname, lnprobcut=7.5, imgtype='png'):
         """lumfuncmcmc_z.py:546-585.  As for LumFuncMCMC.triangle_plot: the figure is out of scope, the numbers its code

@@ -257,3 +257,204 @@ def boot_err_log(L, phi, nboot=100, nbin=25):
     var = 1. / (nboot - 1) * np.sum((lfbin - binavg) ** 2, axis=0)
     var[var <= 0.0] = min(var[var > 0.0])
     return Lavg, lfbinorig, var
+
+
+# ---------------------------------------------------------------------------------------------- redshift slices
+SLICES_PURPOSE = 0x736c6963      # the Philox stream word of the slices' bootstrap (csrc/lf_veffslices.h: VEFFS_PURPOSE)
+SLICES_MAX = 64                  # slices, and luminosity bins, of one call (VEFFS_MAXSLICE, VEFFS_MAXBIN)
+SLICES_CHUNK = 4096              # draws per chunk of the device's summation order (VEFFS_CHUNK)
+
+
+def slice_edges(z, S):
+    """The S + 1 edges of S equal-count redshift slices (V.get_bins + V.zEvolSteps, VmaxLumFunc.py:45-48, :619-630): ranks from
+    a stable argsort of z, the source of rank r in slice floor(r S / N); e_0 = min(z), e_S = max(z), an inner edge the mean
+    of the largest z below it and the smallest above it."""
+    z = np.asarray(z, dtype=np.float64)
+    N, S = z.size, int(S)
+    if not 1 <= S <= min(N, SLICES_MAX):
+        raise ValueError("the number of slices must be between 1 and min(N, %d), not %d" % (SLICES_MAX, S))
+    zs = z[np.argsort(z, kind="stable")]
+    sl = (np.arange(N, dtype=np.int64) * S) // N                # the slice of every rank
+    first = np.searchsorted(sl, np.arange(1, S))                # the first rank of slices 1 .. S - 1
+    return np.concatenate([[zs[0]], (zs[first - 1] + zs[first]) / 2.0, [zs[-1]]])
+
+
+def slice_index(z, z_edges):
+    """slice_of per source: s where e_s <= z < e_s+1, the last slice also taking z == e_S; -1 for a source outside every slice."""
+    z = np.asarray(z, dtype=np.float64)
+    e = np.asarray(z_edges, dtype=np.float64)
+    S = e.size - 1
+    if S < 1 or S > SLICES_MAX or not np.all(np.diff(e) > 0):
+        raise ValueError("z_edges must hold 2 to %d strictly increasing redshifts" % (SLICES_MAX + 1))
+    s = np.searchsorted(e, z, side="right") - 1
+    s[z == e[-1]] = S - 1
+    s[(s < 0) | (s >= S) | ~np.isfinite(z)] = -1
+    return s.astype(np.int32)
+
+
+def slice_volumes(dVdzf, z_edges, slice_of, zmaxval):
+    """vol_i = int dV/dz dz from e_s to min(e_s+1, zmax_i) for the source's own slice s - the exact integral of the interpolant
+    (_interp_integral), 0 where the upper limit is not above the lower; a source without a slice gets the volume of all the
+    slices together, e_0 to min(e_S, zmax_i).  zmaxval: scalar or per source."""
+    e = np.asarray(z_edges, dtype=np.float64)
+    s = np.asarray(slice_of, dtype=np.int64)
+    has = s >= 0
+    lo = np.where(has, e[np.where(has, s, 0)], e[0])
+    hi = np.minimum(np.where(has, e[np.where(has, s, 0) + 1], e[-1]), np.broadcast_to(np.asarray(zmaxval, dtype=np.float64), s.shape))
+    ok = hi > lo
+    return np.where(ok, _interp_integral(dVdzf, lo, np.where(ok, hi, lo)), 0.0)
+
+
+def slice_weights(flux, flim, vol, pref0, alpha, fcmin):
+    """phi_i = 1 / (pref0 fleming(F_i, Flim_i, alpha, fcmin) vol_i), 0 where vol_i <= 0: lumfunc_weights' operations with a given
+    volume per source (the NumPy twin of the veff_weights kernel)."""
+    flux, vol = np.asarray(flux, dtype=np.float64), np.asarray(vol, dtype=np.float64)
+    pref = pref0 * hs.fleming(flux, flim, alpha, fcmin)
+    phi = np.zeros_like(flux)
+    ok = vol > 0
+    with np.errstate(divide="ignore"):
+        phi[ok] = 1.0 / (pref[ok] * vol[ok])
+    return phi
+
+
+def slice_bins(L, slice_of, nslice, nbin, bins="common"):
+    """The luminosity bins of the slices: (Lavg (nslice, nbin), dL (nslice,), bin_of per source, nbin = no bin).
+    bins="common": luminosity_bins of the whole catalogue for every slice, so that the slices compare bin by bin; "slice": every
+    slice its own luminosity_bins of its own sources (V.zEvolSteps), NaN centres, dL = NaN and no bins for a slice with fewer
+    than 2 sources, or whose luminosities do not reach past the first edge, 1.001 min(L)."""
+    if bins not in ("common", "slice"):
+        raise ValueError("bins must be 'common' or 'slice', not %r" % (bins,))
+    L = np.asarray(L, dtype=np.float64)
+    s = np.asarray(slice_of)
+    if bins == "common":
+        _, Lavg, dL, idx = luminosity_bins(L, nbin)
+        return np.tile(Lavg, (nslice, 1)), np.full(nslice, dL), idx.astype(np.int32)
+    Lavg, dL, idx = np.full((nslice, nbin), np.nan), np.full(nslice, np.nan), np.full(L.size, nbin, dtype=np.int32)
+    for k in range(nslice):
+        sel = s == k
+        if sel.sum() >= 2 and L[sel].max() > L[sel].min() * 1.001:
+            _, Lavg[k], dL[k], idx[sel] = luminosity_bins(L[sel], nbin)
+    return Lavg, dL, idx
+
+
+def slice_sort(slice_of, nslice):
+    """The stable counting sort by slice of the sources that have one: (order (m,), off (nslice + 1,))."""
+    s = np.asarray(slice_of, dtype=np.int64)
+    has = (s >= 0) & (s < nslice)
+    order = np.flatnonzero(has)
+    order = order[np.argsort(s[order], kind="stable")]
+    off = np.concatenate([[0], np.cumsum(np.bincount(s[has], minlength=nslice)[:nslice])]).astype(np.int64)
+    return order, off
+
+
+def slice_boot_indices(n_s, s, k, seed):
+    """The n_s draws of resample k (1 .. nboot) of slice s, source numbers within the slice: min(floor(u53(r0, r1) n_s),
+    n_s - 1), r = Philox4x32-10(counter (j, s, k, SLICES_PURPOSE), key seed) - veffs_partial's own."""
+    from . import philox
+    j = np.arange(n_s, dtype=np.uint64)
+    seed = int(seed)
+    r = philox.philox4x32(j, np.full(n_s, s, dtype=np.uint64), np.full(n_s, k, dtype=np.uint64),
+                          np.full(n_s, SLICES_PURPOSE, dtype=np.uint64), seed & philox.MASK, (seed >> 32) & philox.MASK)
+    return np.minimum((philox.u53(r[0], r[1]) * float(n_s)).astype(np.int64), n_s - 1)
+
+
+def veff_slices(phi, slice_of, nslice, bin_of, nbin, nboot=0, seed=0, boot_idx=None):
+    """NumPy twin of lf_veff_slices's sums (include/lfmcmc.h): (sums (nboot + 1, nslice, nbin), counts (nslice, nbin) int64,
+    n_slice (nslice,)).  k = 0 is the catalogue; resample k of slice s draws n_s sources of the slice (slice_boot_indices, or
+    boot_idx (nboot, m): source numbers within the slice, for the sources with a slice in slice-sorted order); every sum is one
+    np.bincount over the draws in their order."""
+    phi = np.asarray(phi, dtype=np.float64)
+    order, off = slice_sort(slice_of, nslice)
+    idx = np.asarray(bin_of, dtype=np.int64)[order].copy()
+    idx[(idx < 0) | (idx >= nbin)] = nbin                  # overflow slot, dropped below
+    w = phi[order]
+    if boot_idx is not None:
+        boot_idx = np.asarray(boot_idx, dtype=np.int64)
+        if boot_idx.shape != (nboot, order.size):
+            raise ValueError("boot_idx must be (nboot, sources with a slice)")
+    sums = np.zeros((nboot + 1, nslice, nbin))
+    counts = np.zeros((nslice, nbin), dtype=np.int64)
+    for s in range(nslice):
+        a, n_s = int(off[s]), int(off[s + 1] - off[s])
+        if n_s == 0:
+            continue
+        counts[s] = np.bincount(idx[a:a + n_s], minlength=nbin + 1)[:nbin]
+        for k in range(nboot + 1):
+            if k == 0:
+                boot = np.arange(n_s)
+            elif boot_idx is not None:
+                boot = boot_idx[k - 1, a:a + n_s]
+                if boot.min() < 0 or boot.max() >= n_s:
+                    raise ValueError("boot_idx outside its slice")
+            else:
+                boot = slice_boot_indices(n_s, s, k, seed)
+            sums[k, s] = np.bincount(idx[a + boot], weights=w[a + boot], minlength=nbin + 1)[:nbin]
+    return sums, counts, np.diff(off)
+
+
+def slice_variance(sums, dL):
+    """(lf (nslice, nbin), var (nslice, nbin)) from sums (nboot + 1, nslice, nbin) and the slices' bin widths, per slice exactly
+    as veff_device takes them: lfbin = sums[1:] / dL, ddof = 1, non-positive entries replaced by the slice's smallest positive
+    one - and left 0 where the slice has none (an empty slice, or nboot < 2)."""
+    sums = np.asarray(sums, dtype=np.float64)
+    nboot, nslice, nbin = sums.shape[0] - 1, sums.shape[1], sums.shape[2]
+    lf, var = np.zeros((nslice, nbin)), np.zeros((nslice, nbin))
+    for s in range(nslice):
+        lf[s] = sums[0, s] / dL[s]
+        if nboot < 2:
+            continue
+        lfbin = sums[1:, s] / dL[s]
+        binavg = np.average(lfbin, axis=0)
+        v = 1. / (nboot - 1) * np.sum((lfbin - binavg) ** 2, axis=0)
+        if np.any(v > 0.0):
+            v[~(v > 0.0)] = min(v[v > 0.0])
+            var[s] = v
+    return lf, var
+
+
+def _slices_run(device, L, flux, flim, vol, slice_of, nslice, sum_omega, alpha, fcmin, nboot, nbin, bins, seed, boot_idx, device_index):
+    if not 1 <= nbin <= SLICES_MAX or not 1 <= nslice <= SLICES_MAX:
+        raise ValueError("nbin and the number of slices must be between 1 and %d" % SLICES_MAX)
+    Lavg, dL, idx = slice_bins(L, slice_of, nslice, nbin, bins)
+    if seed is None:
+        seed = int(np.random.randint(0, 2 ** 31 - 1))
+    pref0 = sum_omega / hs.SQARCSEC
+    if device:
+        from . import capi
+        phi, sums, counts = capi.veff_slices(flux, flim, vol, pref0, alpha, fcmin, slice_of, nslice, idx, nbin, nboot=nboot,
+                                             boot_idx=boot_idx, seed=seed, device=device_index)
+        n_slice = np.diff(slice_sort(slice_of, nslice)[1])
+    else:
+        phi = slice_weights(flux, flim, vol, pref0, alpha, fcmin)
+        sums, counts, n_slice = veff_slices(phi, slice_of, nslice, idx, nbin, nboot=nboot, seed=seed, boot_idx=boot_idx)
+    lf, var = slice_variance(sums, dL)
+    return phi, Lavg, lf, var, counts, np.asarray(n_slice, dtype=np.int64)
+
+
+def veff_slices_host(L, flux, flim, vol, slice_of, nslice, sum_omega, alpha, fcmin, nboot=100, nbin=25, bins="common", seed=None,
+                     boot_idx=None):
+    """The sliced 1/Veff points in NumPy: (phi, Lavg (nslice, nbin), lf (nslice, nbin), var (nslice, nbin), counts, n_slice).
+    vol: the volume per source (slice_volumes); slice_of: slice_index; seed None: one draw from numpy's global state."""
+    return _slices_run(False, L, flux, flim, vol, slice_of, nslice, sum_omega, alpha, fcmin, nboot, nbin, bins, seed, boot_idx, 0)
+
+
+def veff_slices_device(L, flux, flim, vol, slice_of, nslice, sum_omega, alpha, fcmin, nboot=100, nbin=25, bins="common", seed=None,
+                       boot_idx=None, device=0):
+    """veff_slices_host on the GPU (lf_veff_slices): the weights, the binned sums and the nboot resamples of every slice in one
+    call, with a fixed order of summation - the same bits on every call.  Same arguments and results."""
+    return _slices_run(True, L, flux, flim, vol, slice_of, nslice, sum_omega, alpha, fcmin, nboot, nbin, bins, seed, boot_idx, device)
+
+
+def slice_nodes(z_edges, G):
+    """Gauss-Legendre nodes and weights of every slice: (z (S, G), w (S, G)), sum_g w_sg = e_s+1 - e_s."""
+    e = np.asarray(z_edges, dtype=np.float64)
+    x, w = np.polynomial.legendre.leggauss(int(G))
+    half, mid = 0.5 * np.diff(e), 0.5 * (e[1:] + e[:-1])
+    return mid[:, None] + half[:, None] * x[None, :], half[:, None] * w[None, :]
+
+
+def slice_model_average(values, zw):
+    """The model LF averaged over each slice in the volume measure: values (R, S, G, nbin) at the slices' nodes, zw (S, G) =
+    w_g dV/dz(z_g); returns sum_g zw_sg values[r, s, g, b] / sum_g zw_sg, (R, S, nbin)."""
+    zw = np.asarray(zw, dtype=np.float64)
+    return np.einsum("rsgb,sg->rsb", values, zw) / zw.sum(axis=1)[None, :, None]
