@@ -117,7 +117,7 @@ __device__ __forceinline__ void mock_philox(unsigned long long row_id, unsigned 
 }
 
 // NumPy's random_loggam (Stirling series), operation for operation
-__device__ inline double mock_loggam(double x) {
+__device__ __forceinline__ double mock_loggam(double x) {
 #pragma clang fp contract(off)
     const double a[10] = {8.333333333333333e-02, -2.777777777777778e-03, 7.936507936507937e-04, -5.952380952380952e-04,
                           8.417508417508418e-04, -1.917526917526918e-03, 6.410256410256410e-03, -2.955065359477124e-02,
@@ -142,8 +142,9 @@ __device__ inline double mock_loggam(double x) {
     return gl;
 }
 
-// the exact Poisson draw of the file comment; -1 for a mean the caller must refuse
-__device__ inline long long mock_poisson(double mu, unsigned long long row_id, int f, unsigned long long seed) {
+// the exact Poisson draw of the file comment; -1 for a mean the caller must refuse.  Forced inline, as mock_loggam: it has two
+// callers (lf_mock_total; lf_mock_count_cut of lf_mock_cut.h), and each keeps the instructions it had as the only one
+__device__ __forceinline__ long long mock_poisson(double mu, unsigned long long row_id, int f, unsigned long long seed) {
 #pragma clang fp contract(off)
     if (!(mu >= 0.0) || !(mu <= MOCK_MAX_MEAN)) return -1;      // (NaN fails both)
     if (mu == 0.0) return 0;

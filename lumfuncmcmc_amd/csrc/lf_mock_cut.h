@@ -38,69 +38,6 @@ struct MockCut {
     unsigned int stream;      // 0: piece "above"; MOCK_CUT_BAND: piece "below"
 };
 
-// lf_mock.h's mock_loggam and mock_poisson, statement for statement, for the band's count.  Copies, not calls: with a second
-// caller the compiler no longer inlines mock_poisson into lf_mock_total, whose code would change; f carries MOCK_CUT_BAND.
-__device__ inline double mock_cut_loggam(double x) {
-#pragma clang fp contract(off)
-    const double a[10] = {8.333333333333333e-02, -2.777777777777778e-03, 7.936507936507937e-04, -5.952380952380952e-04,
-                          8.417508417508418e-04, -1.917526917526918e-03, 6.410256410256410e-03, -2.955065359477124e-02,
-                          1.796443723688307e-01, -1.39243221690590e+00};
-    if (x == 1.0 || x == 2.0) return 0.0;
-    long long n = 0;
-    if (x < 7.0) n = (long long)(7 - x);
-    double x0 = x + (double)n;
-    const double x2 = (1.0 / x0) * (1.0 / x0);
-    const double lg2pi = 1.8378770664093453e+00;
-    double gl0 = a[9];
-    for (int k = 8; k >= 0; --k) {
-        gl0 *= x2;
-        gl0 += a[k];
-    }
-    double gl = gl0 / x0 + 0.5 * lg2pi + (x0 - 0.5) * log(x0) - x0;
-    if (x < 7.0)
-        for (long long k = 1; k <= n; ++k) {
-            gl -= log(x0 - 1.0);
-            x0 -= 1.0;
-        }
-    return gl;
-}
-
-__device__ inline long long mock_cut_poisson(double mu, unsigned long long row_id, int f, unsigned long long seed) {
-#pragma clang fp contract(off)
-    if (!(mu >= 0.0) || !(mu <= MOCK_MAX_MEAN)) return -1;      // (NaN fails both)
-    if (mu == 0.0) return 0;
-    unsigned int r[4];
-    if (mu < 10.0) {
-        mock_philox(row_id, 0u, 0u, f, seed, r);
-        const double u = u53(r[0], r[1]);
-        double p = exp(-mu), F = p;
-        long long k = 0;
-        while (u > F) {
-            ++k;
-            p *= mu / (double)k;
-            if (p == 0.0) break;               // the tail is exhausted: F stays below u only by rounding
-            F += p;
-        }
-        return k;
-    }
-    const double slam = sqrt(mu), loglam = log(mu);
-    const double b = 0.931 + 2.53 * slam;
-    const double a = -0.059 + 0.02483 * b;
-    const double invalpha = 1.1239 + 1.1328 / (b - 3.4);
-    const double vr = 0.9277 - 3.6224 / (b - 2.0);
-    for (unsigned int round = 0;; ++round) {
-        mock_philox(row_id, round, 0u, f, seed, r);
-        const double U = u53(r[0], r[1]) - 0.5;
-        const double V = u53(r[2], r[3]);
-        const double us = 0.5 - fabs(U);
-        const long long k = (long long)floor((2.0 * a / us + b) * U + mu + 0.43);
-        if (us >= 0.07 && V <= vr) return k;
-        if (k < 0 || (us < 0.013 && V > us)) continue;
-        if ((log(V) + log(invalpha) - log(a / (us * us) + b)) <= (-mu + (double)k * loglam - mock_cut_loggam((double)(k + 1))))
-            return k;
-    }
-}
-
 // candidate i of (row, field) rf of one piece: true draw, observation, cut
 __device__ __forceinline__ bool mock_cut_candidate(const MockConst& mc, const MockCut& ct, const double* __restrict__ ld2n,
                                                    const double* __restrict__ nodes, const double* __restrict__ sig, int M, int rf,
@@ -123,7 +60,7 @@ __global__ __launch_bounds__(MOCK_THREADS) void lf_mock_count_cut(int nrf, int n
     const int rf = blockIdx.x * MOCK_THREADS + threadIdx.x;
     if (rf >= nrf) return;
     const int row = rf / nf, f = rf - row * nf;
-    count[rf] = mock_cut_poisson(mean[rf], (unsigned long long)row_ids[row], f | (int)MOCK_CUT_BAND, seed);
+    count[rf] = mock_poisson(mean[rf], (unsigned long long)row_ids[row], f | (int)MOCK_CUT_BAND, seed);
 }
 
 // off: [nrf + 1] this piece's candidates of rf are [off[rf], off[rf + 1]); dst: [nrf] their first slot in the outputs

@@ -3486,8 +3486,10 @@ int mock_fail(lf_mock* m, const char* fn, const std::string& msg) {
     return LF_ERR_ARG;
 }
 
-// the arguments every call shares; row r's theta must be finite
-int mock_check(lf_mock* m, const char* fn, const double* theta, int32_t R) {
+enum MockNeeds { MOCK_NEEDS_NOTHING, MOCK_NEEDS_MODEL, MOCK_NEEDS_BAND };      // what a process needs set: sections 3.23, 3.32
+
+// the arguments every call shares, in the order every call refuses them; row r's theta must be finite
+int mock_check(lf_mock* m, const char* fn, const double* theta, int32_t R, MockNeeds needs = MOCK_NEEDS_NOTHING) {
     if (R <= 0) return mock_fail(m, fn, "R must be >= 1");
     if (!theta) return mock_fail(m, fn, "theta is NULL");
     const int nd = m->mc.ndim;
@@ -3496,36 +3498,209 @@ int mock_check(lf_mock* m, const char* fn, const double* theta, int32_t R) {
             if (!std::isfinite(theta[(size_t)r * nd + d]))
                 return mock_fail(m, fn, "row " + std::to_string(r) + ": theta is not finite");
     m->err.clear();
+    if (needs >= MOCK_NEEDS_MODEL && m->mn.M == 0) return mock_fail(m, fn, "no error model is set (lf_mock_set_error_model)");
+    if (needs >= MOCK_NEEDS_BAND && !m->band)
+        return mock_fail(m, fn, "no cut band is set (lf_mock_set_cut_band, after lf_mock_set_error_model)");
     return LF_OK;
 }
 
-// masses, cumulative sums, means and counts of rows r0 .. r0 + n - 1 (device), means / counts copied to the host
-int mock_masses(lf_mock* m, const char* fn, const double* theta, int32_t r0, int n, const int64_t* row_ids, uint64_t seed,
+int mock_edges_ok(lf_mock* m, const char* fn, const char* name, int32_t n, const double* e) {
+    for (int i = 0; i <= n; ++i)
+        if (!std::isfinite(e[i]) || (i > 0 && !(e[i] >= e[i - 1])))
+            return mock_fail(m, fn, std::string(name) + " must be finite and non-decreasing");
+    return LF_OK;
+}
+
+// the caller's counts [R nf], each in 0 .. 2^32 - 1; *total: their sum
+int mock_counts_ok(lf_mock* m, const char* fn, const int64_t* count, int32_t R, int64_t* total) {
+    const int nf = m->mc.nf;
+    *total = 0;
+    for (int64_t i = 0; i < (int64_t)R * nf; ++i) {
+        if (count[i] < 0 || count[i] > (int64_t)UINT32_MAX)
+            return mock_fail(m, fn, "row " + std::to_string(i / nf) + " field " + std::to_string(i % nf) + ": count out of range");
+        *total += count[i];
+    }
+    return LF_OK;
+}
+
+// One piece of a mock process: what its kernels read, and where a chunk's cumulative sums, means, counts and offsets are.
+// Piece 0 is the process on the integration grid (piece "above" of the cut process), piece 1 the band's (piece "below").
+struct MockPiece {
+    const lf::MockConst& mc;
+    double *cdfL, *colm, *cdfZ, *mean;
+    long long *count, *off;
+    lf::MockCut ct;
+};
+
+MockPiece mock_piece(lf_mock* m, int piece) {
+    if (piece) return {m->mcb, m->d_cdfLb, m->d_colmb, m->d_cdfZb, m->d_meanb, m->d_countb, m->d_offb, {m->d_grid[0], lf::MOCK_CUT_BAND}};
+    return {m->mc, m->d_cdfL, m->d_colm, m->d_cdfZ, m->d_mean, m->d_count, m->d_off, {m->d_grid[0], 0u}};
+}
+
+// masses, cumulative sums, means and counts of one piece for the n rows from r0 that are on the device, means and counts
+// copied to the host; the band draws its counts from its own Poisson stream; a refused mean ends with `suffix`
+int mock_masses(lf_mock* m, const char* fn, const MockPiece& p, const char* suffix, int32_t r0, int n, uint64_t seed,
                 std::vector<double>& mean, std::vector<long long>& count) {
-    const int nf = m->mc.nf, S = m->mc.S, nd = m->mc.ndim;
+    const int nf = m->mc.nf, S = m->mc.S, nrf = n * nf;
+    hipLaunchKernelGGL(lf::lf_mock_mass, dim3((unsigned)S, (unsigned)nrf), dim3(lf::MOCK_THREADS), 0, 0, p.mc, m->d_theta, p.cdfL, p.colm);
+    LF_HIP(m, hipGetLastError());
+    hipLaunchKernelGGL(lf::lf_mock_total, dim3((unsigned)nrf), dim3(lf::MOCK_THREADS), 0, 0, S, nf, p.colm, m->d_rid,
+                       (unsigned long long)seed, p.cdfZ, p.mean, p.count);
+    LF_HIP(m, hipGetLastError());
+    if (p.ct.stream) {
+        hipLaunchKernelGGL(lf::lf_mock_count_cut, dim3((unsigned)((nrf + lf::MOCK_THREADS - 1) / lf::MOCK_THREADS)), dim3(lf::MOCK_THREADS),
+                           0, 0, nrf, nf, p.mean, m->d_rid, (unsigned long long)seed, p.count);
+        LF_HIP(m, hipGetLastError());
+    }
+    mean.resize((size_t)nrf);
+    count.resize((size_t)nrf);
+    LF_HIP(m, hipMemcpy(mean.data(), p.mean, (size_t)nrf * sizeof(double), hipMemcpyDeviceToHost));
+    LF_HIP(m, hipMemcpy(count.data(), p.count, (size_t)nrf * sizeof(long long), hipMemcpyDeviceToHost));
+    for (int i = 0; i < nrf; ++i)
+        if (count[(size_t)i] < 0) {
+            char b[200];
+            std::snprintf(b, sizeof b, "row %d field %d: expected count %.17g is not finite, negative or above 2^31%s", r0 + i / nf, i % nf,
+                          mean[(size_t)i], suffix);
+            return mock_fail(m, fn, b);
+        }
+    return LF_OK;
+}
+
+// rows r0 .. r0 + n - 1 to the device, then mock_masses of the process's pieces: one, or the cut process's two - "above" is
+// refused before "below" is launched, and a refused mean names its piece
+int mock_chunk(lf_mock* m, const char* fn, int npiece, const double* theta, int32_t r0, int n, const int64_t* row_ids, uint64_t seed,
+               std::vector<double> (&mean)[2], std::vector<long long> (&count)[2]) {
+    const int nd = m->mc.ndim;
     std::vector<long long> rid((size_t)n);
     for (int i = 0; i < n; ++i) rid[(size_t)i] = row_ids ? (long long)row_ids[r0 + i] : (long long)(r0 + i);
     LF_HIP(m, hipMemcpy(m->d_theta, theta + (size_t)r0 * nd, (size_t)n * nd * sizeof(double), hipMemcpyHostToDevice));
     LF_HIP(m, hipMemcpy(m->d_rid, rid.data(), (size_t)n * sizeof(long long), hipMemcpyHostToDevice));
-    const int nrf = n * nf;
-    hipLaunchKernelGGL(lf::lf_mock_mass, dim3((unsigned)S, (unsigned)nrf), dim3(lf::MOCK_THREADS), 0, 0, m->mc, m->d_theta, m->d_cdfL,
-                       m->d_colm);
-    LF_HIP(m, hipGetLastError());
-    hipLaunchKernelGGL(lf::lf_mock_total, dim3((unsigned)nrf), dim3(lf::MOCK_THREADS), 0, 0, S, nf, m->d_colm, m->d_rid,
-                       (unsigned long long)seed, m->d_cdfZ, m->d_mean, m->d_count);
-    LF_HIP(m, hipGetLastError());
-    mean.resize((size_t)nrf);
-    count.resize((size_t)nrf);
-    LF_HIP(m, hipMemcpy(mean.data(), m->d_mean, (size_t)nrf * sizeof(double), hipMemcpyDeviceToHost));
-    LF_HIP(m, hipMemcpy(count.data(), m->d_count, (size_t)nrf * sizeof(long long), hipMemcpyDeviceToHost));
-    for (int i = 0; i < nrf; ++i)
-        if (count[(size_t)i] < 0) {
-            char b[160];
-            std::snprintf(b, sizeof b, "row %d field %d: expected count %.17g is not finite, negative or above 2^31", r0 + i / nf, i % nf,
-                          mean[(size_t)i]);
-            return mock_fail(m, fn, b);
-        }
+    static const char* const suffix[2] = {" (piece \"above\")", " (piece \"below\")"};
+    for (int piece = 0; piece < npiece; ++piece) {
+        const int rc = mock_masses(m, fn, mock_piece(m, piece), npiece == 2 ? suffix[piece] : "", r0, n, seed, mean[piece], count[piece]);
+        if (rc != LF_OK) return rc;
+    }
     return LF_OK;
+}
+
+// every buffer that holds fewer than n elements is replaced by one of n (each by its own size: after a failed allocation the
+// empty one is made again)
+int mock_grow(lf_mock*, size_t) { return LF_OK; }
+template <typename T, typename... Rest>
+int mock_grow(lf_mock* m, size_t n, Buf<T>& b, Rest&... rest) {
+    const int rc = n > b.size() ? grow(m, b, n, false) : LF_OK;
+    return rc != LF_OK ? rc : mock_grow(m, n, rest...);
+}
+
+// mock_fetch(m, n, host, buffer, host, buffer, ...): the first n elements of every buffer to its host array
+int mock_fetch(lf_mock*, size_t) { return LF_OK; }
+template <typename H, typename T, typename... Rest>
+int mock_fetch(lf_mock* m, size_t n, H* host, const Buf<T>& b, Rest&&... rest) {
+    static_assert(sizeof(H) == sizeof(T), "host and device element sizes differ");
+    LF_HIP(m, hipMemcpy(host, b, n * sizeof(T), hipMemcpyDeviceToHost));
+    return mock_fetch(m, n, rest...);
+}
+
+// lf_mock_draw (noisy = false: logL_obs and sigma are not used) and lf_mock_draw_err
+int mock_draw(lf_mock* m, const char* fn, bool noisy, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed,
+              const int64_t* count, double* z, double* logL, double* logL_obs, double* sigma, int32_t* field) {
+    if (!m) return LF_ERR_ARG;
+    int rc = mock_check(m, fn, theta, R, noisy ? MOCK_NEEDS_MODEL : MOCK_NEEDS_NOTHING);
+    if (rc != LF_OK) return rc;
+    if (!count) return mock_fail(m, fn, "count is NULL");
+    int64_t total;
+    if ((rc = mock_counts_ok(m, fn, count, R, &total)) != LF_OK) return rc;
+    if (total > 0 && (!z || !logL || !field || (noisy && (!logL_obs || !sigma))))
+        return mock_fail(m, fn, noisy ? "z, logL_true, logL_obs, sigma or field is NULL" : "z, logL or field is NULL");
+    LF_HIP(m, hipSetDevice(m->device));
+    const int nf = m->mc.nf;
+    std::vector<double> mu[2];
+    std::vector<long long> n[2], off;
+    int64_t done = 0;
+    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
+        const int rows = std::min<int32_t>(m->rch, R - r0);
+        const int nrf = rows * nf;
+        off.assign((size_t)nrf + 1, 0);
+        for (int i = 0; i < nrf; ++i) off[(size_t)i + 1] = off[(size_t)i] + count[(size_t)r0 * nf + i];
+        const int64_t tot = off[(size_t)nrf];
+        if (tot == 0) continue;
+        if ((rc = mock_chunk(m, fn, 1, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
+        rc = noisy ? mock_grow(m, (size_t)tot, m->d_z, m->d_L, m->d_Lobs, m->d_sg, m->d_fld)
+                   : mock_grow(m, (size_t)tot, m->d_z, m->d_L, m->d_fld);
+        if (rc != LF_OK) return rc;
+        LF_HIP(m, hipMemcpy(m->d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice));
+        const dim3 grid((unsigned)((tot + lf::MOCK_THREADS - 1) / lf::MOCK_THREADS)), block(lf::MOCK_THREADS);
+        if (noisy)
+            hipLaunchKernelGGL(lf::lf_mock_draw_err, grid, block, 0, 0, m->mc, m->mn, nrf, m->d_off, m->d_rid, (unsigned long long)seed,
+                               m->d_cdfL, m->d_cdfZ, m->d_z, m->d_L, m->d_Lobs, m->d_sg, m->d_fld);
+        else
+            hipLaunchKernelGGL(lf::lf_mock_draw, grid, block, 0, 0, m->mc, nrf, m->d_off, m->d_rid, (unsigned long long)seed, m->d_cdfL,
+                               m->d_cdfZ, m->d_z, m->d_L, m->d_fld);
+        LF_HIP(m, hipGetLastError());
+        rc = noisy ? mock_fetch(m, (size_t)tot, z + done, m->d_z, logL + done, m->d_L, logL_obs + done, m->d_Lobs, sigma + done, m->d_sg,
+                                field + done, m->d_fld)
+                   : mock_fetch(m, (size_t)tot, z + done, m->d_z, logL + done, m->d_L, field + done, m->d_fld);
+        if (rc != LF_OK) return rc;
+        done += tot;
+    }
+    return LF_OK;
+}
+
+// The loop of the six histogram entries, after their checks and the upload of their edges: per chunk of rows the masses of
+// the process's npiece pieces, the caller's counts in the place of the Poisson draws (count: NULL = keep those), d_hist (ns
+// slots per (row, field)) and, with `kept`, d_kept zeroed, per piece the prefix sums of its workgroups and one launch, then
+// hist and kept copied out.  launch(piece view, nrf, grid) starts the entry's kernel: the piece's `off` holds the prefix sums.
+template <typename Launch>
+int mock_binned(lf_mock* m, const char* fn, int npiece, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed,
+                const int64_t* count, int64_t ns, int64_t* hist, int64_t* kept, Launch launch) {
+    int rc;
+    const int nf = m->mc.nf;
+    std::vector<double> mu[2];
+    std::vector<long long> n[2], blk;
+    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
+        const int rows = std::min<int32_t>(m->rch, R - r0);
+        const int nrf = rows * nf;
+        if ((rc = mock_chunk(m, fn, npiece, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
+        if (count) {          // the caller's counts take the place of the Poisson draws lf_mock_total left on the device
+            for (int i = 0; i < nrf; ++i) n[0][(size_t)i] = (long long)count[(size_t)r0 * nf + i];
+            LF_HIP(m, hipMemcpy(m->d_count, n[0].data(), (size_t)nrf * sizeof(long long), hipMemcpyHostToDevice));
+        }
+        if ((rc = mock_grow(m, (size_t)nrf * ns, m->d_hist)) != LF_OK) return rc;
+        LF_HIP(m, hipMemset(m->d_hist, 0, (size_t)nrf * ns * sizeof(unsigned long long)));
+        if (kept) LF_HIP(m, hipMemset(m->d_kept, 0, (size_t)nrf * sizeof(unsigned long long)));
+        for (int piece = 0; piece < npiece; ++piece) {
+            blk.assign((size_t)nrf + 1, 0);
+            for (int i = 0; i < nrf; ++i)
+                blk[(size_t)i + 1] = blk[(size_t)i] + (n[piece][(size_t)i] + lf::MOCK_HIST_CHUNK - 1) / lf::MOCK_HIST_CHUNK;
+            const long long nblk = blk[(size_t)nrf];
+            if (nblk == 0) continue;
+            if (nblk > (long long)INT32_MAX) return mock_fail(m, fn, "too many sources for one launch: pass fewer rows per call");
+            const MockPiece p = mock_piece(m, piece);
+            LF_HIP(m, hipMemcpy(p.off, blk.data(), blk.size() * sizeof(long long), hipMemcpyHostToDevice));
+            launch(p, nrf, dim3((unsigned)nblk));
+            LF_HIP(m, hipGetLastError());
+        }
+        if ((rc = mock_fetch(m, (size_t)nrf * ns, hist + (size_t)r0 * nf * ns, m->d_hist)) != LF_OK) return rc;
+        if (kept && (rc = mock_fetch(m, (size_t)nrf, kept + (size_t)r0 * nf, m->d_kept)) != LF_OK) return rc;
+    }
+    return LF_OK;
+}
+
+// The three histograms in luminosity alone: their checks, the edges to the device, then mock_binned.  needs == MOCK_NEEDS_BAND
+// is the cut process: two pieces, and `kept` is an output
+template <typename Launch>
+int mock_hist1(lf_mock* m, const char* fn, MockNeeds needs, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed,
+               int32_t nbins, const double* edges, int64_t* hist, int64_t* kept, Launch launch) {
+    if (!m) return LF_ERR_ARG;
+    const bool cut = needs == MOCK_NEEDS_BAND;
+    int rc = mock_check(m, fn, theta, R, needs);
+    if (rc != LF_OK) return rc;
+    if (nbins < 1 || nbins > lf::MOCK_MAX_BINS) return mock_fail(m, fn, "nbins must be in 1.." + std::to_string(lf::MOCK_MAX_BINS));
+    if (!edges || !hist || (cut && !kept)) return mock_fail(m, fn, cut ? "edges, hist or kept is NULL" : "edges or hist is NULL");
+    if ((rc = mock_edges_ok(m, fn, "edges", nbins, edges)) != LF_OK) return rc;
+    LF_HIP(m, hipSetDevice(m->device));
+    LF_HIP(m, hipMemcpy(m->d_edges, edges, (size_t)(nbins + 1) * sizeof(double), hipMemcpyHostToDevice));
+    return mock_binned(m, fn, cut ? 2 : 1, theta, R, row_ids, seed, nullptr, nbins + 2, hist, kept, launch);
 }
 
 }  // namespace
@@ -3615,14 +3790,14 @@ int lf_mock_counts(lf_mock* m, const double* theta, int32_t R, const int64_t* ro
     if (!mean || !count) return mock_fail(m, fn, "mean or count is NULL");
     LF_HIP(m, hipSetDevice(m->device));
     const int nf = m->mc.nf;
-    std::vector<double> mu;
-    std::vector<long long> n;
+    std::vector<double> mu[2];
+    std::vector<long long> n[2];
     for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
         const int rows = std::min<int32_t>(m->rch, R - r0);
-        if ((rc = mock_masses(m, fn, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
-        for (size_t i = 0; i < mu.size(); ++i) {
-            mean[(size_t)r0 * nf + i] = mu[i];
-            count[(size_t)r0 * nf + i] = n[i];
+        if ((rc = mock_chunk(m, fn, 1, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
+        for (size_t i = 0; i < mu[0].size(); ++i) {
+            mean[(size_t)r0 * nf + i] = mu[0][i];
+            count[(size_t)r0 * nf + i] = n[0][i];
         }
     }
     return LF_OK;
@@ -3630,81 +3805,16 @@ int lf_mock_counts(lf_mock* m, const double* theta, int32_t R, const int64_t* ro
 
 int lf_mock_draw(lf_mock* m, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed, const int64_t* count, double* z,
                  double* logL, int32_t* field) {
-    static const char* fn = "lf_mock_draw";
-    if (!m) return LF_ERR_ARG;
-    int rc = mock_check(m, fn, theta, R);
-    if (rc != LF_OK) return rc;
-    if (!count) return mock_fail(m, fn, "count is NULL");
-    const int nf = m->mc.nf;
-    int64_t total = 0;
-    for (int64_t i = 0; i < (int64_t)R * nf; ++i) {
-        if (count[i] < 0 || count[i] > (int64_t)UINT32_MAX)
-            return mock_fail(m, fn, "row " + std::to_string(i / nf) + " field " + std::to_string(i % nf) + ": count out of range");
-        total += count[i];
-    }
-    if (total > 0 && (!z || !logL || !field)) return mock_fail(m, fn, "z, logL or field is NULL");
-    LF_HIP(m, hipSetDevice(m->device));
-    std::vector<double> mu;
-    std::vector<long long> n, off;
-    int64_t done = 0;
-    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
-        const int rows = std::min<int32_t>(m->rch, R - r0);
-        const int nrf = rows * nf;
-        off.assign((size_t)nrf + 1, 0);
-        for (int i = 0; i < nrf; ++i) off[(size_t)i + 1] = off[(size_t)i] + count[(size_t)r0 * nf + i];
-        const int64_t tot = off[(size_t)nrf];
-        if (tot == 0) continue;
-        if ((rc = mock_masses(m, fn, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
-        // (each by its own size: after a failed allocation the empty one is made again)
-        if ((size_t)tot > m->d_z.size() && (rc = grow(m, m->d_z, (size_t)tot, false)) != LF_OK) return rc;
-        if ((size_t)tot > m->d_L.size() && (rc = grow(m, m->d_L, (size_t)tot, false)) != LF_OK) return rc;
-        if ((size_t)tot > m->d_fld.size() && (rc = grow(m, m->d_fld, (size_t)tot, false)) != LF_OK) return rc;
-        LF_HIP(m, hipMemcpy(m->d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(lf::lf_mock_draw, dim3((unsigned)((tot + lf::MOCK_THREADS - 1) / lf::MOCK_THREADS)), dim3(lf::MOCK_THREADS), 0, 0,
-                           m->mc, nrf, m->d_off, m->d_rid, (unsigned long long)seed, m->d_cdfL, m->d_cdfZ, m->d_z, m->d_L, m->d_fld);
-        LF_HIP(m, hipGetLastError());
-        LF_HIP(m, hipMemcpy(z + done, m->d_z, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
-        LF_HIP(m, hipMemcpy(logL + done, m->d_L, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
-        LF_HIP(m, hipMemcpy(field + done, m->d_fld, (size_t)tot * sizeof(int), hipMemcpyDeviceToHost));
-        done += tot;
-    }
-    return LF_OK;
+    return mock_draw(m, "lf_mock_draw", false, theta, R, row_ids, seed, count, z, logL, nullptr, nullptr, field);
 }
 
 int lf_mock_hist(lf_mock* m, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed, int32_t nbins, const double* edges,
                  int64_t* hist) {
-    static const char* fn = "lf_mock_hist";
-    if (!m) return LF_ERR_ARG;
-    int rc = mock_check(m, fn, theta, R);
-    if (rc != LF_OK) return rc;
-    if (nbins < 1 || nbins > lf::MOCK_MAX_BINS)
-        return mock_fail(m, fn, "nbins must be in 1.." + std::to_string(lf::MOCK_MAX_BINS));
-    if (!edges || !hist) return mock_fail(m, fn, "edges or hist is NULL");
-    for (int i = 0; i <= nbins; ++i)
-        if (!std::isfinite(edges[i]) || (i > 0 && !(edges[i] >= edges[i - 1])))
-            return mock_fail(m, fn, "edges must be finite and non-decreasing");
-    LF_HIP(m, hipSetDevice(m->device));
-    LF_HIP(m, hipMemcpy(m->d_edges, edges, (size_t)(nbins + 1) * sizeof(double), hipMemcpyHostToDevice));
-    const int nf = m->mc.nf, ns = nbins + 2;
-    std::vector<double> mu;
-    std::vector<long long> n, blk;
-    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
-        const int rows = std::min<int32_t>(m->rch, R - r0);
-        const int nrf = rows * nf;
-        if ((rc = mock_masses(m, fn, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
-        if ((size_t)nrf * ns > m->d_hist.size() && (rc = grow(m, m->d_hist, (size_t)nrf * ns, false)) != LF_OK) return rc;
-        blk.assign((size_t)nrf + 1, 0);
-        for (int i = 0; i < nrf; ++i) blk[(size_t)i + 1] = blk[(size_t)i] + (n[(size_t)i] + lf::MOCK_HIST_CHUNK - 1) / lf::MOCK_HIST_CHUNK;
-        LF_HIP(m, hipMemset(m->d_hist, 0, (size_t)nrf * ns * sizeof(unsigned long long)));
-        if (blk[(size_t)nrf] > 0) {
-            LF_HIP(m, hipMemcpy(m->d_off, blk.data(), blk.size() * sizeof(long long), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(lf::lf_mock_hist, dim3((unsigned)blk[(size_t)nrf]), dim3(lf::MOCK_THREADS), 0, 0, m->mc, nrf, m->d_off,
-                               m->d_count, m->d_rid, (unsigned long long)seed, m->d_cdfL, m->d_cdfZ, nbins, m->d_edges, m->d_hist);
-            LF_HIP(m, hipGetLastError());
-        }
-        LF_HIP(m, hipMemcpy(hist + (size_t)r0 * nf * ns, m->d_hist, (size_t)nrf * ns * sizeof(int64_t), hipMemcpyDeviceToHost));
-    }
-    return LF_OK;
+    auto launch = [&](const MockPiece& p, int nrf, dim3 grid) {
+        hipLaunchKernelGGL(lf::lf_mock_hist, grid, dim3(lf::MOCK_THREADS), 0, 0, p.mc, nrf, p.off, p.count, m->d_rid,
+                           (unsigned long long)seed, p.cdfL, p.cdfZ, nbins, m->d_edges, m->d_hist);
+    };
+    return mock_hist1(m, "lf_mock_hist", MOCK_NEEDS_NOTHING, theta, R, row_ids, seed, nbins, edges, hist, nullptr, launch);
 }
 
 // The error model of the observation step (csrc/lf_mock_noise.h).
@@ -3749,88 +3859,16 @@ int lf_mock_set_error_model(lf_mock* m, int32_t M, const double* logf_nodes, con
 
 int lf_mock_draw_err(lf_mock* m, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed, const int64_t* count, double* z,
                      double* logL_true, double* logL_obs, double* sigma, int32_t* field) {
-    static const char* fn = "lf_mock_draw_err";
-    if (!m) return LF_ERR_ARG;
-    int rc = mock_check(m, fn, theta, R);
-    if (rc != LF_OK) return rc;
-    if (m->mn.M == 0) return mock_fail(m, fn, "no error model is set (lf_mock_set_error_model)");
-    if (!count) return mock_fail(m, fn, "count is NULL");
-    const int nf = m->mc.nf;
-    int64_t total = 0;
-    for (int64_t i = 0; i < (int64_t)R * nf; ++i) {
-        if (count[i] < 0 || count[i] > (int64_t)UINT32_MAX)
-            return mock_fail(m, fn, "row " + std::to_string(i / nf) + " field " + std::to_string(i % nf) + ": count out of range");
-        total += count[i];
-    }
-    if (total > 0 && (!z || !logL_true || !logL_obs || !sigma || !field))
-        return mock_fail(m, fn, "z, logL_true, logL_obs, sigma or field is NULL");
-    LF_HIP(m, hipSetDevice(m->device));
-    std::vector<double> mu;
-    std::vector<long long> n, off;
-    int64_t done = 0;
-    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
-        const int rows = std::min<int32_t>(m->rch, R - r0);
-        const int nrf = rows * nf;
-        off.assign((size_t)nrf + 1, 0);
-        for (int i = 0; i < nrf; ++i) off[(size_t)i + 1] = off[(size_t)i] + count[(size_t)r0 * nf + i];
-        const int64_t tot = off[(size_t)nrf];
-        if (tot == 0) continue;
-        if ((rc = mock_masses(m, fn, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
-        if ((size_t)tot > m->d_z.size() && (rc = grow(m, m->d_z, (size_t)tot, false)) != LF_OK) return rc;
-        if ((size_t)tot > m->d_L.size() && (rc = grow(m, m->d_L, (size_t)tot, false)) != LF_OK) return rc;
-        if ((size_t)tot > m->d_Lobs.size() && (rc = grow(m, m->d_Lobs, (size_t)tot, false)) != LF_OK) return rc;
-        if ((size_t)tot > m->d_sg.size() && (rc = grow(m, m->d_sg, (size_t)tot, false)) != LF_OK) return rc;
-        if ((size_t)tot > m->d_fld.size() && (rc = grow(m, m->d_fld, (size_t)tot, false)) != LF_OK) return rc;
-        LF_HIP(m, hipMemcpy(m->d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(lf::lf_mock_draw_err, dim3((unsigned)((tot + lf::MOCK_THREADS - 1) / lf::MOCK_THREADS)), dim3(lf::MOCK_THREADS), 0,
-                           0, m->mc, m->mn, nrf, m->d_off, m->d_rid, (unsigned long long)seed, m->d_cdfL, m->d_cdfZ, m->d_z, m->d_L, m->d_Lobs,
-                           m->d_sg, m->d_fld);
-        LF_HIP(m, hipGetLastError());
-        LF_HIP(m, hipMemcpy(z + done, m->d_z, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
-        LF_HIP(m, hipMemcpy(logL_true + done, m->d_L, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
-        LF_HIP(m, hipMemcpy(logL_obs + done, m->d_Lobs, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
-        LF_HIP(m, hipMemcpy(sigma + done, m->d_sg, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
-        LF_HIP(m, hipMemcpy(field + done, m->d_fld, (size_t)tot * sizeof(int), hipMemcpyDeviceToHost));
-        done += tot;
-    }
-    return LF_OK;
+    return mock_draw(m, "lf_mock_draw_err", true, theta, R, row_ids, seed, count, z, logL_true, logL_obs, sigma, field);
 }
 
 int lf_mock_hist_err(lf_mock* m, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed, int32_t nbins,
                      const double* edges, int64_t* hist) {
-    static const char* fn = "lf_mock_hist_err";
-    if (!m) return LF_ERR_ARG;
-    int rc = mock_check(m, fn, theta, R);
-    if (rc != LF_OK) return rc;
-    if (m->mn.M == 0) return mock_fail(m, fn, "no error model is set (lf_mock_set_error_model)");
-    if (nbins < 1 || nbins > lf::MOCK_MAX_BINS)
-        return mock_fail(m, fn, "nbins must be in 1.." + std::to_string(lf::MOCK_MAX_BINS));
-    if (!edges || !hist) return mock_fail(m, fn, "edges or hist is NULL");
-    for (int i = 0; i <= nbins; ++i)
-        if (!std::isfinite(edges[i]) || (i > 0 && !(edges[i] >= edges[i - 1])))
-            return mock_fail(m, fn, "edges must be finite and non-decreasing");
-    LF_HIP(m, hipSetDevice(m->device));
-    LF_HIP(m, hipMemcpy(m->d_edges, edges, (size_t)(nbins + 1) * sizeof(double), hipMemcpyHostToDevice));
-    const int nf = m->mc.nf, ns = nbins + 2;
-    std::vector<double> mu;
-    std::vector<long long> n, blk;
-    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
-        const int rows = std::min<int32_t>(m->rch, R - r0);
-        const int nrf = rows * nf;
-        if ((rc = mock_masses(m, fn, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
-        if ((size_t)nrf * ns > m->d_hist.size() && (rc = grow(m, m->d_hist, (size_t)nrf * ns, false)) != LF_OK) return rc;
-        blk.assign((size_t)nrf + 1, 0);
-        for (int i = 0; i < nrf; ++i) blk[(size_t)i + 1] = blk[(size_t)i] + (n[(size_t)i] + lf::MOCK_HIST_CHUNK - 1) / lf::MOCK_HIST_CHUNK;
-        LF_HIP(m, hipMemset(m->d_hist, 0, (size_t)nrf * ns * sizeof(unsigned long long)));
-        if (blk[(size_t)nrf] > 0) {
-            LF_HIP(m, hipMemcpy(m->d_off, blk.data(), blk.size() * sizeof(long long), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(lf::lf_mock_hist_err, dim3((unsigned)blk[(size_t)nrf]), dim3(lf::MOCK_THREADS), 0, 0, m->mc, m->mn, nrf,
-                               m->d_off, m->d_count, m->d_rid, (unsigned long long)seed, m->d_cdfL, m->d_cdfZ, nbins, m->d_edges, m->d_hist);
-            LF_HIP(m, hipGetLastError());
-        }
-        LF_HIP(m, hipMemcpy(hist + (size_t)r0 * nf * ns, m->d_hist, (size_t)nrf * ns * sizeof(int64_t), hipMemcpyDeviceToHost));
-    }
-    return LF_OK;
+    auto launch = [&](const MockPiece& p, int nrf, dim3 grid) {
+        hipLaunchKernelGGL(lf::lf_mock_hist_err, grid, dim3(lf::MOCK_THREADS), 0, 0, p.mc, m->mn, nrf, p.off, p.count, m->d_rid,
+                           (unsigned long long)seed, p.cdfL, p.cdfZ, nbins, m->d_edges, m->d_hist);
+    };
+    return mock_hist1(m, "lf_mock_hist_err", MOCK_NEEDS_MODEL, theta, R, row_ids, seed, nbins, edges, hist, nullptr, launch);
 }
 
 }  // extern "C"
@@ -3838,47 +3876,6 @@ int lf_mock_hist_err(lf_mock* m, const double* theta, int32_t R, const int64_t* 
 // ------------------------------------------------------------------------------------------------------------------------
 // Mock catalogues of the cut process (csrc/lf_mock_cut.h)
 // ------------------------------------------------------------------------------------------------------------------------
-namespace {
-
-// both pieces' masses, cumulative sums, means and counts of rows r0 .. r0 + n - 1: mock_masses for piece "above", the same
-// two kernels on the band grid plus the band's own Poisson stream for piece "below"; a refused mean names its piece
-int mock_masses_cut(lf_mock* m, const char* fn, const double* theta, int32_t r0, int n, const int64_t* row_ids, uint64_t seed,
-                    std::vector<double>& muA, std::vector<long long>& nA, std::vector<double>& muB, std::vector<long long>& nB) {
-    const int nf = m->mc.nf, S = m->mc.S, nrf = n * nf;
-    const int rc = mock_masses(m, fn, theta, r0, n, row_ids, seed, muA, nA);
-    if (rc == LF_ERR_ARG) m->err += " (piece \"above\")";
-    if (rc != LF_OK) return rc;
-    hipLaunchKernelGGL(lf::lf_mock_mass, dim3((unsigned)S, (unsigned)nrf), dim3(lf::MOCK_THREADS), 0, 0, m->mcb, m->d_theta, m->d_cdfLb,
-                       m->d_colmb);
-    LF_HIP(m, hipGetLastError());
-    hipLaunchKernelGGL(lf::lf_mock_total, dim3((unsigned)nrf), dim3(lf::MOCK_THREADS), 0, 0, S, nf, m->d_colmb, m->d_rid,
-                       (unsigned long long)seed, m->d_cdfZb, m->d_meanb, m->d_countb);
-    LF_HIP(m, hipGetLastError());
-    hipLaunchKernelGGL(lf::lf_mock_count_cut, dim3((unsigned)((nrf + lf::MOCK_THREADS - 1) / lf::MOCK_THREADS)), dim3(lf::MOCK_THREADS), 0,
-                       0, nrf, nf, m->d_meanb, m->d_rid, (unsigned long long)seed, m->d_countb);
-    LF_HIP(m, hipGetLastError());
-    muB.resize((size_t)nrf);
-    nB.resize((size_t)nrf);
-    LF_HIP(m, hipMemcpy(muB.data(), m->d_meanb, (size_t)nrf * sizeof(double), hipMemcpyDeviceToHost));
-    LF_HIP(m, hipMemcpy(nB.data(), m->d_countb, (size_t)nrf * sizeof(long long), hipMemcpyDeviceToHost));
-    for (int i = 0; i < nrf; ++i)
-        if (nB[(size_t)i] < 0) {
-            char b[200];
-            std::snprintf(b, sizeof b, "row %d field %d: expected count %.17g is not finite, negative or above 2^31 (piece \"below\")",
-                          r0 + i / nf, i % nf, muB[(size_t)i]);
-            return mock_fail(m, fn, b);
-        }
-    return LF_OK;
-}
-
-int mock_cut_ready(lf_mock* m, const char* fn) {
-    if (m->mn.M == 0) return mock_fail(m, fn, "no error model is set (lf_mock_set_error_model)");
-    if (!m->band) return mock_fail(m, fn, "no cut band is set (lf_mock_set_cut_band, after lf_mock_set_error_model)");
-    return LF_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int lf_mock_set_cut_band(lf_mock* m, const double* logLb, const double* integ_part_b) {
@@ -3937,26 +3934,25 @@ int lf_mock_draw_cut(lf_mock* m, const double* theta, int32_t R, const int64_t* 
                      int64_t* kept) {
     static const char* fn = "lf_mock_draw_cut";
     if (!m) return LF_ERR_ARG;
-    int rc = mock_check(m, fn, theta, R);
+    int rc = mock_check(m, fn, theta, R, MOCK_NEEDS_BAND);
     if (rc != LF_OK) return rc;
-    if ((rc = mock_cut_ready(m, fn)) != LF_OK) return rc;
     if (!n_cand || !mean) return mock_fail(m, fn, "n_cand or mean is NULL");
     if (cap < 0) return mock_fail(m, fn, "cap must be >= 0");
     if (cap > 0 && (!z || !logL_true || !logL_obs || !sigma || !field || !keep || !kept))
         return mock_fail(m, fn, "z, logL_true, logL_obs, sigma, field, keep or kept is NULL");
     LF_HIP(m, hipSetDevice(m->device));
     const int nf = m->mc.nf;
-    std::vector<double> muA, muB;
-    std::vector<long long> nA, nB, off, dst;
+    std::vector<double> mu[2];
+    std::vector<long long> n[2], off, dst;
     int64_t total = 0;
     for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
         const int rows = std::min<int32_t>(m->rch, R - r0);
-        if ((rc = mock_masses_cut(m, fn, theta, r0, rows, row_ids, seed, muA, nA, muB, nB)) != LF_OK) return rc;
+        if ((rc = mock_chunk(m, fn, 2, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
         for (int i = 0; i < rows * nf; ++i) {
             const size_t o = 2 * ((size_t)r0 * nf + i);
-            n_cand[o] = nA[(size_t)i], n_cand[o + 1] = nB[(size_t)i];
-            mean[o] = muA[(size_t)i], mean[o + 1] = muB[(size_t)i];
-            total += nA[(size_t)i] + nB[(size_t)i];
+            n_cand[o] = n[0][(size_t)i], n_cand[o + 1] = n[1][(size_t)i];
+            mean[o] = mu[0][(size_t)i], mean[o + 1] = mu[1][(size_t)i];
+            total += n[0][(size_t)i] + n[1][(size_t)i];
         }
     }
     if (total > cap || cap == 0) return LF_OK;          // the counts alone: the caller sizes the arrays and calls again
@@ -3966,7 +3962,7 @@ int lf_mock_draw_cut(lf_mock* m, const double* theta, int32_t R, const int64_t* 
         const int rows = std::min<int32_t>(m->rch, R - r0);
         const int nrf = rows * nf;
         // (one chunk: its cumulative sums are still on the device)
-        if (R > m->rch && (rc = mock_masses_cut(m, fn, theta, r0, rows, row_ids, seed, muA, nA, muB, nB)) != LF_OK) return rc;
+        if (R > m->rch && (rc = mock_chunk(m, fn, 2, theta, r0, rows, row_ids, seed, mu, n)) != LF_OK) return rc;
         const int64_t* nc = n_cand + 2 * (size_t)r0 * nf;
         dst.assign(2 * (size_t)nrf, 0);
         long long tot = 0;
@@ -3976,33 +3972,23 @@ int lf_mock_draw_cut(lf_mock* m, const double* theta, int32_t R, const int64_t* 
             tot += nc[2 * i] + nc[2 * i + 1];
         }
         if (tot == 0) continue;
-        if ((size_t)tot > m->d_z.size() && (rc = grow(m, m->d_z, (size_t)tot, false)) != LF_OK) return rc;
-        if ((size_t)tot > m->d_L.size() && (rc = grow(m, m->d_L, (size_t)tot, false)) != LF_OK) return rc;
-        if ((size_t)tot > m->d_Lobs.size() && (rc = grow(m, m->d_Lobs, (size_t)tot, false)) != LF_OK) return rc;
-        if ((size_t)tot > m->d_sg.size() && (rc = grow(m, m->d_sg, (size_t)tot, false)) != LF_OK) return rc;
-        if ((size_t)tot > m->d_fld.size() && (rc = grow(m, m->d_fld, (size_t)tot, false)) != LF_OK) return rc;
-        if ((size_t)tot > m->d_keep.size() && (rc = grow(m, m->d_keep, (size_t)tot, false)) != LF_OK) return rc;
+        if ((rc = mock_grow(m, (size_t)tot, m->d_z, m->d_L, m->d_Lobs, m->d_sg, m->d_fld, m->d_keep)) != LF_OK) return rc;
         LF_HIP(m, hipMemcpy(m->d_dst, dst.data(), dst.size() * sizeof(long long), hipMemcpyHostToDevice));
         for (int piece = 0; piece < 2; ++piece) {
             off.assign((size_t)nrf + 1, 0);
             for (int i = 0; i < nrf; ++i) off[(size_t)i + 1] = off[(size_t)i] + nc[2 * i + piece];
-            const long long n = off[(size_t)nrf];
-            if (n == 0) continue;
-            long long* d_off = piece ? m->d_offb : m->d_off;
-            LF_HIP(m, hipMemcpy(d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice));
-            const lf::MockCut ct{m->d_grid[0], piece ? lf::MOCK_CUT_BAND : 0u};
-            hipLaunchKernelGGL(lf::lf_mock_draw_cut, dim3((unsigned)((n + lf::MOCK_THREADS - 1) / lf::MOCK_THREADS)), dim3(lf::MOCK_THREADS), 0,
-                               0, piece ? m->mcb : m->mc, m->mn, ct, nrf, d_off, m->d_dst + (size_t)piece * nrf, m->d_rid,
-                               (unsigned long long)seed, piece ? m->d_cdfLb : m->d_cdfL, piece ? m->d_cdfZb : m->d_cdfZ, m->d_z, m->d_L,
-                               m->d_Lobs, m->d_sg, m->d_fld, m->d_keep);
+            const long long np = off[(size_t)nrf];
+            if (np == 0) continue;
+            const MockPiece p = mock_piece(m, piece);
+            LF_HIP(m, hipMemcpy(p.off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(lf::lf_mock_draw_cut, dim3((unsigned)((np + lf::MOCK_THREADS - 1) / lf::MOCK_THREADS)), dim3(lf::MOCK_THREADS),
+                               0, 0, p.mc, m->mn, p.ct, nrf, p.off, m->d_dst + (size_t)piece * nrf, m->d_rid, (unsigned long long)seed,
+                               p.cdfL, p.cdfZ, m->d_z, m->d_L, m->d_Lobs, m->d_sg, m->d_fld, m->d_keep);
             LF_HIP(m, hipGetLastError());
         }
-        LF_HIP(m, hipMemcpy(z + done, m->d_z, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
-        LF_HIP(m, hipMemcpy(logL_true + done, m->d_L, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
-        LF_HIP(m, hipMemcpy(logL_obs + done, m->d_Lobs, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
-        LF_HIP(m, hipMemcpy(sigma + done, m->d_sg, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
-        LF_HIP(m, hipMemcpy(field + done, m->d_fld, (size_t)tot * sizeof(int), hipMemcpyDeviceToHost));
-        LF_HIP(m, hipMemcpy(keep + done, m->d_keep, (size_t)tot * sizeof(int), hipMemcpyDeviceToHost));
+        if ((rc = mock_fetch(m, (size_t)tot, z + done, m->d_z, logL_true + done, m->d_L, logL_obs + done, m->d_Lobs, sigma + done, m->d_sg,
+                             field + done, m->d_fld, keep + done, m->d_keep)) != LF_OK)
+            return rc;
         for (int i = 0; i < nrf; ++i) {
             const int64_t a = done + dst[(size_t)i], b = a + nc[2 * i] + nc[2 * i + 1];
             int64_t k = 0;
@@ -4016,46 +4002,11 @@ int lf_mock_draw_cut(lf_mock* m, const double* theta, int32_t R, const int64_t* 
 
 int lf_mock_hist_cut(lf_mock* m, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed, int32_t nbins,
                      const double* edges, int64_t* hist, int64_t* kept) {
-    static const char* fn = "lf_mock_hist_cut";
-    if (!m) return LF_ERR_ARG;
-    int rc = mock_check(m, fn, theta, R);
-    if (rc != LF_OK) return rc;
-    if ((rc = mock_cut_ready(m, fn)) != LF_OK) return rc;
-    if (nbins < 1 || nbins > lf::MOCK_MAX_BINS)
-        return mock_fail(m, fn, "nbins must be in 1.." + std::to_string(lf::MOCK_MAX_BINS));
-    if (!edges || !hist || !kept) return mock_fail(m, fn, "edges, hist or kept is NULL");
-    for (int i = 0; i <= nbins; ++i)
-        if (!std::isfinite(edges[i]) || (i > 0 && !(edges[i] >= edges[i - 1])))
-            return mock_fail(m, fn, "edges must be finite and non-decreasing");
-    LF_HIP(m, hipSetDevice(m->device));
-    LF_HIP(m, hipMemcpy(m->d_edges, edges, (size_t)(nbins + 1) * sizeof(double), hipMemcpyHostToDevice));
-    const int nf = m->mc.nf, ns = nbins + 2;
-    std::vector<double> muA, muB;
-    std::vector<long long> nA, nB, blk;
-    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
-        const int rows = std::min<int32_t>(m->rch, R - r0);
-        const int nrf = rows * nf;
-        if ((rc = mock_masses_cut(m, fn, theta, r0, rows, row_ids, seed, muA, nA, muB, nB)) != LF_OK) return rc;
-        if ((size_t)nrf * ns > m->d_hist.size() && (rc = grow(m, m->d_hist, (size_t)nrf * ns, false)) != LF_OK) return rc;
-        LF_HIP(m, hipMemset(m->d_hist, 0, (size_t)nrf * ns * sizeof(unsigned long long)));
-        LF_HIP(m, hipMemset(m->d_kept, 0, (size_t)nrf * sizeof(unsigned long long)));
-        for (int piece = 0; piece < 2; ++piece) {
-            const std::vector<long long>& n = piece ? nB : nA;
-            blk.assign((size_t)nrf + 1, 0);
-            for (int i = 0; i < nrf; ++i) blk[(size_t)i + 1] = blk[(size_t)i] + (n[(size_t)i] + lf::MOCK_HIST_CHUNK - 1) / lf::MOCK_HIST_CHUNK;
-            if (blk[(size_t)nrf] == 0) continue;
-            long long* d_blk = piece ? m->d_offb : m->d_off;
-            LF_HIP(m, hipMemcpy(d_blk, blk.data(), blk.size() * sizeof(long long), hipMemcpyHostToDevice));
-            const lf::MockCut ct{m->d_grid[0], piece ? lf::MOCK_CUT_BAND : 0u};
-            hipLaunchKernelGGL(lf::lf_mock_hist_cut, dim3((unsigned)blk[(size_t)nrf]), dim3(lf::MOCK_THREADS), 0, 0, piece ? m->mcb : m->mc,
-                               m->mn, ct, nrf, d_blk, piece ? m->d_countb : m->d_count, m->d_rid, (unsigned long long)seed,
-                               piece ? m->d_cdfLb : m->d_cdfL, piece ? m->d_cdfZb : m->d_cdfZ, nbins, m->d_edges, m->d_hist, m->d_kept);
-            LF_HIP(m, hipGetLastError());
-        }
-        LF_HIP(m, hipMemcpy(hist + (size_t)r0 * nf * ns, m->d_hist, (size_t)nrf * ns * sizeof(int64_t), hipMemcpyDeviceToHost));
-        LF_HIP(m, hipMemcpy(kept + (size_t)r0 * nf, m->d_kept, (size_t)nrf * sizeof(int64_t), hipMemcpyDeviceToHost));
-    }
-    return LF_OK;
+    auto launch = [&](const MockPiece& p, int nrf, dim3 grid) {
+        hipLaunchKernelGGL(lf::lf_mock_hist_cut, grid, dim3(lf::MOCK_THREADS), 0, 0, p.mc, m->mn, p.ct, nrf, p.off, p.count, m->d_rid,
+                           (unsigned long long)seed, p.cdfL, p.cdfZ, nbins, m->d_edges, m->d_hist, m->d_kept);
+    };
+    return mock_hist1(m, "lf_mock_hist_cut", MOCK_NEEDS_BAND, theta, R, row_ids, seed, nbins, edges, hist, kept, launch);
 }
 
 }  // extern "C"
@@ -4065,21 +4016,13 @@ int lf_mock_hist_cut(lf_mock* m, const double* theta, int32_t R, const int64_t* 
 // ------------------------------------------------------------------------------------------------------------------------
 namespace {
 
-int mock_edges_ok(lf_mock* m, const char* fn, const char* name, int32_t n, const double* e) {
-    for (int i = 0; i <= n; ++i)
-        if (!std::isfinite(e[i]) || (i > 0 && !(e[i] >= e[i - 1])))
-            return mock_fail(m, fn, std::string(name) + " must be finite and non-decreasing");
-    return LF_OK;
-}
-
 // the three entries: P = lf::MOCK_HIST2_PLAIN (count: NULL = the Poisson counts), _NOISY (the same), _CUT (count NULL; kept)
 int mock_hist2(lf_mock* m, const char* fn, int P, const double* theta, int32_t R, const int64_t* row_ids, uint64_t seed,
                const int64_t* count, int32_t nz, const double* z_edges, int32_t nl, const double* edges, int64_t* hist, int64_t* kept) {
     if (!m) return LF_ERR_ARG;
-    int rc = mock_check(m, fn, theta, R);
+    const MockNeeds needs = P == lf::MOCK_HIST2_CUT ? MOCK_NEEDS_BAND : P == lf::MOCK_HIST2_NOISY ? MOCK_NEEDS_MODEL : MOCK_NEEDS_NOTHING;
+    int rc = mock_check(m, fn, theta, R, needs);
     if (rc != LF_OK) return rc;
-    if (P == lf::MOCK_HIST2_NOISY && m->mn.M == 0) return mock_fail(m, fn, "no error model is set (lf_mock_set_error_model)");
-    if (P == lf::MOCK_HIST2_CUT && (rc = mock_cut_ready(m, fn)) != LF_OK) return rc;
     // (the slot count before the axes' upper limits: a grid that is too large hears of the limit it broke first)
     if (nz < 1) return mock_fail(m, fn, "nz must be in 1.." + std::to_string(lf::MOCK_MAX_BINS));
     if (nl < 1) return mock_fail(m, fn, "nl must be in 1.." + std::to_string(lf::MOCK_MAX_BINS));
@@ -4093,62 +4036,25 @@ int mock_hist2(lf_mock* m, const char* fn, int P, const double* theta, int32_t R
         return mock_fail(m, fn, P == lf::MOCK_HIST2_CUT ? "z_edges, edges, hist or kept is NULL" : "z_edges, edges or hist is NULL");
     if ((rc = mock_edges_ok(m, fn, "z_edges", nz, z_edges)) != LF_OK) return rc;
     if ((rc = mock_edges_ok(m, fn, "edges", nl, edges)) != LF_OK) return rc;
-    const int nf = m->mc.nf;
-    if (count)
-        for (int64_t i = 0; i < (int64_t)R * nf; ++i)
-            if (count[i] < 0 || count[i] > (int64_t)UINT32_MAX)
-                return mock_fail(m, fn, "row " + std::to_string(i / nf) + " field " + std::to_string(i % nf) + ": count out of range");
+    int64_t total;
+    if (count && (rc = mock_counts_ok(m, fn, count, R, &total)) != LF_OK) return rc;
     LF_HIP(m, hipSetDevice(m->device));
     if (m->d_zedges.size() == 0 && (rc = grow(m, m->d_zedges, (size_t)lf::MOCK_MAX_BINS + 1, false)) != LF_OK) return rc;
     LF_HIP(m, hipMemcpy(m->d_zedges, z_edges, (size_t)(nz + 1) * sizeof(double), hipMemcpyHostToDevice));
     LF_HIP(m, hipMemcpy(m->d_edges, edges, (size_t)(nl + 1) * sizeof(double), hipMemcpyHostToDevice));
-    const int npiece = P == lf::MOCK_HIST2_CUT ? 2 : 1;
-    std::vector<double> muA, muB;
-    std::vector<long long> nA, nB, blk;
-    for (int32_t r0 = 0; r0 < R; r0 += m->rch) {
-        const int rows = std::min<int32_t>(m->rch, R - r0);
-        const int nrf = rows * nf;
-        if (P == lf::MOCK_HIST2_CUT) rc = mock_masses_cut(m, fn, theta, r0, rows, row_ids, seed, muA, nA, muB, nB);
-        else rc = mock_masses(m, fn, theta, r0, rows, row_ids, seed, muA, nA);
-        if (rc != LF_OK) return rc;
-        if (count) {          // the caller's counts take the place of the Poisson draws lf_mock_total left on the device
-            for (int i = 0; i < nrf; ++i) nA[(size_t)i] = (long long)count[(size_t)r0 * nf + i];
-            LF_HIP(m, hipMemcpy(m->d_count, nA.data(), (size_t)nrf * sizeof(long long), hipMemcpyHostToDevice));
-        }
-        if ((size_t)nrf * ns > m->d_hist.size() && (rc = grow(m, m->d_hist, (size_t)nrf * ns, false)) != LF_OK) return rc;
-        LF_HIP(m, hipMemset(m->d_hist, 0, (size_t)nrf * ns * sizeof(unsigned long long)));
-        if (P == lf::MOCK_HIST2_CUT) LF_HIP(m, hipMemset(m->d_kept, 0, (size_t)nrf * sizeof(unsigned long long)));
-        for (int piece = 0; piece < npiece; ++piece) {
-            const std::vector<long long>& n = piece ? nB : nA;
-            blk.assign((size_t)nrf + 1, 0);
-            for (int i = 0; i < nrf; ++i) blk[(size_t)i + 1] = blk[(size_t)i] + (n[(size_t)i] + lf::MOCK_HIST_CHUNK - 1) / lf::MOCK_HIST_CHUNK;
-            const long long nblk = blk[(size_t)nrf];
-            if (nblk == 0) continue;
-            if (nblk > (long long)INT32_MAX) return mock_fail(m, fn, "too many sources for one launch: pass fewer rows per call");
-            long long* d_blk = piece ? m->d_offb : m->d_off;
-            LF_HIP(m, hipMemcpy(d_blk, blk.data(), blk.size() * sizeof(long long), hipMemcpyHostToDevice));
-            const lf::MockCut ct{m->d_grid[0], piece ? lf::MOCK_CUT_BAND : 0u};
-            const lf::MockConst& mc = piece ? m->mcb : m->mc;
-            const long long* d_n = piece ? m->d_countb : m->d_count;
-            const double* cL = piece ? m->d_cdfLb : m->d_cdfL;
-            const double* cZ = piece ? m->d_cdfZb : m->d_cdfZ;
-            const dim3 grid((unsigned)nblk), block(lf::MOCK_THREADS);
-            if (P == lf::MOCK_HIST2_PLAIN)
-                hipLaunchKernelGGL(lf::lf_mock_hist2<lf::MOCK_HIST2_PLAIN>, grid, block, 0, 0, mc, m->mn, ct, nrf, d_blk, d_n, m->d_rid,
-                                   (unsigned long long)seed, cL, cZ, nz, m->d_zedges, nl, m->d_edges, m->d_hist, nullptr);
-            else if (P == lf::MOCK_HIST2_NOISY)
-                hipLaunchKernelGGL(lf::lf_mock_hist2<lf::MOCK_HIST2_NOISY>, grid, block, 0, 0, mc, m->mn, ct, nrf, d_blk, d_n, m->d_rid,
-                                   (unsigned long long)seed, cL, cZ, nz, m->d_zedges, nl, m->d_edges, m->d_hist, nullptr);
-            else
-                hipLaunchKernelGGL(lf::lf_mock_hist2<lf::MOCK_HIST2_CUT>, grid, block, 0, 0, mc, m->mn, ct, nrf, d_blk, d_n, m->d_rid,
-                                   (unsigned long long)seed, cL, cZ, nz, m->d_zedges, nl, m->d_edges, m->d_hist, m->d_kept);
-            LF_HIP(m, hipGetLastError());
-        }
-        LF_HIP(m, hipMemcpy(hist + (size_t)r0 * nf * ns, m->d_hist, (size_t)nrf * ns * sizeof(int64_t), hipMemcpyDeviceToHost));
-        if (P == lf::MOCK_HIST2_CUT)
-            LF_HIP(m, hipMemcpy(kept + (size_t)r0 * nf, m->d_kept, (size_t)nrf * sizeof(int64_t), hipMemcpyDeviceToHost));
-    }
-    return LF_OK;
+    auto launch = [&](const MockPiece& p, int nrf, dim3 grid) {
+        const dim3 block(lf::MOCK_THREADS);
+        if (P == lf::MOCK_HIST2_PLAIN)
+            hipLaunchKernelGGL(lf::lf_mock_hist2<lf::MOCK_HIST2_PLAIN>, grid, block, 0, 0, p.mc, m->mn, p.ct, nrf, p.off, p.count, m->d_rid,
+                               (unsigned long long)seed, p.cdfL, p.cdfZ, nz, m->d_zedges, nl, m->d_edges, m->d_hist, nullptr);
+        else if (P == lf::MOCK_HIST2_NOISY)
+            hipLaunchKernelGGL(lf::lf_mock_hist2<lf::MOCK_HIST2_NOISY>, grid, block, 0, 0, p.mc, m->mn, p.ct, nrf, p.off, p.count, m->d_rid,
+                               (unsigned long long)seed, p.cdfL, p.cdfZ, nz, m->d_zedges, nl, m->d_edges, m->d_hist, nullptr);
+        else
+            hipLaunchKernelGGL(lf::lf_mock_hist2<lf::MOCK_HIST2_CUT>, grid, block, 0, 0, p.mc, m->mn, p.ct, nrf, p.off, p.count, m->d_rid,
+                               (unsigned long long)seed, p.cdfL, p.cdfZ, nz, m->d_zedges, nl, m->d_edges, m->d_hist, m->d_kept);
+    };
+    return mock_binned(m, fn, P == lf::MOCK_HIST2_CUT ? 2 : 1, theta, R, row_ids, seed, count, ns, hist, kept, launch);
 }
 
 }  // namespace

@@ -346,30 +346,33 @@ class MockTwin(object):
         cat = lambda v, dt: np.concatenate(v).astype(dt) if v else np.zeros(0, dtype=dt)   # noqa: E731
         return cat(zs, np.float64), cat(Ls, np.float64), cat(fs, np.int32), off
 
+    def _binned(self, draw, edges, z_edges=None):
+        """Bin what draw() returns (draw, draw_noisy or draw_cut) by its last luminosity column - with z_edges by (z, that column) -
+        after the edges are checked; from draw_cut: (hist, kept)."""
+        ze, e = (None, _edges(edges)) if z_edges is None else _edges2(z_edges, edges)
+        d = draw()
+        z, L, off = (d[0], d[1], d[3]) if len(d) == 4 else (d[0], d[2], d[5])
+        if ze is None:
+            h = bin_sources(L, off, e).reshape(-1, self.nf, e.size + 1)
+        else:
+            h = bin_sources2(z, L, off, ze, e).reshape(-1, self.nf, ze.size + 1, e.size + 1)
+        return (h, d[6]["kept"]) if len(d) == 7 else h
+
     def hist(self, thetas, edges, seed, row_ids=None):
         """(R, nf, nbins + 2) counts of logL per slot searchsorted(edges, logL, side="right")."""
-        edges = _edges(edges)
-        z, L, fld, off = self.draw(thetas, seed, row_ids)
-        R = np.atleast_2d(thetas).shape[0]
-        return bin_sources(L, off, edges).reshape(R, self.nf, edges.size + 1)
+        return self._binned(lambda: self.draw(thetas, seed, row_ids), edges)
 
     def hist2(self, thetas, z_edges, edges, seed, row_ids=None, count=None):
         """(R, nf, nz + 2, nl + 2) counts of (z, logL) per slot pair (bin_sources2); count as draw takes it."""
-        ze, e = _edges2(z_edges, edges)
-        z, L, fld, off = self.draw(thetas, seed, row_ids, count)
-        return bin_sources2(z, L, off, ze, e).reshape(-1, self.nf, ze.size + 1, e.size + 1)
+        return self._binned(lambda: self.draw(thetas, seed, row_ids, count), edges, z_edges)
 
     def hist2_noisy(self, thetas, z_edges, edges, seed, row_ids=None, count=None):
         """hist2() of the true redshifts and the observed luminosities."""
-        ze, e = _edges2(z_edges, edges)
-        z, L, Lobs, sg, fld, off = self.draw_noisy(thetas, seed, row_ids, count)
-        return bin_sources2(z, Lobs, off, ze, e).reshape(-1, self.nf, ze.size + 1, e.size + 1)
+        return self._binned(lambda: self.draw_noisy(thetas, seed, row_ids, count), edges, z_edges)
 
     def hist2_cut(self, thetas, z_edges, edges, seed, row_ids=None):
         """(hist (R, nf, nz + 2, nl + 2) of the catalogued sources' (z, L_obs), kept (R, nf))."""
-        ze, e = _edges2(z_edges, edges)
-        z, L, Lobs, sg, fld, off, info = self.draw_cut(thetas, seed, row_ids)
-        return bin_sources2(z, Lobs, off, ze, e).reshape(-1, self.nf, ze.size + 1, e.size + 1), info["kept"]
+        return self._binned(lambda: self.draw_cut(thetas, seed, row_ids), edges, z_edges)
 
     # ---------------------------------------------------------------- the observation step (lf_mock_noise.h)
     def set_error_model(self, nodes, sigma):
@@ -408,10 +411,7 @@ class MockTwin(object):
 
     def hist_noisy(self, thetas, edges, seed, row_ids=None):
         """hist() of the observed luminosities."""
-        edges = _edges(edges)
-        z, L, Lobs, sg, fld, off = self.draw_noisy(thetas, seed, row_ids)
-        R = np.atleast_2d(thetas).shape[0]
-        return bin_sources(Lobs, off, edges).reshape(R, self.nf, edges.size + 1)
+        return self._binned(lambda: self.draw_noisy(thetas, seed, row_ids), edges)
 
     # ---------------------------------------------------------------- the cut process (lf_mock_cut.h; DESIGN.md section 3.32)
     def set_cut_band(self, logLb, integ_part_b=None):
@@ -495,10 +495,7 @@ class MockTwin(object):
 
     def hist_cut(self, thetas, edges, seed, row_ids=None):
         """(hist (R, nf, nbins + 2) of the catalogued sources' L_obs, kept (R, nf))."""
-        edges = _edges(edges)
-        z, L, Lobs, sg, fld, off, info = self.draw_cut(thetas, seed, row_ids)
-        R = np.atleast_2d(thetas).shape[0]
-        return bin_sources(Lobs, off, edges).reshape(R, self.nf, edges.size + 1), info["kept"]
+        return self._binned(lambda: self.draw_cut(thetas, seed, row_ids), edges)
 
 
 CUT_BAND = 0x400              # piece "below": ORed into the field word of the streams, purposes 4 + (0 .. 3) (lf_mock_cut.h)
@@ -727,6 +724,14 @@ def bin_sources2(z, logL, offsets, z_edges, edges):
 
 
 # --------------------------------------------------------------------------------------------------------------- device
+def _i64(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if a is not None else None
+
+
+def _i32(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if a is not None else None
+
+
 class MockGenerator(object):
     """lf_mock_* on the GPU.  `inputs` is the dict LFContext takes (kernel_inputs()); the catalogue arrays are not read."""
 
@@ -785,49 +790,61 @@ class MockGenerator(object):
         if rc != capi.LF_OK:
             raise capi.LFError("liblfmcmc error %d: %s" % (rc, self._lib.lf_mock_last_error(self._h).decode()))
 
+    def _head(self, thetas, seed, row_ids):
+        """(thetas (R, ndim), R, row ids, the five arguments every lf_mock_* call starts with)"""
+        from . import capi
+        th = _rows(thetas, self.ndim)
+        R = th.shape[0]
+        rid = _row_ids(row_ids, R)
+        return th, R, rid, (self._h, capi._ptr(th), R, _i64(rid), ctypes.c_uint64(int(seed)))
+
+    def _need_band(self):
+        """a generator on which set_cut_band was never called lets the library refuse"""
+        if not getattr(self, "_band_set", True):
+            raise MockError("no cut band is set (set_cut_band, after set_error_model)")
+
     def counts(self, thetas, seed, row_ids=None):
         """(mean (R, nf), count (R, nf) int64): expected counts M and their Poisson draws."""
         from . import capi
-        th = _rows(thetas, self.ndim)
-        R = th.shape[0]
-        rid = _row_ids(row_ids, R)
+        th, R, rid, head = self._head(thetas, seed, row_ids)
         mean = np.empty((R, self.nf))
         cnt = np.empty((R, self.nf), dtype=np.int64)
-        self._check(self._lib.lf_mock_counts(self._h, capi._ptr(th), R, rid.ctypes.data_as(capi._c_int64_p), ctypes.c_uint64(int(seed)),
-                                             capi._ptr(mean), cnt.ctypes.data_as(capi._c_int64_p)))
+        self._check(self._lib.lf_mock_counts(*head, capi._ptr(mean), _i64(cnt)))
         return mean, cnt
 
-    def draw(self, thetas, seed, row_ids=None, count=None):
-        """(z, logL, field, offsets): the sources of every (row, field) in that order (count: from .counts unless given);
-        sources of (r, f) are [offsets[r nf + f], offsets[r nf + f + 1])."""
+    def _draw(self, entry, thetas, seed, row_ids, count, ncol):
+        """lf_mock_draw (ncol = 2 columns of doubles: z, logL) and lf_mock_draw_err (4: z, L_true, L_obs, sigma): the columns,
+        field, offsets"""
         from . import capi
-        th = _rows(thetas, self.ndim)
-        R = th.shape[0]
-        rid = _row_ids(row_ids, R)
+        th, R, rid, head = self._head(thetas, seed, row_ids)
         if count is None:
             count = self.counts(th, seed, rid)[1]
         cnt = np.ascontiguousarray(np.asarray(count, dtype=np.int64).reshape(R, self.nf))
         total = int(cnt.sum())
-        z, L = np.empty(total), np.empty(total)
+        cols = tuple(np.empty(total) for _ in range(ncol))
         fld = np.empty(total, dtype=np.int32)
-        self._check(self._lib.lf_mock_draw(self._h, capi._ptr(th), R, rid.ctypes.data_as(capi._c_int64_p), ctypes.c_uint64(int(seed)),
-                                           cnt.ctypes.data_as(capi._c_int64_p), capi._ptr(z), capi._ptr(L),
-                                           fld.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
-        off = np.concatenate([[0], np.cumsum(cnt.ravel())]).astype(np.int64)
-        return z, L, fld, off
+        self._check(getattr(self._lib, entry)(*head, _i64(cnt), *[capi._ptr(c) for c in cols], _i32(fld)))
+        return cols + (fld, np.concatenate([[0], np.cumsum(cnt.ravel())]).astype(np.int64))
+
+    def draw(self, thetas, seed, row_ids=None, count=None):
+        """(z, logL, field, offsets): the sources of every (row, field) in that order (count: from .counts unless given);
+        sources of (r, f) are [offsets[r nf + f], offsets[r nf + f + 1])."""
+        return self._draw("lf_mock_draw", thetas, seed, row_ids, count, 2)
+
+    def _hist1(self, entry, thetas, edges, seed, row_ids, with_kept):
+        from . import capi
+        th, R, rid, head = self._head(thetas, seed, row_ids)
+        if with_kept:
+            self._need_band()
+        e = _edges(edges)
+        out = np.empty((R, self.nf, e.size + 1), dtype=np.int64)
+        kept = np.empty((R, self.nf), dtype=np.int64) if with_kept else None
+        self._check(getattr(self._lib, entry)(*head, e.size - 1, capi._ptr(e), _i64(out), *([_i64(kept)] if with_kept else [])))
+        return (out, kept) if with_kept else out
 
     def hist(self, thetas, edges, seed, row_ids=None):
         """(R, nf, nbins + 2) int64: logL of every (row, field) binned by searchsorted(edges, x, side="right")."""
-        from . import capi
-        th = _rows(thetas, self.ndim)
-        R = th.shape[0]
-        rid = _row_ids(row_ids, R)
-        e = _edges(edges)
-        nb = e.size - 1
-        out = np.empty((R, self.nf, nb + 2), dtype=np.int64)
-        self._check(self._lib.lf_mock_hist(self._h, capi._ptr(th), R, rid.ctypes.data_as(capi._c_int64_p), ctypes.c_uint64(int(seed)), nb,
-                                           capi._ptr(e), out.ctypes.data_as(capi._c_int64_p)))
-        return out
+        return self._hist1("lf_mock_hist", thetas, edges, seed, row_ids, False)
 
     # ---------------------------------------------------------------- the observation step (lf_mock_noise.h)
     def set_error_model(self, nodes, sigma):
@@ -847,34 +864,11 @@ class MockGenerator(object):
     def draw_noisy(self, thetas, seed, row_ids=None, count=None):
         """(z, L_true, L_obs, sigma, field, offsets): draw()'s sources and what the catalogue records of them, the noise
         added on the device (lf_mock_draw_err)."""
-        from . import capi
-        th = _rows(thetas, self.ndim)
-        R = th.shape[0]
-        rid = _row_ids(row_ids, R)
-        if count is None:
-            count = self.counts(th, seed, rid)[1]
-        cnt = np.ascontiguousarray(np.asarray(count, dtype=np.int64).reshape(R, self.nf))
-        total = int(cnt.sum())
-        z, L, Lobs, sg = np.empty(total), np.empty(total), np.empty(total), np.empty(total)
-        fld = np.empty(total, dtype=np.int32)
-        self._check(self._lib.lf_mock_draw_err(self._h, capi._ptr(th), R, rid.ctypes.data_as(capi._c_int64_p), ctypes.c_uint64(int(seed)),
-                                               cnt.ctypes.data_as(capi._c_int64_p), capi._ptr(z), capi._ptr(L), capi._ptr(Lobs),
-                                               capi._ptr(sg), fld.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
-        off = np.concatenate([[0], np.cumsum(cnt.ravel())]).astype(np.int64)
-        return z, L, Lobs, sg, fld, off
+        return self._draw("lf_mock_draw_err", thetas, seed, row_ids, count, 4)
 
     def hist_noisy(self, thetas, edges, seed, row_ids=None):
         """hist() of the observed luminosities (lf_mock_hist_err)."""
-        from . import capi
-        th = _rows(thetas, self.ndim)
-        R = th.shape[0]
-        rid = _row_ids(row_ids, R)
-        e = _edges(edges)
-        nb = e.size - 1
-        out = np.empty((R, self.nf, nb + 2), dtype=np.int64)
-        self._check(self._lib.lf_mock_hist_err(self._h, capi._ptr(th), R, rid.ctypes.data_as(capi._c_int64_p), ctypes.c_uint64(int(seed)),
-                                               nb, capi._ptr(e), out.ctypes.data_as(capi._c_int64_p)))
-        return out
+        return self._hist1("lf_mock_hist_err", thetas, edges, seed, row_ids, False)
 
     # ---------------------------------------------------------------- the cut process (lf_mock_cut.h; DESIGN.md section 3.32)
     def set_cut_band(self, logLb, integ_part_b=None):
@@ -898,22 +892,15 @@ class MockGenerator(object):
     def candidates_cut(self, thetas, seed, row_ids=None):
         """As MockTwin.candidates_cut, drawn, observed and cut on the device (lf_mock_draw_cut)."""
         from . import capi
-        th = _rows(thetas, self.ndim)
-        R = th.shape[0]
-        rid = _row_ids(row_ids, R)
-        if not getattr(self, "_band_set", True):
-            raise MockError("no cut band is set (set_cut_band, after set_error_model)")
+        th, R, rid, head = self._head(thetas, seed, row_ids)
+        self._need_band()
         n_cand = np.zeros((R, self.nf, 2), dtype=np.int64)
         mean = np.zeros((R, self.nf, 2))
         kept = np.zeros((R, self.nf), dtype=np.int64)
-        i32 = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))   # noqa: E731
 
         def call(cap, z, L, Lobs, sg, fld, keep):
-            self._check(self._lib.lf_mock_draw_cut(self._h, capi._ptr(th), R, rid.ctypes.data_as(capi._c_int64_p), ctypes.c_uint64(int(seed)),
-                                                   cap, capi._ptr(z), capi._ptr(L), capi._ptr(Lobs), capi._ptr(sg),
-                                                   i32(fld) if fld is not None else None, i32(keep) if keep is not None else None,
-                                                   n_cand.ctypes.data_as(capi._c_int64_p), capi._ptr(mean),
-                                                   kept.ctypes.data_as(capi._c_int64_p)))
+            self._check(self._lib.lf_mock_draw_cut(*head, cap, capi._ptr(z), capi._ptr(L), capi._ptr(Lobs), capi._ptr(sg), _i32(fld),
+                                                   _i32(keep), _i64(n_cand), capi._ptr(mean), _i64(kept)))
 
         call(0, None, None, None, None, None, None)
         total = int(n_cand.sum())
@@ -930,40 +917,23 @@ class MockGenerator(object):
 
     def hist_cut(self, thetas, edges, seed, row_ids=None):
         """(hist (R, nf, nbins + 2) of the catalogued sources' L_obs, kept (R, nf)) without writing sources (lf_mock_hist_cut)."""
-        from . import capi
-        th = _rows(thetas, self.ndim)
-        R = th.shape[0]
-        rid = _row_ids(row_ids, R)
-        if not getattr(self, "_band_set", True):
-            raise MockError("no cut band is set (set_cut_band, after set_error_model)")
-        e = _edges(edges)
-        nb = e.size - 1
-        out = np.empty((R, self.nf, nb + 2), dtype=np.int64)
-        kept = np.empty((R, self.nf), dtype=np.int64)
-        self._check(self._lib.lf_mock_hist_cut(self._h, capi._ptr(th), R, rid.ctypes.data_as(capi._c_int64_p), ctypes.c_uint64(int(seed)),
-                                               nb, capi._ptr(e), out.ctypes.data_as(capi._c_int64_p),
-                                               kept.ctypes.data_as(capi._c_int64_p)))
-        return out, kept
+        return self._hist1("lf_mock_hist_cut", thetas, edges, seed, row_ids, True)
 
     # ---------------------------------------------------------------- binned in (z, L) (lf_mock_hist2.h; DESIGN.md section 3.35)
     def _hist2(self, entry, thetas, z_edges, edges, seed, row_ids, count, with_kept):
         from . import capi
         ze, e = _edges2(z_edges, edges)         # (first: a refused grid reaches no library call)
-        th = _rows(thetas, self.ndim)
-        R = th.shape[0]
-        rid = _row_ids(row_ids, R)
-        i64 = lambda a: a.ctypes.data_as(capi._c_int64_p)   # noqa: E731
+        th, R, rid, head = self._head(thetas, seed, row_ids)
         out = np.empty((R, self.nf, ze.size + 1, e.size + 1), dtype=np.int64)
-        head = (self._h, capi._ptr(th), R, i64(rid), ctypes.c_uint64(int(seed)))
-        grid = (ze.size - 1, capi._ptr(ze), e.size - 1, capi._ptr(e), i64(out))
+        grid = (ze.size - 1, capi._ptr(ze), e.size - 1, capi._ptr(e), _i64(out))
         if with_kept:
             kept = np.empty((R, self.nf), dtype=np.int64)
-            self._check(getattr(self._lib, entry)(*head, *grid, i64(kept)))
+            self._check(getattr(self._lib, entry)(*head, *grid, _i64(kept)))
             return out, kept
         cnt = None
         if count is not None:
             cnt = np.ascontiguousarray(np.asarray(count, dtype=np.int64).reshape(R, self.nf))
-        self._check(getattr(self._lib, entry)(*head, i64(cnt) if cnt is not None else None, *grid))
+        self._check(getattr(self._lib, entry)(*head, _i64(cnt), *grid))
         return out
 
     def hist2(self, thetas, z_edges, edges, seed, row_ids=None, count=None):
@@ -978,8 +948,7 @@ class MockGenerator(object):
     def hist2_cut(self, thetas, z_edges, edges, seed, row_ids=None):
         """(hist (R, nf, nz + 2, nl + 2) of the catalogued sources' (z, L_obs), kept (R, nf)) (lf_mock_hist2_cut)."""
         _edges2(z_edges, edges)
-        if not getattr(self, "_band_set", True):
-            raise MockError("no cut band is set (set_cut_band, after set_error_model)")
+        self._need_band()
         return self._hist2("lf_mock_hist2_cut", thetas, z_edges, edges, seed, row_ids, None, True)
 
     def close(self):
